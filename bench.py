@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: DeepFM training step on synthetic Criteo-shape input.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`)
 
 A "step" = one pass of the hot path over one batch already resident in HBM: device-side id hashing
@@ -64,7 +64,15 @@ def parse_args():
                        'oracle then holds only the rows the parity batches read - no CPU timing is possible on that state)')
   ap.add_argument('--parity_steps', type=int, default=2,
                   help='N=1: steps of the full-size GPU-vs-oracle loss comparison (0 = skip; needs the CPU baseline)')
-  return ap.parse_args()
+  ap.add_argument('--dump-outputs', dest='dump_outputs', default='', metavar='DIR',
+                  help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / '
+                       'float64, at most 64 MB): its losses, the dense variables and their optimizer slots, and a fixed, '
+                       'seeded sample of every embedding table\'s rows and slots.  Reading the state brings every lazily '
+                       'decayed row current, so the untimed sections after the timed steps start from that state')
+  args = ap.parse_args()
+  if args.steps < 1:
+    ap.error('--steps must be at least 1')
+  return args
 
 
 def workload_name(cfg, args):
@@ -731,6 +739,56 @@ def parity_full_size(cfg, est, ring, host_batches, batch_size, n_steps):
           'per_step': per_step, 'from_global_step': int(est.global_step - n_steps)}, orc
 
 
+DUMP_BYTES = 64 * 2 ** 20
+DUMP_ROWS_PER_TABLE = 4096
+DUMP_SEED = 20240607
+
+
+def dump_outputs(est, losses, out_dir, write):
+  """--dump-outputs: what the last timed step left to its caller - the loss values it returned and the model state it
+  updated (dense variables, their optimizer slots, embedding rows and their slots) - as out_dir/<name>.npy, '/' in names
+  written as '.'.  Embedding tables are sampled: the same seeded row ids for the same config, at most
+  DUMP_ROWS_PER_TABLE per table and fewer if needed to stay under DUMP_BYTES in all; a hash-table embedding's sample is
+  taken by position among its ids in ascending order, and those ids are written too, as <table>.keys: float64 [n, 2]
+  (id >> 32, id & 0xFFFFFFFF), exact for any int64 id.  Reading the state goes through state_dict(), which brings every
+  lazily decayed row current (flush_decay): the untimed sections after the dump start from that state.  Every rank takes
+  part (the embedding-parallel state_dict gathers the sampled rows); `write` is True on the rank that writes.
+  -> {'dir', 'arrays', 'bytes', 'rows_per_table', 'note'}"""
+  tables = est.engine.tables
+  dense_bytes = sum(v.size * 4 * 3 for v in est.varstore.state_dict().values())
+  per_row = sum(t['dim'] * 4 * 3 + (16 if t.get('kv') else 0) for t in tables.values())  # a row, its two slots (, its id)
+  n_rows = max(1, min(DUMP_ROWS_PER_TABLE, (DUMP_BYTES - dense_bytes - 4096) // max(per_row, 1)))
+  rng = np.random.default_rng(DUMP_SEED)
+  picks = {name: np.unique(rng.integers(0, t['rows'], size=min(n_rows, t['rows']), dtype=np.int64))
+           for name, t in sorted(tables.items()) if not t.get('kv')}
+  state = est.state_dict(slots=True, rows_of=picks)
+  for name, t in tables.items():
+    if t.get('kv') and name in state:
+      # hash-table embeddings: rows in ascending id order; the same seeded positions among them
+      n = state[name].shape[0]
+      pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, max(n, 1), size=min(n_rows, n), dtype=np.int64))
+      for key in (name, name + '/m', name + '/v', name + '/keys'):
+        if key in state:
+          state[key] = state[key][pos]
+      keys = state.pop(name + '/keys').astype(np.int64)
+      state[name + '/keys'] = np.stack([keys >> 32, keys & 0xFFFFFFFF], axis=1).astype(np.float64)
+  arrays = {'loss.' + k: np.array(v, dtype=np.float64) for k, v in losses.items()}
+  for key, v in state.items():
+    v = np.asarray(v)
+    if v.dtype.kind != 'f' or key.endswith('/kv_meta'):
+      continue  # the hash-table filter's counters, a hash table's settings: not computed values
+    arrays[key.replace('/', '.')] = np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+  total = sum(a.nbytes for a in arrays.values())
+  assert total <= DUMP_BYTES, 'dump of %d bytes exceeds %d' % (total, DUMP_BYTES)
+  if write:
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+      np.save(os.path.join(out_dir, name + '.npy'), a)
+  return {'dir': out_dir, 'arrays': len(arrays), 'bytes': total, 'rows_per_table': int(n_rows),
+          'note': 'read through state_dict(), which brings every lazily decayed row current: the untimed sections after '
+                  'the timed steps (roofline, steady_state, parity, cpu_baseline) start from that state'}
+
+
 def cpu_baseline(cfg, est_state, batches, batch_size, budget_s=12.0, max_steps=8, orc=None):
   """The CPU restatement of the reference path (oracle/model_oracle.py) on the host cores: a bounded
   sample (about `budget_s` seconds) of the same workload."""
@@ -844,6 +902,7 @@ def main():
     dt = float(t.item())
   losses = est.loss_values()
   assert all(np.isfinite(v) for v in losses.values()), losses
+  dumped = dump_outputs(est, losses, args.dump_outputs, rank == 0) if args.dump_outputs else None
 
   if rank != 0:
     return
@@ -878,6 +937,8 @@ def main():
       'device': kernels.hip().device_info(),
       'clocks': gpu_clocks(),
   }
+  if dumped is not None:
+    out['dump_outputs'] = dumped
   if world == 1 and not ep:
     lazy_bytes, sweep_bytes, per_kernel_bytes = embedding_bytes_per_step(est, host_ring) if criteo else (0.0, 0.0, {})
     if criteo:  # (the byte accounting of SURVEY.md 8d is written for the Criteo schema)

@@ -633,7 +633,23 @@ class ShardedEmbeddingEngine(EmbeddingEngine):
         mine = view.detach()[rows.to(view.device)].contiguous()
         out[name + suffix] = torch.cat(self.comm.all_gather_varlen(mine)).cpu().numpy()[order]
 
-  def state_dict(self, slots=False):
+  def _gather_ids(self, name, local, ids):
+    """Rows `ids` (global row numbers, the same on every rank) of a table, in that order (collective): row r of a
+    sharded table is local row r // world of rank r % world."""
+    kind = self.placement[name][0]
+    ids = torch.as_tensor(ids, dtype=torch.int64, device=local.device)
+    if kind == 'rep':
+      return local.detach()[ids]
+    owner = ids % self.world
+    mine = local.detach()[ids[owner == self.rank] // self.world].contiguous()
+    got = torch.cat(self.comm.all_gather_varlen(mine))  # rank 0's ids in their order, then rank 1's, ...
+    out = torch.empty_like(got)
+    out[torch.argsort(owner, stable=True)] = got
+    return out
+
+  def state_dict(self, slots=False, rows_of=None):
+    """rows_of: {table name: int64 ids}, the same on every rank: only those rows of the named (dense) tables - and of
+    their slots - are gathered, in the order given (as EmbeddingEngine.state_dict)."""
     out = OrderedDict()
     self.flush_decay()
     self.check_kv_overflow()
@@ -641,12 +657,12 @@ class ShardedEmbeddingEngine(EmbeddingEngine):
       if self.tables[name].get('kv'):
         self._kv_state(name, out, slots)
         continue
-      out[name] = self._gather_full(name, self.table_view(name)).cpu().numpy()
-      if slots:
-        for s in ('m', 'v'):
-          sv = self.slot_view(name, s)
-          if sv is not None:
-            out[name + '/' + s] = self._gather_full(name, sv).cpu().numpy()
+      ids = rows_of.get(name) if rows_of is not None else None
+      views = [('', self.table_view(name))] + ([('/' + s, self.slot_view(name, s)) for s in ('m', 'v')] if slots else [])
+      for suffix, view in views:
+        if view is not None:
+          full = self._gather_full(name, view) if ids is None else self._gather_ids(name, view, ids)
+          out[name + suffix] = full.cpu().numpy()
     return out
 
   def load_kv_table(self, name, keys, values, slot_values, seen=None, freq=None, version=None):

@@ -301,9 +301,9 @@ class EmbeddingParallelEstimator(EasyRecEstimator):
     self.engine.check_overflow()
     return super(EmbeddingParallelEstimator, self).evaluate(batches, eval_config)
 
-  def state_dict(self, slots=False):
+  def state_dict(self, slots=False, rows_of=None):
     self.engine.check_overflow()
-    return super(EmbeddingParallelEstimator, self).state_dict(slots=slots)
+    return super(EmbeddingParallelEstimator, self).state_dict(slots=slots, rows_of=rows_of)
 
   def whole_graph_default(self):
     """May capture() put the collectives INSIDE the graph?  Only the fixed-capacity exchange (nothing in it waits for the

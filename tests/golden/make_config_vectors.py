@@ -4,8 +4,9 @@
 /root/reference exists.  The function is executed unmodified (tf.gfile -> open, the protos -> this package's message
 classes, which ARE the reference's schema); the fixture (tests/golden/config_vectors.json) holds, per config, the
 SHA-256 of the deterministic serialisation of the loaded message, plus the full text of three small ones.
-tests/test_config_pins.py loads the same files with easyrec_amd/utils/config_util.py where the reference tree is
-present (the 224 files are not copied into this repository) and always checks the three embedded ones.
+tests/test_config_pins.py checks the three embedded ones with easyrec_amd/utils/config_util.py, and
+tests/test_proto_config.py the digest of examples/configs/deepfm_on_criteo.config against configs/deepfm_criteo.config
+(the 224 files are not copied into this repository).
 
 usage: python tests/golden/make_config_vectors.py [/root/reference]
 """

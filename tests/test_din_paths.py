@@ -4,14 +4,12 @@
   * batches whose longest sequence is below max_seq_len: the model must see the BATCH's longest length (BatchNorm
     inside the attention MLP normalises over B x L positions) - checked against the oracle, and against the same
     batch padded wider giving a DIFFERENT result (so the test can tell the two paddings apart);
-  * backbone `input_layer { wide_output_dim }` (deepfm_backbone_on_criteo's shape);
-  * the reference's eight fixture configs BUILD and run a step when /root/reference exists."""
+  * backbone `input_layer { wide_output_dim }` (deepfm_backbone_on_criteo's shape)."""
 import os
 
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, reference_available
 from easyrec_amd.utils import config_util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -93,22 +91,3 @@ def test_batch_without_a_max_length_sequence(ref_backend, config):
   att = [k for k in sa if k.endswith('moving_mean') and ('din' in k.lower() or 'seq_dnn' in k)]
   assert att, list(sa)[:20]
   assert any(not np.allclose(sa[k], sb[k], rtol=1e-3, atol=1e-9) for k in att), att
-
-
-@pytest.mark.skipif(not reference_available(), reason='needs /root/reference (not present on the GPU box)')
-def test_reference_fixture_configs_build_and_step(ref_backend):
-  from easyrec_amd.input.synthetic import SyntheticBatches
-  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
-  fixtures = ['examples/configs/deepfm_on_criteo.config', 'examples/configs/deepfm_backbone_on_criteo.config'] + \
-      ['samples/model_config/%s.config' % n for n in ('dcn_on_taobao', 'dcn_backbone_on_taobao', 'din_on_taobao',
-                                                        'din_backbone_on_taobao', 'mmoe_on_taobao',
-                                                        'mmoe_backbone_on_taobao')]
-  # + neighbours built on the same blocks: xDeepFM (CIN), DLRM as a backbone (DotInteraction), wide & deep with `Add`
-  fixtures += ['samples/model_config/xdeepfm_on_taobao_backbone.config', 'examples/configs/dlrm_backbone_on_criteo.config',
-               'examples/configs/wide_and_deep_backbone_on_movielens.config']
-  for rel in fixtures:
-    est = EasyRecEstimator(os.path.join(REFERENCE, rel), device='cpu', batch_size=8, seed=1).build()
-    gen = SyntheticBatches(est.pipeline_config.data_config, est.feature_configs, batch_size=8, seed=3)
-    est.train_step(gen.next_batch())
-    lv = est.loss_values()
-    assert all(np.isfinite(v) for v in lv.values()), (rel, lv)

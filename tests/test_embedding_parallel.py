@@ -88,9 +88,14 @@ def _gloo_worker(rank, world, port, B, optimizer, out_dir, config=None):
   for b in batches:  # the SAME batch on every rank
     est.train_step(b)
   state = est.state_dict(slots=True)  # collective: gathers the shards
+  # ... and only chosen rows (unsorted, repeated, spread over both shards), in the order asked for
+  picks = {n: np.random.default_rng(5).integers(0, t['rows'], size=37) for n, t in est.engine.tables.items() if not t['kv']}
+  rows = est.state_dict(slots=True, rows_of=picks)
   losses = est.loss_values(average=True)
   if rank == 0:
     np.savez(os.path.join(out_dir, 'state.npz'), **{k.replace('/', '|'): v for k, v in state.items()})
+    np.savez(os.path.join(out_dir, 'rows.npz'), **{k.replace('/', '|'): v for k, v in rows.items()})
+    np.savez(os.path.join(out_dir, 'picks.npz'), **{k.replace('/', '|'): v for k, v in picks.items()})
     np.save(os.path.join(out_dir, 'loss.npy'), np.array([losses['total_loss']]))
   dist.barrier()
   dist.destroy_process_group()
@@ -109,6 +114,12 @@ def test_world2_gloo_same_batch_equals_single_process(ref_backend, tmp_path, opt
   ref_state, ref_losses = _run_single(cfg, batches, B, seed=3)
   got = {k.replace('|', '/'): v for k, v in np.load(os.path.join(str(tmp_path), 'state.npz')).items()}
   _compare(got, ref_state, 2e-5)
+  rows = {k.replace('|', '/'): v for k, v in np.load(os.path.join(str(tmp_path), 'rows.npz')).items()}
+  picks = {k.replace('|', '/'): v for k, v in np.load(os.path.join(str(tmp_path), 'picks.npz')).items()}
+  assert picks and sorted(rows) == sorted(got)
+  for k in got:
+    table = k.rsplit('/', 1)[0] if k.endswith(('/m', '/v')) else k
+    assert np.array_equal(rows[k], got[k][picks[table]] if table in picks else got[k]), k
   loss = float(np.load(os.path.join(str(tmp_path), 'loss.npy'))[0])
   assert abs(loss - ref_losses[-1]['total_loss']) <= 1e-5 * abs(ref_losses[-1]['total_loss'])
 

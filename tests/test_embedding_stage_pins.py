@@ -280,22 +280,3 @@ def test_stand_in_backend_and_oracle(check, built_lib):
 @pytest.mark.parametrize('check', CHECKS, ids=lambda f: f.__name__[7:])
 def test_hip_kernels(check):
   check('cuda:0')
-
-
-def test_fixture_is_what_the_generator_writes(tmp_path):
-  """Where /root/reference exists: re-run the generator and compare array by array."""
-  import subprocess
-  import sys
-  from conftest import REFERENCE, reference_available
-  if not reference_available():
-    pytest.skip('no /root/reference on this box')
-  gen = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'make_embedding_stage_vectors.py')
-  src = open(gen).read().replace("path = os.path.join(HERE, 'embedding_stage_vectors.npz')",
-                                 "path = %r" % str(tmp_path / 'v.npz'))
-  script = tmp_path / 'gen.py'
-  script.write_text(src)
-  subprocess.run([sys.executable, str(script), REFERENCE], check=True, capture_output=True, timeout=300)
-  fresh = np.load(str(tmp_path / 'v.npz'))
-  assert sorted(fresh.files) == sorted(V.files)
-  for k in V.files:
-    assert np.array_equal(fresh[k], V[k]), k
