@@ -1970,6 +1970,56 @@ class HipBackend(object):
                                  ctypes.c_float(scale), _p(dscores), _p(dhist), int(bool(acc_h)), _stream()), 'er_din_pool_bwd')
     return dscores, dhist
 
+  # -- K8b BST transformer block (model/multi_tower_bst.py)
+  BST_MAX_T = 64
+  BST_MAX_E = 64
+
+  def bst_param_count(self, E, H):
+    self.lib.er_bst_param_count.restype = ctypes.c_int64
+    return int(self.lib.er_bst_param_count(int(E), int(H)))
+
+  def bst_grid(self, B):
+    return int(self.lib.er_bst_grid(ctypes.c_int64(int(B))))
+
+  def _bst_flops(self, B, T, E, H):
+    # per example: Q / K / V (2 T sum p_h^2 each), S and P V (2 T^2 E each), the two E x E projections (2 T E^2 each)
+    p = -(-E // H)
+    nh = -(-E // p)
+    last = E - (nh - 1) * p
+    qkv = 3 * 2.0 * T * ((nh - 1) * p * p + last * last)
+    return B * (qkv + 4.0 * T * T * E + 4.0 * T * E * E)
+
+  def bst_fwd(self, key, hist, seq_len, theta, T, H):
+    """key [B, E], hist [B, L, E] (the lookup's static buffer), seq_len [B] int32, theta: the packed parameters
+    (er_bst_param_count).  Returns [B, T * E]."""
+    B, L, E = hist.shape
+    assert key.shape == (B, E) and seq_len.dtype == torch.int32
+    out = torch.empty(B, T * E, dtype=torch.float32, device=hist.device)
+    self._ck(self.lib.er_bst_fwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), ctypes.c_int64(B), L, T,
+                                 E, H, _p(out), _stream()), 'er_bst_fwd')
+    if self.op_log is not None:
+      self.op_log.append(('er::bst_fwd_kernel', self._bst_flops(B, T, E, H)))
+    return out
+
+  def bst_bwd(self, key, hist, seq_len, theta, dout, T, H, grads, dhist=None, acc_h=False):
+    """dkey [B, E] and dhist [B, L, E] (written, or added into with acc_h); the parameter gradients are ADDED into
+    `grads` (a BstGradTable: the variables' gradient buffers in theta's order)."""
+    B, L, E = hist.shape
+    dkey = torch.empty(B, E, dtype=torch.float32, device=hist.device)
+    if dhist is None:
+      assert not acc_h
+      dhist = torch.empty_like(hist)
+    assert dhist.shape == hist.shape and dhist.is_contiguous()
+    rows = self.bst_grid(B)
+    partials = torch.empty(rows * self.bst_param_count(E, H), dtype=torch.float32, device=hist.device)
+    self._ck(self.lib.er_bst_bwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), _p(_f32c(dout)),
+                                 ctypes.c_int64(B), L, T, E, H, _p(dkey), _p(dhist), int(bool(acc_h)), _p(partials),
+                                 _stream()), 'er_bst_bwd')
+    self._ck(self.lib.er_bst_grad_reduce(_p(partials), rows, E, H, grads.table, 1, _stream()), 'er_bst_grad_reduce')
+    if self.op_log is not None:
+      self.op_log.append(('er::bst_bwd_kernel', 2.0 * self._bst_flops(B, T, E, H)))
+    return dkey, dhist
+
   # -- K1b hash-table (KV) embedding tables
   def kv_create(self, var_rows, capacity, seed, init_mean, init_stddev, filter_freq=0, steps_to_live=0, step=None):
     """The map of one KV table whose arena is `var_rows` ([capacity, dim] view of the table group's storage).
@@ -3756,6 +3806,60 @@ class DINPoolFn(torch.autograd.Function):
     buf, acc, first = grad_slot(ctx.slots, hist)
     dscores, _ = hip().din_pool_bwd(probs, hist, seq_len, dout.contiguous(), ctx.scale, dhist=buf, acc_h=acc)
     return dscores, (buf if first else None), None, None
+
+
+class BstGradTable(object):
+  """The gradient-buffer addresses er_bst_grad_reduce writes through, in theta's order: a host array, passed in the
+  launch's kernel arguments (nothing to build on the device, so a first call inside a stream capture is fine)."""
+
+  def __init__(self, grads):
+    self.grads = list(grads)
+    self.table = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+
+  @classmethod
+  def of(cls, grads):
+    return cls(grads)
+
+
+class BSTBlockFn(torch.autograd.Function):
+  """reference model/multi_tower_bst.py:127-151: the sequence [hist rows (sliced / zero-padded to T - 1), key], the
+  multi-head self-attention, add & LayerNorm, the feed-forward dense, add & LayerNorm -> [B, T * E] (er_bst_*).
+  apply(key [B, E], hist [B, L, E] (the lookup's static buffer: rows t >= len are zero), seq_len, T, H, grads, *params)
+  with params in er_bst_param_count's order and grads their gradient buffers: the parameter gradients are ADDED into
+  those (zeroed once per step by VarStore.zero_grad; towers that share variables accumulate in launch order)."""
+
+  @staticmethod
+  def forward(ctx, key, hist, seq_len, T, H, grads, *params):
+    be = hip()
+    E = hist.shape[2]
+    theta = torch.empty(be.bst_param_count(E, H), dtype=torch.float32, device=hist.device)
+    pairs, o = [], 0
+    for prm in params:
+      n = prm.numel()
+      pairs.append((theta[o:o + n], prm.detach().reshape(-1)))
+      o += n
+    assert o == theta.numel(), 'BSTBlockFn: %d parameter floats, the kernel expects %d' % (o, theta.numel())
+    be.copy_multi(pairs)  # one launch
+    key = key.contiguous()
+    out = be.bst_fwd(key, hist, seq_len, theta, T, H)
+    ctx.save_for_backward(key, hist, seq_len, theta)
+    ctx.T, ctx.H = T, H
+    ctx.table = BstGradTable.of(grads) if grads is not None else None
+    ctx.slots = grad_slots_of_step() if hist.is_contiguous() else None
+    return out
+
+  @staticmethod
+  def backward(ctx, dout):
+    be = hip()
+    key, hist, seq_len, theta = ctx.saved_tensors
+    nparams = len(ctx.needs_input_grad) - 6
+    assert ctx.table is not None, 'BSTBlockFn: backward without the parameters\' gradient buffers'
+    if ctx.slots is None:
+      dkey, dhist = be.bst_bwd(key, hist.contiguous(), seq_len, theta, dout.contiguous(), ctx.T, ctx.H, ctx.table)
+      return (dkey, dhist, None, None, None, None) + (None,) * nparams
+    buf, acc, first = grad_slot(ctx.slots, hist)
+    dkey, _ = be.bst_bwd(key, hist, seq_len, theta, dout.contiguous(), ctx.T, ctx.H, ctx.table, dhist=buf, acc_h=acc)
+    return (dkey, (buf if first else None), None, None, None, None) + (None,) * nparams
 
 
 class MMoEMixManyFn(torch.autograd.Function):

@@ -85,7 +85,10 @@ class SeqInputLayer(object):
         all_own=all(kind == 'own' for kind, _ in key_plan), hist_width=sum(c.dimension for c in hists))
 
   def __call__(self, features, group_name, feature_name_to_output_tensors={}, allow_key_search=True,
-               scope_name=None, requires_grad=True):
+               scope_name=None, requires_grad=True, static_history=False):
+    """static_history: hand out the history as the lookup's static [B, max_seq_len, E] buffer instead of the batch-max
+    view (rows past a sequence's end are zero in both; a launch that reads the static buffer does not depend on the
+    batch's longest sequence: MultiTowerBST)."""
     import torch
     scope_name = scope_name or group_name
     given = feature_name_to_output_tensors or {}
@@ -115,7 +118,7 @@ class SeqInputLayer(object):
       key = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
     hist3 = hist.view(B, p['L'], p['hist_width'])
     Lm = features.seq_pad_len(p['len_name'])
-    if Lm < p['L']:
+    if Lm < p['L'] and not static_history:
       hist3 = hist3[:, :Lm]  # the batch's longest sequence: what the reference's padded tensor holds
     return {
         'key': key,

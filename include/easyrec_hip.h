@@ -619,6 +619,37 @@ int er_din_pool_bwd(const float* probs, const float* hist, const int32_t* seq_le
                     float* dscores, float* dhist, int acc_h, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8b BST transformer block.  Replaces the pad/slice + ConcatV2 of the sequence, the per-head
+ *     dense / MatMul / SequenceMask / Select / Softmax / MatMul, the output projection, both
+ *     add & LayerNorm and the feed-forward dense of MultiTowerBST.bst
+ *     model/multi_tower_bst.py:78-151 (LayerNorm: layers/layer_norm.py:28-37, epsilon 1e-6).
+ * X [T, E] per example: rows t < T-1 = hist[b, t, :] (zero for t >= L), row T-1 = key[b, :].
+ * Heads: width p = ceil(E / H), starts 0, p, 2p, ..; each head's Q/K/V is a dense p_h -> p_h on
+ * its own slice; S = Q K^T (no scaling); key columns t < T-1 with t >= min(len[b], T-1) masked
+ * (-2^32 + 1); O = concat_h softmax(S) V; Y1 = LN1(X + O Wo + bo); Y2 = LN2(Y1 + Y1 Wf + bf).
+ * `theta` holds the block's parameters packed in this order ([in, out] kernels, row-major):
+ *   Wq_0 .. Wq_{nh-1}, bq_0 .., Wk_h .., bk_h .., Wv_h .., bv_h .., Wo, bo, Wf, bf, g1, b1, g2, b2
+ * (er_bst_param_count gives its length).  hist: [B, L, E] (L = the lookup's static max_seq_len).
+ * er_bst_fwd: out [B, T * E] (row-major over t, the key row last).
+ * er_bst_bwd: recomputes the forward per example, then dkey [B, E] =, dhist [B, L, E] (+)= (rows
+ *   t >= min(T - 1, L) get nothing, or 0 without acc_h), and per-workgroup partial sums of the
+ *   packed parameter gradient into partials [grid, er_bst_param_count] (no atomics).
+ * er_bst_grad_reduce: sums partials over the grid rows in fixed order and adds (acc != 0) or
+ *   writes the result into the variables' gradient buffers: grads_host is a HOST array of
+ *   6 * nh + 8 pointers in theta's order (passed in the kernel arguments: capture-safe).
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_bst_param_count(int32_t E, int32_t H);
+int64_t er_bst_lds_bytes(int32_t T, int32_t E, int32_t H);  /* the backward's LDS per workgroup (the larger) */
+int32_t er_bst_grid(int64_t B);                              /* rows of `partials` for a batch of B */
+int er_bst_fwd(const float* key, const float* hist, const int32_t* seq_len, const float* theta, int64_t B,
+               int32_t L, int32_t T, int32_t E, int32_t H, float* out, er_stream_t stream);
+int er_bst_bwd(const float* key, const float* hist, const int32_t* seq_len, const float* theta, const float* dout,
+               int64_t B, int32_t L, int32_t T, int32_t E, int32_t H, float* dkey, float* dhist, int acc_h,
+               float* partials, er_stream_t stream);
+int er_bst_grad_reduce(const float* partials, int32_t rows, int32_t E, int32_t H, float* const* grads_host, int acc,
+                       er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K9  MLP layer pieces around the GEMM.  Replaces BiasAdd / FusedBatchNorm(train) / Relu of
  *     DNN.__call__ layers/dnn.py:57-79 (keras MLP layers/keras/blocks.py:84-110) and Dice
  *     layers/keras/activation.py:47-70.

@@ -254,6 +254,23 @@ def din_taobao(**kw):
   return cfg
 
 
+def bst_taobao(**kw):
+  """MultiTowerBST: din_taobao's shape with the DIN tower replaced by a BST tower over the same key / history pairs
+  (samples/model_config/bst_on_taobao.config: seq_len 50, 4 heads)."""
+  cfg = din_taobao(**kw)
+  cfg.model_dir = 'experiments/bst_taobao_ckpt'
+  mc = cfg.model_config
+  mc.model_class = 'MultiTowerBST'
+  mc.seq_att_groups[0].group_name = 'bst'
+  mt = mc.multi_tower
+  del mt.din_towers[:]
+  bt = mt.bst_towers.add()
+  bt.input = 'bst'
+  bt.seq_len = 50
+  bt.multi_head_size = 4
+  return cfg
+
+
 def mmoe_taobao(n_tasks=2, **kw):
   """MMoE, the shape of samples/model_config/mmoe_on_taobao.config (BASELINE config 5 uses 4 tasks)."""
   cfg = taobao_base('tag', **kw)
@@ -745,6 +762,7 @@ if __name__ == '__main__':
   write(din_taobao(item_rows=10000000), 'din_taobao_10m.config')
   write(din_taobao(batch_size=128, scale=0.01, seq_len=12), 'din_taobao_small.config')
   write(mmoe_taobao(), 'mmoe_taobao.config')
+  write(bst_taobao(item_rows=10000000), 'bst_taobao_10m.config')
   write(mmoe_taobao(n_tasks=4, embedding_dim=64, batch_size=8192), 'mmoe_taobao_4task_d64.config')
   # BASELINE config 5 at full size (200 M embedding rows of 64 floats: 51 GB + Adam slots, row-sharded over 8 GPUs) and
   # the share one GPU owns of it (25 M rows) for single-GPU runs
