@@ -2020,6 +2020,50 @@ class HipBackend(object):
       self.op_log.append(('er::bst_bwd_kernel', 2.0 * self._bst_flops(B, T, E, H)))
     return dkey, dhist
 
+  # -- K8c AutoInt self-attention core (layers/multihead_attention.py)
+  AUTOINT_LDS_BUDGET = 65536  # bytes per workgroup (csrc/er_autoint.hip)
+
+  def autoint_lds_bytes(self, F, H, ds):
+    self.lib.er_autoint_lds_bytes.restype = ctypes.c_int64
+    return int(self.lib.er_autoint_lds_bytes(int(F), int(H), int(ds)))
+
+  def autoint_epb(self, F, H, ds, bwd):
+    return int(self.lib.er_autoint_epb(int(F), int(H), int(ds), int(bool(bwd))))
+
+  def autoint_pack(self, wq, wk, wv, wr):
+    """[wq | wk | wv | wr] ([din, d] each) -> [din, 4d]: one launch."""
+    din, d = wq.shape
+    assert all(w.shape == (din, d) for w in (wk, wv, wr))
+    out = torch.empty(din, 4 * d, dtype=torch.float32, device=wq.device)
+    self._ck(self.lib.er_autoint_pack(_p(_f32c(wq)), _p(_f32c(wk)), _p(_f32c(wv)), _p(_f32c(wr)), din, d, _p(out),
+                                      _stream()), 'er_autoint_pack')
+    return out
+
+  def autoint_attn_fwd(self, qkvr, F, H, ds):
+    """qkvr [B * F, 4d] (Q | K | V | R per field row) -> y = relu(softmax(Q_h K_h^T sqrt(ds)) V_h + R) [B * F, d]."""
+    rows, w = qkvr.shape
+    d = H * ds
+    assert w == 4 * d and rows % F == 0
+    B = rows // F
+    y = torch.empty(rows, d, dtype=torch.float32, device=qkvr.device)
+    self._ck(self.lib.er_autoint_attn_fwd(_p(_f32c(qkvr)), ctypes.c_int64(B), F, H, ds, _p(y), _stream()),
+             'er_autoint_attn_fwd')
+    if self.op_log is not None:
+      self.op_log.append(('er::autoint_attn_fwd_kernel', 4.0 * B * F * F * d))
+    return y
+
+  def autoint_attn_bwd(self, qkvr, y, dy, F, H, ds):
+    """-> dqkvr [B * F, 4d] = dQ | dK | dV | dR (easyrec_hip.h K8c)."""
+    rows, w = qkvr.shape
+    B = rows // F
+    assert y.shape == dy.shape == (rows, H * ds)
+    dq = torch.empty_like(qkvr)
+    self._ck(self.lib.er_autoint_attn_bwd(_p(_f32c(qkvr)), _p(_f32c(y)), _p(_f32c(dy)), ctypes.c_int64(B), F, H, ds,
+                                          _p(dq), _stream()), 'er_autoint_attn_bwd')
+    if self.op_log is not None:
+      self.op_log.append(('er::autoint_attn_bwd_kernel', 12.0 * B * F * F * H * ds))
+    return dq
+
   # -- K1b hash-table (KV) embedding tables
   def kv_create(self, var_rows, capacity, seed, init_mean, init_stddev, filter_freq=0, steps_to_live=0, step=None):
     """The map of one KV table whose arena is `var_rows` ([capacity, dim] view of the table group's storage).
@@ -3860,6 +3904,60 @@ class BSTBlockFn(torch.autograd.Function):
     buf, acc, first = grad_slot(ctx.slots, hist)
     dkey, _ = be.bst_bwd(key, hist, seq_len, theta, dout.contiguous(), ctx.T, ctx.H, ctx.table, dhist=buf, acc_h=acc)
     return (dkey, (buf if first else None), None, None, None, None) + (None,) * nparams
+
+
+class AutoIntProjFn(torch.autograd.Function):
+  """The four bias-free projections of one MultiHeadAttention layer (reference layers/multihead_attention.py:71-95,
+  :145-151): x [rows, din] . [Wq | Wk | Wv | Wr] -> [rows, 4d], ONE contraction on an operand packed by one launch.
+  Backward: dx is one NT contraction against the packed operand; each weight gradient is x^T . its column slice of the
+  incoming gradient, ADDED into the variable's gradient buffer (`grads`, zeroed once per step by VarStore.zero_grad)
+  through the step's weight-gradient queue, or returned to autograd when no buffers are given."""
+
+  @staticmethod
+  def forward(ctx, x, grads, wq, wk, wv, wr):
+    be = hip()
+    x = x if x.is_contiguous() else x.contiguous()
+    w = be.autoint_pack(wq.detach(), wk.detach(), wv.detach(), wr.detach())
+    out = be.gemm(GEMM_NN, x, w)
+    ctx.save_for_backward(x, w)
+    ctx.grads = grads
+    ctx.sink = be.wgrad_sink()
+    return out
+
+  @staticmethod
+  def backward(ctx, dg):
+    be = hip()
+    x, w = ctx.saved_tensors
+    dg = dg if dg.is_contiguous() else dg.contiguous()
+    d = w.shape[1] // 4
+    dx = be.gemm(GEMM_NT, dg, w) if ctx.needs_input_grad[0] else None
+    dws = [None] * 4
+    for k in range(4):
+      # (given buffers always receive their gradient; the weights themselves may be detached views)
+      if ctx.grads is not None or ctx.needs_input_grad[2 + k]:
+        dws[k] = _wgrad(be, x, dg[:, k * d:(k + 1) * d], None if ctx.grads is None else ctx.grads[k], False, ctx.sink)
+    return (dx, None) + tuple(dws)
+
+
+class AutoIntAttnFn(torch.autograd.Function):
+  """reference layers/multihead_attention.py:50-161 (use_res) between the projections and the next layer:
+  apply(qkvr [B * F, 4d], F, H, ds) -> relu(concat_h softmax(Q_h K_h^T / ds ** -0.5) V_h + R) [B * F, d]
+  (er_autoint_attn_fwd / _bwd: the backward recomputes the attention from qkvr; only y is kept)."""
+
+  @staticmethod
+  def forward(ctx, qkvr, F, H, ds):
+    be = hip()
+    qkvr = qkvr if qkvr.is_contiguous() else qkvr.contiguous()
+    y = be.autoint_attn_fwd(qkvr, F, H, ds)
+    ctx.save_for_backward(qkvr, y)
+    ctx.shape = (F, H, ds)
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    qkvr, y = ctx.saved_tensors
+    F, H, ds = ctx.shape
+    return hip().autoint_attn_bwd(qkvr, y, dy.contiguous(), F, H, ds), None, None, None
 
 
 class MMoEMixManyFn(torch.autograd.Function):

@@ -650,6 +650,29 @@ int er_bst_grad_reduce(const float* partials, int32_t rows, int32_t E, int32_t H
                        er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8c AutoInt self-attention core.  Replaces the per-head Reshape / Transpose / BatchMatMul(transpose_b) /
+ *     RealDiv / Softmax / BatchMatMul, the head combine, the residual Add and Relu of
+ *     MultiHeadAttention._multi_head_attention (use_res) layers/multihead_attention.py:50-161, as
+ *     AutoInt.build_predict_graph model/autoint.py:54-75 stacks it.
+ * qkvr [B * F, 4d] (d = H * ds): per field row Q | K | V | R, the four projections of one contraction.
+ * Per example and head h (columns h * ds .. of Q, K, V): S = Q_h K_h^T * sqrt(ds) (the reference divides
+ * by ds ** -0.5), P = softmax over all F fields (no mask), O_h = P V_h; y = relu(O + R) [B * F, d].
+ * er_autoint_attn_bwd: recomputes P from qkvr; dA = dy * [y > 0]; writes dqkvr [B * F, 4d] =
+ *   dQ_h = sqrt(ds) dS K_h | dK_h = sqrt(ds) dS^T Q_h | dV_h = P^T dA_h | dR = dA,
+ *   dS = P o (dP - rowsum(dP o P)), dP = dA_h V_h^T.  No atomics; fixed summation order.
+ * Envelope: er_autoint_lds_bytes(F, H, ds) = 4 * (F * odd(3d) + F * odd(d) + 2 * H * F^2) <= 65536
+ *   (odd(n) = n | 1); er_autoint_epb gives the examples per workgroup (0 outside the envelope).
+ * er_autoint_pack: w [din, 4d] = [wq | wk | wv | wr] ([din, d] row-major each): the contraction's operand.
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_autoint_lds_bytes(int32_t F, int32_t H, int32_t ds);
+int32_t er_autoint_epb(int32_t F, int32_t H, int32_t ds, int bwd);
+int er_autoint_attn_fwd(const float* qkvr, int64_t B, int32_t F, int32_t H, int32_t ds, float* y, er_stream_t stream);
+int er_autoint_attn_bwd(const float* qkvr, const float* y, const float* dy, int64_t B, int32_t F, int32_t H, int32_t ds,
+                        float* dqkvr, er_stream_t stream);
+int er_autoint_pack(const float* wq, const float* wk, const float* wv, const float* wr, int32_t din, int32_t d,
+                    float* w, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K9  MLP layer pieces around the GEMM.  Replaces BiasAdd / FusedBatchNorm(train) / Relu of
  *     DNN.__call__ layers/dnn.py:57-79 (keras MLP layers/keras/blocks.py:84-110) and Dice
  *     layers/keras/activation.py:47-70.

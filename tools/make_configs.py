@@ -271,6 +271,40 @@ def bst_taobao(**kw):
   return cfg
 
 
+TAOBAO_AUTOINT = ['user_id', 'cms_segid', 'cms_group_id', 'final_gender_code', 'age_level', 'pvalue_level',
+                  'shopping_level', 'occupation', 'new_user_class_level', 'adgroup_id', 'cate_id', 'campaign_id',
+                  'customer', 'brand', 'price', 'pid']
+
+
+def autoint_taobao(sequence=False, **kw):
+  """AutoInt, the model section of samples/model_config/autoint_on_taobao.config (18 fields of D = 16, 2 heads x 32,
+  3 interacting layers, l2 1e-6).  sequence: autoint_on_sequence_feature_taobao.config's group instead - the 16 plain
+  fields and a target attention over (brand, cate_id) / (tag_brand_list, tag_category_list): 20 fields."""
+  cfg = taobao_base('seq' if sequence else 'tag', **kw)
+  cfg.model_dir = 'experiments/autoint_taobao_ckpt'
+  cfg.data_config.label_fields.append('clk')
+  mc = cfg.model_config
+  mc.model_class = 'AutoInt'
+  g = mc.feature_groups.add()
+  g.group_name = 'all'
+  g.feature_names.extend(TAOBAO_AUTOINT)
+  g.wide_deep = WideOrDeep.DEEP
+  if sequence:
+    sf = g.sequence_features.add()
+    sf.group_name = 'seq_fea'
+    sf.tf_summary = False
+    m = sf.seq_att_map.add()
+    m.key.extend(['brand', 'cate_id'])
+    m.hist_seq.extend(['tag_brand_list', 'tag_category_list'])
+  else:
+    g.feature_names.extend(['tag_category_list', 'tag_brand_list'])
+  ai = mc.autoint
+  ai.multi_head_num, ai.multi_head_size, ai.interacting_layer_num = 2, 32, 3
+  ai.l2_regularization = 1e-6
+  mc.embedding_regularization = 1e-6
+  return cfg
+
+
 def mmoe_taobao(n_tasks=2, **kw):
   """MMoE, the shape of samples/model_config/mmoe_on_taobao.config (BASELINE config 5 uses 4 tasks)."""
   cfg = taobao_base('tag', **kw)
@@ -763,6 +797,7 @@ if __name__ == '__main__':
   write(din_taobao(batch_size=128, scale=0.01, seq_len=12), 'din_taobao_small.config')
   write(mmoe_taobao(), 'mmoe_taobao.config')
   write(bst_taobao(item_rows=10000000), 'bst_taobao_10m.config')
+  write(autoint_taobao(item_rows=10000000), 'autoint_taobao_10m.config')
   write(mmoe_taobao(n_tasks=4, embedding_dim=64, batch_size=8192), 'mmoe_taobao_4task_d64.config')
   # BASELINE config 5 at full size (200 M embedding rows of 64 floats: 51 GB + Adam slots, row-sharded over 8 GPUs) and
   # the share one GPU owns of it (25 M rows) for single-GPU runs
