@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: DeepFM training step on synthetic Criteo-shape input.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line.  --full adds,
+after the timed steps, everything measured or checked beside the headline: GPU clocks, the embedding stage's bytes,
+the per-kernel roofline, the steady state over distinct batches, the full-size parity check against the CPU oracle,
+the CPU baseline and (when asked for) the from-file rate.
 
 A "step" = one pass of the hot path over one batch already resident in HBM: device-side id hashing
 -> fused embedding lookup (78 lookups, one launch) -> wide sum / FM / MLP(+BatchNorm) -> sigmoid CE
@@ -40,11 +45,14 @@ def parse_args():
   ap.add_argument('--no_graph', action='store_true', help='eager launches instead of hipGraph replay')
   ap.add_argument('--dense_dtype', default='f32', choices=['f32', 'bf16'],
                   help="bf16: BASELINE config 3 (bf16 dense contractions with fp32 accumulate, fp32 embeddings and master weights)")
-  ap.add_argument('--no_cpu_baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='after the timed steps, also measure and check what the headline does not need (see the module '
+                       'docstring); the options whose help starts with --full act only with it')
+  ap.add_argument('--no_cpu_baseline', action='store_true', help='--full: skip the CPU baseline')
   ap.add_argument('--dense_sweep', action='store_true', help='TF-exact Adam by streaming every row every step (default: lazy dense decay, bit-identical)')
   ap.add_argument('--force_ep', action='store_true', help='run the embedding-parallel code path even at 1 GPU')
   ap.add_argument('--overlap', action='store_true', help='TF-exact Adam: dense-decay sweep on a second stream (measured slower)')
-  ap.add_argument('--cpu_seconds', type=float, default=12.0, help='time budget of the CPU baseline sample')
+  ap.add_argument('--cpu_seconds', type=float, default=12.0, help='--full: time budget of the CPU baseline sample')
   ap.add_argument('--rccl', action='store_true',
                   help='with --force_ep at 1 GPU: issue the collectives through a world-1 RCCL process group (not local copies)')
   ap.add_argument('--ring', type=int, default=256, help='distinct device-generated batches the timed loop cycles over')
@@ -53,17 +61,17 @@ def parse_args():
                        'see tables in their steady state (rows with Adam history and realistic idle lengths) instead of '
                        'freshly initialised ones, whose lazy dense decay is trivially cheap; 0 = skip')
   ap.add_argument('--steady_steps', type=int, default=2048,
-                  help='N=1: after the timed region, this many further steps over as many DISTINCT device-generated '
+                  help='--full, N=1: after the timed region, this many further steps over as many DISTINCT device-generated '
                        'batches (realistic idle lengths for the lazy dense decay); 0 = skip')
   ap.add_argument('--from_file', default='', choices=['', 'csv', 'criteo'],
-                  help='N=1, Criteo-shaped configs: after the device-resident measurement, train from FILES written to a temp '
+                  help='--full, N=1, Criteo-shaped configs: after the device-resident measurement, train from FILES written to a temp '
                        'directory - Input -> pack (prefetch thread) -> train_step - and report the end-to-end examples/s as an '
                        'extra key (never the headline value)')
   ap.add_argument('--parity_only', action='store_true',
-                  help='with --no_cpu_baseline: still run the full-size GPU-vs-oracle parity check (the 200 M-row config: the '
+                  help='--full with --no_cpu_baseline: still run the full-size GPU-vs-oracle parity check (the 200 M-row config: the '
                        'oracle then holds only the rows the parity batches read - no CPU timing is possible on that state)')
   ap.add_argument('--parity_steps', type=int, default=2,
-                  help='N=1: steps of the full-size GPU-vs-oracle loss comparison (0 = skip; needs the CPU baseline)')
+                  help='--full, N=1: steps of the full-size GPU-vs-oracle loss comparison (0 = skip; needs the CPU baseline)')
   ap.add_argument('--dump-outputs', dest='dump_outputs', default='', metavar='DIR',
                   help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / '
                        'float64, at most 64 MB): its losses, the dense variables and their optimizer slots, and a fixed, '
@@ -72,6 +80,8 @@ def parse_args():
   args = ap.parse_args()
   if args.steps < 1:
     ap.error('--steps must be at least 1')
+  if not args.full and (args.from_file or args.parity_only):
+    ap.error('--from_file and --parity_only run only with --full')
   return args
 
 
@@ -935,10 +945,14 @@ def main():
       },
       'final_loss': losses.get('total_loss'),
       'device': kernels.hip().device_info(),
-      'clocks': gpu_clocks(),
   }
+  if args.full:
+    out['clocks'] = gpu_clocks()
   if dumped is not None:
     out['dump_outputs'] = dumped
+  if not args.full:
+    print(json.dumps(out))
+    return
   if world == 1 and not ep:
     lazy_bytes, sweep_bytes, per_kernel_bytes = embedding_bytes_per_step(est, host_ring) if criteo else (0.0, 0.0, {})
     if criteo:  # (the byte accounting of SURVEY.md 8d is written for the Criteo schema)

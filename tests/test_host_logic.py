@@ -447,6 +447,26 @@ def test_bench_helpers_describe_every_baseline_config(ref_backend):
   assert 'examples/sec' in bench.baseline_metric()
 
 
+def test_bench_measures_beside_the_headline_only_with_full(monkeypatch):
+  """A plain bench run times the steps and prints the headline; what it measures or checks beside that runs with --full,
+  and the options that only ask for such extras are refused without it."""
+  import importlib.util
+  import sys
+  ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  spec = importlib.util.spec_from_file_location('bench_module', os.path.join(ROOT, 'bench.py'))
+  bench = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(bench)
+  monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '5', '--warmup', '2'])
+  assert not bench.parse_args().full
+  monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--from_file', 'csv'])
+  args = bench.parse_args()
+  assert args.full and args.from_file == 'csv'
+  for extra in (['--from_file', 'csv'], ['--no_cpu_baseline', '--parity_only']):
+    monkeypatch.setattr(sys, 'argv', ['bench.py'] + extra)
+    with pytest.raises(SystemExit):
+      bench.parse_args()
+
+
 def test_fm_over_fields_of_unequal_widths_is_rejected(ref_backend):
   """layers/fm.py:20 stacks the fields (tf.stack): fields of different embedding_dim fail when the reference builds the
   graph (the shape of examples/configs/fm_on_criteo.config: embedding_dim 10 beside 16).  The product raises too instead
