@@ -9,6 +9,7 @@ library has not been built or no MI355X is visible - there is no CPU fallback in
 import ctypes
 import threading
 import os
+import re
 from dataclasses import dataclass
 from typing import Optional
 
@@ -40,6 +41,49 @@ class CastDesc(ctypes.Structure):
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EASYREC_AMD_LIB: another build of the same ABI (same-box A/B of a kernel change, tools/gpu_ab.sh)
 LIB_PATH = os.environ.get('EASYREC_AMD_LIB') or os.path.join(_HERE, 'csrc', 'libeasyrec_hip.so')
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'easyrec_hip.h')
+
+# C scalar types of the header -> ctypes; every pointer (and er_stream_t) is c_void_p, which also takes an int address,
+# None, bytes, a ctypes array and byref()
+_C_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint32_t': ctypes.c_uint32,
+              'uint64_t': ctypes.c_uint64, 'uint8_t': ctypes.c_uint8, 'float': ctypes.c_float, 'double': ctypes.c_double,
+              'er_stream_t': ctypes.c_void_p}
+
+
+def _ctype(decl, what, ret=False):
+  decl = ' '.join(decl.replace('*', ' * ').split())
+  if '*' in decl:
+    return ctypes.c_char_p if ret and decl == 'const char *' else ctypes.c_void_p
+  if decl not in _C_SCALARS:
+    raise RuntimeError('easyrec_amd: %s: no ctypes type for %r (%s)' % (what, decl, HEADER_PATH))
+  return _C_SCALARS[decl]
+
+
+def load_library(path=LIB_PATH):
+  """Open libeasyrec_hip.so and bind it (bind_library)."""
+  if not os.path.exists(path):
+    raise RuntimeError(
+        'easyrec_amd: %s not found. Build it with `python -c "import __graft_entry__ as g; '
+        'g.build()"` or `make -C easyrec_amd/csrc`; there is no CPU fallback.' % path)
+  return bind_library(ctypes.CDLL(path))
+
+
+def bind_library(lib):
+  """Give every function include/easyrec_hip.h declares argtypes / restype on `lib` (a ctypes.CDLL of
+  libeasyrec_hip.so), so that ctypes converts (and type-checks) each argument as the header says: plain Python ints /
+  floats / bools for scalars, an address, None, bytes, a ctypes array or byref() for pointers.  Returns lib."""
+  with open(HEADER_PATH) as f:
+    text = re.sub(r'/\*.*?\*/', ' ', f.read(), flags=re.S)
+  text = re.sub(r'^\s*#.*$', '', text, flags=re.M)  # (preprocessor lines)
+  for ret, name, params in re.findall(r'([\w\s*]+?)\b(er_\w+)\s*\(([^()]*)\)\s*;', text):
+    params = ' '.join(params.split())
+    decls = [] if params in ('', 'void') else [re.sub(r'\w+$', '', p) for p in params.split(',')]
+    if not hasattr(lib, name):
+      raise RuntimeError('easyrec_amd: %s declares %s, %s does not export it' % (HEADER_PATH, name, lib._name))
+    fn = getattr(lib, name)
+    fn.restype = _ctype(ret, name + ' return type', ret=True)
+    fn.argtypes = [_ctype(d, '%s argument %d' % (name, i + 1)) for i, d in enumerate(decls)]
+  return lib
 
 COMBINER_SUM, COMBINER_MEAN, COMBINER_SQRTN = 0, 1, 2
 COMBINERS = {'sum': COMBINER_SUM, 'mean': COMBINER_MEAN, 'sqrtn': COMBINER_SQRTN}
@@ -277,10 +321,6 @@ def bn_source_of(x):
   return src
 
 
-def _ptr(t):
-  return None if t is None else t.data_ptr()
-
-
 class GemmProblem(ctypes.Structure):  # = er_gemm_problem
   _fields_ = [('M', ctypes.c_int32), ('N', ctypes.c_int32), ('K', ctypes.c_int32), ('A', ctypes.c_void_p),
               ('lda', ctypes.c_int32), ('B', ctypes.c_void_p), ('ldb', ctypes.c_int32), ('C', ctypes.c_void_p),
@@ -368,13 +408,9 @@ def same_lookup_keys(group, leader):
   for k in ('world', 'shard_stride', 'local_base'):
     if group.get(k) != leader.get(k):
       return False
-
-  def ptr(t):
-    return None if t is None else t.data_ptr()
-
   for x, y in zip(a, b):
-    if (ptr(x.ids), ptr(x.offsets), x.rows, x.key_base, x.n_rows, x.max_nnz) != \
-        (ptr(y.ids), ptr(y.offsets), y.rows, y.key_base, y.n_rows, y.max_nnz):
+    if (_p(x.ids), _p(x.offsets), x.rows, x.key_base, x.n_rows, x.max_nnz) != \
+        (_p(y.ids), _p(y.offsets), y.rows, y.key_base, y.n_rows, y.max_nnz):
       return False
   return True
 
@@ -410,13 +446,15 @@ class LookupSpec:
 
 
 def _p(t):
-  if t is None:
-    return ctypes.c_void_p(0)
-  return ctypes.c_void_p(t.data_ptr())
+  return None if t is None else t.data_ptr()
+
+
+def _np(a):
+  return a.ctypes.data
 
 
 def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+  return torch.cuda.current_stream().cuda_stream
 
 
 def _f32c(t, name='tensor'):
@@ -523,15 +561,19 @@ class HipBackend(object):
   name = 'hip'
 
   def __init__(self):
-    if not os.path.exists(LIB_PATH):
-      raise RuntimeError(
-          'easyrec_amd: %s not found. Build it with `python -c "import __graft_entry__ as g; '
-          'g.build()"` or `make -C easyrec_amd/csrc`; there is no CPU fallback.' % LIB_PATH)
-    self.lib = ctypes.CDLL(LIB_PATH)
-    self.lib.er_last_error.restype = ctypes.c_char_p
-    self.lib.er_emb_group_num_entries.restype = ctypes.c_int64
+    self._lib = load_library(LIB_PATH)
     if self.lib.er_abi_version() != 1:
       raise RuntimeError('easyrec_amd: ABI version mismatch in %s' % LIB_PATH)
+
+  @property
+  def lib(self):
+    return self._lib
+
+  @lib.setter
+  def lib(self, lib):
+    # a library opened elsewhere (a host-only backend made without __init__) is bound here: every wrapper passes plain
+    # Python values, which an unbound CDLL would truncate to C ints
+    self._lib = bind_library(lib)
 
   # -- measurement hook (bench.py): with `op_log` a list, every contraction appends (kernel name as rocprof prints it,
   # flops): one eager step gives the algorithmic work behind each GEMM kernel of the step's profile
@@ -556,10 +598,10 @@ class HipBackend(object):
                          '(there is no CPU fallback).')
 
   def reserve_scratch(self, floats):
-    self._ck(self.lib.er_reserve_scratch(ctypes.c_int64(int(floats))), 'er_reserve_scratch')
+    self._ck(self.lib.er_reserve_scratch(int(floats)), 'er_reserve_scratch')
 
   def config_set(self, key, value):
-    self._ck(self.lib.er_config_set(key.encode(), ctypes.c_int64(int(value))), 'er_config_set')
+    self._ck(self.lib.er_config_set(key.encode(), int(value)), 'er_config_set')
 
   def device_info(self):
     cu, wave = ctypes.c_int(0), ctypes.c_int(0)
@@ -571,29 +613,24 @@ class HipBackend(object):
   def save_dense_embed(self, ckpt_path, var_name, task_index, task_num, vals_np):
     vals_np = np.ascontiguousarray(vals_np, dtype=np.float32)
     rows, dim = vals_np.shape
-    self._ck(self.lib.er_save_dense_embed(ckpt_path.encode(), var_name.encode(), ctypes.c_int32(task_index),
-                                          ctypes.c_int32(task_num), vals_np.ctypes.data_as(ctypes.c_void_p),
-                                          ctypes.c_int64(rows), ctypes.c_int32(dim)), 'er_save_dense_embed')
+    self._ck(self.lib.er_save_dense_embed(ckpt_path.encode(), var_name.encode(), task_index, task_num,
+                                          _np(vals_np), rows, dim), 'er_save_dense_embed')
 
   def load_dense_embed(self, ckpt_path, var_name, task_index, task_num, embed_dim, embed_part_size):
     out = np.empty((embed_part_size, embed_dim), dtype=np.float32)
     n = ctypes.c_int64(0)
-    self._ck(self.lib.er_load_dense_embed(ckpt_path.encode(), var_name.encode(), ctypes.c_int32(task_index),
-                                          ctypes.c_int32(task_num), ctypes.c_int32(embed_dim),
-                                          ctypes.c_int64(embed_part_size), out.ctypes.data_as(ctypes.c_void_p),
-                                          ctypes.byref(n)), 'er_load_dense_embed')
+    self._ck(self.lib.er_load_dense_embed(ckpt_path.encode(), var_name.encode(), task_index, task_num, embed_dim,
+                                          embed_part_size, _np(out), ctypes.byref(n)), 'er_load_dense_embed')
     return out
 
   def load_kv_embed(self, ckpt_path, var_name, task_index, task_num, embed_dim):
     n = ctypes.c_int64(0)
-    args = (ckpt_path.encode(), var_name.encode(), ctypes.c_int32(task_index), ctypes.c_int32(task_num),
-            ctypes.c_int32(embed_dim))
-    self._ck(self.lib.er_load_kv_embed(*args, ctypes.c_int64(0), None, None, ctypes.byref(n)), 'er_load_kv_embed')
+    args = (ckpt_path.encode(), var_name.encode(), task_index, task_num, embed_dim)
+    self._ck(self.lib.er_load_kv_embed(*args, 0, None, None, ctypes.byref(n)), 'er_load_kv_embed')
     keys = np.empty(n.value, dtype=np.int64)
     vals = np.empty((n.value, embed_dim), dtype=np.float32)
     if n.value:
-      self._ck(self.lib.er_load_kv_embed(*args, ctypes.c_int64(n.value), keys.ctypes.data_as(ctypes.c_void_p),
-                                         vals.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n)), 'er_load_kv_embed')
+      self._ck(self.lib.er_load_kv_embed(*args, n.value, _np(keys), _np(vals), ctypes.byref(n)), 'er_load_kv_embed')
     return keys, vals
 
   # -- K1 hashing
@@ -626,19 +663,16 @@ class HipBackend(object):
 
     if text.size == 0:
       return 0, 0, ints, flts, empty, begin, length
-
-    def ptr(a):
-      return a.ctypes.data_as(ctypes.c_void_p)
     if int(threads) == 1:
-      self._ck(self.lib.er_decode_csv_host(ptr(text), ctypes.c_int64(text.size), ctypes.c_uint8(sep_b[0]), ctypes.c_int32(F),
-                                           ptr(kinds), ctypes.c_int64(int(max_rows)), ptr(ints), ptr(flts), ptr(empty),
-                                           ptr(begin), ptr(length), ctypes.byref(n_rows), ctypes.byref(consumed)),
+      self._ck(self.lib.er_decode_csv_host(_np(text), text.size, sep_b[0], F,
+                                           _np(kinds), int(max_rows), _np(ints), _np(flts), _np(empty),
+                                           _np(begin), _np(length), ctypes.byref(n_rows), ctypes.byref(consumed)),
                'er_decode_csv_host')
     else:
-      self._ck(self.lib.er_decode_csv_host_mt(ptr(text), ctypes.c_int64(text.size), ctypes.c_uint8(sep_b[0]), ctypes.c_int32(F),
-                                              ptr(kinds), ctypes.c_int64(int(max_rows)), ctypes.c_int64(int(pitch)), ptr(ints),
-                                              ptr(flts), ptr(empty), ptr(begin), ptr(length), ctypes.byref(n_rows),
-                                              ctypes.byref(consumed), ctypes.c_int32(int(threads))), 'er_decode_csv_host_mt')
+      self._ck(self.lib.er_decode_csv_host_mt(_np(text), text.size, sep_b[0], F,
+                                              _np(kinds), int(max_rows), int(pitch), _np(ints),
+                                              _np(flts), _np(empty), _np(begin), _np(length), ctypes.byref(n_rows),
+                                              ctypes.byref(consumed), int(threads)), 'er_decode_csv_host_mt')
     return n_rows.value, consumed.value, ints, flts, empty, begin, length
 
   def pack_cells_host(self, text, begin, length):
@@ -649,11 +683,8 @@ class HipBackend(object):
     n = len(begin)
     out = np.empty(max(int(length.sum(dtype=np.int64)), 1), dtype=np.uint8)
     offsets = np.empty(n + 1, dtype=np.int64)
-
-    def ptr(a):
-      return a.ctypes.data_as(ctypes.c_void_p)
-    self._ck(self.lib.er_pack_cells_host(ptr(text) if text.size else ptr(out), ptr(begin), ptr(length), ctypes.c_int64(n),
-                                         ptr(out), ptr(offsets)), 'er_pack_cells_host')
+    self._ck(self.lib.er_pack_cells_host(_np(text if text.size else out), _np(begin), _np(length), n,
+                                         _np(out), _np(offsets)), 'er_pack_cells_host')
     return out[:int(offsets[-1])], offsets
 
   def split_cells_host(self, text, begin, length, seps, keep_empty=False, max_tokens=0):
@@ -667,12 +698,8 @@ class HipBackend(object):
     tb, tl = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int32)
     offs = np.empty(n + 1, dtype=np.int64)
     sb = np.frombuffer(seps if isinstance(seps, bytes) else seps.encode('utf-8'), dtype=np.uint8)
-
-    def ptr(a):
-      return a.ctypes.data_as(ctypes.c_void_p)
-    self._ck(self.lib.er_split_cells_host(ptr(text) if text.size else ptr(tb), ptr(begin), ptr(length), ctypes.c_int64(n), ptr(sb),
-                                          ctypes.c_int32(len(sb)), ctypes.c_int32(int(bool(keep_empty))),
-                                          ctypes.c_int32(int(max_tokens)), ptr(tb), ptr(tl), ctypes.c_int64(cap), ptr(offs)),
+    self._ck(self.lib.er_split_cells_host(_np(text if text.size else tb), _np(begin), _np(length), n, _np(sb),
+                                          len(sb), keep_empty, int(max_tokens), _np(tb), _np(tl), cap, _np(offs)),
              'er_split_cells_host')
     T = int(offs[-1])
     return tb[:T], tl[:T], offs
@@ -683,10 +710,7 @@ class HipBackend(object):
     n = values.size
     out = np.empty(max(20 * n, 1), dtype=np.uint8)
     offsets = np.empty(n + 1, dtype=np.int64)
-
-    def ptr(a):
-      return a.ctypes.data_as(ctypes.c_void_p)
-    self._ck(self.lib.er_pack_int_decimal_host(ptr(values), ctypes.c_int64(n), ptr(out), ptr(offsets)), 'er_pack_int_decimal_host')
+    self._ck(self.lib.er_pack_int_decimal_host(_np(values), n, _np(out), _np(offsets)), 'er_pack_int_decimal_host')
     return out[:int(offsets[-1])], offsets
 
   def sparse_cross_hashed_host(self, bytes_np, offsets_np, n_rows, n_cols, num_buckets, hash_key=None):
@@ -698,11 +722,8 @@ class HipBackend(object):
     if bytes_np.size == 0:
       bytes_np = np.zeros(1, dtype=np.uint8)
     key = CROSS_HASH_KEY if hash_key is None else int(hash_key)
-    self._ck(
-        self.lib.er_sparse_cross_hashed_host(
-            bytes_np.ctypes.data_as(ctypes.c_void_p), offsets_np.ctypes.data_as(ctypes.c_void_p),
-            ctypes.c_int64(int(n_rows)), ctypes.c_int32(int(n_cols)), ctypes.c_uint64(int(num_buckets)),
-            ctypes.c_uint64(key), out.ctypes.data_as(ctypes.c_void_p)), 'er_sparse_cross_hashed_host')
+    self._ck(self.lib.er_sparse_cross_hashed_host(_np(bytes_np), _np(offsets_np), int(n_rows), int(n_cols), int(num_buckets),
+                                                  key, _np(out)), 'er_sparse_cross_hashed_host')
     return out
 
   def hash_bucket_fast_host(self, bytes_np, offsets_np, n_per_col, num_buckets, drop_empty):
@@ -714,11 +735,8 @@ class HipBackend(object):
     out = np.empty(n, dtype=np.int64)
     if bytes_np.size == 0:
       bytes_np = np.zeros(1, dtype=np.uint8)
-    self._ck(
-        self.lib.er_hash_bucket_fast_host(
-            bytes_np.ctypes.data_as(ctypes.c_void_p), offsets_np.ctypes.data_as(ctypes.c_void_p),
-            ctypes.c_int64(n), ctypes.c_int64(int(n_per_col)), nb.ctypes.data_as(ctypes.c_void_p),
-            ctypes.c_int(int(drop_empty)), out.ctypes.data_as(ctypes.c_void_p)), 'er_hash_bucket_fast_host')
+    self._ck(self.lib.er_hash_bucket_fast_host(_np(bytes_np), _np(offsets_np), n, int(n_per_col), _np(nb), int(drop_empty),
+                                               _np(out)), 'er_hash_bucket_fast_host')
     return out
 
   def hash_bucket_fast(self, bytes_t, offsets_t, n_per_col, num_buckets_t, drop_empty, out=None):
@@ -726,9 +744,8 @@ class HipBackend(object):
     if out is None:
       out = torch.empty(n, dtype=torch.int64, device=bytes_t.device)
     self._ck(
-        self.lib.er_hash_bucket_fast(_p(bytes_t), _p(offsets_t), ctypes.c_int64(n),
-                                     ctypes.c_int64(int(n_per_col)), _p(num_buckets_t),
-                                     ctypes.c_int(int(drop_empty)), _p(out), _stream()), 'er_hash_bucket_fast')
+        self.lib.er_hash_bucket_fast(_p(bytes_t), _p(offsets_t), n, int(n_per_col), _p(num_buckets_t), int(drop_empty),
+                                     _p(out), _stream()), 'er_hash_bucket_fast')
     return out
 
   def hash_bucket_fast_int64(self, values_t, n_per_col, num_buckets_t, out=None):
@@ -736,7 +753,7 @@ class HipBackend(object):
     if out is None:
       out = torch.empty(n, dtype=torch.int64, device=values_t.device)
     self._ck(
-        self.lib.er_hash_bucket_fast_int64(_p(values_t), ctypes.c_int64(n), ctypes.c_int64(int(n_per_col)),
+        self.lib.er_hash_bucket_fast_int64(_p(values_t), n, int(n_per_col),
                                            _p(num_buckets_t), _p(out), _stream()), 'er_hash_bucket_fast_int64')
     return out
 
@@ -777,8 +794,7 @@ class HipBackend(object):
   def emb_group_create(self, specs, dim, total_rows, var, m, v, bitmap):
     grp = ctypes.c_void_p(0)
     self._ck(
-        self.lib.er_emb_group_create(self._descs(specs), len(specs), ctypes.c_int32(dim),
-                                     ctypes.c_int64(total_rows), _p(var), _p(m), _p(v), _p(bitmap),
+        self.lib.er_emb_group_create(self._descs(specs), len(specs), dim, total_rows, _p(var), _p(m), _p(v), _p(bitmap),
                                      ctypes.byref(grp)), 'er_emb_group_create')
     n_ent = self.lib.er_emb_group_num_entries(grp)
     group = {'handle': grp, 'specs': list(specs), 'dim': dim, 'total_rows': total_rows, 'var': var,
@@ -796,14 +812,14 @@ class HipBackend(object):
     assert var.dim() != 2 or var.stride(1) == 1
     ls_ld = 1 if ls is None else (ls.stride(0) if ls.numel() > 1 else 1)
     if ld != group['dim'] or ls_ld != 1:
-      self._ck(self.lib.er_emb_group_set_row_pitch(group['handle'], ctypes.c_int64(ld), ctypes.c_int64(ls_ld)),
+      self._ck(self.lib.er_emb_group_set_row_pitch(group['handle'], ld, ls_ld),
                'er_emb_group_set_row_pitch')
 
   def emb_group_destroy(self, group):
     self.lib.er_emb_group_destroy(group['handle'])
 
   def emb_bwd_update(self, group, opt_kind, hyper):
-    self._ck(self.lib.er_emb_bwd_update(group['handle'], ctypes.c_int(opt_kind), _p(hyper), _stream()),
+    self._ck(self.lib.er_emb_bwd_update(group['handle'], opt_kind, _p(hyper), _stream()),
              'er_emb_bwd_update')
 
   def emb_bwd_reduce(self, group, out=None):
@@ -822,10 +838,10 @@ class HipBackend(object):
 
   # -- K13 GEMM on the matrix cores
   def gemm_reserve(self, floats):
-    self._ck(self.lib.er_gemm_reserve(ctypes.c_int64(int(floats))), 'er_gemm_reserve')
+    self._ck(self.lib.er_gemm_reserve(int(floats)), 'er_gemm_reserve')
 
   def gemm_row_tiles(self, M):
-    return int(self.lib.er_gemm_row_tiles(ctypes.c_int32(int(M))))
+    return int(self.lib.er_gemm_row_tiles(int(M)))
 
   def bn_apply_from_stats(self, x, bias, col_stats, chunks, gamma, beta, eps, momentum, moving_mean, moving_var, act,
                           bf16_state=None):
@@ -837,10 +853,9 @@ class HipBackend(object):
     invstd = torch.empty(N, dtype=torch.float32, device=x.device)
     yb = bf16_state.new_copy(y) if bf16_state is not None else None
     self._ck(
-        self.lib.er_bn_apply_from_stats_b16(_p(_f32c(x)), _p(bias), _p(col_stats), ctypes.c_int32(int(chunks)), _p(gamma),
-                                            _p(beta), B, N, ctypes.c_float(eps), ctypes.c_float(momentum),
-                                            _p(moving_mean), _p(moving_var), int(act), _p(y), _p(mean), _p(invstd),
-                                            _p(yb), ctypes.c_int32(0 if yb is None else yb.stride(0)),
+        self.lib.er_bn_apply_from_stats_b16(_p(_f32c(x)), _p(bias), _p(col_stats), int(chunks), _p(gamma), _p(beta), B,
+                                            N, eps, momentum, _p(moving_mean), _p(moving_var), int(act), _p(y),
+                                            _p(mean), _p(invstd), _p(yb), 0 if yb is None else yb.stride(0),
                                             _stream()), 'er_bn_apply_from_stats')
     return y, mean, invstd
 
@@ -868,9 +883,8 @@ class HipBackend(object):
     fn = self.lib.er_gemm_bf16 if bf16 else self.lib.er_gemm_f32
     if col_stats is not None:
       assert col_stats.numel() >= self.gemm_row_tiles(M) * N * 3 and col_stats.dtype == torch.float32
-    self._ck(fn(ctypes.c_int(layout), M, N, K, _p(a), ctypes.c_int32(a.stride(0)), _p(b), ctypes.c_int32(b.stride(0)),
-                _p(out), ctypes.c_int32(out.stride(0)), _p(bias), int(bool(accumulate)), _p(col_stats), _stream()),
-             'er_gemm')
+    self._ck(fn(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), _p(bias), accumulate,
+                _p(col_stats), _stream()), 'er_gemm')
     return out
 
   # -- bf16 operands in HBM (dense_dtype 'bf16'): er_gemm_bf16_nt
@@ -917,12 +931,10 @@ class HipBackend(object):
     assert a.stride(0) >= Kp and bt.stride(0) >= Kp and a.stride(0) % 8 == 0 and bt.stride(0) % 8 == 0
     kind = 0 if epi is None else int(epi.kind)
     self._log_gemm('gemm_bf16_nt_kernel<4, %d>' % kind, None, M, N, K)
-    self._ck(self.lib.er_gemm_bf16_nt_epi(M, N, Kp, ctypes.c_void_p(a.data_ptr()), ctypes.c_int32(a.stride(0)),
-                                          ctypes.c_void_p(bt.data_ptr()), ctypes.c_int32(bt.stride(0)), _p(out),
-                                          ctypes.c_int32(0 if out is None else out.stride(0)),
-                                          ctypes.c_void_p(0 if out_bf16 is None else out_bf16.data_ptr()),
-                                          ctypes.c_int32(0 if out_bf16 is None else out_bf16.stride(0)), _p(bias),
-                                          int(bool(accumulate)), None if epi is None else ctypes.byref(epi), _stream()),
+    self._ck(self.lib.er_gemm_bf16_nt_epi(M, N, Kp, _p(a), a.stride(0), _p(bt), bt.stride(0), _p(out),
+                                          0 if out is None else out.stride(0), _p(out_bf16),
+                                          0 if out_bf16 is None else out_bf16.stride(0), _p(bias), accumulate,
+                                          None if epi is None else ctypes.byref(epi), _stream()),
              'er_gemm_bf16_nt')
     return out
 
@@ -976,8 +988,8 @@ class HipBackend(object):
         return None
       assert K == K2 and src.z.shape == (M, n_src) and c0 + n_src <= N and partial.numel() >= self.gemm_row_tiles(M) * n_src * 2
       out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-      epi = GemmEpilogue(kind=EPI_BN_BWD, bn_z=src.z.data_ptr(), bn_zbias=_ptr(src.zbias), bn_y=src.y.data_ptr(),
-                         bn_mean=_ptr(src.mean), bn_invstd=_ptr(src.invstd), bn_partial=partial.data_ptr(),
+      epi = GemmEpilogue(kind=EPI_BN_BWD, bn_z=src.z.data_ptr(), bn_zbias=_p(src.zbias), bn_y=src.y.data_ptr(),
+                         bn_mean=_p(src.mean), bn_invstd=_p(src.invstd), bn_partial=partial.data_ptr(),
                          bn_ld=src.y.stride(0), bn_use_bn=int(src.mean is not None), bn_act=int(src.act), bn_col0=c0,
                          bn_n_src=n_src)
       w, plain, t = st.weight(b)
@@ -989,11 +1001,10 @@ class HipBackend(object):
       assert partial.numel() >= self.gemm_row_tiles(M) * n_src * 2
       self._log_gemm('gemm_f32_bn_bwd_kernel', layout, M, N, K)
       out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-      self._ck(self.lib.er_gemm_f32_bn_bwd_cols(ctypes.c_int(layout), M, N, K, _p(a), ctypes.c_int32(a.stride(0)), _p(b),
-                                                ctypes.c_int32(b.stride(0)), _p(out), ctypes.c_int32(out.stride(0)),
-                                                _p(src.z), _p(src.zbias), _p(src.y), _p(src.mean), _p(src.invstd),
-                                                ctypes.c_int32(src.y.stride(0)), int(src.mean is not None), int(src.act),
-                                                _p(partial), ctypes.c_int32(int(col0)), ctypes.c_int32(n_src), _stream()),
+      self._ck(self.lib.er_gemm_f32_bn_bwd_cols(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out),
+                                                out.stride(0), _p(src.z), _p(src.zbias), _p(src.y), _p(src.mean),
+                                                _p(src.invstd), src.y.stride(0), int(src.mean is not None),
+                                                int(src.act), _p(partial), int(col0), n_src, _stream()),
                'er_gemm_f32_bn_bwd_cols')
       return out
     assert K == K2 and src.z.shape == (M, N) and src.y.shape == (M, N) and src.y.stride() == src.z.stride()
@@ -1001,10 +1012,9 @@ class HipBackend(object):
     self._log_gemm('gemm_f32_bn_bwd_kernel', layout, M, N, K)
     out = torch.empty(M, N, dtype=torch.float32, device=a.device)
     use_bn = src.mean is not None
-    self._ck(self.lib.er_gemm_f32_bn_bwd(ctypes.c_int(layout), M, N, K, _p(a), ctypes.c_int32(a.stride(0)), _p(b),
-                                         ctypes.c_int32(b.stride(0)), _p(out), ctypes.c_int32(out.stride(0)),
-                                         _p(src.z), _p(src.zbias), _p(src.y), _p(src.mean), _p(src.invstd),
-                                         ctypes.c_int32(src.y.stride(0)), int(use_bn), int(src.act), _p(partial),
+    self._ck(self.lib.er_gemm_f32_bn_bwd(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out),
+                                         out.stride(0), _p(src.z), _p(src.zbias), _p(src.y), _p(src.mean),
+                                         _p(src.invstd), src.y.stride(0), int(use_bn), int(src.act), _p(partial),
                                          _stream()), 'er_gemm_f32_bn_bwd')
     return out
 
@@ -1029,13 +1039,13 @@ class HipBackend(object):
       y = torch.empty_like(x)
       mean = torch.empty(N, dtype=torch.float32, device=x.device) if l['use_bn'] else None
       invstd = torch.empty(N, dtype=torch.float32, device=x.device) if l['use_bn'] else None
-      q.x, q.bias, q.gamma, q.beta = x.data_ptr(), _ptr(l.get('bias')), _ptr(l.get('gamma')), _ptr(l.get('beta'))
-      q.moving_mean, q.moving_var = _ptr(l.get('moving_mean')), _ptr(l.get('moving_var'))
+      q.x, q.bias, q.gamma, q.beta = x.data_ptr(), _p(l.get('bias')), _p(l.get('gamma')), _p(l.get('beta'))
+      q.moving_mean, q.moving_var = _p(l.get('moving_mean')), _p(l.get('moving_var'))
       q.B, q.N, q.use_bn, q.act = B, N, int(l['use_bn']), int(l['act'])
       q.eps, q.momentum = float(l.get('eps', 0.0)), float(l.get('momentum', 0.0))
       if int(l['use_bn']) == BN_BATCH:
         q.col_stats, q.chunks = l['col_stats'].data_ptr(), self.gemm_row_tiles(B)
-      q.y, q.save_mean, q.save_invstd = y.data_ptr(), _ptr(mean), _ptr(invstd)
+      q.y, q.save_mean, q.save_invstd = y.data_ptr(), _p(mean), _p(invstd)
       outs.append((y, mean, invstd))
     self._ck(self.lib.er_bn_fwd_multi(arr, len(layers), _stream()), 'er_bn_fwd_multi')
     return outs
@@ -1063,15 +1073,15 @@ class HipBackend(object):
       partial = l.get('partial')
       if partial is not None and dy.stride(0) != N:
         partial = None
-      q.x, q.bias, q.gamma, q.beta = x.data_ptr(), _ptr(l.get('bias')), _ptr(l.get('gamma')), _ptr(l.get('beta'))
+      q.x, q.bias, q.gamma, q.beta = x.data_ptr(), _p(l.get('bias')), _p(l.get('gamma')), _p(l.get('beta'))
       q.B, q.N, q.use_bn, q.act = B, N, int(l['use_bn']), int(l['act'])
-      q.save_mean, q.save_invstd = _ptr(l.get('mean')), _ptr(l.get('invstd'))
-      q.y_in = _ptr(l['y'])
+      q.save_mean, q.save_invstd = _p(l.get('mean')), _p(l.get('invstd'))
+      q.y_in = _p(l['y'])
       q.dy, q.dy_ld = dy.data_ptr(), dy.stride(0)
       if partial is not None:
         q.partial, q.chunks = partial.data_ptr(), self.gemm_row_tiles(B)
       assert not dx_done or (partial is not None and int(l['use_bn']) == BN_FROZEN)
-      q.dx, q.dbias, q.dgamma, q.dbeta = (None if dx_done else dx.data_ptr()), _ptr(dbias), _ptr(dgamma), _ptr(dbeta)
+      q.dx, q.dbias, q.dgamma, q.dbeta = (None if dx_done else dx.data_ptr()), _p(dbias), _p(dgamma), _p(dbeta)
       q.accumulate = int(into is not None)
       outs.append((dx, None, None, None) if into is not None else (dx, dbias, dgamma, dbeta))
     self._ck(self.lib.er_bn_bwd_multi(arr, len(layers), _stream()), 'er_bn_bwd_multi')
@@ -1082,9 +1092,9 @@ class HipBackend(object):
     bf16: operands rounded to bf16 while staged (er_gemm_grouped_bf16)."""
     arr = self._gemm_problems(layout, problems, bf16)
     if bf16:
-      self._ck(self.lib.er_gemm_grouped_bf16(ctypes.c_int(layout), arr, len(problems), _stream()), 'er_gemm_grouped_bf16')
+      self._ck(self.lib.er_gemm_grouped_bf16(layout, arr, len(problems), _stream()), 'er_gemm_grouped_bf16')
     else:
-      self._ck(self.lib.er_gemm_grouped_f32(ctypes.c_int(layout), arr, len(problems), _stream()), 'er_gemm_grouped_f32')
+      self._ck(self.lib.er_gemm_grouped_f32(layout, arr, len(problems), _stream()), 'er_gemm_grouped_f32')
 
   def _gemm_problems(self, layout, problems, bf16=False, log_as=None):
     """The er_gemm_problem array of a grouped launch (log_as: the kernel the op log books the contractions under)."""
@@ -1121,11 +1131,11 @@ class HipBackend(object):
         src, partial = bn[:2]
         if len(bn) > 2 and bn[2]:  # (the layer's elementwise backward in this launch's epilogue: frozen statistics only)
           assert src.frozen and layout == GEMM_NT
-          q.bn_gamma, q.bn_dz_out = _ptr(src.gamma), 1
+          q.bn_gamma, q.bn_dz_out = _p(src.gamma), 1
         assert src.z.shape == (M, N) and partial.numel() >= self.gemm_row_tiles(M) * N * 2 and not accumulate
-        q.bn_z, q.bn_zbias = _ptr(src.z), _ptr(src.zbias)
-        q.bn_y = _ptr(src.y)
-        q.bn_mean, q.bn_invstd = _ptr(src.mean), _ptr(src.invstd)
+        q.bn_z, q.bn_zbias = _p(src.z), _p(src.zbias)
+        q.bn_y = _p(src.y)
+        q.bn_mean, q.bn_invstd = _p(src.mean), _p(src.invstd)
         q.bn_ld, q.bn_use_bn, q.bn_act = src.z.stride(0), int(src.mean is not None), int(src.act)
         q.bn_partial = partial.data_ptr()
       fz = pr[7] if len(pr) > 7 else None  # (the frozen-BatchNorm forward epilogue: er_gemm_problem.fz_*)
@@ -1134,7 +1144,7 @@ class HipBackend(object):
         y, save = fz['y'], fz['save']
         assert y.shape == (M, N) and y.stride(0) == out.stride(0) and y.stride(1) == 1 and save.is_contiguous() and \
             save.numel() == 2 * N
-        q.fz_bias, q.fz_gamma, q.fz_beta = _ptr(fz.get('bias')), _ptr(fz.get('gamma')), _ptr(fz.get('beta'))
+        q.fz_bias, q.fz_gamma, q.fz_beta = _p(fz.get('bias')), _p(fz.get('gamma')), _p(fz.get('beta'))
         q.fz_mean, q.fz_var = fz['moving_mean'].data_ptr(), fz['moving_var'].data_ptr()
         q.fz_eps, q.fz_act = float(fz['eps']), int(fz['act'])
         q.fz_y, q.fz_save = y.data_ptr(), save.data_ptr()
@@ -1194,7 +1204,7 @@ class HipBackend(object):
     for q, (x, out) in zip(arr, jobs):
       assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and out.is_contiguous() and out.numel() == x.shape[1]
       q.x, q.rows, q.cols, q.x_stride, q.out = x.data_ptr(), x.shape[0], x.shape[1], x.stride(0), out.data_ptr()
-    self._ck(self.lib.er_colsum_narrow_multi(arr, ctypes.c_int32(len(jobs)), int(bool(accumulate)), _stream()),
+    self._ck(self.lib.er_colsum_narrow_multi(arr, len(jobs), accumulate, _stream()),
              'er_colsum_narrow_multi')
 
   def colsum_partials_multi(self, jobs, accumulate=True):
@@ -1203,7 +1213,7 @@ class HipBackend(object):
     for q, (partial, d, n_cols) in zip(arr, jobs):
       assert partial.dim() == 2 and partial.stride(1) == 1 and d.is_contiguous() and d.numel() == n_cols
       q.partial, q.dst, q.n_parts, q.n_cols, q.ld = partial.data_ptr(), d.data_ptr(), partial.shape[0], int(n_cols), partial.stride(0)
-    self._ck(self.lib.er_colsum_partials_multi(arr, ctypes.c_int32(len(jobs)), int(bool(accumulate)), _stream()),
+    self._ck(self.lib.er_colsum_partials_multi(arr, len(jobs), accumulate, _stream()),
              'er_colsum_partials_multi')
 
   # the step's tail in one grid (er_emb_bwd_fused_wgrad); A/B switch, and the workgroups its contraction's k-splits aim at
@@ -1219,12 +1229,12 @@ class HipBackend(object):
   # -- K12 embedding-parallel routing (include/easyrec_hip.h)
   def emb_group_set_routing(self, group, world, shard_stride, local_base):
     arr = (ctypes.c_int64 * len(local_base))(*[int(x) for x in local_base])
-    self._ck(self.lib.er_emb_group_set_routing(group['handle'], ctypes.c_int32(world), ctypes.c_int64(shard_stride), arr),
+    self._ck(self.lib.er_emb_group_set_routing(group['handle'], world, shard_stride, arr),
              'er_emb_group_set_routing')
     group['world'], group['shard_stride'], group['local_base'] = world, shard_stride, list(local_base)
 
   def emb_group_set_active(self, group, n_rows):
-    self._ck(self.lib.er_emb_group_set_active(group['handle'], ctypes.c_int64(int(n_rows))), 'er_emb_group_set_active')
+    self._ck(self.lib.er_emb_group_set_active(group['handle'], int(n_rows)), 'er_emb_group_set_active')
     group['n_active'] = int(n_rows)
 
   def emb_group_share_sort(self, group, leader):
@@ -1248,7 +1258,7 @@ class HipBackend(object):
 
   def emb_bwd_reduce_routed(self, group, unique_grads):
     assert unique_grads.dtype == torch.float32 and unique_grads.dim() == 2 and unique_grads.stride(1) == 1
-    self._ck(self.lib.er_emb_bwd_reduce_routed(group['handle'], _p(unique_grads), ctypes.c_int32(unique_grads.stride(0)),
+    self._ck(self.lib.er_emb_bwd_reduce_routed(group['handle'], _p(unique_grads), unique_grads.stride(0),
                                                _stream()), 'er_emb_bwd_reduce_routed')
 
   # the embedding-parallel requester's local reductions + the step's weight gradients + the loss tail as two launches
@@ -1275,20 +1285,19 @@ class HipBackend(object):
       lt = self._deferred_loss_tail
       self._deferred_loss_tail = None
     self._ck(self.lib.er_emb_reduce_local_tail(gh, modes, outs, ld, n, pr, len(wgrads) if wgrads else 0,
-                                               ctypes.c_int32(int(self.tail_wgrad_blocks) if wgrads else 0),
+                                               int(self.tail_wgrad_blocks) if wgrads else 0,
                                                ctypes.byref(lt[0]) if lt is not None else None, _stream()),
              'er_emb_reduce_local_tail')
 
   def gather_rows(self, table, keys, n, key_sub, out):
     assert keys.dtype == torch.int32 and table.dim() == 2 and table.stride(1) == 1
-    self._ck(self.lib.er_gather_rows_ld(_p(table), ctypes.c_int64(table.stride(0)), ctypes.c_int64(table.shape[0]),
-                                        ctypes.c_int32(table.shape[1]), _p(keys), ctypes.c_int64(int(n)),
-                                        ctypes.c_int64(int(key_sub)), _p(out), _stream()), 'er_gather_rows_ld')
+    self._ck(self.lib.er_gather_rows_ld(_p(table), table.stride(0), table.shape[0], table.shape[1], _p(keys), int(n),
+                                        int(key_sub), _p(out), _stream()), 'er_gather_rows_ld')
 
   def scatter_unique(self, keys, grads, n_unique, capacity, dim, dense):
     assert dense.dim() == 2 and dense.stride(1) == 1
-    self._ck(self.lib.er_scatter_unique(_p(keys), _p(grads), _p(n_unique), ctypes.c_int64(int(capacity)),
-                                        ctypes.c_int32(dim), _p(dense), ctypes.c_int32(dense.stride(0)), _stream()),
+    self._ck(self.lib.er_scatter_unique(_p(keys), _p(grads), _p(n_unique), int(capacity),
+                                        dim, _p(dense), dense.stride(0), _stream()),
              'er_scatter_unique')
 
   def emb_owner_merge(self, group, run_counts):
@@ -1298,8 +1307,7 @@ class HipBackend(object):
     self._ck(self.lib.er_emb_owner_merge(group['handle'], rc, n, _stream()), 'er_emb_owner_merge')
 
   def emb_group_set_peer_capacity(self, group, peer_cap, count_header=True):
-    self._ck(self.lib.er_emb_group_set_peer_capacity(group['handle'], ctypes.c_int64(int(peer_cap)),
-                                                     ctypes.c_int32(1 if count_header else 0)),
+    self._ck(self.lib.er_emb_group_set_peer_capacity(group['handle'], int(peer_cap), 1 if count_header else 0),
              'er_emb_group_set_peer_capacity')
     group['peer_cap'], group['peer_hdr'] = int(peer_cap), bool(count_header)
 
@@ -1314,9 +1322,8 @@ class HipBackend(object):
     assert recv_keys.dtype == torch.int32 and ids.dtype == torch.int64 and counts_out.dtype == torch.int32
     assert recv_keys.numel() >= n_runs * (peer_cap + hdr) and ids.numel() >= n_runs * peer_cap and counts_out.numel() >= n_runs
     assert counts is None or (counts.dtype == torch.int32 and counts.numel() >= n_runs)
-    self._ck(self.lib.er_emb_owner_ids(_p(recv_keys), None if counts is None else _p(counts), ctypes.c_int(n_runs),
-                                       ctypes.c_int64(int(peer_cap)), ctypes.c_int64(int(key_sub)), _p(ids), _p(counts_out),
-                                       _stream()), 'er_emb_owner_ids')
+    self._ck(self.lib.er_emb_owner_ids(_p(recv_keys), None if counts is None else _p(counts), n_runs, int(peer_cap),
+                                       int(key_sub), _p(ids), _p(counts_out), _stream()), 'er_emb_owner_ids')
 
   # owner ids + entry build + merge (+ the serve launch's lag-1 replay table) as one launch - A/B switch
   ep_owner_fused = os.environ.get('EASYREC_AMD_EP_OWNER_FUSED', '1') != '0'
@@ -1325,15 +1332,14 @@ class HipBackend(object):
     """er_emb_owner_ids_merge: emb_owner_ids (runs with their count in front) + emb_owner_merge_padded in one launch."""
     assert recv_keys.dtype == torch.int32 and ids.dtype == torch.int64 and counts_out.dtype == torch.int32
     assert recv_keys.numel() >= n_runs * (peer_cap + 1) and ids.numel() >= n_runs * peer_cap and counts_out.numel() >= n_runs
-    self._ck(self.lib.er_emb_owner_ids_merge(group['handle'], _p(recv_keys), None, ctypes.c_int(n_runs),
-                                             ctypes.c_int64(int(peer_cap)), ctypes.c_int64(int(key_sub)), _p(ids),
-                                             _p(counts_out), ctypes.c_int(1 if build_tables else 0), _stream()),
+    self._ck(self.lib.er_emb_owner_ids_merge(group['handle'], _p(recv_keys), None, n_runs, int(peer_cap), int(key_sub),
+                                             _p(ids), _p(counts_out), 1 if build_tables else 0, _stream()),
              'er_emb_owner_ids_merge')
 
   def emb_owner_merge_padded(self, group, counts, n_runs, peer_cap):
     assert counts.dtype == torch.int32 and counts.numel() >= n_runs
-    self._ck(self.lib.er_emb_owner_merge_padded(group['handle'], _p(counts), ctypes.c_int(n_runs),
-                                                ctypes.c_int64(int(peer_cap)), _stream()), 'er_emb_owner_merge_padded')
+    self._ck(self.lib.er_emb_owner_merge_padded(group['handle'], _p(counts), n_runs,
+                                                int(peer_cap), _stream()), 'er_emb_owner_merge_padded')
 
   def emb_owner_serve(self, groups, rows_out, hyper):
     """Catch up (lazy dense decay) and reply the received rows of up to 4 owner groups in one launch."""
@@ -1366,7 +1372,7 @@ class HipBackend(object):
       assert all(t is None or t.stride() == var.stride() for t in (m, v))
       descs[i] = DenseApplyDesc(var.data_ptr(), None if m is None else m.data_ptr(), None if v is None else v.data_ptr(),
                                 dense.data_ptr(), dense.stride(0), var.shape[1], var.shape[0], var.stride(0))
-    self._ck(self.lib.er_emb_dense_apply(descs, n, ctypes.c_int(opt_kind), _p(hyper), _stream()), 'er_emb_dense_apply')
+    self._ck(self.lib.er_emb_dense_apply(descs, n, opt_kind, _p(hyper), _stream()), 'er_emb_dense_apply')
 
   def emb_mark_touched(self, group):
     self._ck(self.lib.er_emb_mark_touched(group['handle'], _stream()), 'er_emb_mark_touched')
@@ -1377,14 +1383,13 @@ class HipBackend(object):
   def stream_copy(self, src, dst):
     nbytes = src.numel() * src.element_size()
     assert dst.numel() * dst.element_size() >= nbytes
-    self._ck(self.lib.er_stream_copy(_p(src), _p(dst), ctypes.c_int64(nbytes), _stream()), 'er_stream_copy')
+    self._ck(self.lib.er_stream_copy(_p(src), _p(dst), nbytes, _stream()), 'er_stream_copy')
 
   def adam_decay_sweep(self, var, m, v, bitmap, total_rows, dim, hyper):
     ld = var.stride(0) if var.dim() == 2 else dim
     assert var.dim() != 2 or (m.stride() == var.stride() and v.stride() == var.stride() and var.stride(1) == 1)
     self._ck(
-        self.lib.er_adam_decay_sweep_ld(_p(var), _p(m), _p(v), _p(bitmap), ctypes.c_int64(total_rows),
-                                        ctypes.c_int32(dim), ctypes.c_int64(ld), _p(hyper), _stream()),
+        self.lib.er_adam_decay_sweep_ld(_p(var), _p(m), _p(v), _p(bitmap), total_rows, dim, ld, _p(hyper), _stream()),
         'er_adam_decay_sweep_ld')
 
   # -- K5 FM / wide
@@ -1411,8 +1416,8 @@ class HipBackend(object):
     assert probs.numel() == labels.numel() and counts.dtype == torch.int64 and counts.is_contiguous()
     assert counts.numel() == 2 * (thresholds.numel() + 1)
     w = None if weights is None else _f32c(weights.reshape(-1))
-    self._ck(self.lib.er_auc_update(_p(probs), _p(labels), _p(w), ctypes.c_int64(probs.numel()), _p(thresholds),
-                                    ctypes.c_int32(thresholds.numel()), _p(counts), _stream()), 'er_auc_update')
+    self._ck(self.lib.er_auc_update(_p(probs), _p(labels), _p(w), probs.numel(), _p(thresholds),
+                                    thresholds.numel(), _p(counts), _stream()), 'er_auc_update')
 
   def grouped_auc(self, keys, preds, labels, reduction):
     """gAUC / session AUC of the accumulated rows (int64 keys, fp32 predictions, labels != 0 positive) -> (sum of
@@ -1427,7 +1432,7 @@ class HipBackend(object):
       order = by_pred[torch.sort(keys.reshape(-1)[by_pred], stable=True).indices]
       k, p, y = keys.reshape(-1)[order].contiguous(), preds[order].contiguous(), labels[order].contiguous()
       work = torch.zeros(3 * n, dtype=torch.float64, device=keys.device)
-      self._ck(self.lib.er_grouped_auc(_p(k), _p(p), _p(y), ctypes.c_int64(n), ctypes.c_int32(int(reduction)), _p(work), _p(out),
+      self._ck(self.lib.er_grouped_auc(_p(k), _p(p), _p(y), n, int(reduction), _p(work), _p(out),
                                        _stream()), 'er_grouped_auc')
     return tuple(float(x) for x in out.cpu().tolist())
 
@@ -1436,7 +1441,7 @@ class HipBackend(object):
     B = x.shape[0]
     P = F * (F - 1) // 2 + (F if self_interaction else 0)
     out = torch.empty(B, P, dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_dot_interaction_fwd(_p(x), B, F, D, x.stride(0), int(bool(self_interaction)), _p(out),
+    self._ck(self.lib.er_dot_interaction_fwd(_p(x), B, F, D, x.stride(0), self_interaction, _p(out),
                                              out.stride(0), _stream()), 'er_dot_interaction_fwd')
     return out
 
@@ -1444,7 +1449,7 @@ class HipBackend(object):
     B = x.shape[0]
     dx = torch.empty(B, F * D, dtype=torch.float32, device=x.device)
     g = _f32c(g)
-    self._ck(self.lib.er_dot_interaction_bwd(_p(x), _p(g), B, F, D, x.stride(0), int(bool(self_interaction)),
+    self._ck(self.lib.er_dot_interaction_bwd(_p(x), _p(g), B, F, D, x.stride(0), self_interaction,
                                              g.stride(0), _p(dx), dx.stride(0), 0, _stream()),
              'er_dot_interaction_bwd')
     return dx
@@ -1478,8 +1483,8 @@ class HipBackend(object):
     width = 1 + D + N
     out = torch.empty(B, (width + 3) // 4 * 4, dtype=torch.float32, device=wide.device)[:, :width]
     S = torch.empty(B, D, dtype=torch.float32, device=wide.device)
-    rc = self.lib.er_bn_apply_wide_fm(_p(z), _p(pend['stats']), ctypes.c_int32(int(pend['chunks'])), _p(pend['gamma']),
-                                      _p(pend['beta']), B, N, ctypes.c_float(pend['eps']), ctypes.c_float(pend['momentum']),
+    rc = self.lib.er_bn_apply_wide_fm(_p(z), _p(pend['stats']), int(pend['chunks']), _p(pend['gamma']),
+                                      _p(pend['beta']), B, N, pend['eps'], pend['momentum'],
                                       _p(pend['moving_mean']), _p(pend['moving_var']), int(pend['act']), _p(y),
                                       _p(pend['mean']), _p(pend['invstd']), _p(wide), n_w, wide.stride(0), _p(fm_x), F, D,
                                       fm_x.stride(0), _p(out), out.stride(0), _p(S), _stream())
@@ -1492,11 +1497,11 @@ class HipBackend(object):
     """the deferred BatchNorm finalize + apply as the launch of its own it would have been"""
     z = pend['z']
     B, N = z.shape
-    self._ck(self.lib.er_bn_apply_from_stats_b16(_p(z), None, _p(pend['stats']), ctypes.c_int32(int(pend['chunks'])),
-                                                 _p(pend['gamma']), _p(pend['beta']), B, N, ctypes.c_float(pend['eps']),
-                                                 ctypes.c_float(pend['momentum']), _p(pend['moving_mean']),
+    self._ck(self.lib.er_bn_apply_from_stats_b16(_p(z), None, _p(pend['stats']), int(pend['chunks']),
+                                                 _p(pend['gamma']), _p(pend['beta']), B, N, pend['eps'],
+                                                 pend['momentum'], _p(pend['moving_mean']),
                                                  _p(pend['moving_var']), int(pend['act']), _p(pend['y']), _p(pend['mean']),
-                                                 _p(pend['invstd']), None, ctypes.c_int32(0), _stream()),
+                                                 _p(pend['invstd']), None, 0, _stream()),
              'er_bn_apply_from_stats')
 
   # the last BatchNorm apply of DeepFM's deep tower inside the [sum(wide) | FM | deep] launch (er_bn_apply_wide_fm) - A/B switch
@@ -1540,11 +1545,11 @@ class HipBackend(object):
       self.op_log.append(('er::gemv_bna_kernel<%d>' % N, 2.0 * M * N * K))
     bn = pend is not None
     y = pend['y'] if bn else None
-    self._ck(self.lib.er_gemv_f32_bn_a(M, N, K, _p(x), ctypes.c_int32(x.stride(0)), _p(pend['mean']) if bn else None,
+    self._ck(self.lib.er_gemv_f32_bn_a(M, N, K, _p(x), x.stride(0), _p(pend['mean']) if bn else None,
                                        _p(pend['invstd']) if bn else None, _p(pend['gamma']) if bn else None,
                                        _p(pend['beta']) if bn else None, int(pend['act']) if bn else 0, _p(y),
-                                       ctypes.c_int32(y.stride(0) if bn else 0), _p(w), ctypes.c_int32(w.stride(0)), _p(out),
-                                       ctypes.c_int32(out.stride(0)), _p(bias), _stream()), 'er_gemv_f32_bn_a')
+                                       y.stride(0) if bn else 0, _p(w), w.stride(0), _p(out),
+                                       out.stride(0), _p(bias), _stream()), 'er_gemv_f32_bn_a')
     return out
 
   def wgrad_tall_narrow_ok(self, x, dz):
@@ -1562,9 +1567,9 @@ class HipBackend(object):
     scratch = torch.empty(513 * (K + 1) * N, dtype=torch.float32, device=x.device)
     if self.op_log is not None:
       self.op_log.append(('er::wgrad_narrow_partial_kernel<%d>' % N, 2.0 * rows * N * K))
-    self._ck(self.lib.er_wgrad_tall_narrow(rows, K, N, _p(x), ctypes.c_int32(x.stride(0)), _p(dz), ctypes.c_int32(dz.stride(0)),
-                                           _p(out), ctypes.c_int32(out.stride(0)), _p(bias_grad), int(bool(accumulate)), _p(scratch),
-                                           ctypes.c_int64(scratch.numel()), _stream()), 'er_wgrad_tall_narrow')
+    self._ck(self.lib.er_wgrad_tall_narrow(rows, K, N, _p(x), x.stride(0), _p(dz), dz.stride(0),
+                                           _p(out), out.stride(0), _p(bias_grad), accumulate, _p(scratch),
+                                           scratch.numel(), _stream()), 'er_wgrad_tall_narrow')
     return out
 
   def gemm_bn_a(self, pend, w, bias, col_stats=None):
@@ -1574,8 +1579,8 @@ class HipBackend(object):
     z, y = pend['z'], pend['y']
     M, K = z.shape
     N = w.shape[1]
-    self._ck(self.lib.er_bn_finalize_from_stats(_p(pend['stats']), ctypes.c_int32(int(pend['chunks'])), M, K,
-                                                ctypes.c_float(pend['eps']), ctypes.c_float(pend['momentum']),
+    self._ck(self.lib.er_bn_finalize_from_stats(_p(pend['stats']), int(pend['chunks']), M, K,
+                                                pend['eps'], pend['momentum'],
                                                 _p(pend['moving_mean']), _p(pend['moving_var']), _p(pend['mean']),
                                                 _p(pend['invstd']), _stream()), 'er_bn_finalize_from_stats')
     if col_stats is None and self.gemv_ok(z, M, N, K):
@@ -1584,10 +1589,10 @@ class HipBackend(object):
     if col_stats is not None:
       assert col_stats.numel() >= self.gemm_row_tiles(M) * N * 3 and col_stats.dtype == torch.float32
     self._log_gemm('gemm_f32_bna_kernel', None, M, N, K)
-    self._ck(self.lib.er_gemm_f32_bn_a(M, N, K, _p(z), ctypes.c_int32(z.stride(0)), _p(pend['mean']), _p(pend['invstd']),
+    self._ck(self.lib.er_gemm_f32_bn_a(M, N, K, _p(z), z.stride(0), _p(pend['mean']), _p(pend['invstd']),
                                        _p(pend['gamma']), _p(pend['beta']), int(pend['act']), _p(y),
-                                       ctypes.c_int32(y.stride(0)), _p(w), ctypes.c_int32(w.stride(0)), _p(out),
-                                       ctypes.c_int32(out.stride(0)), _p(bias), _p(col_stats), _stream()), 'er_gemm_f32_bn_a')
+                                       y.stride(0), _p(w), w.stride(0), _p(out),
+                                       out.stride(0), _p(bias), _p(col_stats), _stream()), 'er_gemm_f32_bn_a')
     return out
 
   def rowsum_bwd(self, g, n, into=None, accumulate=False):
@@ -1617,7 +1622,7 @@ class HipBackend(object):
     n = len(groups)
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
     flags = (1 if skip_one_row else 0) | (2 if defer else 0)
-    rc = self.lib.er_emb_front(gh, n, ctypes.c_int(flags), _p(hyper), _stream())
+    rc = self.lib.er_emb_front(gh, n, flags, _p(hyper), _stream())
     if rc == 3:
       return False
     self._ck(rc, 'er_emb_front')
@@ -1634,7 +1639,7 @@ class HipBackend(object):
     -> False when the groups need the general path (nothing launched)."""
     n = len(groups)
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
-    rc = self.lib.er_emb_front_fwd(gh, n, ctypes.c_int((1 if skip_one_row else 0) | 2), plan['handle'], _p(hyper),
+    rc = self.lib.er_emb_front_fwd(gh, n, (1 if skip_one_row else 0) | 2, plan['handle'], _p(hyper),
                                    _p(sumsq_partials), _stream())
     if rc == 3:
       return False
@@ -1645,7 +1650,7 @@ class HipBackend(object):
   prologue_tables = os.environ.get('EASYREC_AMD_PROLOGUE_TABLES', '1') != '0'
 
   def decay_tables_set_prologue_build(self, tabs, on):
-    self._ck(self.lib.er_decay_tables_set_prologue_build(tabs['handle'], int(bool(on))), 'er_decay_tables_set_prologue_build')
+    self._ck(self.lib.er_decay_tables_set_prologue_build(tabs['handle'], on), 'er_decay_tables_set_prologue_build')
     tabs['prologue_build'] = bool(on)
 
   def decay_tables_sync(self, tabs):
@@ -1674,9 +1679,9 @@ class HipBackend(object):
       oj = None
       if dense_opt is not None:
         w, m, v, grad, l2coef, kind, hyp, l2p = dense_opt
-        oj = DenseOptJob(_ptr(w), _ptr(m), _ptr(v), _ptr(grad), _ptr(l2coef), w.numel(), int(kind), _ptr(hyp), _ptr(l2p))
-      self._ck(self.lib.er_emb_bwd_fused_tail(gh, n, arr, len(finish), ctypes.c_int(opt_kind), _p(hyper), pr, len(wgrads),
-                                              ctypes.c_int32(int(self.tail_wgrad_blocks)),
+        oj = DenseOptJob(_p(w), _p(m), _p(v), _p(grad), _p(l2coef), w.numel(), int(kind), _p(hyp), _p(l2p))
+      self._ck(self.lib.er_emb_bwd_fused_tail(gh, n, arr, len(finish), opt_kind, _p(hyper), pr, len(wgrads),
+                                              int(self.tail_wgrad_blocks),
                                               ctypes.byref(lt[0]) if lt is not None else None,
                                               ctypes.byref(oj) if oj is not None else None, _stream()),
                'er_emb_bwd_fused_tail')
@@ -1685,7 +1690,7 @@ class HipBackend(object):
         if st is not None:
           st.refresh()  # (a bf16 step whose dense optimizer ran in the tail: the weights' bf16 shadows follow the masters)
       return oj is not None
-    self._ck(self.lib.er_emb_bwd_fused(gh, n, arr, len(finish), ctypes.c_int(opt_kind), _p(hyper), _stream()),
+    self._ck(self.lib.er_emb_bwd_fused(gh, n, arr, len(finish), opt_kind, _p(hyper), _stream()),
              'er_emb_bwd_fused')
     return False
 
@@ -1724,7 +1729,7 @@ class HipBackend(object):
     rows, cols = x.shape
     assert x.stride(1) == 1 and y.stride(1) == 1 and y.shape == x.shape
     self._ck(
-        self.lib.er_axpy2d(_p(x), x.stride(0), ctypes.c_float(alpha), _p(y), y.stride(0), rows, cols,
+        self.lib.er_axpy2d(_p(x), x.stride(0), alpha, _p(y), y.stride(0), rows, cols,
                            int(accumulate), _stream()), 'er_axpy2d')
 
   # -- K6 / K7 cross
@@ -1756,7 +1761,7 @@ class HipBackend(object):
     out = torch.empty_like(x0)
     self._ck(
         self.lib.er_cross_v2_epilogue_fwd(_p(_f32c(x0)), _p(_f32c(x)), _p(_f32c(u)), _p(bias),
-                                          ctypes.c_float(diag_scale), B, d, _p(out), _stream()),
+                                          diag_scale, B, d, _p(out), _stream()),
         'er_cross_v2_epilogue_fwd')
     return out
 
@@ -1764,7 +1769,7 @@ class HipBackend(object):
     B, d = x0.shape
     dx0, dx, du = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
     self._ck(
-        self.lib.er_cross_v2_epilogue_bwd(_p(x0), _p(x), _p(u), _p(bias), ctypes.c_float(diag_scale),
+        self.lib.er_cross_v2_epilogue_bwd(_p(x0), _p(x), _p(u), _p(bias), diag_scale,
                                           _p(_f32c(dout)), B, d, _p(dx0), 0, _p(dx), _p(du), _stream()),
         'er_cross_v2_epilogue_bwd')
     return dx0, dx, du
@@ -1801,8 +1806,8 @@ class HipBackend(object):
       self.gemm_bf16_nt(st.act(x, cache=True), t, B, d, d, out=out, out_bf16=st.new_copy(out), bias=bias, epi=epi)
     else:
       self._log_gemm('gemm_f32_cross_kernel<true, false, 3>', None, B, d, d)
-      self._ck(self.lib.er_gemm_f32_cross(ctypes.c_int(GEMM_NN), B, d, d, _p(x), ctypes.c_int32(x.stride(0)), _p(w),
-                                          ctypes.c_int32(w.stride(0)), _p(out), ctypes.c_int32(out.stride(0)), _p(bias), 0,
+      self._ck(self.lib.er_gemm_f32_cross(GEMM_NN, B, d, d, _p(x), x.stride(0), _p(w),
+                                          w.stride(0), _p(out), out.stride(0), _p(bias), 0,
                                           ctypes.byref(epi), _stream()), 'er_gemm_f32_cross')
     return out, u
 
@@ -1817,9 +1822,8 @@ class HipBackend(object):
     if st:
       dub = torch.empty(B, st.pad8(d), dtype=torch.bfloat16, device=x0.device)  # (the kernel zeroes the k-tail columns)
       st.register(du, dub)
-    self._ck(self.lib.er_cross_v2_bwd_top(_p(x0), _p(x), _p(u), _p(bias), ctypes.c_float(diag), _p(dout),
-                                          ctypes.c_int32(dout.stride(0)), B, d, _p(dx0), ctypes.c_int32(dx0.stride(0)),
-                                          int(bool(acc0)), _p(du), _p(dub), ctypes.c_int32(0 if dub is None else dub.stride(0)),
+    self._ck(self.lib.er_cross_v2_bwd_top(_p(x0), _p(x), _p(u), _p(bias), diag, _p(dout), dout.stride(0), B, d, _p(dx0),
+                                          dx0.stride(0), acc0, _p(du), _p(dub), 0 if dub is None else dub.stride(0),
                                           _p(partial), _stream()), 'er_cross_v2_bwd_top')
     return du, partial
 
@@ -1841,7 +1845,7 @@ class HipBackend(object):
       partial = torch.empty(self.gemm_row_tiles(B), d, dtype=torch.float32, device=du.device)
       epi.x0, epi.ld_x0 = prev['x0'].data_ptr(), prev['x0'].stride(0)
       epi.prev_u, epi.ld_prev_u = prev['u'].data_ptr(), prev['u'].stride(0)
-      epi.prev_bias = _ptr(prev['bias'])
+      epi.prev_bias = _p(prev['bias'])
       if diag != 0:
         epi.xl, epi.ld_xl = prev['xl'].data_ptr(), prev['xl'].stride(0)
       epi.dx0, epi.ld_dx0, epi.accumulate_dx0 = prev['dx0'].data_ptr(), prev['dx0'].stride(0), int(bool(prev['acc0']))
@@ -1855,9 +1859,8 @@ class HipBackend(object):
       self.gemm_bf16_nt(st.act(du), plain, B, d, d, out=dst, accumulate=acc, epi=epi)
     else:
       self._log_gemm('gemm_f32_cross_kernel<true, true, 4>', None, B, d, d)
-      self._ck(self.lib.er_gemm_f32_cross(ctypes.c_int(GEMM_NT), B, d, d, _p(du), ctypes.c_int32(du.stride(0)), _p(w),
-                                          ctypes.c_int32(w.stride(0)), _p(dst), ctypes.c_int32(dst.stride(0)), None,
-                                          int(bool(acc)), ctypes.byref(epi), _stream()), 'er_gemm_f32_cross')
+      self._ck(self.lib.er_gemm_f32_cross(GEMM_NT, B, d, d, _p(du), du.stride(0), _p(w), w.stride(0), _p(dst),
+                                          dst.stride(0), None, acc, ctypes.byref(epi), _stream()), 'er_gemm_f32_cross')
     return du_prev, partial
 
   def cross_v2_bwd_acc(self, x0, x, u, bias, diag_scale, dout, dx0, acc0, dx, accx):
@@ -1867,9 +1870,9 @@ class HipBackend(object):
     du = torch.empty_like(x0)
     assert dx0.stride(1) == 1 and (dx is None or dx.stride(1) == 1)
     assert dout.dim() == 2 and dout.stride(1) == 1 and dout.dtype == torch.float32
-    self._ck(self.lib.er_cross_v2_epilogue_bwd_acc(_p(x0), _p(x), _p(u), _p(bias), ctypes.c_float(diag_scale), _p(dout),
-                                                   ctypes.c_int32(dout.stride(0)), B, d, _p(dx0), ctypes.c_int32(dx0.stride(0)), int(bool(acc0)), _p(dx),
-                                                   ctypes.c_int32(dx.stride(0) if dx is not None else 0), int(bool(accx)),
+    self._ck(self.lib.er_cross_v2_epilogue_bwd_acc(_p(x0), _p(x), _p(u), _p(bias), diag_scale, _p(dout),
+                                                   dout.stride(0), B, d, _p(dx0), dx0.stride(0), acc0, _p(dx),
+                                                   dx.stride(0) if dx is not None else 0, accx,
                                                    _p(du), _stream()), 'er_cross_v2_epilogue_bwd_acc')
     return du
 
@@ -1890,7 +1893,7 @@ class HipBackend(object):
       dh = torch.empty_like(h)
     assert dh.shape == h.shape and dh.is_contiguous()
     self._ck(
-        self.lib.er_din_concat_bwd(_p(q), _p(h), _p(_f32c(dout)), B, L, E, _p(dq), 0, _p(dh), int(bool(acc_h)), _stream()),
+        self.lib.er_din_concat_bwd(_p(q), _p(h), _p(_f32c(dout)), B, L, E, _p(dq), 0, _p(dh), acc_h, _stream()),
         'er_din_concat_bwd')
     return dq, dh
 
@@ -1914,9 +1917,8 @@ class HipBackend(object):
     N = w.shape[1]
     z = torch.empty(B * L, N, dtype=torch.float32, device=h.device)
     self._log_gemm('gemm_f32_din_kernel<true, false, 1>', None, B * L, N, 4 * E)
-    self._ck(self.lib.er_din_gemm_fwd(_p(q), ctypes.c_int32(q.stride(0)), _p(h), ctypes.c_int32(E), B, L, E, _p(w),
-                                      ctypes.c_int32(w.stride(0)), N, _p(bias), _p(z), ctypes.c_int32(N), _p(col_stats),
-                                      _stream()), 'er_din_gemm_fwd')
+    self._ck(self.lib.er_din_gemm_fwd(_p(q), q.stride(0), _p(h), E, B, L, E, _p(w), w.stride(0), N, _p(bias), _p(z), N,
+                                      _p(col_stats), _stream()), 'er_din_gemm_fwd')
     return z
 
   def din_gemm_wgrad(self, q, h, dz, out, accumulate=True):
@@ -1925,9 +1927,8 @@ class HipBackend(object):
     N = dz.shape[1]
     assert dz.shape[0] == B * L and dz.stride(1) == 1 and out.shape == (4 * E, N) and out.stride(1) == 1
     self._log_gemm('gemm_f32_din_kernel<false, false, 1>', None, 4 * E, N, B * L)
-    self._ck(self.lib.er_din_gemm_wgrad(_p(q), ctypes.c_int32(q.stride(0)), _p(h), ctypes.c_int32(E), B, L, E, _p(dz),
-                                        ctypes.c_int32(dz.stride(0)), N, _p(out), ctypes.c_int32(out.stride(0)),
-                                        int(bool(accumulate)), _stream()), 'er_din_gemm_wgrad')
+    self._ck(self.lib.er_din_gemm_wgrad(_p(q), q.stride(0), _p(h), E, B, L, E, _p(dz), dz.stride(0), N, _p(out),
+                                        out.stride(0), accumulate, _stream()), 'er_din_gemm_wgrad')
     return out
 
   def din_gemm_dgrad(self, dz, w, q, h, dh=None, acc_h=False):
@@ -1940,13 +1941,11 @@ class HipBackend(object):
       assert not acc_h
       dh = torch.empty_like(h)
     assert dh.shape == h.shape and dh.is_contiguous()
-    self.lib.er_din_dq_partial_floats.restype = ctypes.c_int64
     n_part = int(self.lib.er_din_dq_partial_floats(B, L, E))
     partial = torch.empty(n_part, dtype=torch.float32, device=h.device)
     self._log_gemm('gemm_f32_din_kernel<true, true, 2>', None, B * L, 4 * E, N)
-    self._ck(self.lib.er_din_gemm_dgrad(_p(dz), ctypes.c_int32(dz.stride(0)), N, _p(w), ctypes.c_int32(w.stride(0)), _p(q),
-                                        ctypes.c_int32(q.stride(0)), _p(h), ctypes.c_int32(E), B, L, E, _p(dq), ctypes.c_int32(E),
-                                        _p(dh), ctypes.c_int32(E), int(bool(acc_h)), _p(partial), _stream()), 'er_din_gemm_dgrad')
+    self._ck(self.lib.er_din_gemm_dgrad(_p(dz), dz.stride(0), N, _p(w), w.stride(0), _p(q), q.stride(0), _p(h), E, B, L,
+                                        E, _p(dq), E, _p(dh), E, acc_h, _p(partial), _stream()), 'er_din_gemm_dgrad')
     return dq, dh
 
   def din_pool_fwd(self, scores, hist, seq_len, scale=1.0):
@@ -1954,7 +1953,7 @@ class HipBackend(object):
     probs = torch.empty(B, L, dtype=torch.float32, device=hist.device)
     out = torch.empty(B, E, dtype=torch.float32, device=hist.device)
     self._ck(
-        self.lib.er_din_pool_fwd(_p(_f32c(scores)), _p(_f32c(hist)), _p(seq_len), B, L, E, ctypes.c_float(scale),
+        self.lib.er_din_pool_fwd(_p(_f32c(scores)), _p(_f32c(hist)), _p(seq_len), B, L, E, scale,
                                  _p(probs), _p(out), _stream()), 'er_din_pool_fwd')
     return out, probs
 
@@ -1967,7 +1966,7 @@ class HipBackend(object):
     assert dhist.shape == hist.shape and dhist.is_contiguous()
     self._ck(
         self.lib.er_din_pool_bwd(_p(probs), _p(hist), _p(seq_len), _p(_f32c(dout)), B, L, E,
-                                 ctypes.c_float(scale), _p(dscores), _p(dhist), int(bool(acc_h)), _stream()), 'er_din_pool_bwd')
+                                 scale, _p(dscores), _p(dhist), acc_h, _stream()), 'er_din_pool_bwd')
     return dscores, dhist
 
   # -- K8b BST transformer block (model/multi_tower_bst.py)
@@ -1975,11 +1974,10 @@ class HipBackend(object):
   BST_MAX_E = 64
 
   def bst_param_count(self, E, H):
-    self.lib.er_bst_param_count.restype = ctypes.c_int64
     return int(self.lib.er_bst_param_count(int(E), int(H)))
 
   def bst_grid(self, B):
-    return int(self.lib.er_bst_grid(ctypes.c_int64(int(B))))
+    return int(self.lib.er_bst_grid(int(B)))
 
   def _bst_flops(self, B, T, E, H):
     # per example: Q / K / V (2 T sum p_h^2 each), S and P V (2 T^2 E each), the two E x E projections (2 T E^2 each)
@@ -1995,7 +1993,7 @@ class HipBackend(object):
     B, L, E = hist.shape
     assert key.shape == (B, E) and seq_len.dtype == torch.int32
     out = torch.empty(B, T * E, dtype=torch.float32, device=hist.device)
-    self._ck(self.lib.er_bst_fwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), ctypes.c_int64(B), L, T,
+    self._ck(self.lib.er_bst_fwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), B, L, T,
                                  E, H, _p(out), _stream()), 'er_bst_fwd')
     if self.op_log is not None:
       self.op_log.append(('er::bst_fwd_kernel', self._bst_flops(B, T, E, H)))
@@ -2012,9 +2010,8 @@ class HipBackend(object):
     assert dhist.shape == hist.shape and dhist.is_contiguous()
     rows = self.bst_grid(B)
     partials = torch.empty(rows * self.bst_param_count(E, H), dtype=torch.float32, device=hist.device)
-    self._ck(self.lib.er_bst_bwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), _p(_f32c(dout)),
-                                 ctypes.c_int64(B), L, T, E, H, _p(dkey), _p(dhist), int(bool(acc_h)), _p(partials),
-                                 _stream()), 'er_bst_bwd')
+    self._ck(self.lib.er_bst_bwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), _p(_f32c(dout)), B, L,
+                                 T, E, H, _p(dkey), _p(dhist), acc_h, _p(partials), _stream()), 'er_bst_bwd')
     self._ck(self.lib.er_bst_grad_reduce(_p(partials), rows, E, H, grads.table, 1, _stream()), 'er_bst_grad_reduce')
     if self.op_log is not None:
       self.op_log.append(('er::bst_bwd_kernel', 2.0 * self._bst_flops(B, T, E, H)))
@@ -2024,11 +2021,10 @@ class HipBackend(object):
   AUTOINT_LDS_BUDGET = 65536  # bytes per workgroup (csrc/er_autoint.hip)
 
   def autoint_lds_bytes(self, F, H, ds):
-    self.lib.er_autoint_lds_bytes.restype = ctypes.c_int64
     return int(self.lib.er_autoint_lds_bytes(int(F), int(H), int(ds)))
 
   def autoint_epb(self, F, H, ds, bwd):
-    return int(self.lib.er_autoint_epb(int(F), int(H), int(ds), int(bool(bwd))))
+    return int(self.lib.er_autoint_epb(int(F), int(H), int(ds), bwd))
 
   def autoint_pack(self, wq, wk, wv, wr):
     """[wq | wk | wv | wr] ([din, d] each) -> [din, 4d]: one launch."""
@@ -2046,7 +2042,7 @@ class HipBackend(object):
     assert w == 4 * d and rows % F == 0
     B = rows // F
     y = torch.empty(rows, d, dtype=torch.float32, device=qkvr.device)
-    self._ck(self.lib.er_autoint_attn_fwd(_p(_f32c(qkvr)), ctypes.c_int64(B), F, H, ds, _p(y), _stream()),
+    self._ck(self.lib.er_autoint_attn_fwd(_p(_f32c(qkvr)), B, F, H, ds, _p(y), _stream()),
              'er_autoint_attn_fwd')
     if self.op_log is not None:
       self.op_log.append(('er::autoint_attn_fwd_kernel', 4.0 * B * F * F * d))
@@ -2058,7 +2054,7 @@ class HipBackend(object):
     B = rows // F
     assert y.shape == dy.shape == (rows, H * ds)
     dq = torch.empty_like(qkvr)
-    self._ck(self.lib.er_autoint_attn_bwd(_p(_f32c(qkvr)), _p(_f32c(y)), _p(_f32c(dy)), ctypes.c_int64(B), F, H, ds,
+    self._ck(self.lib.er_autoint_attn_bwd(_p(_f32c(qkvr)), _p(_f32c(y)), _p(_f32c(dy)), B, F, H, ds,
                                           _p(dq), _stream()), 'er_autoint_attn_bwd')
     if self.op_log is not None:
       self.op_log.append(('er::autoint_attn_bwd_kernel', 12.0 * B * F * F * H * ds))
@@ -2093,11 +2089,10 @@ class HipBackend(object):
 
   @staticmethod
   def _kv_job(kv, ids, rows_out, limit=None):
-    opt = lambda t: 0 if t is None else t.data_ptr()
     return KvJob(ids.data_ptr(), ids.numel(), kv['keys'].data_ptr(), kv['rows'].data_ptr(), kv['keys'].numel(),
                  kv['next_row'].data_ptr(), kv['var'].data_ptr(), kv['seed'], rows_out.data_ptr(),
-                 kv['overflow'].data_ptr(), kv['capacity'], kv['dim'], kv['mean'], kv['stddev'], opt(limit),
-                 opt(kv['freq']), opt(kv['version']), opt(kv['n_keys']), opt(kv['step']), kv['filter_freq'],
+                 kv['overflow'].data_ptr(), kv['capacity'], kv['dim'], kv['mean'], kv['stddev'], _p(limit),
+                 _p(kv['freq']), _p(kv['version']), _p(kv['n_keys']), _p(kv['step']), kv['filter_freq'],
                  kv['var'].stride(0) if kv['var'].stride(0) != kv['dim'] else 0)
 
   def kv_translate(self, kv, ids, rows_out, insert):
@@ -2106,7 +2101,7 @@ class HipBackend(object):
     assert ids.dtype == torch.int64 and rows_out.dtype == torch.int64 and ids.is_contiguous() and rows_out.is_contiguous()
     assert ids.numel() == rows_out.numel()
     job = self._kv_job(kv, ids, rows_out)
-    self._ck(self.lib.er_kv_translate_job(ctypes.byref(job), int(bool(insert)), _stream()), 'er_kv_translate_job')
+    self._ck(self.lib.er_kv_translate_job(ctypes.byref(job), insert, _stream()), 'er_kv_translate_job')
 
   def kv_jobs_create(self, jobs):
     """jobs: [(kv, ids, rows_out[, n_limit])] -> the device-resident descriptor table of er_kv_translate_multi (built
@@ -2130,7 +2125,7 @@ class HipBackend(object):
     if handle['blocks'] == 0:
       return
     self._ck(self.lib.er_kv_translate_multi(_p(handle['table']), _p(handle['blk_start']), handle['n'], handle['blocks'],
-                                            int(bool(insert)), _stream()), 'er_kv_translate_multi')
+                                            insert, _stream()), 'er_kv_translate_multi')
 
   def kv_route_create(self, jobs, world):
     """Embedding-parallel hash tables: jobs [(ids, rows_out[, n_limit])] -> the buffers and descriptor table of
@@ -2160,13 +2155,13 @@ class HipBackend(object):
 
   def kv_bucket(self, h):
     if h['blocks']:
-      self._ck(self.lib.er_kv_bucket(_p(h['table']), _p(h['blk_start']), h['n'], h['blocks'], h['world'], ctypes.c_int64(h['C']),
+      self._ck(self.lib.er_kv_bucket(_p(h['table']), _p(h['blk_start']), h['n'], h['blocks'], h['world'], h['C'],
                                      _p(h['send']), _p(h['counts']), _stream()), 'er_kv_bucket')
 
   def kv_unbucket(self, h):
     if h['blocks']:
       self._ck(self.lib.er_kv_unbucket(_p(h['table']), _p(h['blk_start']), h['n'], h['blocks'], h['world'],
-                                       ctypes.c_int64(h['C']), _p(h['back']), _stream()), 'er_kv_unbucket')
+                                       h['C'], _p(h['back']), _stream()), 'er_kv_unbucket')
 
   def kv_export(self, kv):
     """(keys ascending, arena rows) of the table's materialised ids (host sync)."""
@@ -2174,7 +2169,7 @@ class HipBackend(object):
     keys = torch.empty(n_max, dtype=torch.int64, device=kv['keys'].device)
     rows = torch.empty(n_max, dtype=torch.int32, device=kv['keys'].device)
     count = torch.zeros(1, dtype=torch.int32, device=kv['keys'].device)
-    self._ck(self.lib.er_kv_export(_p(kv['keys']), _p(kv['rows']), ctypes.c_int64(kv['keys'].numel()), _p(keys), _p(rows),
+    self._ck(self.lib.er_kv_export(_p(kv['keys']), _p(kv['rows']), kv['keys'].numel(), _p(keys), _p(rows),
                                    _p(count), _stream()), 'er_kv_export')
     n = int(count.item())
     keys, rows = keys[:n], rows[:n]
@@ -2190,9 +2185,8 @@ class HipBackend(object):
     keys = torch.empty(n_max, dtype=torch.int64, device=dev)
     rows, freq, version = (torch.empty(n_max, dtype=torch.int32, device=dev) for _ in range(3))
     count = torch.zeros(1, dtype=torch.int32, device=dev)
-    opt = lambda t: None if t is None else _p(t)
-    self._ck(self.lib.er_kv_export_all(_p(kv['keys']), _p(kv['rows']), opt(kv['freq']), opt(kv['version']),
-                                       ctypes.c_int64(slots), _p(keys), _p(rows), _p(freq), _p(version), _p(count), _stream()),
+    self._ck(self.lib.er_kv_export_all(_p(kv['keys']), _p(kv['rows']), _p(kv['freq']), _p(kv['version']),
+                                       slots, _p(keys), _p(rows), _p(freq), _p(version), _p(count), _stream()),
              'er_kv_export_all')
     n = int(count.item())
     order = torch.argsort(keys[:n])
@@ -2206,17 +2200,16 @@ class HipBackend(object):
     rows32 = rows.to(dev, torch.int32).contiguous()
     kv['keys'].fill_(-1)
     kv['rows'].fill_(-1)
-    opt = lambda t: None if t is None else _p(t)
     if kv['freq'] is not None:
       kv['freq'].zero_()
       freq = None if freq is None else freq.to(dev, torch.int32).contiguous()
     if kv['version'] is not None:
       kv['version'].zero_()
       version = None if version is None else version.to(dev, torch.int32).contiguous()
-    self._ck(self.lib.er_kv_rebuild(opt(keys), opt(rows32), opt(freq) if kv['freq'] is not None else None,
-                                    opt(version) if kv['version'] is not None else None, ctypes.c_int64(keys.numel()),
-                                    _p(kv['keys']), _p(kv['rows']), opt(kv['freq']), opt(kv['version']),
-                                    ctypes.c_int64(kv['keys'].numel()), _p(kv['overflow']), _stream()), 'er_kv_rebuild')
+    self._ck(self.lib.er_kv_rebuild(_p(keys), _p(rows32), _p(freq) if kv['freq'] is not None else None,
+                                    _p(version) if kv['version'] is not None else None, keys.numel(),
+                                    _p(kv['keys']), _p(kv['rows']), _p(kv['freq']), _p(kv['version']),
+                                    kv['keys'].numel(), _p(kv['overflow']), _stream()), 'er_kv_rebuild')
     kv['next_row'].fill_(int((rows32 >= 0).sum().item()))
     if kv['n_keys'] is not None:
       kv['n_keys'].fill_(keys.numel())
@@ -2226,32 +2219,27 @@ class HipBackend(object):
     """z[(b, d), h * H0 + m] = xi[b, h, d] * x0[b, m, d]; xi addressed by strides = (stride_b, stride_h, stride_d)."""
     B, H0, D = x0.shape
     assert z.shape == (B * D, H * H0) and z.is_contiguous() and x0.is_contiguous()
-    self._ck(self.lib.er_cin_outer_fwd(_p(xi), ctypes.c_int64(strides[0]), ctypes.c_int32(strides[1]),
-                                       ctypes.c_int32(strides[2]), ctypes.c_int32(H), _p(x0), ctypes.c_int32(H0),
-                                       ctypes.c_int32(D), ctypes.c_int64(B), _p(z), _stream()), 'er_cin_outer_fwd')
+    self._ck(self.lib.er_cin_outer_fwd(_p(xi), strides[0], strides[1], strides[2], H, _p(x0), H0, D, B, _p(z),
+                                       _stream()), 'er_cin_outer_fwd')
 
   def cin_act_pool_fwd(self, c, bias, B, D, pooled, col0):
     """c [B * D, N] <- relu(c + bias) in place; pooled[:, col0 : col0 + N] = its sum over d."""
     N = c.shape[1]
     assert c.is_contiguous() and pooled.stride(1) == 1
-    self._ck(self.lib.er_cin_act_pool_fwd(_p(c), _p(bias), ctypes.c_int64(B), ctypes.c_int32(D), ctypes.c_int32(N),
-                                          _p(pooled), ctypes.c_int32(pooled.stride(0)), ctypes.c_int32(col0), _stream()),
+    self._ck(self.lib.er_cin_act_pool_fwd(_p(c), _p(bias), B, D, N, _p(pooled), pooled.stride(0), col0, _stream()),
              'er_cin_act_pool_fwd')
 
   def cin_act_pool_bwd(self, fm, dpooled, col0, dnext, B, D, dc):
     N = fm.shape[1]
     assert fm.is_contiguous() and dc.is_contiguous() and dpooled.stride(1) == 1 and (dnext is None or dnext.is_contiguous())
-    self._ck(self.lib.er_cin_act_pool_bwd(_p(fm), _p(dpooled), ctypes.c_int32(dpooled.stride(0)), ctypes.c_int32(col0),
-                                          _p(dnext), ctypes.c_int64(B), ctypes.c_int32(D), ctypes.c_int32(N), _p(dc),
+    self._ck(self.lib.er_cin_act_pool_bwd(_p(fm), _p(dpooled), dpooled.stride(0), col0, _p(dnext), B, D, N, _p(dc),
                                           _stream()), 'er_cin_act_pool_bwd')
 
   def cin_outer_bwd(self, dz, xi, strides, H, x0, dxi, add_xi, dx0):
     B, H0, D = x0.shape
     assert dz.shape == (B * D, H * H0) and dz.is_contiguous() and dx0.is_contiguous()
-    self._ck(self.lib.er_cin_outer_bwd(_p(dz), _p(xi), ctypes.c_int64(strides[0]), ctypes.c_int32(strides[1]),
-                                       ctypes.c_int32(strides[2]), ctypes.c_int32(H), _p(x0), ctypes.c_int32(H0),
-                                       ctypes.c_int32(D), ctypes.c_int64(B), _p(dxi), int(bool(add_xi)), _p(dx0),
-                                       _stream()), 'er_cin_outer_bwd')
+    self._ck(self.lib.er_cin_outer_bwd(_p(dz), _p(xi), strides[0], strides[1], strides[2], H, _p(x0), H0, D, B, _p(dxi),
+                                       add_xi, _p(dx0), _stream()), 'er_cin_outer_bwd')
 
   # -- K9 MLP pieces
   def bn_act_fwd(self, x, bias, gamma, beta, use_bn, eps, momentum, moving_mean, moving_var, act):
@@ -2261,7 +2249,7 @@ class HipBackend(object):
     invstd = torch.empty(N, dtype=torch.float32, device=x.device) if use_bn else None
     self._ck(
         self.lib.er_bn_act_fwd(_p(_f32c(x)), _p(bias), _p(gamma), _p(beta), B, N, int(use_bn),
-                               ctypes.c_float(eps), ctypes.c_float(momentum), _p(moving_mean), _p(moving_var),
+                               eps, momentum, _p(moving_mean), _p(moving_var),
                                int(act), _p(y), _p(mean), _p(invstd), _stream()), 'er_bn_act_fwd')
     return y, mean, invstd
 
@@ -2300,8 +2288,8 @@ class HipBackend(object):
       pp = (ctypes.c_void_p * len(chunk))(*[t.data_ptr() for t in chunk])
       ww = (ctypes.c_int32 * len(chunk))(*[t.shape[1] for t in chunk])
       ll = (ctypes.c_int32 * len(chunk))(*[t.stride(0) for t in chunk])
-      self._ck(self.lib.er_concat_cols_b16(pp, ww, ll, len(chunk), B, _p(dst), ctypes.c_int32(out.stride(0)), _p(outb),
-                                           ctypes.c_int32(0 if outb is None else outb.stride(0)), _stream()),
+      self._ck(self.lib.er_concat_cols_b16(pp, ww, ll, len(chunk), B, _p(dst), out.stride(0), _p(outb),
+                                           0 if outb is None else outb.stride(0), _stream()),
                'er_concat_cols')
     return out
 
@@ -2315,7 +2303,7 @@ class HipBackend(object):
     dx = torch.empty_like(x)
     dev = x.device
     dxb = bf16_state.new_copy(dx) if bf16_state is not None else None
-    ldb = ctypes.c_int32(0 if dxb is None else dxb.stride(0))
+    ldb = 0 if dxb is None else dxb.stride(0)
     acc = into is not None
     if acc:
       dbias, dgamma, dbeta = into
@@ -2327,14 +2315,14 @@ class HipBackend(object):
     if partial is not None:
       self._ck(
           self.lib.er_bn_act_bwd_from_partials_ld_b16(_p(x), _p(bias), _p(gamma), _p(y), _p(mean), _p(invstd), _p(dy),
-                                                      ctypes.c_int32(dy.stride(0)), B, N, int(use_bn), int(act), _p(partial),
-                                                      ctypes.c_int32(self.gemm_row_tiles(B)), _p(dx), _p(dbias), _p(dgamma),
+                                                      dy.stride(0), B, N, int(use_bn), int(act), _p(partial),
+                                                      self.gemm_row_tiles(B), _p(dx), _p(dbias), _p(dgamma),
                                                       _p(dbeta), int(acc), _p(dxb), ldb, _stream()),
           'er_bn_act_bwd_from_partials_ld')
     else:  # (dy may be a column block of a wider gradient - ConcatFn's backward -: read in place)
       self._ck(
           self.lib.er_bn_act_bwd_ld_b16(_p(x), _p(bias), _p(gamma), _p(y), _p(mean), _p(invstd), _p(dy),
-                                        ctypes.c_int32(dy.stride(0)), B, N, int(use_bn), int(act), _p(dx), _p(dbias),
+                                        dy.stride(0), B, N, int(use_bn), int(act), _p(dx), _p(dbias),
                                         _p(dgamma), _p(dbeta), int(acc), _p(dxb), ldb, _stream()), 'er_bn_act_bwd_ld')
     if acc:
       return dx, None, None, None
@@ -2346,7 +2334,7 @@ class HipBackend(object):
     if out is None:
       assert not accumulate
       out = torch.empty(cols, dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_colsum_acc(_p(x), rows, cols, x.stride(0), _p(out), int(bool(accumulate)), _stream()),
+    self._ck(self.lib.er_colsum_acc(_p(x), rows, cols, x.stride(0), _p(out), accumulate, _stream()),
              'er_colsum_acc')
     return out
 
@@ -2356,7 +2344,7 @@ class HipBackend(object):
     mean = torch.empty(N, dtype=torch.float32, device=x.device)
     invstd = torch.empty(N, dtype=torch.float32, device=x.device)
     self._ck(
-        self.lib.er_dice_fwd(_p(_f32c(x)), _p(alpha), B, N, ctypes.c_float(eps), ctypes.c_float(momentum),
+        self.lib.er_dice_fwd(_p(_f32c(x)), _p(alpha), B, N, eps, momentum,
                              _p(moving_mean), _p(moving_var), _p(y), _p(mean), _p(invstd), _stream()),
         'er_dice_fwd')
     return y, mean, invstd
@@ -2380,7 +2368,7 @@ class HipBackend(object):
     probs = torch.empty(B, dtype=torch.float32, device=dev)
     self._ck(
         self.lib.er_sigmoid_ce_fwd_bwd(_p(_f32c(logits)), _p(_f32c(labels)), _p(weights), B,
-                                       ctypes.c_float(loss_scale), _p(loss), _p(dlogits), _p(probs), _stream()),
+                                       loss_scale, _p(loss), _p(dlogits), _p(probs), _stream()),
         'er_sigmoid_ce_fwd_bwd')
     return loss, dlogits, probs
 
@@ -2393,7 +2381,7 @@ class HipBackend(object):
       B = z.numel()
       loss = torch.empty(1, dtype=torch.float32, device=z.device)
       dz = torch.empty(B, dtype=torch.float32, device=z.device)
-      q.logits, q.labels, q.weights = z.data_ptr(), y.data_ptr(), _ptr(weights)
+      q.logits, q.labels, q.weights = z.data_ptr(), y.data_ptr(), _p(weights)
       q.B, q.loss_scale = B, float(scale)
       q.loss_out, q.dlogits, q.probs_out = loss.data_ptr(), dz.data_ptr(), None
       outs.append((loss, dz))
@@ -2417,8 +2405,7 @@ class HipBackend(object):
     dst = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in reports])
     n_part = 0 if emb_partials is None else emb_partials.numel()
     n_dense = 0 if dense_partials is None else dense_partials.numel()
-    self._ck(self.lib.er_reg_total_loss(_p(emb_partials), ctypes.c_int32(n_part), ctypes.c_float(emb_scale),
-                                        _p(dense_partials), ctypes.c_int32(n_dense), src, dst, ctypes.c_int32(n),
+    self._ck(self.lib.er_reg_total_loss(_p(emb_partials), n_part, emb_scale, _p(dense_partials), n_dense, src, dst, n,
                                         _p(reg_out), _p(total_out), _stream()), 'er_reg_total_loss')
 
   # the binary head of a rank model (dense(K -> 1) + sigmoid cross entropy + their gradients) as ONE launch, its dW / db
@@ -2441,11 +2428,10 @@ class HipBackend(object):
       assert src.y is not None and src.y.data_ptr() == x.data_ptr() and src.zbias is None
       out['bn_partials'] = f(T, K, 2)
       sz, smean, sinv, sld, sact = src.z, src.mean, src.invstd, src.z.stride(0), src.act
-    self._ck(self.lib.er_head_sigmoid_ce(_p(x), ctypes.c_int32(x.stride(0)), _p(w), _p(b), _p(_f32c(labels)), ctypes.c_int32(B),
-                                         ctypes.c_int32(K), ctypes.c_float(loss_scale), _p(out['logits']), _p(out['probs']),
-                                         _p(out['dlogits']), _p(out['dx']), _p(out['loss_partials']), _p(out['wb_partials']),
-                                         _p(sz), ctypes.c_int32(sld), _p(smean), _p(sinv), ctypes.c_int32(int(sact)),
-                                         _p(out['bn_partials']), _stream()), 'er_head_sigmoid_ce')
+    self._ck(self.lib.er_head_sigmoid_ce(_p(x), x.stride(0), _p(w), _p(b), _p(_f32c(labels)), B, K, loss_scale,
+                                         _p(out['logits']), _p(out['probs']), _p(out['dlogits']), _p(out['dx']),
+                                         _p(out['loss_partials']), _p(out['wb_partials']), _p(sz), sld, _p(smean),
+                                         _p(sinv), int(sact), _p(out['bn_partials']), _stream()), 'er_head_sigmoid_ce')
     return out
 
   def loss_tail(self, emb_partials, emb_scale, dense_partials, losses, reports, reg_out, total_out, jobs=(), defer=False):
@@ -2476,17 +2462,17 @@ class HipBackend(object):
     if defer:
       assert self._deferred_loss_tail is None, 'the previous deferred loss tail was never run'
       vp = ctypes.c_void_p
-      job = LossTailJob(_ptr(emb_partials), n_part, float(emb_scale), _ptr(dense_partials), n_dense,
+      job = LossTailJob(_p(emb_partials), n_part, float(emb_scale), _p(dense_partials), n_dense,
                         ctypes.cast(src, vp), ctypes.cast(dst, vp), ctypes.cast(parts, vp), ctypes.cast(scales, vp),
                         ctypes.cast(divs, vp), ctypes.cast(values, vp), n, ctypes.cast(arr, vp), len(jobs),
-                        _ptr(reg_out), _ptr(total_out))
+                        _p(reg_out), _p(total_out))
       # (the record points into the ctypes arrays and the tensors: both stay alive with it)
       self._deferred_loss_tail = (job, (src, dst, parts, scales, divs, values, arr, emb_partials, dense_partials, list(losses),
                                         list(reports), reg_out, total_out, list(jobs)))
       return
-    self._ck(self.lib.er_loss_tail(_p(emb_partials), ctypes.c_int32(n_part), ctypes.c_float(emb_scale), _p(dense_partials),
-                                   ctypes.c_int32(n_dense), src, dst, parts, scales, divs, values, ctypes.c_int32(n), arr,
-                                   ctypes.c_int32(len(jobs)), _p(reg_out), _p(total_out), _stream()), 'er_loss_tail')
+    self._ck(self.lib.er_loss_tail(_p(emb_partials), n_part, emb_scale, _p(dense_partials),
+                                   n_dense, src, dst, parts, scales, divs, values, n, arr,
+                                   len(jobs), _p(reg_out), _p(total_out), _stream()), 'er_loss_tail')
 
   # the deferred loss tail is per THREAD: the embedding-parallel tests run their ranks as threads over this one backend
   _tail_tls = threading.local()
@@ -2511,28 +2497,24 @@ class HipBackend(object):
       return
     self._deferred_loss_tail = None
     j = pending[0]
-    I32, F32, VP = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_void_p)
-    self._ck(self.lib.er_loss_tail(ctypes.c_void_p(j.emb_partials), ctypes.c_int32(j.n_partials), ctypes.c_float(j.emb_scale),
-                                   ctypes.c_void_p(j.dense_partials), ctypes.c_int32(j.n_dense), ctypes.cast(j.losses, VP),
-                                   ctypes.cast(j.report, VP), ctypes.cast(j.loss_parts, I32), ctypes.cast(j.loss_scales, F32),
-                                   ctypes.cast(j.loss_divs, F32), ctypes.cast(j.loss_values, VP), ctypes.c_int32(j.n_losses),
-                                   ctypes.cast(j.jobs, ctypes.POINTER(TailJob)), ctypes.c_int32(j.n_jobs),
-                                   ctypes.c_void_p(j.reg_out), ctypes.c_void_p(j.total_out), _stream()), 'er_loss_tail')
+    self._ck(self.lib.er_loss_tail(j.emb_partials, j.n_partials, j.emb_scale, j.dense_partials, j.n_dense, j.losses,
+                                   j.report, j.loss_parts, j.loss_scales, j.loss_divs, j.loss_values, j.n_losses, j.jobs,
+                                   j.n_jobs, j.reg_out, j.total_out, _stream()), 'er_loss_tail')
 
   def l2_partials(self, w, coef, partials):
     """partials[b] = sum over weights [256 b, 256 b + 256) of 0.5 * coef * w^2 (what dense_opt_step(l2_partials=) keeps
     current from then on)."""
     assert partials.numel() == (w.numel() + 255) // 256
-    self._ck(self.lib.er_l2_partials(_p(w), _p(coef), ctypes.c_int64(w.numel()), _p(partials), _stream()),
+    self._ck(self.lib.er_l2_partials(_p(w), _p(coef), w.numel(), _p(partials), _stream()),
              'er_l2_partials')
 
   def reduce_sum(self, partials, scale, out, accumulate=False):
     self._ck(
-        self.lib.er_reduce_sum(_p(partials), partials.numel(), ctypes.c_float(scale), _p(out), int(accumulate),
+        self.lib.er_reduce_sum(_p(partials), partials.numel(), scale, _p(out), int(accumulate),
                                _stream()), 'er_reduce_sum')
 
   def l2_loss(self, w, coef, out, accumulate=False):
-    self._ck(self.lib.er_l2_loss(_p(w), _p(coef), ctypes.c_int64(w.numel()), _p(out), int(accumulate), _stream()),
+    self._ck(self.lib.er_l2_loss(_p(w), _p(coef), w.numel(), _p(out), int(accumulate), _stream()),
              'er_l2_loss')
 
   # -- K11 MMoE
@@ -2561,7 +2543,7 @@ class HipBackend(object):
     n_slots = table.shape[0]
     cap = 0 if history is None else history.numel() // 2
     self._ck(self.lib.er_hyper_select(_p(table), _p(counter), n_slots, table[0].numel(), _p(out), _p(history),
-                                      ctypes.c_int64(cap), ctypes.c_int32(history_index), _stream()),
+                                      cap, history_index, _stream()),
              'er_hyper_select')
 
   def step_prologue(self, table, counter, out, history=None, zero=None, history_index=HYPER_LR_T, decay_tables=None,
@@ -2581,24 +2563,22 @@ class HipBackend(object):
       hn = ho.numel() - 1
       assert hout.dtype == torch.int64 and hout.numel() >= hn
     self._ck(self.lib.er_step_prologue_hash(_p(table), _p(counter), n_slots, table[0].numel(), _p(out), _p(history),
-                                            ctypes.c_int64(cap), ctypes.c_int32(history_index), _p(zero),
-                                            ctypes.c_int64(nz), decay_tables['handle'] if decay_tables else None,
-                                            _p(hb), _p(ho), ctypes.c_int64(hn), ctypes.c_int64(int(hpc)), _p(hk),
-                                            ctypes.c_int(int(hdrop)), _p(hout), _stream()), 'er_step_prologue_hash')
+                                            cap, history_index, _p(zero), nz,
+                                            decay_tables['handle'] if decay_tables else None, _p(hb), _p(ho), hn,
+                                            int(hpc), _p(hk), int(hdrop), _p(hout), _stream()), 'er_step_prologue_hash')
 
   # -- closed-form replay of TF-Adam's decay-only steps (csrc/er_decay.h)
   def decay_tables_create(self, lr_hist, step_counter, beta1, beta2):
     """The tables of the closed-form replay for the history buffer `lr_hist` ([2 * capacity]) - or None when the
     betas are outside its range (the groups then keep the exact step-by-step replay)."""
-    self.lib.er_decay_tables_bytes.restype = ctypes.c_int64
-    if self.lib.er_decay_tables_supported(ctypes.c_float(beta1), ctypes.c_float(beta2)) <= 0:
+    if self.lib.er_decay_tables_supported(beta1, beta2) <= 0:
       return None
     cap = lr_hist.numel() // 2
-    nbytes = int(self.lib.er_decay_tables_bytes(ctypes.c_int64(cap)))
+    nbytes = int(self.lib.er_decay_tables_bytes(cap))
     buf = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=lr_hist.device)
     handle = ctypes.c_void_p()
-    self._ck(self.lib.er_decay_tables_create(_p(buf), ctypes.c_int64(cap), _p(lr_hist), _p(step_counter),
-                                             ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.byref(handle)),
+    self._ck(self.lib.er_decay_tables_create(_p(buf), cap, _p(lr_hist), _p(step_counter),
+                                             beta1, beta2, ctypes.byref(handle)),
              'er_decay_tables_create')
     return {'handle': handle, 'buffer': buf, 'lr_hist': lr_hist, 'step_counter': step_counter,
             'betas': (float(beta1), float(beta2))}
@@ -2630,8 +2610,7 @@ class HipBackend(object):
     variant that runs concurrently with the step (after its catch-up, on another stream)."""
     n = len(groups)
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
-    self._ck(self.lib.er_emb_flush_window(gh, n, ctypes.c_int32(int(n_windows)), ctypes.c_int32(int(lag)),
-                                          ctypes.c_int32(int(max_blocks)), _p(hyper), _stream()),
+    self._ck(self.lib.er_emb_flush_window(gh, n, int(n_windows), int(lag), int(max_blocks), _p(hyper), _stream()),
              'er_emb_flush_window')
 
   def emb_catch_up(self, group, unique_keys, n_unique, hyper):
@@ -2650,7 +2629,7 @@ class HipBackend(object):
     """er_emb_bwd_update for several table groups: one tile launch and one fix launch for all (same results)."""
     n = len(groups)
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
-    self._ck(self.lib.er_emb_bwd_update_multi(gh, n, ctypes.c_int(opt_kind), _p(hyper), _stream()),
+    self._ck(self.lib.er_emb_bwd_update_multi(gh, n, opt_kind, _p(hyper), _stream()),
              'er_emb_bwd_update_multi')
 
   # the end of an embedding-parallel step - owner fix | replicated apply | dense optimizer - as one launch - A/B switch
@@ -2668,8 +2647,8 @@ class HipBackend(object):
       descs[i] = DenseApplyDesc(var.data_ptr(), None if m is None else m.data_ptr(), None if v is None else v.data_ptr(),
                                 dense.data_ptr(), dense.stride(0), var.shape[1], var.shape[0], var.stride(0))
     w, m, v, grad, l2coef, kind, hyp, l2p = dense_opt
-    oj = DenseOptJob(_ptr(w), _ptr(m), _ptr(v), _ptr(grad), _ptr(l2coef), w.numel(), int(kind), _ptr(hyp), _ptr(l2p))
-    self._ck(self.lib.er_emb_owner_update_tail(gh, n, ctypes.c_int(opt_kind), _p(hyper), descs if nt else None, nt,
+    oj = DenseOptJob(_p(w), _p(m), _p(v), _p(grad), _p(l2coef), w.numel(), int(kind), _p(hyp), _p(l2p))
+    self._ck(self.lib.er_emb_owner_update_tail(gh, n, opt_kind, _p(hyper), descs if nt else None, nt,
                                                ctypes.byref(oj), _stream()), 'er_emb_owner_update_tail')
     st = self._bf16_state_of(w)
     if st is not None:
@@ -2687,33 +2666,32 @@ class HipBackend(object):
     n_seg = 0 if counts is None else counts.numel()
     assert counts is None or counts.dtype == torch.int32
     stride = rows if seg_stride is None else int(seg_stride)
-    self._ck(self.lib.er_gradsq_rows(_p(x), ctypes.c_int64(rows), ctypes.c_int32(int(cols)), ctypes.c_int32(x.stride(0)),
-                                     _p(counts), ctypes.c_int32(n_seg), ctypes.c_int64(max(stride, 1)),
-                                     ctypes.c_float(weight), _p(acc), int(bool(accumulate)), _stream()), 'er_gradsq_rows')
+    self._ck(self.lib.er_gradsq_rows(_p(x), rows, int(cols), x.stride(0), _p(counts), n_seg, max(stride, 1), weight,
+                                     _p(acc), accumulate, _stream()), 'er_gradsq_rows')
 
   def gradsq_dense(self, w, grad, l2coef, hyper, acc, accumulate=False):
     """acc[0] (+)= sum (hyper.grad_scale * grad + l2coef * w)^2: the dense gradient as er_dense_opt_step sees it."""
-    self._ck(self.lib.er_gradsq_dense(_p(w), _p(grad), _p(l2coef), ctypes.c_int64(w.numel()), _p(hyper), _p(acc),
-                                      int(bool(accumulate)), _stream()), 'er_gradsq_dense')
+    self._ck(self.lib.er_gradsq_dense(_p(w), _p(grad), _p(l2coef), w.numel(), _p(hyper), _p(acc),
+                                      accumulate, _stream()), 'er_gradsq_dense')
 
   def clip_scale(self, normsq, clip_norm, records, norm_out=None):
     """records [n, HYPER_FLOATS] (device): records[:, HYPER_CLIP] = clip_norm * min(1 / norm, 1 / clip_norm)."""
     assert records.dim() == 2 and records.shape[1] == HYPER_FLOATS and records.is_contiguous()
-    self._ck(self.lib.er_clip_scale(_p(normsq), ctypes.c_float(clip_norm), _p(records), ctypes.c_int32(records.shape[0]),
+    self._ck(self.lib.er_clip_scale(_p(normsq), clip_norm, _p(records), records.shape[0],
                                     _p(norm_out), _stream()), 'er_clip_scale')
 
   def emb_apply_unique(self, group, keys, grads, n_unique, opt_kind, hyper):
     """The row-wise optimizer of emb_bwd_update on ready-made de-duplicated row sums (emb_bwd_reduce[_routed])."""
     assert keys.dtype == torch.int32 and n_unique.dtype == torch.int32 and grads.dim() == 2 and grads.stride(1) == 1
-    self._ck(self.lib.er_emb_apply_unique(group['handle'], _p(keys), _p(grads), ctypes.c_int32(grads.stride(0)),
-                                          _p(n_unique), ctypes.c_int(opt_kind), _p(hyper), _stream()), 'er_emb_apply_unique')
+    self._ck(self.lib.er_emb_apply_unique(group['handle'], _p(keys), _p(grads), grads.stride(0),
+                                          _p(n_unique), opt_kind, _p(hyper), _stream()), 'er_emb_apply_unique')
 
   # -- dense optimizer
   def dense_opt_step(self, w, m, v, grad, l2coef, opt_kind, hyper, l2_partials=None):
     """l2_partials: left holding the per-256-weight sums of 0.5 * l2coef * w_new^2 (the next step's kernel-L2 loss)."""
     self._ck(
-        self.lib.er_dense_opt_step_l2(_p(w), _p(m), _p(v), _p(grad), _p(l2coef), ctypes.c_int64(w.numel()),
-                                      ctypes.c_int(opt_kind), _p(hyper), _p(l2_partials), _stream()),
+        self.lib.er_dense_opt_step_l2(_p(w), _p(m), _p(v), _p(grad), _p(l2coef), w.numel(),
+                                      opt_kind, _p(hyper), _p(l2_partials), _stream()),
         'er_dense_opt_step_l2')
     st = self._bf16_state_of(w)
     if st is not None:
@@ -3552,7 +3530,7 @@ class CrossV2EpilogueFn(torch.autograd.Function):
         sink = None
         t0, acc0, first0 = grad_slot(ctx.slots, x0)
         ret0 = t0 if first0 else None
-      tx = accx = None
+      tx, accx = None, False
       if not ctx.same:
         tx, accx, firstx = grad_slot(ctx.slots, x)
         retx = tx if firstx else None

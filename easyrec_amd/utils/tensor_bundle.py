@@ -21,7 +21,6 @@ CRC-32C values):
     of block + type; an empty metaindex block; an index block (last key of each data block -> BlockHandle); a 48-byte
     footer (metaindex handle, index handle, padding, magic 0xdb4775248b80fb57).
 """
-import ctypes
 import os
 import struct
 from collections import OrderedDict
@@ -44,9 +43,7 @@ _lib = None
 def _crc32c(data):
   global _lib
   if _lib is None:
-    _lib = ctypes.CDLL(kernels.LIB_PATH)
-    _lib.er_crc32c.restype = ctypes.c_uint32
-    _lib.er_crc32c.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_int64]
+    _lib = kernels.load_library(kernels.LIB_PATH)
   return _lib.er_crc32c(0, data, len(data))
 
 

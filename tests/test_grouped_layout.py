@@ -7,6 +7,8 @@ import random
 
 import pytest
 
+from easyrec_amd import kernels
+
 I = ctypes.c_int32
 
 
@@ -53,7 +55,7 @@ def _expected_region(splits_p, flag):
 @pytest.mark.parametrize('mode', ['legacy', 'xcd', 'mixed'])
 @pytest.mark.parametrize('case', range(len(CASES) + 20))
 def test_every_tile_of_every_split_exactly_once(built_lib, case, mode):
-  lib = ctypes.CDLL(built_lib)
+  lib = kernels.load_library(built_lib)
   if case < len(CASES):
     tiles, splits = CASES[case]
   else:
@@ -100,7 +102,7 @@ def test_every_tile_of_every_split_exactly_once(built_lib, case, mode):
 
 
 def test_deepfm_weight_gradients_keep_a_share_of_the_batch_per_xcd(built_lib):
-  lib = ctypes.CDLL(built_lib)
+  lib = kernels.load_library(built_lib)
   tiles = CASES[0][0]
   lay = _layout(lib, tiles, [8] * 6, [1] * 6)
   assert lay[0] == 544 and lay[2][len(tiles)] == 0

@@ -249,9 +249,7 @@ def test_threaded_csv_decode_equals_the_single_pass_decoder(built_lib, threads, 
   max_rows below and above the number of lines.  Host code: no device needed."""
   from easyrec_amd import kernels
   be = kernels.HipBackend.__new__(kernels.HipBackend)  # (host entry points only: no device is touched)
-  import ctypes
-  be.lib = ctypes.CDLL(built_lib)
-  be.lib.er_last_error.restype = ctypes.c_char_p
+  be.lib = kernels.load_library(built_lib)
   rng = np.random.default_rng(seed)
   kinds = [int(k) for k in rng.integers(0, 3, size=9)]
   n_lines = 1500
@@ -281,10 +279,8 @@ def test_threaded_csv_decode_reports_the_first_bad_line(built_lib):
   """a line with too few fields / a cell that is not a number: the same error, naming the SMALLEST failing line, whatever
   thread met it"""
   from easyrec_amd import kernels
-  import ctypes
   be = kernels.HipBackend.__new__(kernels.HipBackend)
-  be.lib = ctypes.CDLL(built_lib)
-  be.lib.er_last_error.restype = ctypes.c_char_p
+  be.lib = kernels.load_library(built_lib)
   good = '1\t2.5\tabc'
   for bad, what in (('1\t2.5', 'fewer than 3 fields'), ('1\t2.5\tabc\tx', 'more than 3 fields'), ('1\tzz\tabc', "'zz' is not a number")):
     rows = [good] * 2000
@@ -304,11 +300,9 @@ def test_integer_columns_are_hashed_as_their_decimal_strings_by_one_native_pass(
   """er_pack_int_decimal_host: the packed decimal strings of an int64 array are Python's str(int) of every value (the
   reference's `_as_string` of an integer column, input.py:356-376) - digits two at a time, 32-bit arithmetic once they
   fit: the boundaries of both, negative values, the int64 extremes."""
-  import ctypes
   from easyrec_amd import kernels
   be = kernels.HipBackend.__new__(kernels.HipBackend)
-  be.lib = ctypes.CDLL(built_lib)
-  be.lib.er_last_error.restype = ctypes.c_char_p
+  be.lib = kernels.load_library(built_lib)
   rng = np.random.default_rng(3)
   edge = [0, -1, 9, 10, 99, 100, 101, 999, 1000, 2**32 - 1, 2**32, 2**32 + 1, 4294967295000, 10**18, -10**18, 2**63 - 1, -2**63]
   vals = np.concatenate([rng.integers(0, 2**32, size=5000), rng.integers(-2**63, 2**63 - 1, size=2000, dtype=np.int64),
@@ -336,9 +330,7 @@ def test_native_tag_and_sequence_split_equals_the_per_row_path(built_lib, config
   from easyrec_amd.protos.feature_config_pb2 import FeatureConfig
   monkeypatch.setattr(kernels, '_BACKEND', None)
   be = kernels.HipBackend.__new__(kernels.HipBackend)  # (host entry points only: no device is touched)
-  import ctypes
-  be.lib = ctypes.CDLL(built_lib)
-  be.lib.er_last_error.restype = ctypes.c_char_p
+  be.lib = kernels.load_library(built_lib)
   monkeypatch.setattr(kernels, '_BACKEND', be)
   cfg = config_util.get_configs_from_pipeline_file(os.path.join(ROOT, 'configs', config))
   feats = list(cfg.feature_config.features)

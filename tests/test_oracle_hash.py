@@ -1,6 +1,5 @@
 """Pins the hashing oracle to TensorFlow's published vectors, then the library's host entry point
 (er_hash_bucket_fast_host) to the oracle."""
-import ctypes
 import json
 import os
 
@@ -88,6 +87,7 @@ def test_sparse_cross_hashed_known_answer_from_the_keras_docs():
 def test_sparse_cross_hashed_host_entry_equals_the_oracle(built_lib):
   """er_sparse_cross_hashed_host (the product's input-stage entry point) against the restatement: random strings of
   0..40 bytes in 2 and 3 columns ('' included: the crossed column does not filter its inputs)."""
+  from easyrec_amd import kernels
   from easyrec_amd.input.input import pack_strings
   rng = np.random.default_rng(5)
   for n_cols, n_rows, buckets in ((2, 300, 1000), (3, 257, 1 << 33)):
@@ -97,13 +97,12 @@ def test_sparse_cross_hashed_host_entry_equals_the_oracle(built_lib):
       strs.append(bytes(rng.integers(1, 256, size=n, dtype=np.uint8)))
     data, offsets = pack_strings(strs)
     exp = hashing.sparse_cross_hashed_columns(data, offsets, n_rows, n_cols, buckets)
-    lib = ctypes.CDLL(built_lib)
+    lib = kernels.load_library(built_lib)
     out = np.empty(n_rows, dtype=np.int64)
     d = np.ascontiguousarray(data, dtype=np.uint8)
     o = np.ascontiguousarray(offsets, dtype=np.int64)
-    rc = lib.er_sparse_cross_hashed_host(d.ctypes.data_as(ctypes.c_void_p), o.ctypes.data_as(ctypes.c_void_p),
-                                         ctypes.c_int64(n_rows), ctypes.c_int32(n_cols), ctypes.c_uint64(buckets),
-                                         ctypes.c_uint64(hashing.DEFAULT_CROSS_HASH_KEY), out.ctypes.data_as(ctypes.c_void_p))
+    rc = lib.er_sparse_cross_hashed_host(d.ctypes.data, o.ctypes.data, n_rows, n_cols, buckets, hashing.DEFAULT_CROSS_HASH_KEY,
+                                         out.ctypes.data)
     assert rc == 0
     assert np.array_equal(out, exp)
     assert (out >= 0).all()  # '' is crossed like any other value

@@ -2,7 +2,7 @@
 """Probe: per-workgroup stamps of emb_bwd_own_kernel inside one eager DeepFM step (er_debug_stamps; 100 MHz wall clock).
 Round 5 layout of the launch: paired tiles (the dim-1 group rides on the dim-16 group's) first, then the one-row tables'
 column-reduction workgroups of both groups."""
-import ctypes, os, sys
+import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import logging; logging.disable(logging.WARNING)
@@ -16,7 +16,7 @@ for b in bs[:5]: est.train_step(b)
 torch.cuda.synchronize()
 be = kernels.hip()
 buf = torch.zeros(4096 * 16, dtype=torch.int64, device='cuda:0')
-be.lib.er_debug_stamps(ctypes.c_void_p(buf.data_ptr()))
+be.lib.er_debug_stamps(buf.data_ptr())
 est.train_step(bs[5]); torch.cuda.synchronize()
 be.lib.er_debug_stamps(None)
 full = buf.cpu().numpy().reshape(-1, 16)
