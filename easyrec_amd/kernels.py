@@ -2060,6 +2060,83 @@ class HipBackend(object):
       self.op_log.append(('er::autoint_attn_bwd_kernel', 12.0 * B * F * F * H * ds))
     return dq
 
+  # -- K8d FiBiNet's field blocks (layers/keras/fibinet.py)
+  def bilinear_lds_bytes(self, F, D):
+    return int(self.lib.er_bilinear_lds_bytes(int(F), int(D)))
+
+  def bilinear_epb(self, F, D, each):
+    return int(self.lib.er_bilinear_epb(int(F), int(D), bool(each)))
+
+  def bilinear_param_count(self, F, D, each):
+    return int(self.lib.er_bilinear_param_count(int(F), int(D), bool(each)))
+
+  def bilinear_fwd(self, x, theta, F, D, each, plus):
+    """x [B, F * D], theta: the packed dense layers (er_bilinear_param_count) -> [B, F (F - 1) / 2] with plus,
+    [B, F (F - 1) / 2 * D] without."""
+    B = x.shape[0]
+    assert x.shape == (B, F * D) and theta.numel() == self.bilinear_param_count(F, D, each)
+    pairs = F * (F - 1) // 2
+    out = torch.empty(B, pairs if plus else pairs * D, dtype=torch.float32, device=x.device)
+    self._ck(self.lib.er_bilinear_fwd(_p(_f32c(x)), _p(_f32c(theta)), B, F, D, bool(each), bool(plus), _p(out),
+                                      _stream()), 'er_bilinear_fwd')
+    if self.op_log is not None:
+      self.op_log.append(('er::bilinear_fwd_kernel', 2.0 * B * ((F - 1) * D * D + pairs * D)))
+    return out
+
+  def bilinear_bwd(self, x, theta, dout, F, D, each, plus, grads, acc=True):
+    """-> dx [B, F * D]; the parameter gradients are added into (acc) or written to `grads` (a BstGradTable: the
+    buffers in theta's order, kernel and bias per dense layer)."""
+    B = x.shape[0]
+    pairs = F * (F - 1) // 2
+    assert dout.shape == (B, pairs if plus else pairs * D)
+    dx = torch.empty_like(x)
+    rows = int(self.lib.er_bilinear_grid(B, F, D, bool(each)))
+    partials = torch.empty(rows * theta.numel(), dtype=torch.float32, device=x.device)
+    self._ck(self.lib.er_bilinear_bwd(_p(_f32c(x)), _p(_f32c(theta)), _p(_f32c(dout)), B, F, D, bool(each), bool(plus),
+                                      _p(dx), _p(partials), _stream()), 'er_bilinear_bwd')
+    self._ck(self.lib.er_bilinear_grad_reduce(_p(partials), rows, F, D, bool(each), grads.table, bool(acc), _stream()),
+             'er_bilinear_grad_reduce')
+    if self.op_log is not None:
+      self.op_log.append(('er::bilinear_bwd_kernel', 6.0 * B * ((F - 1) * D * D + pairs * D)))
+    return dx
+
+  def senet_lds_bytes(self, F, D, G, R):
+    return int(self.lib.er_senet_lds_bytes(int(F), int(D), int(G), int(R)))
+
+  def senet_epb(self, F, D, G, R, ln, bwd):
+    return int(self.lib.er_senet_epb(int(F), int(D), int(G), int(R), bool(ln), bool(bwd)))
+
+  def senet_param_count(self, F, D, G, R, ln):
+    return int(self.lib.er_senet_param_count(int(F), int(D), int(G), int(R), bool(ln)))
+
+  def senet_fwd(self, x, theta, F, D, G, R, skip, ln, want_a1=False):
+    """x [B, F * D], theta: W1, b1, W2, b2 (, gamma, beta) packed -> y [B, F * D] (and a1 [B, R], the excitation's
+    hidden layer after its ReLU, with want_a1)."""
+    B = x.shape[0]
+    assert x.shape == (B, F * D) and theta.numel() == self.senet_param_count(F, D, G, R, ln)
+    y = torch.empty_like(x)
+    a1 = torch.empty(B, R, dtype=torch.float32, device=x.device) if want_a1 else None
+    self._ck(self.lib.er_senet_fwd(_p(_f32c(x)), _p(_f32c(theta)), B, F, D, G, R, bool(skip), bool(ln), _p(y),
+                                   None if a1 is None else _p(a1), _stream()), 'er_senet_fwd')
+    if self.op_log is not None:
+      self.op_log.append(('er::senet_fwd_kernel', 2.0 * B * R * (2 * F * G + F * D)))
+    return (y, a1) if want_a1 else y
+
+  def senet_bwd(self, x, theta, dy, F, D, G, R, skip, ln, grads, acc=True):
+    """-> dx [B, F * D]; the parameter gradients into `grads` as bilinear_bwd does."""
+    B = x.shape[0]
+    assert dy.shape == x.shape
+    dx = torch.empty_like(x)
+    rows = int(self.lib.er_senet_grid(B, F, D, G, R, bool(ln)))
+    partials = torch.empty(rows * theta.numel(), dtype=torch.float32, device=x.device)
+    self._ck(self.lib.er_senet_bwd(_p(_f32c(x)), _p(_f32c(theta)), _p(_f32c(dy)), B, F, D, G, R, bool(skip), bool(ln),
+                                   _p(dx), _p(partials), _stream()), 'er_senet_bwd')
+    self._ck(self.lib.er_senet_grad_reduce(_p(partials), rows, F, D, G, R, bool(ln), grads.table, bool(acc), _stream()),
+             'er_senet_grad_reduce')
+    if self.op_log is not None:
+      self.op_log.append(('er::senet_bwd_kernel', 6.0 * B * R * (2 * F * G + F * D)))
+    return dx
+
   # -- K1b hash-table (KV) embedding tables
   def kv_create(self, var_rows, capacity, seed, init_mean, init_stddev, filter_freq=0, steps_to_live=0, step=None):
     """The map of one KV table whose arena is `var_rows` ([capacity, dim] view of the table group's storage).
@@ -3936,6 +4013,81 @@ class AutoIntAttnFn(torch.autograd.Function):
     qkvr, y = ctx.saved_tensors
     F, H, ds = ctx.shape
     return hip().autoint_attn_bwd(qkvr, y, dy.contiguous(), F, H, ds), None, None, None
+
+
+def _pack_theta(be, params, count, what):
+  """The block's parameters side by side in one vector (one copy launch)."""
+  theta = torch.empty(count, dtype=torch.float32, device=params[0].device)
+  pairs, o = [], 0
+  for prm in params:
+    n = prm.numel()
+    pairs.append((theta[o:o + n], prm.detach().reshape(-1)))
+    o += n
+  assert o == count, '%s: %d parameter floats, the kernel expects %d' % (what, o, count)
+  be.copy_multi(pairs)
+  return theta
+
+
+def _theta_grads(ctx, params):
+  """-> (table, acc, returned): the gradient buffers the reduce launch writes through.  With the variables' buffers
+  (`grads`, zeroed once per step by VarStore.zero_grad) the gradients are ADDED there and autograd gets nothing; without,
+  fresh tensors are written and returned to autograd."""
+  if ctx.grads is not None:
+    return BstGradTable.of(ctx.grads), True, (None,) * len(params)
+  fresh = [torch.empty_like(p) for p in params]
+  return BstGradTable.of(fresh), False, tuple(fresh)
+
+
+class BiLinearFn(torch.autograd.Function):
+  """reference layers/keras/fibinet.py:175-203 up to the concatenation (types `all` and `each`):
+  apply(x [B, F * D], F, D, each, plus, grads, kernel_0, bias_0[, kernel_1, bias_1, ..]) -> the pairs' <u_i, x_j>
+  [B, F (F - 1) / 2] (plus) or u_i * x_j [B, F (F - 1) / 2 * D], u_i = x_i kernel_i + bias_i (er_bilinear_*: one
+  launch each way and a fixed-order reduce of the parameter gradients; the backward recomputes u)."""
+
+  @staticmethod
+  def forward(ctx, x, F, D, each, plus, grads, *params):
+    be = hip()
+    x = x if x.is_contiguous() else x.contiguous()
+    theta = _pack_theta(be, params, be.bilinear_param_count(F, D, each), 'BiLinearFn')
+    out = be.bilinear_fwd(x, theta, F, D, each, plus)
+    ctx.save_for_backward(x, theta, *params)
+    ctx.cfg = (F, D, each, plus)
+    ctx.grads = grads
+    return out
+
+  @staticmethod
+  def backward(ctx, dout):
+    x, theta = ctx.saved_tensors[:2]
+    F, D, each, plus = ctx.cfg
+    table, acc, ret = _theta_grads(ctx, ctx.saved_tensors[2:])
+    dx = hip().bilinear_bwd(x, theta, dout.contiguous(), F, D, each, plus, table, acc=acc)
+    return (dx, None, None, None, None, None) + ret
+
+
+class SENetFn(torch.autograd.Function):
+  """reference layers/keras/fibinet.py:63-93: apply(x [B, F * D], F, D, G, R, skip, ln, grads, W1, b1, W2, b2[, gamma,
+  beta]) -> the re-weighted (+ skip connection) (+ layer-normalised) fields [B, F * D] (er_senet_*: one launch each way
+  and a fixed-order reduce of the parameter gradients; the backward recomputes the squeeze and the excitation)."""
+
+  @staticmethod
+  def forward(ctx, x, F, D, G, R, skip, ln, grads, *params):
+    be = hip()
+    x = x if x.is_contiguous() else x.contiguous()
+    assert len(params) == (6 if ln else 4)
+    theta = _pack_theta(be, params, be.senet_param_count(F, D, G, R, ln), 'SENetFn')
+    y = be.senet_fwd(x, theta, F, D, G, R, skip, ln)
+    ctx.save_for_backward(x, theta, *params)
+    ctx.cfg = (F, D, G, R, skip, ln)
+    ctx.grads = grads
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    x, theta = ctx.saved_tensors[:2]
+    F, D, G, R, skip, ln = ctx.cfg
+    table, acc, ret = _theta_grads(ctx, ctx.saved_tensors[2:])
+    dx = hip().senet_bwd(x, theta, dy.contiguous(), F, D, G, R, skip, ln, table, acc=acc)
+    return (dx, None, None, None, None, None, None, None) + ret
 
 
 class MMoEMixManyFn(torch.autograd.Function):

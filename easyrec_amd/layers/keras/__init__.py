@@ -4,5 +4,5 @@ from .blocks import MLP, Add  # noqa: F401
 from .interaction import CIN, FM, Cross, DotInteraction  # noqa: F401
 from .multi_task import MMoE  # noqa: F401
 from .din import DIN  # noqa: F401
-from .fibinet import SENet  # noqa: F401
+from .fibinet import BiLinear, FiBiNet, SENet  # noqa: F401
 from .standard import Activation, Dense, Dropout  # noqa: F401

@@ -673,6 +673,60 @@ int er_autoint_pack(const float* wq, const float* wk, const float* wv, const flo
                     float* w, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8d FiBiNet's field blocks.  x [B, F * D]: F fields of the same width D side by side, fp32.
+ * Bilinear.  Replaces the per-field Dense (MatMul + BiasAdd), the per-pair expand_dims / MatMul / Squeeze
+ *     (use_plus) or Mul, and the ConcatV2 of BiLinear.call layers/keras/fibinet.py:175-203 (types `all`
+ *     and `each`; the Dense `output` after it stays a contraction).
+ * theta: n_w dense layers (each != 0: F - 1, else 1), layer l = kernel [D, D] ([in, out] row-major) then
+ *   bias [D] (er_bilinear_param_count).  u_i = x_i W_i + b_i for i < F - 1 (`all`: the one layer); for the
+ *   pairs (i, j), i < j, in itertools.combinations order: plus != 0: out [B, F (F - 1) / 2] = <u_i, x_j>;
+ *   else out [B, F (F - 1) / 2 * D] = u_i * x_j.
+ * er_bilinear_bwd: recomputes u; dx [B, F * D] = (a field as x_i, through W_i^T, and as x_j); per-workgroup
+ *   partial sums of the packed parameter gradient into partials [er_bilinear_grid, param_count].
+ * er_bilinear_grad_reduce: sums the rows in fixed order and adds (acc != 0) or writes the result into the
+ *   variables' gradient buffers: grads_host is a HOST array of 2 n_w pointers in theta's order (passed in
+ *   the kernel arguments: capture-safe).  No atomics anywhere.
+ * Envelope: 2 <= F <= 64, 1 <= D <= 64 and er_bilinear_lds_bytes(F, D) =
+ *   4 * ((F - 1) * (D * odd(D) + D) + F (F - 1) / 2 + F * D + 2 * (F - 1) * D) <= 65536 (odd(n) = n | 1):
+ *   the `each` parameters at an odd row pitch, the pair table, one example's x, u and du.
+ *   er_bilinear_epb: examples per workgroup round, min(8, what fits beside theta); 0 outside the envelope.
+ * SENet.  Replaces the Reshape / Max / Mean / ConcatV2 squeeze, both Dense layers, the Mul / Add and the
+ *     LayerNormalization of SENet.call layers/keras/fibinet.py:63-93.
+ * G squeeze groups of D / G columns per field; z [2 F G] = per field the G maxima, then the G means;
+ *   a1 = relu(z W1 + b1) [R]; w = a1 W2 + b2 [F * D]; o = x * w (+ x with skip); with ln
+ *   y = (o - mean) / sqrt(var + 1e-3) * gamma + beta over the row, else y = o.
+ * theta: W1 [2 F G, R], b1 [R], W2 [R, F * D], b2 [F * D] (, gamma [F * D], beta [F * D] with ln).
+ * er_senet_fwd: y [B, F * D]; a1 [B, R] when not null (the ReLU pattern the backward will recompute).
+ * er_senet_bwd: recomputes the forward; dx; partials [er_senet_grid, param_count].  The gradient of a
+ *   group's max follows TensorFlow's reduce_max: it is split EVENLY among the columns that equal the
+ *   maximum (dz / count of ties to each), nothing to the others.
+ * er_senet_grad_reduce: as above, 4 (6 with ln) pointers in theta's order.
+ * Envelope: F, D <= 64, D % G == 0, 1 <= R <= 2 F G and er_senet_lds_bytes(F, D, G, R) =
+ *   4 * (param_count with ln + 4 * F * D + 4 * F * G + 2 * R + 2) <= 65536: theta and one example's
+ *   backward state (x, w, o, do; z, dz; a1, da1; mean, rstd).  er_senet_epb as above.
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_bilinear_param_count(int32_t F, int32_t D, int each);
+int64_t er_bilinear_lds_bytes(int32_t F, int32_t D);
+int32_t er_bilinear_epb(int32_t F, int32_t D, int each);
+int32_t er_bilinear_grid(int64_t B, int32_t F, int32_t D, int each);  /* rows of `partials` */
+int er_bilinear_fwd(const float* x, const float* theta, int64_t B, int32_t F, int32_t D, int each, int plus, float* out,
+                    er_stream_t stream);
+int er_bilinear_bwd(const float* x, const float* theta, const float* dout, int64_t B, int32_t F, int32_t D, int each,
+                    int plus, float* dx, float* partials, er_stream_t stream);
+int er_bilinear_grad_reduce(const float* partials, int32_t rows, int32_t F, int32_t D, int each,
+                            float* const* grads_host, int acc, er_stream_t stream);
+int64_t er_senet_param_count(int32_t F, int32_t D, int32_t G, int32_t R, int ln);
+int64_t er_senet_lds_bytes(int32_t F, int32_t D, int32_t G, int32_t R);
+int32_t er_senet_epb(int32_t F, int32_t D, int32_t G, int32_t R, int ln, int bwd);
+int32_t er_senet_grid(int64_t B, int32_t F, int32_t D, int32_t G, int32_t R, int ln);  /* rows of `partials` */
+int er_senet_fwd(const float* x, const float* theta, int64_t B, int32_t F, int32_t D, int32_t G, int32_t R, int skip,
+                 int ln, float* y, float* a1, er_stream_t stream);
+int er_senet_bwd(const float* x, const float* theta, const float* dy, int64_t B, int32_t F, int32_t D, int32_t G,
+                 int32_t R, int skip, int ln, float* dx, float* partials, er_stream_t stream);
+int er_senet_grad_reduce(const float* partials, int32_t rows, int32_t F, int32_t D, int32_t G, int32_t R, int ln,
+                         float* const* grads_host, int acc, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K9  MLP layer pieces around the GEMM.  Replaces BiasAdd / FusedBatchNorm(train) / Relu of
  *     DNN.__call__ layers/dnn.py:57-79 (keras MLP layers/keras/blocks.py:84-110) and Dice
  *     layers/keras/activation.py:47-70.

@@ -305,6 +305,33 @@ def autoint_taobao(sequence=False, **kw):
   return cfg
 
 
+def fibinet_taobao(bilinear_type='each', use_plus=True, **kw):
+  """FiBiNet, the model section of samples/model_config/fibinet_on_taobao.config: RankModel over a backbone whose
+  input-layer block batch-normalises the 17 fields of D = 16 and hands them on as a list, and a `FiBiNet` block (SENet
+  with reduction ratio 4, bilinear `each` -> 512, MLP [512, 256]); l2 1e-6, embedding l2 1e-4."""
+  cfg = taobao_base('tag', **kw)
+  cfg.model_dir = 'experiments/fibinet_taobao_ckpt'
+  cfg.data_config.label_fields.append('clk')
+  feats = TAOBAO_USER + TAOBAO_ITEM + ['tag_category_list', 'tag_brand_list']
+  names = ' '.join("feature_names: '%s'" % n for n in feats)
+  return _model_text(cfg, '''
+    model_class: 'RankModel'
+    feature_groups { group_name: 'all' %s wide_deep: DEEP }
+    backbone {
+      blocks { name: 'all' inputs { feature_group_name: 'all' }
+               input_layer { do_batch_norm: true only_output_feature_list: true } }
+      blocks { name: 'fibinet' inputs { block_name: 'all' }
+               keras_layer { class_name: 'FiBiNet'
+                             fibinet { senet { reduction_ratio: 4 }
+                                       bilinear { type: '%s' use_plus: %s num_output_units: 512 }
+                                       mlp { hidden_units: [512, 256] } } } }
+      concat_blocks: 'fibinet'
+    }
+    model_params { l2_regularization: 1e-6 }
+    embedding_regularization: 1e-4
+  ''' % (names, bilinear_type, 'true' if use_plus else 'false'))
+
+
 def mmoe_taobao(n_tasks=2, **kw):
   """MMoE, the shape of samples/model_config/mmoe_on_taobao.config (BASELINE config 5 uses 4 tasks)."""
   cfg = taobao_base('tag', **kw)
@@ -798,6 +825,7 @@ if __name__ == '__main__':
   write(mmoe_taobao(), 'mmoe_taobao.config')
   write(bst_taobao(item_rows=10000000), 'bst_taobao_10m.config')
   write(autoint_taobao(item_rows=10000000), 'autoint_taobao_10m.config')
+  write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
   write(mmoe_taobao(n_tasks=4, embedding_dim=64, batch_size=8192), 'mmoe_taobao_4task_d64.config')
   # BASELINE config 5 at full size (200 M embedding rows of 64 floats: 51 GB + Adam slots, row-sharded over 8 GPUs) and
   # the share one GPU owns of it (25 M rows) for single-GPU runs
