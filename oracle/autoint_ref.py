@@ -1,4 +1,6 @@
-"""A torch restatement of AutoInt's interacting layers (reference layers/multihead_attention.py:50-161 with use_res,
+"""ORACLE - TEST INFRASTRUCTURE ONLY.  Never imported by easyrec_amd/.
+
+A torch restatement of AutoInt's interacting layers (reference layers/multihead_attention.py:50-161 with use_res,
 model/autoint.py:54-75), written op by op like the reference graph: the kernels' and the model's yardstick.  Any dtype
 / device.
 
@@ -57,28 +59,3 @@ def random_case(B, F, d_in, H, ds, seed, dtype=torch.float64, device='cpu'):
   ws = [(torch.rand(d_in, d, generator=g, dtype=torch.float64) * 2 - 1) * lim for _ in range(4)]
   return x.to(device=device, dtype=dtype), [w.to(device=device, dtype=dtype) for w in ws]
 
-
-class AutoIntRefMixin(object):
-  """autoint_* of kernels.HipBackend restated in torch (autograd for the backward): a RefBackend subclass for the CPU
-  tests adds it."""
-
-  def autoint_pack(self, wq, wk, wv, wr):
-    return torch.cat([wq, wk, wv, wr], dim=1).contiguous()
-
-  def autoint_attn_fwd(self, qkvr, F, H, ds):
-    d = H * ds
-    B = qkvr.shape[0] // F
-    g = qkvr.view(B, F, 4 * d)
-    with torch.no_grad():
-      y = attention_core(g[..., :d], g[..., d:2 * d], g[..., 2 * d:3 * d], g[..., 3 * d:], H, ds)
-    return y.reshape(B * F, d).to(torch.float32)
-
-  def autoint_attn_bwd(self, qkvr, y, dy, F, H, ds):
-    d = H * ds
-    B = qkvr.shape[0] // F
-    with torch.enable_grad():
-      g = qkvr.detach().clone().requires_grad_(True)
-      gv = g.view(B, F, 4 * d)
-      out = attention_core(gv[..., :d], gv[..., d:2 * d], gv[..., 2 * d:3 * d], gv[..., 3 * d:], H, ds)
-      out.backward(dy.view(B, F, d))
-    return g.grad

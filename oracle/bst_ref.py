@@ -1,4 +1,6 @@
-"""A torch restatement of the BST block (reference model/multi_tower_bst.py:78-151, layers/layer_norm.py:28-37), written
+"""ORACLE - TEST INFRASTRUCTURE ONLY.  Never imported by easyrec_amd/.
+
+A torch restatement of the BST block (reference model/multi_tower_bst.py:78-151, layers/layer_norm.py:28-37), written
 op by op like the reference graph: the kernels' and the model's yardstick.  Any dtype / device.
 
   bst_block(key [B, E], hist [B, L, E], seq_len [B], T, H, params) -> [B, T * E]
@@ -75,47 +77,7 @@ def unpack(theta, E, H, ln_names=('layer_normalization', 'layer_normalization_1'
   return out
 
 
-class BstRefMixin(object):
-  """bst_* of kernels.HipBackend restated in torch (autograd for the backward): a RefBackend subclass for the CPU
-  tests adds it."""
-
-  def bst_param_count(self, E, H):
-    return _count(E, H)
-
-  def bst_grid(self, B):
-    return 1
-
-  def bst_fwd(self, key, hist, seq_len, theta, T, H):
-    E = hist.shape[2]
-    with torch.no_grad():
-      return bst_block(key, hist, seq_len, T, H, unpack(theta, E, H)).to(torch.float32)
-
-  def bst_bwd(self, key, hist, seq_len, theta, dout, T, H, grads, dhist=None, acc_h=False):
-    E = hist.shape[2]
-    with torch.enable_grad():
-      k = key.detach().clone().requires_grad_(True)
-      h = hist.detach().clone().requires_grad_(True)
-      th = theta.detach().clone().requires_grad_(True)
-      out = bst_block(k, h, seq_len, T, H, unpack(th, E, H))
-      out.backward(dout)
-    keep = min(T - 1, h.shape[1])
-    g = h.grad
-    g[:, keep:] = 0
-    if dhist is None:
-      dhist = g
-    elif acc_h:
-      dhist += g
-    else:
-      dhist.copy_(g)
-    o = 0
-    for dst in grads.grads:
-      n = dst.numel()
-      dst += th.grad[o:o + n].view(dst.shape)
-      o += n
-    return k.grad, dhist
-
-
-def _count(E, H):
+def param_count(E, H):
   heads = head_split(E, H)
   return 3 * (sum(w * w for _, w in heads) + E) + 2 * (E * E + E) + 4 * E
 

@@ -1,4 +1,6 @@
-"""A torch restatement of FiBiNet's blocks (reference layers/keras/fibinet.py: SENet :63-93, BiLinear :175-203,
+"""ORACLE - TEST INFRASTRUCTURE ONLY.  Never imported by easyrec_amd/.
+
+A torch restatement of FiBiNet's blocks (reference layers/keras/fibinet.py: SENet :63-93, BiLinear :175-203,
 FiBiNet.call :235-251) and of the input-layer block's batch norm (layers/common_layers.py:142-191), written op by op
 like the reference graph: the kernels' and the model's yardstick.  Any dtype / device.
 

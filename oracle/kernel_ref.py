@@ -23,7 +23,7 @@ Reference call sites restated (all under /root/reference/easy_rec/python):
 import numpy as np
 import torch
 
-from oracle import hashing
+from oracle import autoint_ref, bst_ref, hashing
 
 OPT_SGD, OPT_ADAM, OPT_LAZY_ADAM, OPT_ADAGRAD = 0, 1, 2, 3
 ACT_NONE, ACT_RELU = 0, 1
@@ -1368,6 +1368,64 @@ class RefBackend(object):
     dg = torch.einsum('tbh,ebh->tbe', dout, experts)
     dlogits = gates * (dg - (gates * dg).sum(dim=-1, keepdim=True))
     return dexperts, dlogits
+
+  # -- the BST block (oracle/bst_ref.py; autograd for the backward)
+  def bst_param_count(self, E, H):
+    return bst_ref.param_count(E, H)
+
+  def bst_grid(self, B):
+    return 1
+
+  def bst_fwd(self, key, hist, seq_len, theta, T, H):
+    E = hist.shape[2]
+    with torch.no_grad():
+      return bst_ref.bst_block(key, hist, seq_len, T, H, bst_ref.unpack(theta, E, H)).to(torch.float32)
+
+  def bst_bwd(self, key, hist, seq_len, theta, dout, T, H, grads, dhist=None, acc_h=False):
+    E = hist.shape[2]
+    with torch.enable_grad():
+      k = key.detach().clone().requires_grad_(True)
+      h = hist.detach().clone().requires_grad_(True)
+      th = theta.detach().clone().requires_grad_(True)
+      out = bst_ref.bst_block(k, h, seq_len, T, H, bst_ref.unpack(th, E, H))
+      out.backward(dout)
+    keep = min(T - 1, h.shape[1])
+    g = h.grad
+    g[:, keep:] = 0
+    if dhist is None:
+      dhist = g
+    elif acc_h:
+      dhist += g
+    else:
+      dhist.copy_(g)
+    o = 0
+    for dst in grads.grads:
+      n = dst.numel()
+      dst += th.grad[o:o + n].view(dst.shape)
+      o += n
+    return k.grad, dhist
+
+  # -- AutoInt's attention core (oracle/autoint_ref.py; autograd for the backward)
+  def autoint_pack(self, wq, wk, wv, wr):
+    return torch.cat([wq, wk, wv, wr], dim=1).contiguous()
+
+  def autoint_attn_fwd(self, qkvr, F, H, ds):
+    d = H * ds
+    B = qkvr.shape[0] // F
+    g = qkvr.view(B, F, 4 * d)
+    with torch.no_grad():
+      y = autoint_ref.attention_core(g[..., :d], g[..., d:2 * d], g[..., 2 * d:3 * d], g[..., 3 * d:], H, ds)
+    return y.reshape(B * F, d).to(torch.float32)
+
+  def autoint_attn_bwd(self, qkvr, y, dy, F, H, ds):
+    d = H * ds
+    B = qkvr.shape[0] // F
+    with torch.enable_grad():
+      g = qkvr.detach().clone().requires_grad_(True)
+      gv = g.view(B, F, 4 * d)
+      out = autoint_ref.attention_core(gv[..., :d], gv[..., d:2 * d], gv[..., 2 * d:3 * d], gv[..., 3 * d:], H, ds)
+      out.backward(dy.view(B, F, d))
+    return g.grad
 
   def hyper_select(self, table, counter, out, history=None, history_index=HYPER_LR_T):  # history: [values | maxima]
     c = int(counter.item())

@@ -11,6 +11,10 @@ to /root/reference/easy_rec/python) and TF's documented op semantics (SURVEY.md 
   DeepFM         model/deepfm.py:53-109; FM layers/fm.py:20-26; DNN layers/dnn.py:50-87
   DCN            model/dcn.py:32-70
   MultiTowerDIN  model/multi_tower_din.py:62-130, layers/seq_input_layer.py:34-124
+  MultiTowerBST  model/multi_tower_bst.py:19-190 (the block: oracle/bst_ref.py)
+  AutoInt        model/autoint.py:16-80 (the interacting layers: oracle/autoint_ref.py)
+  FiBiNet        layers/keras/fibinet.py (BiLinear's pair terms: oracle/fibinet_ref.py), the input-layer block's
+                 do_batch_norm layers/common_layers.py:142-191
   MMoE           model/mmoe.py:35-70, layers/mmoe.py:62-83, model/multi_task_model.py:33-141
   loss           model/rank_model.py:105-111,213-332, builders/loss_builder.py:35-39
   regularisation model/easy_rec_estimator.py:166-184, compat/regularizers.py:76-108
@@ -42,7 +46,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from oracle import hashing
+from oracle import autoint_ref, bst_ref, fibinet_ref, hashing
 
 F32 = np.float32
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
@@ -171,6 +175,7 @@ class OracleTrainer(object):
     self.emb_mult = float(oc[0].embedding_learning_rate_multiplier) \
         if oc[0].HasField('embedding_learning_rate_multiplier') else 1.0
     self.model_class = cfg.model_config.model_class
+    self.last_bst = []  # MultiTowerBST: the BST towers' block outputs of the last forward pass
 
   def resume(self, global_step, slots):
     """Continue from a training state taken elsewhere: `global_step` finished steps (LR schedule position, Adam's beta
@@ -795,6 +800,61 @@ class OracleTrainer(object):
     out = self.dense(V, all_fea, mc.num_class, 'output', 0.0)
     return {'logits': out.squeeze(1)}
 
+  def _multi_tower_bst(self, V, batch):
+    """model/multi_tower_bst.py:19-190: the plain towers (BatchNorm + DNN), then every BST tower's block (oracle/bst_ref.py,
+    on the batch-max history) in config order, concatenated -> final_dnn -> output.  seq_input_layer regularises the key
+    and the history once; the second L2 term of the key (:57-58) is added here."""
+    mc = self.cfg.model_config
+    c = mc.multi_tower
+    l2 = self._l2_of(mc)
+    lam = mc.embedding_regularization
+    feas, scope_id = [], 0
+    for tower in c.towers:
+      scope = 'input_layer' if scope_id == 0 else 'input_layer_%d' % scope_id
+      scope_id += 1
+      fea, _ = self.input_layer(V, batch, tower.input, scope)
+      feas.append(fea)
+    bst_feas = []
+    for tower in c.bst_towers:
+      fea = self.seq_input_layer(V, batch, tower.input)
+      if lam > 0:  # the key's second term (the history's is seq_input_layer's own)
+        self._reg = self._reg + lam * 0.5 * (fea['key'] * fea['key']).sum()
+      bst_feas.append(fea)
+    arr = []
+    for tower, fea in zip(c.towers, feas):
+      fea = self.batch_norm(V, fea, '%s_fea_bn' % tower.input)
+      arr.append(self.dnn(V, fea, tower.dnn, '%s_dnn' % tower.input, l2))
+    self.last_bst = []
+    for i, (tower, fea) in enumerate(zip(c.bst_towers, bst_feas)):
+      E = fea['hist_seq_emb'].shape[-1]
+      lns = ('layer_normalization' if i == 0 else 'layer_normalization_%d' % (2 * i), 'layer_normalization_%d' % (2 * i + 1))
+      params = {n: V.get(n) for n in bst_ref.param_names(E, tower.multi_head_size, lns)}
+      out = bst_ref.bst_block(fea['key'], fea['hist_seq_emb'], torch.as_tensor(fea['hist_seq_len']), tower.seq_len,
+                              tower.multi_head_size, params, ln_names=lns)
+      self.last_bst.append(out.detach())
+      arr.append(out)
+    all_fea = self.dnn(V, torch.cat(arr, dim=1), c.final_dnn, 'final_dnn', l2)
+    out = self.dense(V, all_fea, mc.num_class, 'output', 0.0)
+    return {'logits': out.squeeze(1)}
+
+  def _autoint(self, V, batch):
+    """model/autoint.py:16-80: the `all` group through the input layer (its sequence_features' target attention appended,
+    embedding L2 included), reshaped to [B, F, D], the interacting layers of oracle/autoint_ref.py with their kernels' L2
+    (l2_regularization of the autoint message), then dense(num_class, 'output') without a regulariser."""
+    mc = self.cfg.model_config
+    ai = mc.autoint
+    l2 = self._l2_of(mc)
+    fea, _ = self.input_layer(V, batch, 'all', 'input_layer')
+    D = self.features[0].embedding_dim
+    B = fea.shape[0]
+    x = fea.reshape(B, -1, D)
+    for i in range(ai.interacting_layer_num):
+      name = autoint_ref.layer_name(i)
+      params = {n: V.get(n, l2=l2) for n in autoint_ref.names(name)}
+      x = autoint_ref.mha_layer(x, ai.multi_head_num, ai.multi_head_size, params, name)
+    out = self.dense(V, x.reshape(B, -1), mc.num_class, 'output', 0.0)
+    return {'logits': out.squeeze(1)}
+
   def _mmoe_layer(self, V, x, expert_cfgs, num_task, l2, name='mmoe', training=False):
     """layers/mmoe.py:62-83: expert DNNs stacked on axis 1, per task a softmax gate over the experts, the mixture.
     The model classes build the layer without is_training (model/mmoe.py:37-47, model/dbmtl.py:66-70; the layer's
@@ -1062,6 +1122,23 @@ class OracleTrainer(object):
       out = (out - mean) / torch.sqrt(var + 1e-3) * V.get(name + '/output_ln/gamma') + V.get(name + '/output_ln/beta')
     return out
 
+  def _keras_bilinear(self, V, fields, cfg, name):
+    """layers/keras/fibinet.py:175-203: the pair terms (oracle/fibinet_ref.py) -> Dense `output`."""
+    kind = cfg.type.lower()
+    params = {n: V.get(n) for n in fibinet_ref.bilinear_names(name, kind, len(fields))}
+    p = fibinet_ref.bilinear_pairs(fields, kind, cfg.use_plus, params, name)
+    return self.dense(V, p, cfg.num_output_units, name + '/output', 0.0)
+
+  def _keras_fibinet(self, V, fields, cfg, name, l2):
+    """layers/keras/fibinet.py:235-251: [SENet, BiLinear] concatenated -> MLP."""
+    feats = [self._keras_senet(V, fields, cfg.senet, name + '/senet')]
+    if cfg.HasField('bilinear'):
+      feats.append(self._keras_bilinear(V, fields, cfg.bilinear, name + '/bilinear'))
+    out = torch.cat(feats, dim=-1) if len(feats) > 1 else feats[0]
+    if cfg.HasField('mlp'):
+      out = self._keras_mlp(V, out, cfg.mlp, name + '/mlp', l2)
+    return out
+
   def _rank_backbone(self, V, batch):
     """model/rank_model.py:38-55: the backbone's output, top_mlp aside, + the head `output` dense when its width is
     not num_class."""
@@ -1100,7 +1177,7 @@ class OracleTrainer(object):
     mc = self.cfg.model_config
     bb = mc.backbone
     l2 = mc.model_params.l2_regularization
-    outs, scope_id = {}, 0
+    outs, scope_id, bn_id = {}, 0, 0
     groups = {g.group_name for g in mc.feature_groups}
 
     def group_out(name):
@@ -1134,6 +1211,13 @@ class OracleTrainer(object):
           scope_id += 1
           fea, flist = self.input_layer(V, batch, gname, scope)
           il = blk.input_layer
+          if il.do_batch_norm:
+            # layers/common_layers.py:142-191: tf.layers.batch_normalization on the 2-D tensor and on every feature,
+            # under TF's default names, numbered over the graph in block order
+            if not il.only_output_feature_list:
+              fea = self.batch_norm(V, fea, fibinet_ref.bn_name(bn_id))
+            flist = [self.batch_norm(V, f, fibinet_ref.bn_name(bn_id + 1 + k)) for k, f in enumerate(flist)]
+            bn_id += 1 + len(flist)
           outs[blk.name] = flist if il.only_output_feature_list else ((fea, flist) if il.output_2d_tensor_and_feature_list else fea)
         continue
       ins = []
@@ -1180,6 +1264,10 @@ class OracleTrainer(object):
           x = self._standard_keras(V, x, kl, blk.name)
         elif kl.class_name == 'SENet':
           x = self._keras_senet(V, x, kl.senet, blk.name)
+        elif kl.class_name == 'FiBiNet':
+          x = self._keras_fibinet(V, list(x), kl.fibinet, blk.name, l2)
+        elif kl.class_name == 'BiLinear':
+          x = self._keras_bilinear(V, list(x), kl.bilinear, blk.name)
         elif kl.class_name == 'FM':
           fl = torch.stack(list(x), dim=1)  # [B, F, D]
           x = 0.5 * (fl.sum(dim=1) ** 2 - (fl ** 2).sum(dim=1))
@@ -1312,6 +1400,10 @@ class OracleTrainer(object):
         pred = self._dcn(V, batch)
       elif self.model_class == 'MultiTowerDIN':
         pred = self._multi_tower_din(V, batch)
+      elif self.model_class == 'MultiTowerBST':
+        pred = self._multi_tower_bst(V, batch)
+      elif self.model_class == 'AutoInt':
+        pred = self._autoint(V, batch)
       elif self.model_class == 'RankModel':
         pred = self._rank_backbone(V, batch)
       elif self.model_class == 'WideAndDeep':

@@ -1,0 +1,85 @@
+"""Test infrastructure shared by the -m gpu model tests (tests/test_models_gpu.py, test_bst_gpu.py, test_autoint_gpu.py,
+test_fibinet_gpu.py): a model's first training steps against the CPU oracle, the two-runs-and-a-hipGraph-replay bit
+identity check of a kernel sequence, and the max-error-over-max-value comparison."""
+import numpy as np
+import torch
+
+from easyrec_amd.input.synthetic import SyntheticBatches
+from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
+from oracle.model_oracle import OracleTrainer
+
+
+def _f64(x):
+  return x.detach().cpu().double().numpy() if torch.is_tensor(x) else np.asarray(x, dtype=np.float64)
+
+
+def close(got, want, tol, what, scale=None):
+  """max |got - want| <= tol * max |want|; scale: a floor for max |want| (a gradient that is zero up to rounding)."""
+  got, want = _f64(got), _f64(want)
+  scale = max(float(np.abs(want).max()), scale or 1e-30)
+  err = float(np.abs(got - want).max())
+  assert err <= tol * scale, (what, err, scale)
+
+
+def first_steps(cfg, B, seed, steps=2, step0_tol=1e-5, device='cuda:0', grad_views=True, skip_bn_shadowed_bias=True,
+                coverage=None):
+  """`steps` training steps of the product and of the oracle from the same state on the same synthetic batches: every
+  loss within step0_tol (first step) / 1e-4 (later steps) relative; after the first step the logits (1e-4) and the
+  gradient of every variable, read back as Adam's first moment, within 2e-4 of the tensor's gradient scale.
+  grad_views: autograd accumulated in place into the flat gradient buffer; skip_bn_shadowed_bias: a dense bias under
+  BatchNorm has a zero gradient (rounding noise) and is not compared; coverage(names, cfg): the caller's own assertions
+  on the list of compared variables."""
+  est = EasyRecEstimator(cfg, device=device, batch_size=B, seed=seed).build()
+  orc = OracleTrainer(cfg, est.state_dict(), batch_size=B)
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 100)
+  for step in range(steps):
+    b = gen.next_batch()
+    est.train_step(b)
+    got, exp = est.loss_values(), orc.train_step(b)
+    for k in exp:
+      assert abs(got[k] - exp[k]) <= (step0_tol if step == 0 else 1e-4) * max(1e-3, abs(exp[k])), (step, k, got[k], exp[k])
+    if step > 0:
+      continue
+    for k, ref in orc.last_pred.items():
+      if k.startswith('logits'):
+        got_l = est.model._prediction_dict[k].detach().cpu().numpy()
+        assert np.allclose(got_l, ref, rtol=1e-4, atol=1e-5), k
+    if grad_views:
+      est.varstore.check_grad_views()
+    st = est.state_dict(slots=True)
+    names = set(orc.state)
+    gmax = max(float(np.max(np.abs(v))) for kk, v in orc.slots.items() if kk.endswith('/m'))
+    compared = []
+    for k in orc.state:
+      key = k + '/m'
+      if key not in orc.slots or key not in st:
+        continue
+      if skip_bn_shadowed_bias and k.endswith('/bias') and (k[:-len('/bias')] + '/bn/gamma') in names:
+        continue  # d(loss)/d(bias) == 0 under BatchNorm: rounding noise
+      ref = orc.slots[key]
+      d, scale = float(np.max(np.abs(st[key] - ref))), float(np.max(np.abs(ref)))
+      assert d <= 2e-4 * scale + 2e-6 * gmax, (key, d, scale)
+      compared.append(k)
+    assert len(compared) > 5
+    if coverage is not None:
+      coverage(compared, cfg)
+  return est
+
+
+def assert_runs_and_replay_bit_identical(run):
+  """run() -> list of tensors: two eager runs, and a replay of run() captured as a hipGraph, give the same bits."""
+  first = run()
+  second = run()
+  torch.cuda.synchronize()
+  assert all(torch.equal(a, b) for a, b in zip(first, second))
+  s = torch.cuda.Stream()
+  s.wait_stream(torch.cuda.current_stream())
+  with torch.cuda.stream(s):
+    run()  # (warm-up on the capture stream)
+  torch.cuda.current_stream().wait_stream(s)
+  graph = torch.cuda.CUDAGraph()
+  with torch.cuda.graph(graph):
+    static = run()
+  graph.replay()
+  torch.cuda.synchronize()
+  assert all(torch.equal(a, b) for a, b in zip(first, static))

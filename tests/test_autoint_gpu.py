@@ -1,5 +1,5 @@
 """AutoInt's HIP attention core (csrc/er_autoint.hip) on the GPU: forward and every gradient against the fp64 torch
-restatement (tests/_autoint_ref.py) and the reference's own outputs (tests/golden/autoint_vectors.npz), bit-identity
+restatement (oracle/autoint_ref.py) and the reference's own outputs (tests/golden/autoint_vectors.npz), bit-identity
 (two runs, eager vs hipGraph replay), and the model against the oracle."""
 import logging
 import os
@@ -14,8 +14,9 @@ from easyrec_amd import kernels  # noqa: E402
 from easyrec_amd.input.synthetic import SyntheticBatches  # noqa: E402
 from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator  # noqa: E402
 from easyrec_amd.utils import config_util  # noqa: E402
-from tests import _autoint_ref as ref  # noqa: E402
-from tests._autoint_oracle import AutoIntOracle  # noqa: E402
+from oracle import autoint_ref as ref  # noqa: E402
+from tests._oracle_steps import assert_runs_and_replay_bit_identical, first_steps  # noqa: E402
+from tests._oracle_steps import close as _close  # noqa: E402
 from tests.test_autoint_pins import autoint_cfg  # noqa: E402
 
 logging.disable(logging.WARNING)
@@ -32,14 +33,6 @@ CASES = [
     (11, 6, 12, 1, 12),
     (4096, 18, 64, 2, 32),
 ]
-
-
-def _close(got, want, tol, what):
-  want = want.detach().cpu().double().numpy()
-  got = got.detach().cpu().double().numpy()
-  scale = max(float(np.abs(want).max()), 1e-30)
-  err = float(np.abs(got - want).max())
-  assert err <= tol * scale, (what, err, scale)
 
 
 def _layer(x, ws, H, ds):
@@ -153,57 +146,18 @@ def test_two_runs_and_graph_replay_are_bit_identical():
     return [y.detach(), xi.grad] + [g.clone() for g in grads]
 
   assert not be.wgrad_sink().active  # (the weight gradients are launched inside backward here)
-  first = run()
-  second = run()
-  torch.cuda.synchronize()
-  assert all(torch.equal(a, b) for a, b in zip(first, second))
-
-  s = torch.cuda.Stream()
-  s.wait_stream(torch.cuda.current_stream())
-  with torch.cuda.stream(s):
-    run()  # (warm-up on the capture stream)
-  torch.cuda.current_stream().wait_stream(s)
-  graph = torch.cuda.CUDAGraph()
-  with torch.cuda.graph(graph):
-    static = run()
-  graph.replay()
-  torch.cuda.synchronize()
-  assert all(torch.equal(a, b) for a, b in zip(first, static))
+  assert_runs_and_replay_bit_identical(run)
 
 
 # ---------------------------------------------------------------------------------------- the model against the oracle
-def _first_steps(cfg, B, seed, steps=2, step0_tol=1e-5):
-  est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=seed).build()
-  orc = AutoIntOracle(cfg, est.state_dict(), batch_size=B)
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 100)
-  for step in range(steps):
-    b = gen.next_batch()
-    est.train_step(b)
-    got, exp = est.loss_values(), orc.train_step(b)
-    for k in exp:
-      assert abs(got[k] - exp[k]) <= (step0_tol if step == 0 else 1e-4) * max(1e-3, abs(exp[k])), (step, k, got[k], exp[k])
-    if step > 0:
-      continue
-    for k, r in orc.last_pred.items():
-      if k.startswith('logits'):
-        got_l = est.model._prediction_dict[k].detach().cpu().numpy()
-        assert np.allclose(got_l, r, rtol=1e-4, atol=1e-5), k
-    st = est.state_dict(slots=True)
-    gmax = max(float(np.max(np.abs(v))) for kk, v in orc.slots.items() if kk.endswith('/m'))
-    n_cmp, n_att, n_emb = 0, 0, 0
-    for k in orc.state:
-      key = k + '/m'
-      if key not in orc.slots or key not in st:
-        continue
-      r = orc.slots[key]
-      d, scale = float(np.max(np.abs(st[key] - r))), float(np.max(np.abs(r)))
-      assert d <= 2e-4 * scale + 2e-6 * gmax, (key, d, scale)
-      n_cmp += 1
-      n_att += k.startswith('multi_head_self_attention_layer_')
-      n_emb += 'embedding_weights' in k
-    layers = cfg.model_config.autoint.interacting_layer_num
-    assert n_cmp > 5 and n_att == 4 * layers and n_emb >= 2, (n_cmp, n_att, n_emb)
-  return est
+def _coverage(names, cfg):
+  n_att = sum(k.startswith('multi_head_self_attention_layer_') for k in names)
+  n_emb = sum('embedding_weights' in k for k in names)
+  assert n_att == 4 * cfg.model_config.autoint.interacting_layer_num and n_emb >= 2, (len(names), n_att, n_emb)
+
+
+def _first_steps(cfg, B, seed, **kw):
+  return first_steps(cfg, B, seed, skip_bn_shadowed_bias=False, coverage=_coverage, **kw)
 
 
 @pytest.mark.parametrize('sequence', [False, True])

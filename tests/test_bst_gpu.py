@@ -1,5 +1,5 @@
 """MultiTowerBST's fused HIP block (csrc/er_bst.hip) on the GPU: forward and every gradient against the fp64 torch
-restatement (tests/_bst_ref.py), bit-identity (two runs, eager vs hipGraph replay, accumulation into shared buffers),
+restatement (oracle/bst_ref.py), bit-identity (two runs, eager vs hipGraph replay, accumulation into shared buffers),
 and the model's first training steps."""
 import logging
 import os
@@ -14,8 +14,8 @@ from easyrec_amd import kernels  # noqa: E402
 from easyrec_amd.input.synthetic import SyntheticBatches  # noqa: E402
 from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator  # noqa: E402
 from easyrec_amd.utils import config_util  # noqa: E402
-from tests import _bst_ref as ref  # noqa: E402
-from tests._bst_oracle import BSTOracle  # noqa: E402
+from oracle import bst_ref as ref  # noqa: E402
+from tests._oracle_steps import assert_runs_and_replay_bit_identical, close, first_steps  # noqa: E402
 
 logging.disable(logging.WARNING)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,13 +61,6 @@ def test_kernels_match_the_fp64_restatement(case):
   exp = ref.bst_block(k64, h64, lens, T, H, p64)
   (exp * dout64).sum().backward()
 
-  def close(got, want, tol, what, scale=None):
-    want = want.detach().numpy()
-    got = got.detach().cpu().double().numpy()
-    scale = max(float(np.abs(want).max()), scale or 1e-30)
-    err = float(np.abs(got - want).max())
-    assert err <= tol * scale, (what, err, scale)
-
   close(out, exp, 1e-5, 'forward')
   close(dkey, k64.grad, 1e-4, 'dkey')
   close(dhist, h64.grad, 1e-4, 'dhist')
@@ -95,22 +88,7 @@ def test_two_runs_and_graph_replay_are_bit_identical():
     dkey, dhist = be.bst_bwd(k, h, ln, theta, dout, T, H, table)
     return [out, dkey, dhist] + [g.clone() for g in grads]
 
-  first = run()
-  second = run()
-  torch.cuda.synchronize()
-  assert all(torch.equal(a, b) for a, b in zip(first, second))
-
-  s = torch.cuda.Stream()
-  s.wait_stream(torch.cuda.current_stream())
-  with torch.cuda.stream(s):
-    run()  # (warm-up on the capture stream)
-  torch.cuda.current_stream().wait_stream(s)
-  graph = torch.cuda.CUDAGraph()
-  with torch.cuda.graph(graph):
-    static = run()
-  graph.replay()
-  torch.cuda.synchronize()
-  assert all(torch.equal(a, b) for a, b in zip(first, static))
+  assert_runs_and_replay_bit_identical(run)
 
 
 def test_accumulation_into_filled_buffers():
@@ -185,7 +163,6 @@ def test_model_trains_deterministically(seq_len, towers, lazy):
   assert ('layer_normalization_3/layer_norm_scale' in names) == (towers == 2)
 
 
-
 # ---------------------------------------------------------------------------------------- the reference's own outputs
 GOLD = np.load(os.path.join(ROOT, 'tests', 'golden', 'bst_vectors.npz'))
 GOLD_CASES = sorted({k.split(':')[0] for k in GOLD.files})
@@ -209,41 +186,10 @@ def test_kernels_match_the_reference_fixture(tag):
 
 
 # ---------------------------------------------------------------------------------------- the model against the oracle
-def _first_steps(cfg, B, seed, steps=2, step0_tol=1e-5):
-  est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=seed).build()
-  orc = BSTOracle(cfg, est.state_dict(), batch_size=B)
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 100)
-  for step in range(steps):
-    b = gen.next_batch()
-    est.train_step(b)
-    got, exp = est.loss_values(), orc.train_step(b)
-    for k in exp:
-      assert abs(got[k] - exp[k]) <= (step0_tol if step == 0 else 1e-4) * max(1e-3, abs(exp[k])), (step, k, got[k], exp[k])
-    if step > 0:
-      continue
-    for k, r in orc.last_pred.items():
-      if k.startswith('logits'):
-        got_l = est.model._prediction_dict[k].detach().cpu().numpy()
-        assert np.allclose(got_l, r, rtol=1e-4, atol=1e-5), k
-    est.varstore.check_grad_views()
-    st = est.state_dict(slots=True)
-    names = set(orc.state)
-    gmax = max(float(np.max(np.abs(v))) for kk, v in orc.slots.items() if kk.endswith('/m'))
-    n_cmp, n_bst, n_emb = 0, 0, 0
-    for k in orc.state:
-      key = k + '/m'
-      if key not in orc.slots or key not in st:
-        continue
-      if k.endswith('/bias') and (k[:-len('/bias')] + '/bn/gamma') in names:
-        continue  # d(loss)/d(bias) == 0 under BatchNorm: rounding noise
-      r = orc.slots[key]
-      d, scale = float(np.max(np.abs(st[key] - r))), float(np.max(np.abs(r)))
-      assert d <= 2e-4 * scale + 2e-6 * gmax, (key, d, scale)
-      n_cmp += 1
-      n_bst += k.startswith(('multi_head_', 'layer_normalization', 'feed_forward_net'))
-      n_emb += 'embedding_weights' in k
-    assert n_cmp > 5 and n_bst >= 20 and n_emb >= 2, (n_cmp, n_bst, n_emb)
-  return est
+def _coverage(names, cfg):
+  n_bst = sum(k.startswith(('multi_head_', 'layer_normalization', 'feed_forward_net')) for k in names)
+  n_emb = sum('embedding_weights' in k for k in names)
+  assert n_bst >= 20 and n_emb >= 2, (len(names), n_bst, n_emb)
 
 
 @pytest.mark.parametrize('seq_len,towers,lazy', [(8, 1, False), (8, 1, True), (20, 1, False), (20, 1, True),
@@ -251,12 +197,12 @@ def _first_steps(cfg, B, seed, steps=2, step0_tol=1e-5):
 def test_model_matches_the_oracle(seq_len, towers, lazy):
   """B = 128, two steps: seq_len 8 truncates the max_seq_len-12 histories, 20 pads them; two towers share the dense
   variables."""
-  _first_steps(_bst_cfg(seq_len, towers, lazy), 128, 31 + seq_len + towers)
+  first_steps(_bst_cfg(seq_len, towers, lazy), 128, 31 + seq_len + towers, coverage=_coverage)
 
 
 def test_full_size_config_matches_the_oracle():
   cfg = config_util.get_configs_from_pipeline_file(os.path.join(ROOT, 'configs', 'bst_taobao_10m.config'))
-  _first_steps(cfg, 4096, 8, step0_tol=1e-4)
+  first_steps(cfg, 4096, 8, step0_tol=1e-4, coverage=_coverage)
 
 
 # ---------------------------------------------------------------------------------------- the static sequence buffer

@@ -1,11 +1,10 @@
 """FiBiNet's HIP field kernels (csrc/er_fibinet.hip) on the GPU: forward and every gradient against the fp64 torch
-restatement (tests/_fibinet_ref.py) and the reference's own outputs (tests/golden/fibinet_vectors.npz), the max's tie
+restatement (oracle/fibinet_ref.py) and the reference's own outputs (tests/golden/fibinet_vectors.npz), the max's tie
 rule, the composed path outside the envelope, bit-identity (two runs, eager vs hipGraph replay), and the model against
 the oracle."""
 import logging
 import os
 
-import numpy as np
 import pytest
 import torch
 
@@ -16,23 +15,15 @@ from easyrec_amd.input.synthetic import SyntheticBatches  # noqa: E402
 from easyrec_amd.layers.keras import fibinet as fb  # noqa: E402
 from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator  # noqa: E402
 from easyrec_amd.utils import config_util  # noqa: E402
-from tests import _fibinet_ref as ref  # noqa: E402
-from tests._fibinet_oracle import FiBiNetOracle  # noqa: E402
+from oracle import fibinet_ref as ref  # noqa: E402
+from tests._oracle_steps import assert_runs_and_replay_bit_identical, first_steps  # noqa: E402
+from tests._oracle_steps import close as _close  # noqa: E402
 from tests.test_fibinet_pins import GOLD, GOLD_CASES, fibinet_cfg, gold_case  # noqa: E402
 
 logging.disable(logging.WARNING)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = 'cuda:0'
 PATTERN_TOL = 1e-5  # where the kernels' ReLU / arg-max pattern may differ from fp64's: within this of a tie
-
-
-def _close(got, want, tol, what):
-  want = want.detach().cpu().double().numpy()
-  got = got.detach().cpu().double().numpy()
-  scale = max(float(np.abs(want).max()), 1e-30)
-  err = float(np.abs(got - want).max())
-  print(what, 'err', err, 'scale', scale)
-  assert err <= tol * scale, (what, err, scale)
 
 
 # ---------------------------------------------------------------------------------------- bilinear
@@ -270,61 +261,23 @@ def test_two_runs_and_graph_replay_are_bit_identical():
     torch.autograd.backward([y, p], [dy, dp])
     return [y.detach(), p.detach(), xi.grad] + [g.clone() for g in sg + bg]
 
-  first = run()
-  second = run()
-  torch.cuda.synchronize()
-  assert all(torch.equal(a, b) for a, b in zip(first, second))
-
-  s = torch.cuda.Stream()
-  s.wait_stream(torch.cuda.current_stream())
-  with torch.cuda.stream(s):
-    run()  # (warm-up on the capture stream)
-  torch.cuda.current_stream().wait_stream(s)
-  graph = torch.cuda.CUDAGraph()
-  with torch.cuda.graph(graph):
-    static = run()
-  graph.replay()
-  torch.cuda.synchronize()
-  assert all(torch.equal(a, b) for a, b in zip(first, static))
+  assert_runs_and_replay_bit_identical(run)
 
 
 # ---------------------------------------------------------------------------------------- the model against the oracle
-def _first_steps(cfg, B, seed, steps=2, step0_tol=1e-5):
-  est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=seed).build()
-  orc = FiBiNetOracle(cfg, est.state_dict(), batch_size=B)
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 100)
+def _coverage(names, cfg):
   fbn = cfg.model_config.backbone.blocks[1].keras_layer.fibinet
-  for step in range(steps):
-    b = gen.next_batch()
-    est.train_step(b)
-    got, exp = est.loss_values(), orc.train_step(b)
-    for k in exp:
-      print(step, k, got[k], exp[k])
-      assert abs(got[k] - exp[k]) <= (step0_tol if step == 0 else 1e-4) * max(1e-3, abs(exp[k])), (step, k, got[k], exp[k])
-    if step > 0:
-      continue
-    for k, r in orc.last_pred.items():
-      if k.startswith('logits'):
-        got_l = est.model._prediction_dict[k].detach().cpu().numpy()
-        assert np.allclose(got_l, r, rtol=1e-4, atol=1e-5), k
-    st = est.state_dict(slots=True)
-    gmax = max(float(np.max(np.abs(v))) for kk, v in orc.slots.items() if kk.endswith('/m'))
-    n_cmp, n_se, n_bi, n_bn, n_emb = 0, 0, 0, 0, 0
-    for k in orc.state:
-      key = k + '/m'
-      if key not in orc.slots or key not in st:
-        continue
-      r = orc.slots[key]
-      d, scale = float(np.max(np.abs(st[key] - r))), float(np.max(np.abs(r)))
-      assert d <= 2e-4 * scale + 2e-6 * gmax, (key, d, scale)
-      n_cmp += 1
-      n_se += k.startswith('fibinet/senet/')
-      n_bi += k.startswith('fibinet/bilinear/')
-      n_bn += k.startswith('batch_normalization_')
-      n_emb += 'embedding_weights' in k
-    n_w = 0 if not fbn.HasField('bilinear') else (1 if fbn.bilinear.type == 'all' else 16)
-    assert n_se == 6 and n_bi == (2 * n_w + 2 if n_w else 0) and n_bn == 2 * 17 and n_emb >= 2, (n_cmp, n_se, n_bi, n_bn, n_emb)
-  return est
+  n_se = sum(k.startswith('fibinet/senet/') for k in names)
+  n_bi = sum(k.startswith('fibinet/bilinear/') for k in names)
+  n_bn = sum(k.startswith('batch_normalization_') for k in names)
+  n_emb = sum('embedding_weights' in k for k in names)
+  n_w = 0 if not fbn.HasField('bilinear') else (1 if fbn.bilinear.type == 'all' else 16)
+  assert n_se == 6 and n_bi == (2 * n_w + 2 if n_w else 0) and n_bn == 2 * 17 and n_emb >= 2, \
+      (len(names), n_se, n_bi, n_bn, n_emb)
+
+
+def _first_steps(cfg, B, seed, **kw):
+  return first_steps(cfg, B, seed, skip_bn_shadowed_bias=False, coverage=_coverage, **kw)
 
 
 @pytest.mark.parametrize('kind', ['each', 'all', None])

@@ -14,6 +14,7 @@ from easyrec_amd.input.synthetic import SyntheticBatches  # noqa: E402
 from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator  # noqa: E402
 from easyrec_amd.utils import config_util  # noqa: E402
 from oracle.model_oracle import OracleTrainer  # noqa: E402
+from tests._oracle_steps import first_steps as _first_steps  # noqa: E402
 
 logging.disable(logging.WARNING)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,41 +27,6 @@ def _cfg(name, lazy=False):
     oc = cfg.train_config.optimizer_config[0]
     oc.lazy_adam_optimizer.learning_rate.CopyFrom(oc.adam_optimizer.learning_rate)
   return cfg
-
-
-def _first_steps(cfg, B, seed, steps=2):
-  est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=seed).build()
-  orc = OracleTrainer(cfg, est.state_dict(), batch_size=B)
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 100)
-  for step in range(steps):
-    b = gen.next_batch()
-    est.train_step(b)
-    got, exp = est.loss_values(), orc.train_step(b)
-    for k in exp:
-      assert abs(got[k] - exp[k]) <= (1e-5 if step == 0 else 1e-4) * max(1e-3, abs(exp[k])), (step, k, got[k], exp[k])
-    if step > 0:
-      continue
-    for k, ref in orc.last_pred.items():
-      if k.startswith('logits'):
-        got_l = est.model._prediction_dict[k].detach().cpu().numpy()
-        assert np.allclose(got_l, ref, rtol=1e-4, atol=1e-5), k
-    est.varstore.check_grad_views()
-    st = est.state_dict(slots=True)
-    names = set(orc.state)
-    gmax = max(float(np.max(np.abs(v))) for kk, v in orc.slots.items() if kk.endswith('/m'))
-    n_cmp = 0
-    for k in orc.state:
-      key = k + '/m'
-      if key not in orc.slots or key not in st:
-        continue
-      if k.endswith('/bias') and (k[:-len('/bias')] + '/bn/gamma') in names:
-        continue  # d(loss)/d(bias) == 0 under BatchNorm: rounding noise
-      ref = orc.slots[key]
-      d, scale = float(np.max(np.abs(st[key] - ref))), float(np.max(np.abs(ref)))
-      assert d <= 2e-4 * scale + 2e-6 * gmax, (key, d, scale)
-      n_cmp += 1
-    assert n_cmp > 5
-  return est
 
 
 @pytest.mark.parametrize('lazy', [False, True])
