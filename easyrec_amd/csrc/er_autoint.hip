@@ -12,13 +12,9 @@
 // over rows is conflict-free for ds_read_b32 / ds_write_b32), then each phase is one flat loop over (example, ...)
 // items separated by workgroup barriers.  epb = min(8, 64 KiB / the backward's LDS per example); the envelope is
 // where one example fits: 4 * (F * odd(3d) + F * odd(d) + 2 * H * F^2) <= 65536 bytes (er_autoint_lds_bytes).
-#include "er_common.h"
+#include "er_field_block.h"
 
 namespace er {
-
-constexpr int kAiThreads = 256;
-constexpr int kAiMaxEpb = 8;
-constexpr int kAiLdsBudget = 65536;  // bytes per workgroup: no opt-in beyond the default, >= 2 workgroups per CU
 
 struct AiGeom {
   int F, H, ds, d;
@@ -27,16 +23,14 @@ struct AiGeom {
   float scale;  // sqrt(ds)
 };
 
-__host__ __device__ inline int ai_odd(int n) { return n | 1; }
-
 inline AiGeom ai_geom(int F, int H, int ds) {
   AiGeom g;
   g.F = F;
   g.H = H;
   g.ds = ds;
   g.d = H * ds;
-  g.ldq = ai_odd(3 * g.d);
-  g.lda = ai_odd(g.d);
+  g.ldq = odd(3 * g.d);
+  g.lda = odd(g.d);
   g.scale = sqrtf(static_cast<float>(ds));
   return g;
 }
@@ -44,16 +38,11 @@ inline AiGeom ai_geom(int F, int H, int ds) {
 __host__ __device__ inline int ai_fwd_floats(const AiGeom& g) { return g.F * g.ldq + g.H * g.F * g.F; }
 __host__ __device__ inline int ai_bwd_floats(const AiGeom& g) { return g.F * g.ldq + g.F * g.lda + 2 * g.H * g.F * g.F; }
 
-inline int ai_epb(int floats) {
-  const int n = kAiLdsBudget / (4 * floats);
-  return n < kAiMaxEpb ? n : kAiMaxEpb;
-}
-
 // Q | K | V of the workgroup's examples -> LDS (example e at lds + e * per, row i at + i * ldq)
 __device__ inline void ai_stage_qkv(const float* __restrict__ Gb, int ne, const AiGeom& g, int per, float* lds) {
   const int d3 = 3 * g.d, d4 = 4 * g.d;
   const int n = ne * g.F * d3;
-  for (int t = threadIdx.x; t < n; t += kAiThreads) {
+  for (int t = threadIdx.x; t < n; t += kFieldThreads) {
     const int c = t % d3, r = t / d3;  // r = e * F + i
     const int e = r / g.F, i = r - e * g.F;
     lds[e * per + i * g.ldq + c] = Gb[static_cast<int64_t>(r) * d4 + c];
@@ -64,7 +53,7 @@ __device__ inline void ai_stage_qkv(const float* __restrict__ Gb, int ne, const 
 __device__ inline void ai_softmax_scores(int ne, const AiGeom& g, int per, int soff, float* lds) {
   const int F = g.F, H = g.H, ds = g.ds, FF = F * F;
   const int n = ne * H * FF;
-  for (int t = threadIdx.x; t < n; t += kAiThreads) {
+  for (int t = threadIdx.x; t < n; t += kFieldThreads) {
     const int j = t % F;
     int q = t / F;
     const int i = q % F;
@@ -79,7 +68,7 @@ __device__ inline void ai_softmax_scores(int ne, const AiGeom& g, int per, int s
   }
   __syncthreads();
   const int rows = ne * H * F;
-  for (int t = threadIdx.x; t < rows; t += kAiThreads) {
+  for (int t = threadIdx.x; t < rows; t += kFieldThreads) {
     const int e = t / (H * F), hi = t - e * (H * F);
     float* p = lds + e * per + soff + hi * F;
     float m = p[0];
@@ -95,7 +84,7 @@ __device__ inline void ai_softmax_scores(int ne, const AiGeom& g, int per, int s
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kAiThreads) void autoint_attn_fwd_kernel(const float* __restrict__ G, int64_t B, AiGeom g,
+__global__ __launch_bounds__(kFieldThreads) void autoint_attn_fwd_kernel(const float* __restrict__ G, int64_t B, AiGeom g,
                                                                        int epb, float* __restrict__ Y) {
   extern __shared__ float lds[];
   const int64_t b0 = static_cast<int64_t>(blockIdx.x) * epb;
@@ -108,7 +97,7 @@ __global__ __launch_bounds__(kAiThreads) void autoint_attn_fwd_kernel(const floa
   ai_softmax_scores(ne, g, per, soff, lds);
   // O = P V_h, Y = relu(O + R)
   const int n = ne * F * d;
-  for (int t = threadIdx.x; t < n; t += kAiThreads) {
+  for (int t = threadIdx.x; t < n; t += kFieldThreads) {
     const int c = t % d, r = t / d;
     const int e = r / F, i = r - e * F, h = c / g.ds;
     const float* X = lds + e * per;
@@ -121,7 +110,7 @@ __global__ __launch_bounds__(kAiThreads) void autoint_attn_fwd_kernel(const floa
   }
 }
 
-__global__ __launch_bounds__(kAiThreads) void autoint_attn_bwd_kernel(const float* __restrict__ G,
+__global__ __launch_bounds__(kFieldThreads) void autoint_attn_bwd_kernel(const float* __restrict__ G,
                                                                        const float* __restrict__ Y,
                                                                        const float* __restrict__ dY, int64_t B,
                                                                        AiGeom g, int epb, float* __restrict__ dG) {
@@ -138,7 +127,7 @@ __global__ __launch_bounds__(kAiThreads) void autoint_attn_bwd_kernel(const floa
   ai_stage_qkv(Gb, ne, g, per, lds);
   // dA = dY * [Y > 0] -> LDS, and it is dR
   const int nrd = ne * F * d;
-  for (int t = threadIdx.x; t < nrd; t += kAiThreads) {
+  for (int t = threadIdx.x; t < nrd; t += kFieldThreads) {
     const int c = t % d, r = t / d;
     const int e = r / F, i = r - e * F;
     const int64_t o = (b0 * F + r) * d + c;
@@ -150,7 +139,7 @@ __global__ __launch_bounds__(kAiThreads) void autoint_attn_bwd_kernel(const floa
   ai_softmax_scores(ne, g, per, poff, lds);
   // dP[h, i, j] = dA_h[i] . V_h[j]
   const int nsc = ne * H * FF;
-  for (int t = threadIdx.x; t < nsc; t += kAiThreads) {
+  for (int t = threadIdx.x; t < nsc; t += kFieldThreads) {
     const int j = t % F;
     int q = t / F;
     const int i = q % F;
@@ -164,7 +153,7 @@ __global__ __launch_bounds__(kAiThreads) void autoint_attn_bwd_kernel(const floa
     lds[e * per + soff + (h * F + i) * F + j] = s;
   }
   // dV_h[j] = sum_i P[h, i, j] dA_h[i]
-  for (int t = threadIdx.x; t < nrd; t += kAiThreads) {
+  for (int t = threadIdx.x; t < nrd; t += kFieldThreads) {
     const int c = t % d, r = t / d;
     const int e = r / F, j = r - e * F, h = c / ds;
     const float* X = lds + e * per;
@@ -177,7 +166,7 @@ __global__ __launch_bounds__(kAiThreads) void autoint_attn_bwd_kernel(const floa
   __syncthreads();
   // dS = P * (dP - rowsum(dP * P))
   const int rows = ne * H * F;
-  for (int t = threadIdx.x; t < rows; t += kAiThreads) {
+  for (int t = threadIdx.x; t < rows; t += kFieldThreads) {
     const int e = t / (H * F), hi = t - e * (H * F);
     const float* p = lds + e * per + poff + hi * F;
     float* s = lds + e * per + soff + hi * F;
@@ -187,7 +176,7 @@ __global__ __launch_bounds__(kAiThreads) void autoint_attn_bwd_kernel(const floa
   }
   __syncthreads();
   // dQ_h[i] = sqrt(ds) sum_j dS[h, i, j] K_h[j];  dK_h[j] = sqrt(ds) sum_i dS[h, i, j] Q_h[i]
-  for (int t = threadIdx.x; t < nrd; t += kAiThreads) {
+  for (int t = threadIdx.x; t < nrd; t += kFieldThreads) {
     const int c = t % d, r = t / d;
     const int e = r / F, i = r - e * F, h = c / ds;
     const float* X = lds + e * per;
@@ -197,7 +186,7 @@ __global__ __launch_bounds__(kAiThreads) void autoint_attn_bwd_kernel(const floa
     for (int j = 0; j < F; ++j) acc += s[j] * k[j * g.ldq];
     dGb[static_cast<int64_t>(r) * d4 + c] = acc * g.scale;
   }
-  for (int t = threadIdx.x; t < nrd; t += kAiThreads) {
+  for (int t = threadIdx.x; t < nrd; t += kFieldThreads) {
     const int c = t % d, r = t / d;
     const int e = r / F, j = r - e * F, h = c / ds;
     const float* X = lds + e * per;
@@ -227,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void autoint_pack_kernel(AiPackSrc src, int
 
 bool ai_shape_ok(int F, int H, int ds) {
   if (F < 1 || H < 1 || ds < 1 || H * ds > 4096) return false;
-  return 4 * ai_bwd_floats(ai_geom(F, H, ds)) <= kAiLdsBudget;
+  return 4 * ai_bwd_floats(ai_geom(F, H, ds)) <= kFieldLdsBudget;
 }
 
 }  // namespace er
@@ -242,17 +231,17 @@ int64_t er_autoint_lds_bytes(int32_t F, int32_t H, int32_t ds) {
 int32_t er_autoint_epb(int32_t F, int32_t H, int32_t ds, int bwd) {
   if (!er::ai_shape_ok(F, H, ds)) return 0;
   const er::AiGeom g = er::ai_geom(F, H, ds);
-  return er::ai_epb(bwd ? er::ai_bwd_floats(g) : er::ai_fwd_floats(g));
+  return er::epb(0, bwd ? er::ai_bwd_floats(g) : er::ai_fwd_floats(g));
 }
 
 int er_autoint_attn_fwd(const float* qkvr, int64_t B, int32_t F, int32_t H, int32_t ds, float* y, er_stream_t stream) {
   ER_REQUIRE(qkvr && y && B > 0, "er_autoint_attn_fwd: bad arguments");
   ER_REQUIRE(er::ai_shape_ok(F, H, ds), "er_autoint_attn_fwd: F = %d, H = %d, ds = %d outside the envelope", F, H, ds);
   const er::AiGeom g = er::ai_geom(F, H, ds);
-  const int epb = er::ai_epb(er::ai_fwd_floats(g));
+  const int epb = er::epb(0, er::ai_fwd_floats(g));
   const int64_t grid = (B + epb - 1) / epb;
   ER_REQUIRE(grid <= 0x7fffffff, "er_autoint_attn_fwd: B = %lld too large", static_cast<long long>(B));
-  hipLaunchKernelGGL(er::autoint_attn_fwd_kernel, dim3(static_cast<unsigned>(grid)), dim3(er::kAiThreads),
+  hipLaunchKernelGGL(er::autoint_attn_fwd_kernel, dim3(static_cast<unsigned>(grid)), dim3(er::kFieldThreads),
                      4 * epb * er::ai_fwd_floats(g), er::as_stream(stream), qkvr, B, g, epb, y);
   ER_LAUNCH_CHECK();
   return 0;
@@ -263,10 +252,10 @@ int er_autoint_attn_bwd(const float* qkvr, const float* y, const float* dy, int6
   ER_REQUIRE(qkvr && y && dy && dqkvr && B > 0, "er_autoint_attn_bwd: bad arguments");
   ER_REQUIRE(er::ai_shape_ok(F, H, ds), "er_autoint_attn_bwd: F = %d, H = %d, ds = %d outside the envelope", F, H, ds);
   const er::AiGeom g = er::ai_geom(F, H, ds);
-  const int epb = er::ai_epb(er::ai_bwd_floats(g));
+  const int epb = er::epb(0, er::ai_bwd_floats(g));
   const int64_t grid = (B + epb - 1) / epb;
   ER_REQUIRE(grid <= 0x7fffffff, "er_autoint_attn_bwd: B = %lld too large", static_cast<long long>(B));
-  hipLaunchKernelGGL(er::autoint_attn_bwd_kernel, dim3(static_cast<unsigned>(grid)), dim3(er::kAiThreads),
+  hipLaunchKernelGGL(er::autoint_attn_bwd_kernel, dim3(static_cast<unsigned>(grid)), dim3(er::kFieldThreads),
                      4 * epb * er::ai_bwd_floats(g), er::as_stream(stream), qkvr, y, dy, B, g, epb, dqkvr);
   ER_LAUNCH_CHECK();
   return 0;

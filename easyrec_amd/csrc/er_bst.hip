@@ -4,20 +4,17 @@
 // head's Q / K / V and its [T, T] score tile live in LDS, the ~11 KB of block weights (E = 32) are read through the
 // vector L1.  The backward recomputes the forward of its example (nothing per example is saved: P alone would be
 // 4 * B * H * T^2 bytes) and keeps its share of the parameter gradient in its own row of `partials` - every entry is
-// read, added and written by the same thread for every example, and er_bst_grad_reduce sums the rows in a fixed order:
+// read, added and written by the same thread for every example, and er_theta_grad_reduce sums the rows in a fixed order:
 // no atomics, so two runs and a graph replay give the same bits.
 //
 // Both envelope limits (T, E <= 64) make a row of the sequence or of a score tile one lane per element of a wave:
 // LayerNorm and softmax rows are wave reductions.  fp32 throughout.
-#include "er_common.h"
+#include "er_field_block.h"
 
 namespace er {
 
-constexpr int kBstThreads = 256;
-constexpr int kBstWaves = kBstThreads / kWave;
 constexpr int kBstMaxT = 64;
 constexpr int kBstMaxE = 64;
-constexpr int kBstGrid = 512;               // persistent workgroups (2 per CU on MI355X); rows of `partials`
 constexpr float kBstMasked = -4294967296.f;  // -2^32 + 1 in fp32 (multi_tower_bst.py:91)
 constexpr float kLnEps = 1e-6f;              // layers/layer_norm.py:16
 
@@ -70,7 +67,7 @@ __host__ __device__ inline int bst_bwd_lds(const BstGeom& g) { return 3 * g.T * 
 // dst[t, j] = bias[j] + sum_i src[t, s + i] * W[i, j] for one head (W: [w, w]); src rows have E floats
 __device__ inline void bst_head_dense(const float* src, int E, int T, int s, int w, const float* W, const float* bias,
                                       float* dst) {
-  for (int idx = threadIdx.x; idx < T * w; idx += kBstThreads) {
+  for (int idx = threadIdx.x; idx < T * w; idx += kFieldThreads) {
     const int t = idx / w, j = idx - t * w;
     const float* x = src + t * E + s;
     float acc = 0.f;
@@ -90,7 +87,7 @@ __device__ void bst_attention(const BstGeom& g, const float* theta, const float*
     bst_head_dense(X, E, T, s, w, theta + g.wk + wo, theta + g.bk + s, k);
     bst_head_dense(X, E, T, s, w, theta + g.wv + wo, theta + g.bv + s, v);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < T * T; idx += kBstThreads) {
+    for (int idx = threadIdx.x; idx < T * T; idx += kFieldThreads) {
       const int t = idx / T, u = idx - t * T;
       float acc = 0.f;
       for (int c = 0; c < w; ++c) acc = fmaf(q[t * w + c], k[u * w + c], acc);
@@ -98,7 +95,7 @@ __device__ void bst_attention(const BstGeom& g, const float* theta, const float*
     }
     __syncthreads();
     // masked softmax over the keys (:84-96): column T-1 is never masked, so exp of a masked score is exactly 0
-    for (int t = wave; t < T; t += kBstWaves) {
+    for (int t = wave; t < T; t += kFieldWaves) {
       const bool ok = lane < T && (lane < nvalid || lane == T - 1);
       const float sc = ok ? S[t * T + lane] : kBstMasked;
       const float m = wave_max(sc);
@@ -107,7 +104,7 @@ __device__ void bst_attention(const BstGeom& g, const float* theta, const float*
       if (lane < T) S[t * T + lane] = e / z;
     }
     __syncthreads();
-    for (int idx = threadIdx.x; idx < T * w; idx += kBstThreads) {
+    for (int idx = threadIdx.x; idx < T * w; idx += kFieldThreads) {
       const int t = idx / w, c = idx - t * w;
       float acc = 0.f;
       for (int u = 0; u < nvalid; ++u) acc = fmaf(S[t * T + u], v[u * w + c], acc);
@@ -121,7 +118,7 @@ __device__ void bst_attention(const BstGeom& g, const float* theta, const float*
 // dst[t, j] = add[t, j] + (b[j] + sum_i src[t, i] * W[i, j])   (W: [E, E])
 __device__ inline void bst_dense_add(const float* src, const float* W, const float* b, const float* add, int T, int E,
                                      float* dst) {
-  for (int idx = threadIdx.x; idx < T * E; idx += kBstThreads) {
+  for (int idx = threadIdx.x; idx < T * E; idx += kFieldThreads) {
     const int t = idx / E, j = idx - t * E;
     const float* x = src + t * E;
     float acc = 0.f;
@@ -135,7 +132,7 @@ __device__ inline void bst_layer_norm(const float* Z, int T, int E, const float*
                                       float* rs, float* y) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   const float inv = 1.f / static_cast<float>(E);
-  for (int t = wave; t < T; t += kBstWaves) {
+  for (int t = wave; t < T; t += kFieldWaves) {
     const float z = lane < E ? Z[t * E + lane] : 0.f;
     const float m = wave_sum(z) * inv;
     const float d = lane < E ? z - m : 0.f;
@@ -149,7 +146,7 @@ __device__ inline void bst_layer_norm(const float* Z, int T, int E, const float*
   }
 }
 
-__global__ void __launch_bounds__(kBstThreads) bst_fwd_kernel(const float* __restrict__ key,
+__global__ void __launch_bounds__(kFieldThreads) bst_fwd_kernel(const float* __restrict__ key,
                                                               const float* __restrict__ hist,
                                                               const int32_t* __restrict__ seq_len,
                                                               const float* __restrict__ theta, int64_t B, int L,
@@ -165,7 +162,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_fwd_kernel(const float* __res
   float* S = v + T * g.p;
   __shared__ float stat[2 * kBstMaxT];
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
-    for (int idx = threadIdx.x; idx < T * E; idx += kBstThreads) {
+    for (int idx = threadIdx.x; idx < T * E; idx += kFieldThreads) {
       const int t = idx / E, c = idx - t * E;
       X[idx] = t == T - 1 ? key[b * E + c] : (t < L ? hist[(b * L + t) * E + c] : 0.f);
     }
@@ -185,7 +182,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_fwd_kernel(const float* __res
 
 // part[i, j] += sum_t A[t, a0 + i] * D[t, j] for i < m, j < n (A rows of lda floats, D rows of n floats)
 __device__ inline void bst_wgrad(const float* A, int lda, int a0, const float* D, int T, int m, int n, float* part) {
-  for (int idx = threadIdx.x; idx < m * n; idx += kBstThreads) {
+  for (int idx = threadIdx.x; idx < m * n; idx += kFieldThreads) {
     const int i = idx / n, j = idx - i * n;
     float acc = 0.f;
     for (int t = 0; t < T; ++t) acc = fmaf(A[t * lda + a0 + i], D[t * n + j], acc);
@@ -194,7 +191,7 @@ __device__ inline void bst_wgrad(const float* A, int lda, int a0, const float* D
 }
 // part[j] += sum_t D[t, j]
 __device__ inline void bst_bgrad(const float* D, int T, int n, float* part) {
-  for (int j = threadIdx.x; j < n; j += kBstThreads) {
+  for (int j = threadIdx.x; j < n; j += kFieldThreads) {
     float acc = 0.f;
     for (int t = 0; t < T; ++t) acc += D[t * n + j];
     part[j] += acc;
@@ -205,7 +202,7 @@ __device__ inline void bst_bgrad(const float* D, int T, int n, float* part) {
 // go to part_g / part_b
 __device__ inline void bst_layer_norm_bwd(float* Z, const float* dy, int T, int E, const float* gamma, const float* mu,
                                           const float* rs, float* part_g, float* part_b) {
-  for (int j = threadIdx.x; j < E; j += kBstThreads) {
+  for (int j = threadIdx.x; j < E; j += kFieldThreads) {
     float sg = 0.f, sb = 0.f;
     for (int t = 0; t < T; ++t) {
       const float d = dy[t * E + j];
@@ -218,7 +215,7 @@ __device__ inline void bst_layer_norm_bwd(float* Z, const float* dy, int T, int 
   __syncthreads();
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   const float inv = 1.f / static_cast<float>(E);
-  for (int t = wave; t < T; t += kBstWaves) {
+  for (int t = wave; t < T; t += kFieldWaves) {
     const float xh = lane < E ? (Z[t * E + lane] - mu[t]) * rs[t] : 0.f;
     const float dxh = lane < E ? dy[t * E + lane] * gamma[lane] : 0.f;
     const float m1 = wave_sum(dxh) * inv;
@@ -227,7 +224,7 @@ __device__ inline void bst_layer_norm_bwd(float* Z, const float* dy, int T, int 
   }
 }
 
-__global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __restrict__ key,
+__global__ void __launch_bounds__(kFieldThreads) bst_bwd_kernel(const float* __restrict__ key,
                                                               const float* __restrict__ hist,
                                                               const int32_t* __restrict__ seq_len,
                                                               const float* __restrict__ theta,
@@ -259,11 +256,11 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
   float* P = bd + T * p;
   float* dP = P + T * T;
   float* part = partials + static_cast<int64_t>(blockIdx.x) * g.P;
-  for (int i = threadIdx.x; i < g.P; i += kBstThreads) part[i] = 0.f;
+  for (int i = threadIdx.x; i < g.P; i += kFieldThreads) part[i] = 0.f;
   __syncthreads();
   for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
     // -- recompute the forward (the same code and order as bst_fwd_kernel: the same bits)
-    for (int idx = threadIdx.x; idx < T * E; idx += kBstThreads) {
+    for (int idx = threadIdx.x; idx < T * E; idx += kFieldThreads) {
       const int t = idx / E, c = idx - t * E;
       X[idx] = t == T - 1 ? key[b * E + c] : (t < L ? hist[(b * L + t) * E + c] : 0.f);
     }
@@ -285,7 +282,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
     bst_wgrad(B2, E, 0, Z2, T, E, E, part + g.wf);
     bst_bgrad(Z2, T, E, part + g.bf);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < T * E; idx += kBstThreads) {  // dY1 = dZ2 + dZ2 Wf^T  -> B2
+    for (int idx = threadIdx.x; idx < T * E; idx += kFieldThreads) {  // dY1 = dZ2 + dZ2 Wf^T  -> B2
       const int t = idx / E, i = idx - t * E;
       const float* d = Z2 + t * E;
       const float* w = theta + g.wf + i * E;
@@ -299,7 +296,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
     // -- the output projection
     bst_wgrad(O, E, 0, B3, T, E, E, part + g.wo);
     bst_bgrad(B3, T, E, part + g.bo);
-    for (int idx = threadIdx.x; idx < T * E; idx += kBstThreads) {  // dO = dZ1 Wo^T  -> B2
+    for (int idx = threadIdx.x; idx < T * E; idx += kFieldThreads) {  // dO = dZ1 Wo^T  -> B2
       const int t = idx / E, i = idx - t * E;
       const float* d = B3 + t * E;
       const float* w = theta + g.wo + i * E;
@@ -318,7 +315,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
       bst_head_dense(X, E, T, s, w, Wk, theta + g.bk + s, bk);
       bst_head_dense(X, E, T, s, w, Wv, theta + g.bv + s, bv);
       __syncthreads();
-      for (int idx = threadIdx.x; idx < T * T; idx += kBstThreads) {
+      for (int idx = threadIdx.x; idx < T * T; idx += kFieldThreads) {
         const int t = idx / T, u = idx - t * T;
         float acc = 0.f, dacc = 0.f;
         for (int c = 0; c < w; ++c) {
@@ -329,7 +326,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
         dP[idx] = dacc;
       }
       __syncthreads();
-      for (int t = wave; t < T; t += kBstWaves) {  // softmax as in the forward, then dS = P * (dP - sum_u dP P)
+      for (int t = wave; t < T; t += kFieldWaves) {  // softmax as in the forward, then dS = P * (dP - sum_u dP P)
         const bool ok = lane < T && (lane < nvalid || lane == T - 1);
         const float sc = ok ? P[t * T + lane] : kBstMasked;
         const float m = wave_max(sc);
@@ -344,7 +341,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
         }
       }
       __syncthreads();
-      for (int idx = threadIdx.x; idx < T * w; idx += kBstThreads) {
+      for (int idx = threadIdx.x; idx < T * w; idx += kFieldThreads) {
         const int u = idx / w, c = idx - u * w;
         float dv = 0.f, dk = 0.f;
         for (int t = 0; t < T; ++t) {
@@ -355,7 +352,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
         bd[idx] = dk;
       }
       __syncthreads();
-      for (int idx = threadIdx.x; idx < T * w; idx += kBstThreads) {  // dQ = dS K  -> the Q buffer
+      for (int idx = threadIdx.x; idx < T * w; idx += kFieldThreads) {  // dQ = dS K  -> the Q buffer
         const int t = idx / w, c = idx - t * w;
         float acc = 0.f;
         for (int u = 0; u < T; ++u) acc = fmaf(dP[t * T + u], bk[u * w + c], acc);
@@ -368,7 +365,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
       bst_bgrad(bq, T, w, part + g.bq + s);
       bst_bgrad(bd, T, w, part + g.bk + s);
       bst_bgrad(bv, T, w, part + g.bv + s);
-      for (int idx = threadIdx.x; idx < T * w; idx += kBstThreads) {  // dX_h += dQ Wq^T + dK Wk^T + dV Wv^T
+      for (int idx = threadIdx.x; idx < T * w; idx += kFieldThreads) {  // dX_h += dQ Wq^T + dK Wk^T + dV Wv^T
         const int t = idx / w, i = idx - t * w;
         float acc = 0.f;
         for (int j = 0; j < w; ++j) {
@@ -382,7 +379,7 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
     }
     // -- dX: the history rows the reference's slice / pad kept, and the key row; the rest is dropped
     const int keep = min(T - 1, L);
-    for (int idx = threadIdx.x; idx < L * E; idx += kBstThreads) {
+    for (int idx = threadIdx.x; idx < L * E; idx += kFieldThreads) {
       const int t = idx / E;
       float* dst = dhist + b * static_cast<int64_t>(L) * E + idx;
       if (t < keep) {
@@ -391,56 +388,16 @@ __global__ void __launch_bounds__(kBstThreads) bst_bwd_kernel(const float* __res
         *dst = 0.f;
       }
     }
-    for (int c = threadIdx.x; c < E; c += kBstThreads) dkey[b * E + c] = B3[(T - 1) * E + c];
+    for (int c = threadIdx.x; c < E; c += kFieldThreads) dkey[b * E + c] = B3[(T - 1) * E + c];
     __syncthreads();
   }
-}
-
-// the gradient buffers' addresses travel in the kernel arguments (6 * 64 + 8 pointers at most: 3.1 KB), so that a launch
-// inside a stream capture needs no device-side table built beforehand
-constexpr int kBstMaxSegs = 6 * kBstMaxE + 8;
-struct BstGradPtrs {
-  float* p[kBstMaxSegs];
-};
-
-// grads[seg][k - start(seg)] (+)= sum over rows of partials[row, k], rows in order
-__global__ void bst_grad_reduce_kernel(const float* __restrict__ partials, int rows, BstGeom g, BstGradPtrs grads,
-                                       int acc) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= g.P) return;
-  float s = 0.f;
-  for (int r = 0; r < rows; ++r) s += partials[static_cast<int64_t>(r) * g.P + k];
-  // segment of k: 6 per-head groups (W, b alternating per kind), then Wo, bo, Wf, bf, g1, b1, g2, b2
-  int seg, off;
-  if (k < g.wo) {
-    const int kind = k / (g.QW + g.E);  // 0 q, 1 k, 2 v
-    const int r = k - kind * (g.QW + g.E);
-    if (r < g.QW) {
-      const int h = r / (g.p * g.p);
-      seg = (2 * kind) * g.nh + h;
-      off = r - h * g.p * g.p;
-    } else {
-      const int h = (r - g.QW) / g.p;
-      seg = (2 * kind + 1) * g.nh + h;
-      off = r - g.QW - h * g.p;
-    }
-  } else {
-    const int base = 6 * g.nh;
-    const int starts[8] = {g.wo, g.bo, g.wf, g.bf, g.g1, g.b1, g.g2, g.b2};
-    int j = 7;
-    while (k < starts[j]) --j;
-    seg = base + j;
-    off = k - starts[j];
-  }
-  float* dst = grads.p[seg] + off;
-  *dst = acc ? *dst + s : s;
 }
 
 bool bst_shape_ok(int T, int E, int H) { return T >= 2 && T <= kBstMaxT && E >= 1 && E <= kBstMaxE && H >= 1; }
 
 // opt in to more than 64 KB of dynamic LDS once per kernel and size (no stream work: safe inside a capture)
 int bst_set_lds(const void* fn, int bytes, int* done) {
-  if (bytes > 65536 && bytes > *done) {
+  if (bytes > kFieldLdsBudget && bytes > *done) {
     ER_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     *done = bytes;
   }
@@ -463,7 +420,7 @@ int64_t er_bst_lds_bytes(int32_t T, int32_t E, int32_t H) {
   return 4 * static_cast<int64_t>(max(er::bst_bwd_lds(g), er::bst_fwd_lds(g)));
 }
 
-int32_t er_bst_grid(int64_t B) { return static_cast<int32_t>(B < er::kBstGrid ? B : er::kBstGrid); }
+int32_t er_bst_grid(int64_t B) { return er::persistent_grid(B, 1); }
 
 int er_bst_fwd(const float* key, const float* hist, const int32_t* seq_len, const float* theta, int64_t B, int32_t L,
                int32_t T, int32_t E, int32_t H, float* out, er_stream_t stream) {
@@ -473,7 +430,7 @@ int er_bst_fwd(const float* key, const float* hist, const int32_t* seq_len, cons
   const er::BstGeom g = er::bst_geom(T, E, H);
   const int bytes = 4 * er::bst_fwd_lds(g);
   if (er::bst_set_lds(reinterpret_cast<const void*>(er::bst_fwd_kernel), bytes, &er::g_fwd_lds)) return 1;
-  hipLaunchKernelGGL(er::bst_fwd_kernel, dim3(er_bst_grid(B)), dim3(er::kBstThreads), bytes, er::as_stream(stream), key,
+  hipLaunchKernelGGL(er::bst_fwd_kernel, dim3(er_bst_grid(B)), dim3(er::kFieldThreads), bytes, er::as_stream(stream), key,
                      hist, seq_len, theta, B, L, g, out);
   ER_LAUNCH_CHECK();
   return 0;
@@ -489,23 +446,8 @@ int er_bst_bwd(const float* key, const float* hist, const int32_t* seq_len, cons
   const er::BstGeom g = er::bst_geom(T, E, H);
   const int bytes = 4 * er::bst_bwd_lds(g);
   if (er::bst_set_lds(reinterpret_cast<const void*>(er::bst_bwd_kernel), bytes, &er::g_bwd_lds)) return 1;
-  hipLaunchKernelGGL(er::bst_bwd_kernel, dim3(er_bst_grid(B)), dim3(er::kBstThreads), bytes, er::as_stream(stream), key,
+  hipLaunchKernelGGL(er::bst_bwd_kernel, dim3(er_bst_grid(B)), dim3(er::kFieldThreads), bytes, er::as_stream(stream), key,
                      hist, seq_len, theta, dout, B, L, g, dkey, dhist, acc_h, partials);
-  ER_LAUNCH_CHECK();
-  return 0;
-}
-
-int er_bst_grad_reduce(const float* partials, int32_t rows, int32_t E, int32_t H, float* const* grads_host, int acc,
-                       er_stream_t stream) {
-  ER_REQUIRE(partials && grads_host && rows > 0 && E >= 1 && E <= er::kBstMaxE && H >= 1,
-             "er_bst_grad_reduce: bad arguments");
-  const er::BstGeom g = er::bst_geom(2, E, H);
-  er::BstGradPtrs ptrs;
-  const int nseg = 6 * g.nh + 8;
-  for (int i = 0; i < er::kBstMaxSegs; ++i) ptrs.p[i] = i < nseg ? grads_host[i] : nullptr;
-  for (int i = 0; i < nseg; ++i) ER_REQUIRE(ptrs.p[i] != nullptr, "er_bst_grad_reduce: gradient buffer %d is null", i);
-  hipLaunchKernelGGL(er::bst_grad_reduce_kernel, dim3(static_cast<int>(er::ceil_div(g.P, er::kBlock))),
-                     dim3(er::kBlock), 0, er::as_stream(stream), partials, rows, g, ptrs, acc);
   ER_LAUNCH_CHECK();
   return 0;
 }

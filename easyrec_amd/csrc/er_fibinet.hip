@@ -9,23 +9,16 @@
 //
 // Parameter gradients: every entry of theta belongs to one fixed thread of every workgroup; it sums the chunk's examples
 // in order and adds that to ITS slot of the workgroup's row of `partials` [grid, param_count] (written on the
-// workgroup's first chunk, read, added and written by the same thread after).  er_fibinet_grad_reduce then sums the rows in a fixed
-// order into the variables' gradient buffers: no atomics, so two runs and a graph replay give the same bits.
+// workgroup's first chunk, read, added and written by the same thread after).  er_theta_grad_reduce then sums the rows in a
+// fixed order into the variables' gradient buffers: no atomics, so two runs and a graph replay give the same bits.
 // fp32 throughout.
-#include "er_common.h"
+#include "er_field_block.h"
 
 namespace er {
 
-constexpr int kFbThreads = 256;
-constexpr int kFbWaves = kFbThreads / kWave;
-constexpr int kFbMaxEpb = 8;
-constexpr int kFbLdsBudget = 65536;  // bytes per workgroup: no opt-in beyond the default, 2 workgroups per CU
-constexpr int kFbGrid = 512;         // persistent workgroups; rows of `partials`
 constexpr int kFbMaxF = 64;
 constexpr int kFbMaxD = 64;
 constexpr float kSeLnEps = 1e-3f;    // keras LayerNormalization default
-
-__host__ __device__ inline int fb_odd(int n) { return n | 1; }
 
 // ------------------------------------------------------------------------------------------------ bilinear
 // theta: layer l at l * (D * D + D): kernel [D, D] ([in, out] row-major), bias [D].  In LDS the kernel rows sit at the
@@ -43,7 +36,7 @@ __host__ __device__ inline BlGeom bl_geom(int F, int D, int each, int plus) {
   g.D = D;
   g.nw = each ? F - 1 : 1;
   g.plus = plus;
-  g.ldw = fb_odd(D);
+  g.ldw = odd(D);
   g.np = F * (F - 1) / 2;
   g.P = g.nw * (D * D + D);
   g.lw = g.nw * (D * g.ldw + D);
@@ -57,18 +50,13 @@ __host__ __device__ inline int bl_pair_base(int i, int F) { return i * (2 * F - 
 inline bool bl_shape_ok(int F, int D) {
   if (F < 2 || F > kFbMaxF || D < 1 || D > kFbMaxD) return false;
   const BlGeom g = bl_geom(F, D, 1, 1);  // (`each` holds the most parameters)
-  return 4 * (g.fixed + g.per) <= kFbLdsBudget;
-}
-
-inline int fb_epb(int fixed, int per) {
-  const int n = (kFbLdsBudget / 4 - fixed) / per;
-  return n < kFbMaxEpb ? n : kFbMaxEpb;
+  return 4 * (g.fixed + g.per) <= kFieldLdsBudget;
 }
 
 // theta -> LDS at the padded pitch, and the pair table (i << 8 | j) in itertools.combinations order
 __device__ inline void bl_stage_theta(const float* __restrict__ theta, const BlGeom& g, float* th, int* pairs) {
   const int D = g.D, per_l = D * D + D;
-  for (int t = threadIdx.x; t < g.P; t += kFbThreads) {
+  for (int t = threadIdx.x; t < g.P; t += kFieldThreads) {
     const int l = t / per_l, r = t - l * per_l;
     float* dst = th + l * (D * g.ldw + D);
     if (r < D * D) {
@@ -78,7 +66,7 @@ __device__ inline void bl_stage_theta(const float* __restrict__ theta, const BlG
       dst[D * g.ldw + (r - D * D)] = theta[t];
     }
   }
-  for (int i = threadIdx.x; i < g.F - 1; i += kFbThreads) {
+  for (int i = threadIdx.x; i < g.F - 1; i += kFieldThreads) {
     const int base = bl_pair_base(i, g.F);
     for (int j = i + 1; j < g.F; ++j) pairs[base + j - i - 1] = (i << 8) | j;
   }
@@ -87,13 +75,13 @@ __device__ inline void bl_stage_theta(const float* __restrict__ theta, const BlG
 // a chunk's x rows -> LDS, then u_i = x_i W_i + b_i for i < F - 1
 __device__ inline void bl_stage_x_u(const float* __restrict__ xb, int ne, const BlGeom& g, const float* th, float* ex) {
   const int F = g.F, D = g.D, FD = F * D;
-  for (int t = threadIdx.x; t < ne * FD; t += kFbThreads) {
+  for (int t = threadIdx.x; t < ne * FD; t += kFieldThreads) {
     const int e = t / FD;
     ex[e * g.per + (t - e * FD)] = xb[t];
   }
   __syncthreads();
   const int nu = (F - 1) * D;
-  for (int t = threadIdx.x; t < ne * nu; t += kFbThreads) {
+  for (int t = threadIdx.x; t < ne * nu; t += kFieldThreads) {
     const int e = t / nu, r = t - e * nu;
     const int i = r / D, c = r - i * D;
     const float* W = th + (g.nw == 1 ? 0 : i) * (D * g.ldw + D);
@@ -105,7 +93,7 @@ __device__ inline void bl_stage_x_u(const float* __restrict__ xb, int ne, const 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kFbThreads) void bilinear_fwd_kernel(const float* __restrict__ x,
+__global__ __launch_bounds__(kFieldThreads) void bilinear_fwd_kernel(const float* __restrict__ x,
                                                                    const float* __restrict__ theta, int64_t B, BlGeom g,
                                                                    int epb, float* __restrict__ out) {
   extern __shared__ float lds[];
@@ -122,7 +110,7 @@ __global__ __launch_bounds__(kFbThreads) void bilinear_fwd_kernel(const float* _
     bl_stage_x_u(x + b0 * FD, ne, g, th, ex);
     if (g.plus) {
       float* ob = out + b0 * np;
-      for (int t = threadIdx.x; t < ne * np; t += kFbThreads) {
+      for (int t = threadIdx.x; t < ne * np; t += kFieldThreads) {
         const int e = t / np, p = t - e * np;
         const int i = pairs[p] >> 8, j = pairs[p] & 255;
         const float* u = ex + e * g.per + FD + i * D;
@@ -134,7 +122,7 @@ __global__ __launch_bounds__(kFbThreads) void bilinear_fwd_kernel(const float* _
     } else {
       float* ob = out + b0 * np * D;
       const int n1 = np * D;
-      for (int t = threadIdx.x; t < ne * n1; t += kFbThreads) {
+      for (int t = threadIdx.x; t < ne * n1; t += kFieldThreads) {
         const int e = t / n1, r = t - e * n1;
         const int p = r / D, c = r - p * D;
         const int i = pairs[p] >> 8, j = pairs[p] & 255;
@@ -144,7 +132,7 @@ __global__ __launch_bounds__(kFbThreads) void bilinear_fwd_kernel(const float* _
   }
 }
 
-__global__ __launch_bounds__(kFbThreads) void bilinear_bwd_kernel(const float* __restrict__ x,
+__global__ __launch_bounds__(kFieldThreads) void bilinear_bwd_kernel(const float* __restrict__ x,
                                                                    const float* __restrict__ theta,
                                                                    const float* __restrict__ dout, int64_t B, BlGeom g,
                                                                    int epb, float* __restrict__ dx,
@@ -165,7 +153,7 @@ __global__ __launch_bounds__(kFbThreads) void bilinear_bwd_kernel(const float* _
     bl_stage_x_u(x + b0 * FD, ne, g, th, ex);
     // du_i = sum_{j > i} dp_ij x_j
     const float* db = dout + b0 * np * (g.plus ? 1 : D);
-    for (int t = threadIdx.x; t < ne * nu; t += kFbThreads) {
+    for (int t = threadIdx.x; t < ne * nu; t += kFieldThreads) {
       const int e = t / nu, r = t - e * nu;
       const int i = r / D, c = r - i * D;
       const int base = bl_pair_base(i, F);
@@ -183,7 +171,7 @@ __global__ __launch_bounds__(kFbThreads) void bilinear_bwd_kernel(const float* _
     __syncthreads();
     // dx_f = sum_{i < f} dp_if u_i (the field as x_j) + du_f W_f^T (the field as x_i, f < F - 1)
     float* dxb = dx + b0 * FD;
-    for (int t = threadIdx.x; t < ne * FD; t += kFbThreads) {
+    for (int t = threadIdx.x; t < ne * FD; t += kFieldThreads) {
       const int e = t / FD, r = t - e * FD;
       const int f = r / D, c = r - f * D;
       const float* X = ex + e * g.per;
@@ -205,7 +193,7 @@ __global__ __launch_bounds__(kFbThreads) void bilinear_bwd_kernel(const float* _
     // theta partials: dW_l[k, c] = sum_e sum_{i of l} x_i[k] du_i[c], db_l[c] = sum_e sum_{i of l} du_i[c]
     const int per_l = D * D + D;
     const bool first = chunk == blockIdx.x;
-    for (int t = threadIdx.x; t < g.P; t += kFbThreads) {
+    for (int t = threadIdx.x; t < g.P; t += kFieldThreads) {
       const int l = t / per_l, r = t - l * per_l;
       const int i0 = g.nw == 1 ? 0 : l, i1 = g.nw == 1 ? F - 1 : l + 1;
       float acc = 0.f;
@@ -258,7 +246,7 @@ __host__ __device__ inline SeGeom se_geom(int F, int D, int G, int R, int skip, 
 inline bool se_shape_ok(int F, int D, int G, int R) {
   if (F < 1 || F > kFbMaxF || D < 1 || D > kFbMaxD || G < 1 || D % G != 0 || R < 1 || R > 2 * F * G) return false;
   const SeGeom g = se_geom(F, D, G, R, 1, 1);
-  return 4 * (g.P + g.per_b) <= kFbLdsBudget;
+  return 4 * (g.P + g.per_b) <= kFieldLdsBudget;
 }
 
 // x rows -> LDS; z (per field the G group maxima, then the G group means); a1 = relu(z W1 + b1);
@@ -267,13 +255,13 @@ inline bool se_shape_ok(int F, int D, int G, int R) {
 __device__ inline void se_forward(const float* __restrict__ xb, int ne, const SeGeom& g, const float* th, float* ex,
                                   int per, int xo, int wo, int oo, int zo, int ao, int so) {
   const int FD = g.FD, Z = g.Z, R = g.R, G = g.G, gs = g.gs;
-  for (int t = threadIdx.x; t < ne * FD; t += kFbThreads) {
+  for (int t = threadIdx.x; t < ne * FD; t += kFieldThreads) {
     const int e = t / FD;
     ex[e * per + xo + (t - e * FD)] = xb[t];
   }
   __syncthreads();
   const int nz = g.F * G;
-  for (int t = threadIdx.x; t < ne * nz; t += kFbThreads) {
+  for (int t = threadIdx.x; t < ne * nz; t += kFieldThreads) {
     const int e = t / nz, r = t - e * nz;
     const int f = r / G, q = r - f * G;
     const float* v = ex + e * per + xo + f * g.D + q * gs;
@@ -286,7 +274,7 @@ __device__ inline void se_forward(const float* __restrict__ xb, int ne, const Se
     ex[e * per + zo + f * 2 * G + G + q] = s / static_cast<float>(gs);
   }
   __syncthreads();
-  for (int t = threadIdx.x; t < ne * R; t += kFbThreads) {
+  for (int t = threadIdx.x; t < ne * R; t += kFieldThreads) {
     const int e = t / R, r = t - e * R;
     const float* z = ex + e * per + zo;
     float acc = 0.f;
@@ -295,7 +283,7 @@ __device__ inline void se_forward(const float* __restrict__ xb, int ne, const Se
     ex[e * per + ao + r] = acc > 0.f ? acc : 0.f;
   }
   __syncthreads();
-  for (int t = threadIdx.x; t < ne * FD; t += kFbThreads) {
+  for (int t = threadIdx.x; t < ne * FD; t += kFieldThreads) {
     const int e = t / FD, c = t - e * FD;
     const float* a = ex + e * per + ao;
     float acc = 0.f;
@@ -309,7 +297,7 @@ __device__ inline void se_forward(const float* __restrict__ xb, int ne, const Se
   __syncthreads();
   if (g.ln) {  // one wave per example, lanes strided over the row
     const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    for (int e = wave; e < ne; e += kFbWaves) {
+    for (int e = wave; e < ne; e += kFieldWaves) {
       const float* o = ex + e * per + oo;
       float s = 0.f;
       for (int c = lane; c < FD; c += kWave) s += o[c];
@@ -326,7 +314,7 @@ __device__ inline void se_forward(const float* __restrict__ xb, int ne, const Se
   }
 }
 
-__global__ __launch_bounds__(kFbThreads) void senet_fwd_kernel(const float* __restrict__ x,
+__global__ __launch_bounds__(kFieldThreads) void senet_fwd_kernel(const float* __restrict__ x,
                                                                 const float* __restrict__ theta, int64_t B, SeGeom g,
                                                                 int epb, float* __restrict__ y, float* __restrict__ a1) {
   extern __shared__ float lds[];
@@ -334,7 +322,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_fwd_kernel(const float* __re
   float* ex = lds + g.P;
   const int FD = g.FD, per = g.per_f;
   const int xo = 0, oo = FD, zo = 2 * FD, ao = zo + g.Z, so = ao + g.R;
-  for (int t = threadIdx.x; t < g.P; t += kFbThreads) th[t] = theta[t];
+  for (int t = threadIdx.x; t < g.P; t += kFieldThreads) th[t] = theta[t];
   const int64_t nchunks = (B + epb - 1) / epb;
   for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     const int64_t b0 = chunk * epb;
@@ -342,14 +330,14 @@ __global__ __launch_bounds__(kFbThreads) void senet_fwd_kernel(const float* __re
     __syncthreads();
     se_forward(x + b0 * FD, ne, g, th, ex, per, xo, -1, oo, zo, ao, so);
     float* yb = y + b0 * FD;
-    for (int t = threadIdx.x; t < ne * FD; t += kFbThreads) {
+    for (int t = threadIdx.x; t < ne * FD; t += kFieldThreads) {
       const int e = t / FD, c = t - e * FD;
       float o = ex[e * per + oo + c];
       if (g.ln) o = (o - ex[e * per + so]) * ex[e * per + so + 1] * th[g.gm + c] + th[g.bt + c];
       yb[t] = o;
     }
     if (a1 != nullptr) {
-      for (int t = threadIdx.x; t < ne * g.R; t += kFbThreads) {
+      for (int t = threadIdx.x; t < ne * g.R; t += kFieldThreads) {
         const int e = t / g.R;
         a1[b0 * g.R + t] = ex[e * per + ao + (t - e * g.R)];
       }
@@ -357,7 +345,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_fwd_kernel(const float* __re
   }
 }
 
-__global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __restrict__ x,
+__global__ __launch_bounds__(kFieldThreads) void senet_bwd_kernel(const float* __restrict__ x,
                                                                 const float* __restrict__ theta,
                                                                 const float* __restrict__ dy, int64_t B, SeGeom g,
                                                                 int epb, float* __restrict__ dx,
@@ -368,7 +356,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
   const int FD = g.FD, Z = g.Z, R = g.R, G = g.G, gs = g.gs, per = g.per_b;
   const int xo = 0, wo = FD, oo = 2 * FD, go = 3 * FD;  // x, w, o -> xhat, do -> dw
   const int zo = 4 * FD, dzo = zo + Z, ao = dzo + Z, dao = ao + R, so = dao + R;
-  for (int t = threadIdx.x; t < g.P; t += kFbThreads) th[t] = theta[t];
+  for (int t = threadIdx.x; t < g.P; t += kFieldThreads) th[t] = theta[t];
   float* part = partials + static_cast<int64_t>(blockIdx.x) * g.P;
   const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
   const int64_t nchunks = (B + epb - 1) / epb;
@@ -381,7 +369,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
     const float* dyb = dy + b0 * FD;
     if (g.ln) {
       // xhat over o; dxhat = dy gamma -> go; then do = rstd (dxhat - mean(dxhat) - xhat mean(dxhat xhat))
-      for (int t = threadIdx.x; t < ne * FD; t += kFbThreads) {
+      for (int t = threadIdx.x; t < ne * FD; t += kFieldThreads) {
         const int e = t / FD, c = t - e * FD;
         float* E = ex + e * per;
         E[oo + c] = (E[oo + c] - E[so]) * E[so + 1];
@@ -389,7 +377,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
       }
       __syncthreads();
       // dgamma = sum_e dy xhat, dbeta = sum_e dy
-      for (int c = threadIdx.x; c < FD; c += kFbThreads) {
+      for (int c = threadIdx.x; c < FD; c += kFieldThreads) {
         float ag = 0.f, ab = 0.f;
         for (int e = 0; e < ne; ++e) {
           const float d = dyb[e * FD + c];
@@ -399,7 +387,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
         part[g.gm + c] = first ? ag : part[g.gm + c] + ag;
         part[g.bt + c] = first ? ab : part[g.bt + c] + ab;
       }
-      for (int e = wave; e < ne; e += kFbWaves) {
+      for (int e = wave; e < ne; e += kFieldWaves) {
         float* E = ex + e * per;
         float s1 = 0.f, s2 = 0.f;
         for (int c = lane; c < FD; c += kWave) {
@@ -411,7 +399,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
         for (int c = lane; c < FD; c += kWave) E[go + c] = rstd * (E[go + c] - m1 - E[oo + c] * m2);
       }
     } else {
-      for (int t = threadIdx.x; t < ne * FD; t += kFbThreads) {
+      for (int t = threadIdx.x; t < ne * FD; t += kFieldThreads) {
         const int e = t / FD;
         ex[e * per + go + (t - e * FD)] = dyb[t];
       }
@@ -419,7 +407,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
     __syncthreads();
     // dx = do w (+ do) (the squeeze's part is added below by the same thread); dw = do x -> go
     float* dxb = dx + b0 * FD;
-    for (int t = threadIdx.x; t < ne * FD; t += kFbThreads) {
+    for (int t = threadIdx.x; t < ne * FD; t += kFieldThreads) {
       const int e = t / FD, c = t - e * FD;
       float* E = ex + e * per;
       const float d = E[go + c];
@@ -429,7 +417,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
     }
     __syncthreads();
     // da1[r] = sum_c dw[c] W2[r, c], through the ReLU: one wave per (example, r)
-    for (int t = wave; t < ne * R; t += kFbWaves) {
+    for (int t = wave; t < ne * R; t += kFieldWaves) {
       const int e = t / R, r = t - e * R;
       const float* dw = ex + e * per + go;
       const float* W = th + g.w2 + r * FD;
@@ -439,7 +427,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
       if (lane == 0) ex[e * per + dao + r] = ex[e * per + ao + r] > 0.f ? s : 0.f;
     }
     // db2 = sum_e dw, dW2[r, c] = sum_e a1[r] dw[c]
-    for (int t = threadIdx.x; t < FD + R * FD; t += kFbThreads) {
+    for (int t = threadIdx.x; t < FD + R * FD; t += kFieldThreads) {
       float acc = 0.f;
       int k;
       if (t < FD) {
@@ -454,7 +442,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
     }
     __syncthreads();
     // dz[k] = sum_r dpre1[r] W1[k, r]
-    for (int t = threadIdx.x; t < ne * Z; t += kFbThreads) {
+    for (int t = threadIdx.x; t < ne * Z; t += kFieldThreads) {
       const int e = t / Z, k = t - e * Z;
       const float* d = ex + e * per + dao;
       float acc = 0.f;
@@ -462,7 +450,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
       ex[e * per + dzo + k] = acc;
     }
     // db1 = sum_e dpre1, dW1[k, r] = sum_e z[k] dpre1[r]
-    for (int t = threadIdx.x; t < R + Z * R; t += kFbThreads) {
+    for (int t = threadIdx.x; t < R + Z * R; t += kFieldThreads) {
       float acc = 0.f;
       int k;
       if (t < R) {
@@ -477,7 +465,7 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
     }
     __syncthreads();
     // the squeeze: the mean's share to every column of the group, the max's split evenly among the tied maxima
-    for (int t = threadIdx.x; t < ne * FD; t += kFbThreads) {
+    for (int t = threadIdx.x; t < ne * FD; t += kFieldThreads) {
       const int e = t / FD, c = t - e * FD;
       const int f = c / g.D, q = (c - f * g.D) / gs;
       const float* E = ex + e * per;
@@ -492,59 +480,6 @@ __global__ __launch_bounds__(kFbThreads) void senet_bwd_kernel(const float* __re
       dxb[t] = acc;
     }
   }
-}
-
-// ------------------------------------------------------------------------------------------------ gradient reduce
-constexpr int kFbMaxSegs = 2 * (kFbMaxF - 1);
-struct FbSegs {
-  float* p[kFbMaxSegs];
-  int start[kFbMaxSegs + 1];  // first theta entry of each segment; start[nseg] = P
-};
-
-// grads[seg][k - start[seg]] (+)= sum over the rows of partials[row, k]: 32 columns x 8 row groups per workgroup, each
-// thread its group's rows in order, the 8 sums combined in order
-__global__ __launch_bounds__(kFbThreads) void fibinet_grad_reduce_kernel(const float* __restrict__ partials, int rows,
-                                                                          int P, int nseg, FbSegs segs, int acc) {
-  __shared__ float sums[8][32];
-  const int col = threadIdx.x & 31, rg = threadIdx.x >> 5;
-  const int k = blockIdx.x * 32 + col;
-  float s = 0.f;
-  if (k < P)
-    for (int r = rg; r < rows; r += 8) s += partials[static_cast<int64_t>(r) * P + k];
-  sums[rg][col] = s;
-  __syncthreads();
-  if (rg != 0 || k >= P) return;
-  for (int i = 1; i < 8; ++i) s += sums[i][col];
-  int lo = 0, hi = nseg;  // the segment with start[seg] <= k < start[seg + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) / 2;
-    if (segs.start[mid] <= k) lo = mid; else hi = mid;
-  }
-  float* dst = segs.p[lo] + (k - segs.start[lo]);
-  *dst = acc ? *dst + s : s;
-}
-
-int fb_grid(int64_t B, int epb) {
-  const int64_t n = (B + epb - 1) / epb;
-  return static_cast<int>(n < kFbGrid ? n : kFbGrid);
-}
-
-int fb_reduce(const float* partials, int rows, int P, int nseg, const int* lens, float* const* grads_host, int acc,
-              hipStream_t stream) {
-  FbSegs segs;
-  int o = 0;
-  for (int i = 0; i < kFbMaxSegs; ++i) {
-    segs.p[i] = i < nseg ? grads_host[i] : nullptr;
-    segs.start[i] = o;
-    if (i < nseg) o += lens[i];
-  }
-  segs.start[kFbMaxSegs] = o;
-  for (int i = 0; i < nseg; ++i) ER_REQUIRE(segs.p[i] != nullptr, "er_fibinet_grad_reduce: gradient buffer %d is null", i);
-  ER_REQUIRE(o == P, "er_fibinet_grad_reduce: segments hold %d floats, theta %d", o, P);
-  hipLaunchKernelGGL(fibinet_grad_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(P, 32))), dim3(kFbThreads), 0,
-                     stream, partials, rows, P, nseg, segs, acc);
-  ER_LAUNCH_CHECK();
-  return 0;
 }
 
 }  // namespace er
@@ -566,12 +501,12 @@ int64_t er_bilinear_lds_bytes(int32_t F, int32_t D) {
 int32_t er_bilinear_epb(int32_t F, int32_t D, int each) {
   if (!er::bl_shape_ok(F, D)) return 0;
   const er::BlGeom g = er::bl_geom(F, D, each, 1);
-  return er::fb_epb(g.fixed, g.per);
+  return er::epb(g.fixed, g.per);
 }
 
 int32_t er_bilinear_grid(int64_t B, int32_t F, int32_t D, int each) {
   const int epb = er_bilinear_epb(F, D, each);
-  return epb > 0 && B > 0 ? er::fb_grid(B, epb) : 0;
+  return epb > 0 && B > 0 ? er::persistent_grid(B, epb) : 0;
 }
 
 int er_bilinear_fwd(const float* x, const float* theta, int64_t B, int32_t F, int32_t D, int each, int plus, float* out,
@@ -579,8 +514,8 @@ int er_bilinear_fwd(const float* x, const float* theta, int64_t B, int32_t F, in
   ER_REQUIRE(x && theta && out && B > 0, "er_bilinear_fwd: bad arguments");
   ER_REQUIRE(er::bl_shape_ok(F, D), "er_bilinear_fwd: F = %d, D = %d outside the envelope", F, D);
   const er::BlGeom g = er::bl_geom(F, D, each, plus);
-  const int epb = er::fb_epb(g.fixed, g.per);
-  hipLaunchKernelGGL(er::bilinear_fwd_kernel, dim3(er::fb_grid(B, epb)), dim3(er::kFbThreads),
+  const int epb = er::epb(g.fixed, g.per);
+  hipLaunchKernelGGL(er::bilinear_fwd_kernel, dim3(er::persistent_grid(B, epb)), dim3(er::kFieldThreads),
                      4 * (g.fixed + epb * g.per), er::as_stream(stream), x, theta, B, g, epb, out);
   ER_LAUNCH_CHECK();
   return 0;
@@ -591,24 +526,11 @@ int er_bilinear_bwd(const float* x, const float* theta, const float* dout, int64
   ER_REQUIRE(x && theta && dout && dx && partials && B > 0, "er_bilinear_bwd: bad arguments");
   ER_REQUIRE(er::bl_shape_ok(F, D), "er_bilinear_bwd: F = %d, D = %d outside the envelope", F, D);
   const er::BlGeom g = er::bl_geom(F, D, each, plus);
-  const int epb = er::fb_epb(g.fixed, g.per);
-  hipLaunchKernelGGL(er::bilinear_bwd_kernel, dim3(er::fb_grid(B, epb)), dim3(er::kFbThreads),
+  const int epb = er::epb(g.fixed, g.per);
+  hipLaunchKernelGGL(er::bilinear_bwd_kernel, dim3(er::persistent_grid(B, epb)), dim3(er::kFieldThreads),
                      4 * (g.fixed + epb * g.per), er::as_stream(stream), x, theta, dout, B, g, epb, dx, partials);
   ER_LAUNCH_CHECK();
   return 0;
-}
-
-int er_bilinear_grad_reduce(const float* partials, int32_t rows, int32_t F, int32_t D, int each,
-                            float* const* grads_host, int acc, er_stream_t stream) {
-  ER_REQUIRE(partials && grads_host && rows > 0, "er_bilinear_grad_reduce: bad arguments");
-  ER_REQUIRE(er::bl_shape_ok(F, D), "er_bilinear_grad_reduce: F = %d, D = %d outside the envelope", F, D);
-  const er::BlGeom g = er::bl_geom(F, D, each, 1);
-  int lens[er::kFbMaxSegs];
-  for (int l = 0; l < g.nw; ++l) {
-    lens[2 * l] = D * D;
-    lens[2 * l + 1] = D;
-  }
-  return er::fb_reduce(partials, rows, g.P, 2 * g.nw, lens, grads_host, acc, er::as_stream(stream));
 }
 
 int64_t er_senet_param_count(int32_t F, int32_t D, int32_t G, int32_t R, int ln) {
@@ -627,12 +549,12 @@ int64_t er_senet_lds_bytes(int32_t F, int32_t D, int32_t G, int32_t R) {
 int32_t er_senet_epb(int32_t F, int32_t D, int32_t G, int32_t R, int ln, int bwd) {
   if (!er::se_shape_ok(F, D, G, R)) return 0;
   const er::SeGeom g = er::se_geom(F, D, G, R, 1, ln);
-  return er::fb_epb(g.P, bwd ? g.per_b : g.per_f);
+  return er::epb(g.P, bwd ? g.per_b : g.per_f);
 }
 
 int32_t er_senet_grid(int64_t B, int32_t F, int32_t D, int32_t G, int32_t R, int ln) {
   const int epb = er_senet_epb(F, D, G, R, ln, 1);
-  return epb > 0 && B > 0 ? er::fb_grid(B, epb) : 0;
+  return epb > 0 && B > 0 ? er::persistent_grid(B, epb) : 0;
 }
 
 int er_senet_fwd(const float* x, const float* theta, int64_t B, int32_t F, int32_t D, int32_t G, int32_t R, int skip,
@@ -640,9 +562,9 @@ int er_senet_fwd(const float* x, const float* theta, int64_t B, int32_t F, int32
   ER_REQUIRE(x && theta && y && B > 0, "er_senet_fwd: bad arguments");
   ER_REQUIRE(er::se_shape_ok(F, D, G, R), "er_senet_fwd: F = %d, D = %d, G = %d, R = %d outside the envelope", F, D, G, R);
   const er::SeGeom g = er::se_geom(F, D, G, R, skip, ln);
-  const int epb = er::fb_epb(g.P, g.per_f);
-  hipLaunchKernelGGL(er::senet_fwd_kernel, dim3(er::fb_grid(B, epb)), dim3(er::kFbThreads), 4 * (g.P + epb * g.per_f),
-                     er::as_stream(stream), x, theta, B, g, epb, y, a1);
+  const int epb = er::epb(g.P, g.per_f);
+  hipLaunchKernelGGL(er::senet_fwd_kernel, dim3(er::persistent_grid(B, epb)), dim3(er::kFieldThreads),
+                     4 * (g.P + epb * g.per_f), er::as_stream(stream), x, theta, B, g, epb, y, a1);
   ER_LAUNCH_CHECK();
   return 0;
 }
@@ -652,21 +574,11 @@ int er_senet_bwd(const float* x, const float* theta, const float* dy, int64_t B,
   ER_REQUIRE(x && theta && dy && dx && partials && B > 0, "er_senet_bwd: bad arguments");
   ER_REQUIRE(er::se_shape_ok(F, D, G, R), "er_senet_bwd: F = %d, D = %d, G = %d, R = %d outside the envelope", F, D, G, R);
   const er::SeGeom g = er::se_geom(F, D, G, R, skip, ln);
-  const int epb = er::fb_epb(g.P, g.per_b);
-  hipLaunchKernelGGL(er::senet_bwd_kernel, dim3(er::fb_grid(B, epb)), dim3(er::kFbThreads), 4 * (g.P + epb * g.per_b),
-                     er::as_stream(stream), x, theta, dy, B, g, epb, dx, partials);
+  const int epb = er::epb(g.P, g.per_b);
+  hipLaunchKernelGGL(er::senet_bwd_kernel, dim3(er::persistent_grid(B, epb)), dim3(er::kFieldThreads),
+                     4 * (g.P + epb * g.per_b), er::as_stream(stream), x, theta, dy, B, g, epb, dx, partials);
   ER_LAUNCH_CHECK();
   return 0;
-}
-
-int er_senet_grad_reduce(const float* partials, int32_t rows, int32_t F, int32_t D, int32_t G, int32_t R, int ln,
-                         float* const* grads_host, int acc, er_stream_t stream) {
-  ER_REQUIRE(partials && grads_host && rows > 0, "er_senet_grad_reduce: bad arguments");
-  ER_REQUIRE(er::se_shape_ok(F, D, G, R), "er_senet_grad_reduce: F = %d, D = %d, G = %d, R = %d outside the envelope", F,
-             D, G, R);
-  const er::SeGeom g = er::se_geom(F, D, G, R, 1, ln);
-  const int lens[6] = {g.Z * R, R, R * g.FD, g.FD, g.FD, g.FD};
-  return er::fb_reduce(partials, rows, g.P, ln ? 6 : 4, lens, grads_host, acc, er::as_stream(stream));
 }
 
 }  // extern "C"

@@ -1969,6 +1969,13 @@ class HipBackend(object):
                                  scale, _p(dscores), _p(dhist), acc_h, _stream()), 'er_din_pool_bwd')
     return dscores, dhist
 
+  # -- K8e the gradient reduce of the blocks with packed parameters (K8b, K8d)
+  def theta_grad_reduce(self, partials, rows, grads, row_groups, acc):
+    """`grads` (a ThetaGradTable) (+)= the sum over the rows of partials [rows, P]; row_groups (1 or 8) is the
+    summation order easyrec_hip.h states."""
+    self._ck(self.lib.er_theta_grad_reduce(_p(partials), rows, partials.numel() // rows, grads.lens, len(grads.grads),
+                                           grads.table, row_groups, bool(acc), _stream()), 'er_theta_grad_reduce')
+
   # -- K8b BST transformer block (model/multi_tower_bst.py)
   BST_MAX_T = 64
   BST_MAX_E = 64
@@ -2001,7 +2008,7 @@ class HipBackend(object):
 
   def bst_bwd(self, key, hist, seq_len, theta, dout, T, H, grads, dhist=None, acc_h=False):
     """dkey [B, E] and dhist [B, L, E] (written, or added into with acc_h); the parameter gradients are ADDED into
-    `grads` (a BstGradTable: the variables' gradient buffers in theta's order)."""
+    `grads` (a ThetaGradTable: the variables' gradient buffers in theta's order)."""
     B, L, E = hist.shape
     dkey = torch.empty(B, E, dtype=torch.float32, device=hist.device)
     if dhist is None:
@@ -2012,7 +2019,7 @@ class HipBackend(object):
     partials = torch.empty(rows * self.bst_param_count(E, H), dtype=torch.float32, device=hist.device)
     self._ck(self.lib.er_bst_bwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), _p(_f32c(dout)), B, L,
                                  T, E, H, _p(dkey), _p(dhist), acc_h, _p(partials), _stream()), 'er_bst_bwd')
-    self._ck(self.lib.er_bst_grad_reduce(_p(partials), rows, E, H, grads.table, 1, _stream()), 'er_bst_grad_reduce')
+    self.theta_grad_reduce(partials, rows, grads, 1, True)
     if self.op_log is not None:
       self.op_log.append(('er::bst_bwd_kernel', 2.0 * self._bst_flops(B, T, E, H)))
     return dkey, dhist
@@ -2084,7 +2091,7 @@ class HipBackend(object):
     return out
 
   def bilinear_bwd(self, x, theta, dout, F, D, each, plus, grads, acc=True):
-    """-> dx [B, F * D]; the parameter gradients are added into (acc) or written to `grads` (a BstGradTable: the
+    """-> dx [B, F * D]; the parameter gradients are added into (acc) or written to `grads` (a ThetaGradTable: the
     buffers in theta's order, kernel and bias per dense layer)."""
     B = x.shape[0]
     pairs = F * (F - 1) // 2
@@ -2094,8 +2101,7 @@ class HipBackend(object):
     partials = torch.empty(rows * theta.numel(), dtype=torch.float32, device=x.device)
     self._ck(self.lib.er_bilinear_bwd(_p(_f32c(x)), _p(_f32c(theta)), _p(_f32c(dout)), B, F, D, bool(each), bool(plus),
                                       _p(dx), _p(partials), _stream()), 'er_bilinear_bwd')
-    self._ck(self.lib.er_bilinear_grad_reduce(_p(partials), rows, F, D, bool(each), grads.table, bool(acc), _stream()),
-             'er_bilinear_grad_reduce')
+    self.theta_grad_reduce(partials, rows, grads, 8, acc)
     if self.op_log is not None:
       self.op_log.append(('er::bilinear_bwd_kernel', 6.0 * B * ((F - 1) * D * D + pairs * D)))
     return dx
@@ -2131,8 +2137,7 @@ class HipBackend(object):
     partials = torch.empty(rows * theta.numel(), dtype=torch.float32, device=x.device)
     self._ck(self.lib.er_senet_bwd(_p(_f32c(x)), _p(_f32c(theta)), _p(_f32c(dy)), B, F, D, G, R, bool(skip), bool(ln),
                                    _p(dx), _p(partials), _stream()), 'er_senet_bwd')
-    self._ck(self.lib.er_senet_grad_reduce(_p(partials), rows, F, D, G, R, bool(ln), grads.table, bool(acc), _stream()),
-             'er_senet_grad_reduce')
+    self.theta_grad_reduce(partials, rows, grads, 8, acc)
     if self.op_log is not None:
       self.op_log.append(('er::senet_bwd_kernel', 6.0 * B * R * (2 * F * G + F * D)))
     return dx
@@ -3907,17 +3912,15 @@ class DINPoolFn(torch.autograd.Function):
     return dscores, (buf if first else None), None, None
 
 
-class BstGradTable(object):
-  """The gradient-buffer addresses er_bst_grad_reduce writes through, in theta's order: a host array, passed in the
-  launch's kernel arguments (nothing to build on the device, so a first call inside a stream capture is fine)."""
+class ThetaGradTable(object):
+  """The gradient buffers er_theta_grad_reduce writes through, in theta's order: host arrays of their addresses and
+  lengths, passed in the launch's kernel arguments (nothing to build on the device, so a first call inside a stream
+  capture is fine)."""
 
   def __init__(self, grads):
     self.grads = list(grads)
     self.table = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-
-  @classmethod
-  def of(cls, grads):
-    return cls(grads)
+    self.lens = (ctypes.c_int32 * len(grads))(*[g.numel() for g in grads])
 
 
 class BSTBlockFn(torch.autograd.Function):
@@ -3931,19 +3934,12 @@ class BSTBlockFn(torch.autograd.Function):
   def forward(ctx, key, hist, seq_len, T, H, grads, *params):
     be = hip()
     E = hist.shape[2]
-    theta = torch.empty(be.bst_param_count(E, H), dtype=torch.float32, device=hist.device)
-    pairs, o = [], 0
-    for prm in params:
-      n = prm.numel()
-      pairs.append((theta[o:o + n], prm.detach().reshape(-1)))
-      o += n
-    assert o == theta.numel(), 'BSTBlockFn: %d parameter floats, the kernel expects %d' % (o, theta.numel())
-    be.copy_multi(pairs)  # one launch
+    theta = _pack_theta(be, params, be.bst_param_count(E, H), 'BSTBlockFn')
     key = key.contiguous()
     out = be.bst_fwd(key, hist, seq_len, theta, T, H)
     ctx.save_for_backward(key, hist, seq_len, theta)
     ctx.T, ctx.H = T, H
-    ctx.table = BstGradTable.of(grads) if grads is not None else None
+    ctx.table = ThetaGradTable(grads) if grads is not None else None
     ctx.slots = grad_slots_of_step() if hist.is_contiguous() else None
     return out
 
@@ -4033,9 +4029,9 @@ def _theta_grads(ctx, params):
   (`grads`, zeroed once per step by VarStore.zero_grad) the gradients are ADDED there and autograd gets nothing; without,
   fresh tensors are written and returned to autograd."""
   if ctx.grads is not None:
-    return BstGradTable.of(ctx.grads), True, (None,) * len(params)
+    return ThetaGradTable(ctx.grads), True, (None,) * len(params)
   fresh = [torch.empty_like(p) for p in params]
-  return BstGradTable.of(fresh), False, tuple(fresh)
+  return ThetaGradTable(fresh), False, tuple(fresh)
 
 
 class BiLinearFn(torch.autograd.Function):

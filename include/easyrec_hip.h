@@ -633,10 +633,8 @@ int er_din_pool_bwd(const float* probs, const float* hist, const int32_t* seq_le
  * er_bst_fwd: out [B, T * E] (row-major over t, the key row last).
  * er_bst_bwd: recomputes the forward per example, then dkey [B, E] =, dhist [B, L, E] (+)= (rows
  *   t >= min(T - 1, L) get nothing, or 0 without acc_h), and per-workgroup partial sums of the
- *   packed parameter gradient into partials [grid, er_bst_param_count] (no atomics).
- * er_bst_grad_reduce: sums partials over the grid rows in fixed order and adds (acc != 0) or
- *   writes the result into the variables' gradient buffers: grads_host is a HOST array of
- *   6 * nh + 8 pointers in theta's order (passed in the kernel arguments: capture-safe).
+ *   packed parameter gradient into partials [er_bst_grid, er_bst_param_count] (no atomics), which
+ *   er_theta_grad_reduce (K8e) sums with row_groups = 1 into the 6 * nh + 8 variables.
  * -------------------------------------------------------------------------------------------- */
 int64_t er_bst_param_count(int32_t E, int32_t H);
 int64_t er_bst_lds_bytes(int32_t T, int32_t E, int32_t H);  /* the backward's LDS per workgroup (the larger) */
@@ -646,8 +644,6 @@ int er_bst_fwd(const float* key, const float* hist, const int32_t* seq_len, cons
 int er_bst_bwd(const float* key, const float* hist, const int32_t* seq_len, const float* theta, const float* dout,
                int64_t B, int32_t L, int32_t T, int32_t E, int32_t H, float* dkey, float* dhist, int acc_h,
                float* partials, er_stream_t stream);
-int er_bst_grad_reduce(const float* partials, int32_t rows, int32_t E, int32_t H, float* const* grads_host, int acc,
-                       er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * K8c AutoInt self-attention core.  Replaces the per-head Reshape / Transpose / BatchMatMul(transpose_b) /
@@ -682,10 +678,8 @@ int er_autoint_pack(const float* wq, const float* wk, const float* wv, const flo
  *   pairs (i, j), i < j, in itertools.combinations order: plus != 0: out [B, F (F - 1) / 2] = <u_i, x_j>;
  *   else out [B, F (F - 1) / 2 * D] = u_i * x_j.
  * er_bilinear_bwd: recomputes u; dx [B, F * D] = (a field as x_i, through W_i^T, and as x_j); per-workgroup
- *   partial sums of the packed parameter gradient into partials [er_bilinear_grid, param_count].
- * er_bilinear_grad_reduce: sums the rows in fixed order and adds (acc != 0) or writes the result into the
- *   variables' gradient buffers: grads_host is a HOST array of 2 n_w pointers in theta's order (passed in
- *   the kernel arguments: capture-safe).  No atomics anywhere.
+ *   partial sums of the packed parameter gradient into partials [er_bilinear_grid, param_count] (no atomics),
+ *   which er_theta_grad_reduce (K8e) sums with row_groups = 8 into the 2 n_w variables.
  * Envelope: 2 <= F <= 64, 1 <= D <= 64 and er_bilinear_lds_bytes(F, D) =
  *   4 * ((F - 1) * (D * odd(D) + D) + F (F - 1) / 2 + F * D + 2 * (F - 1) * D) <= 65536 (odd(n) = n | 1):
  *   the `each` parameters at an odd row pitch, the pair table, one example's x, u and du.
@@ -697,10 +691,9 @@ int er_autoint_pack(const float* wq, const float* wk, const float* wv, const flo
  *   y = (o - mean) / sqrt(var + 1e-3) * gamma + beta over the row, else y = o.
  * theta: W1 [2 F G, R], b1 [R], W2 [R, F * D], b2 [F * D] (, gamma [F * D], beta [F * D] with ln).
  * er_senet_fwd: y [B, F * D]; a1 [B, R] when not null (the ReLU pattern the backward will recompute).
- * er_senet_bwd: recomputes the forward; dx; partials [er_senet_grid, param_count].  The gradient of a
+ * er_senet_bwd: recomputes the forward; dx; partials [er_senet_grid, param_count] as above.  The gradient of a
  *   group's max follows TensorFlow's reduce_max: it is split EVENLY among the columns that equal the
  *   maximum (dz / count of ties to each), nothing to the others.
- * er_senet_grad_reduce: as above, 4 (6 with ln) pointers in theta's order.
  * Envelope: F, D <= 64, D % G == 0, 1 <= R <= 2 F G and er_senet_lds_bytes(F, D, G, R) =
  *   4 * (param_count with ln + 4 * F * D + 4 * F * G + 2 * R + 2) <= 65536: theta and one example's
  *   backward state (x, w, o, do; z, dz; a1, da1; mean, rstd).  er_senet_epb as above.
@@ -713,8 +706,6 @@ int er_bilinear_fwd(const float* x, const float* theta, int64_t B, int32_t F, in
                     er_stream_t stream);
 int er_bilinear_bwd(const float* x, const float* theta, const float* dout, int64_t B, int32_t F, int32_t D, int each,
                     int plus, float* dx, float* partials, er_stream_t stream);
-int er_bilinear_grad_reduce(const float* partials, int32_t rows, int32_t F, int32_t D, int each,
-                            float* const* grads_host, int acc, er_stream_t stream);
 int64_t er_senet_param_count(int32_t F, int32_t D, int32_t G, int32_t R, int ln);
 int64_t er_senet_lds_bytes(int32_t F, int32_t D, int32_t G, int32_t R);
 int32_t er_senet_epb(int32_t F, int32_t D, int32_t G, int32_t R, int ln, int bwd);
@@ -723,8 +714,25 @@ int er_senet_fwd(const float* x, const float* theta, int64_t B, int32_t F, int32
                  int ln, float* y, float* a1, er_stream_t stream);
 int er_senet_bwd(const float* x, const float* theta, const float* dy, int64_t B, int32_t F, int32_t D, int32_t G,
                  int32_t R, int skip, int ln, float* dx, float* partials, er_stream_t stream);
-int er_senet_grad_reduce(const float* partials, int32_t rows, int32_t F, int32_t D, int32_t G, int32_t R, int ln,
-                         float* const* grads_host, int acc, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
+ *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
+ *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed
+ *     order and adds (acc != 0) or writes (acc == 0) each stretch of the result into the matching
+ *     variable's gradient buffer, so two runs and a graph replay give the same bits.
+ * lens_host, grads_host: HOST arrays of nseg entries in theta's order, the variables' lengths in
+ *   floats and their gradient buffers.  Required: every pointer non-null, every length >= 1,
+ *   sum(lens) == P < 65536, 1 <= nseg <= 392 (K8b's worst case, 6 * 64 + 8).  Addresses and starts
+ *   travel in the kernel arguments (under 4 KB): nothing is built on the device, so a first call
+ *   inside a stream capture works.
+ * row_groups selects the summation order, part of each block's bit contract; 1 and 8 are accepted.
+ *   A workgroup of 256 threads covers 256 / row_groups columns of partials; the thread of row group
+ *   g sums rows g, g + row_groups, .. in order, each from 0.f; the row_groups sums are then combined
+ *   in order 0, 1, ...  row_groups = 1 is one thread per column over rows 0 .. rows - 1.
+ * -------------------------------------------------------------------------------------------- */
+int er_theta_grad_reduce(const float* partials, int32_t rows, int32_t P, const int32_t* lens_host, int32_t nseg,
+                         float* const* grads_host, int32_t row_groups, int acc, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * K9  MLP layer pieces around the GEMM.  Replaces BiasAdd / FusedBatchNorm(train) / Relu of

@@ -79,7 +79,7 @@ def test_two_runs_and_graph_replay_are_bit_identical():
   k, h, ln = key.to(DEV, torch.float32), hist.to(DEV, torch.float32), lens.to(DEV)
   theta = torch.cat([dev[n].reshape(-1) for n in names])
   dout = torch.randn(B, T * E, device=DEV)
-  table = kernels.BstGradTable.of(grads)
+  table = kernels.ThetaGradTable(grads)
 
   def run():
     for g in grads:
@@ -99,7 +99,7 @@ def test_accumulation_into_filled_buffers():
   k, h, ln = key.to(DEV, torch.float32), hist.to(DEV, torch.float32), lens.to(DEV)
   theta = torch.cat([dev[n].reshape(-1) for n in names])
   dout = torch.randn(B, T * E, device=DEV)
-  table = kernels.BstGradTable.of(grads)
+  table = kernels.ThetaGradTable(grads)
   dkey, dhist = be.bst_bwd(k, h, ln, theta, dout, T, H, table)
   once = [g.clone() for g in grads]
   # a second tower sharing the variables: its gradient is added in
