@@ -2142,6 +2142,80 @@ class HipBackend(object):
       self.op_log.append(('er::senet_bwd_kernel', 6.0 * B * R * (2 * F * G + F * D)))
     return dx
 
+  # -- K8f the head of the two-tower retrieval models (model/match_model.py)
+  MATCH_MAX_D = 128
+
+  def match_lds_bytes(self, D):
+    return int(self.lib.er_match_lds_bytes(int(D)))
+
+  def match_normalize_fwd(self, x):
+    """x [R, D] -> (x * inv_norm, inv_norm [R]), inv_norm = 1 / sqrt(max(sum x^2, 1e-12)) per row."""
+    R, D = x.shape
+    y = torch.empty_like(x)
+    inv = torch.empty(R, dtype=torch.float32, device=x.device)
+    self._ck(self.lib.er_match_normalize_fwd(_p(_f32c(x)), R, D, _p(y), _p(inv), _stream()), 'er_match_normalize_fwd')
+    return y, inv
+
+  def match_normalize_bwd(self, x, inv, dy):
+    R, D = x.shape
+    assert dy.shape == x.shape
+    dx = torch.empty_like(x)
+    self._ck(self.lib.er_match_normalize_bwd(_p(_f32c(x)), _p(inv), _p(_f32c(dy)), R, D, _p(dx), _stream()),
+             'er_match_normalize_bwd')
+    return dx
+
+  @staticmethod
+  def _match_operands(U, I, item_ids, weight):
+    B, D = U.shape
+    M = I.shape[0]
+    assert I.shape == (M, D) and M >= B >= 1
+    assert item_ids is None or (item_ids.dtype == torch.int64 and item_ids.shape == (M,) and item_ids.is_contiguous())
+    assert weight is None or weight.shape == (B,)
+    return B, M, D
+
+  def match_softmax_fwd(self, U, I, inv_temperature, sim_w, sim_b, item_ids, ignore_in_batch, weight):
+    """The list-wise head's forward (easyrec_hip.h K8f) -> (losses [3] = cross_entropy_loss, reg_pos_loss, sum of the
+    weights; stats [4, B] = row maximum, row sum, diagonal logit, hit probability)."""
+    B, M, D = self._match_operands(U, I, item_ids, weight)
+    stats = torch.empty(4, B, dtype=torch.float32, device=U.device)
+    partials = torch.empty(int(self.lib.er_match_grid(B)) * 3, dtype=torch.float32, device=U.device)
+    losses = torch.empty(3, dtype=torch.float32, device=U.device)
+    self._ck(self.lib.er_match_softmax_fwd(
+        _p(_f32c(U)), _p(_f32c(I)), B, M, D, float(inv_temperature), _p(sim_w), _p(sim_b), _p(item_ids),
+        bool(ignore_in_batch), None if weight is None else _p(_f32c(weight)), _p(stats[0]), _p(stats[1]), _p(stats[2]),
+        _p(stats[3]), _p(partials), _p(losses), _stream()), 'er_match_softmax_fwd')
+    if self.op_log is not None:
+      self.op_log.append(('er::match_fwd_kernel', 2.0 * B * M * D))
+    return losses, stats
+
+  def match_softmax_bwd(self, U, I, inv_temperature, sim_w, sim_b, item_ids, ignore_in_batch, weight, stats, losses,
+                        g_ce, g_reg, grads=None, acc=True):
+    """-> (dU, dI); with sim_w / sim_b their gradients are added into (acc) or written to `grads` (a ThetaGradTable of
+    the two one-float buffers)."""
+    B, M, D = self._match_operands(U, I, item_ids, weight)
+    dU, dI = torch.empty_like(U), torch.empty_like(I)
+    rows = int(self.lib.er_match_grid(B))
+    partials = torch.empty(rows * 2, dtype=torch.float32, device=U.device)
+    self._ck(self.lib.er_match_softmax_bwd(
+        _p(_f32c(U)), _p(_f32c(I)), B, M, D, float(inv_temperature), _p(sim_w), _p(sim_b), _p(item_ids),
+        bool(ignore_in_batch), None if weight is None else _p(_f32c(weight)), _p(stats[0]), _p(stats[1]), _p(stats[3]),
+        _p(losses), _p(_f32c(g_ce)), _p(_f32c(g_reg)), _p(dU), _p(dI), _p(partials), _stream()), 'er_match_softmax_bwd')
+    if grads is not None:
+      self.theta_grad_reduce(partials, rows, grads, 1, acc)
+    if self.op_log is not None:
+      self.op_log.append(('er::match_bwd_kernel', 8.0 * B * M * D))
+    return dU, dI
+
+  def match_rank_counts(self, U, I, inv_temperature, sim_w, sim_b, item_ids, ignore_in_batch):
+    """-> (c_in [B], c_neg [B]) int32: how many in-batch columns / extra negatives rank above each row's positive."""
+    B, M, D = self._match_operands(U, I, item_ids, None)
+    c_in = torch.empty(B, dtype=torch.int32, device=U.device)
+    c_neg = torch.empty(B, dtype=torch.int32, device=U.device)
+    self._ck(self.lib.er_match_rank_counts(
+        _p(_f32c(U)), _p(_f32c(I)), B, M, D, float(inv_temperature), _p(sim_w), _p(sim_b), _p(item_ids),
+        bool(ignore_in_batch), _p(c_in), _p(c_neg), _stream()), 'er_match_rank_counts')
+    return c_in, c_neg
+
   # -- K1b hash-table (KV) embedding tables
   def kv_create(self, var_rows, capacity, seed, init_mean, init_stddev, filter_freq=0, steps_to_live=0, step=None):
     """The map of one KV table whose arena is `var_rows` ([capacity, dim] view of the table group's storage).
@@ -4084,6 +4158,59 @@ class SENetFn(torch.autograd.Function):
     table, acc, ret = _theta_grads(ctx, ctx.saved_tensors[2:])
     dx = hip().senet_bwd(x, theta, dy.contiguous(), F, D, G, R, skip, ln, table, acc=acc)
     return (dx, None, None, None, None, None, None, None) + ret
+
+
+class MatchNormalizeFn(torch.autograd.Function):
+  """reference model/match_model.py:141-143, tf.nn.l2_normalize(fea, axis=-1): apply(x [R, D]) -> x / max(|x|, 1e-6)
+  per row (er_match_normalize_*: the forward keeps the rows' inverse norms)."""
+
+  @staticmethod
+  def forward(ctx, x):
+    x = x if x.is_contiguous() else x.contiguous()
+    y, inv = hip().match_normalize_fwd(x)
+    ctx.save_for_backward(x, inv)
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    x, inv = ctx.saved_tensors
+    return hip().match_normalize_bwd(x, inv, dy.contiguous())
+
+
+class MatchSoftmaxLossFn(torch.autograd.Function):
+  """reference model/match_model.py:50-69, :213-234 and model/dssm.py:71-96 from the tower outputs to the two losses:
+  apply(U [B, D], I [M, D], inv_temperature, item_ids [M] int64 or None, ignore_in_batch, weight [B] or None, grads,
+  sim_w, sim_b) -> (cross_entropy_loss, reg_pos_loss, stats) (er_match_softmax_*: the [B, M] logits are never stored;
+  the backward recomputes them from the saved row maxima and sums).  sim_w / sim_b: one-float tensors, or both None for
+  no scale; with `grads` (their gradient buffers) their gradients are ADDED there and autograd gets nothing.  stats
+  [4, B]: the rows' maximum, sum, diagonal logit and hit probability (not differentiable)."""
+
+  @staticmethod
+  def forward(ctx, U, I, inv_temperature, item_ids, ignore_in_batch, weight, grads, sim_w, sim_b):
+    be = hip()
+    U = U if U.is_contiguous() else U.contiguous()
+    I = I if I.is_contiguous() else I.contiguous()
+    assert (sim_w is None) == (sim_b is None)
+    weight = None if weight is None else weight.contiguous()
+    sw = None if sim_w is None else sim_w.detach()
+    sb = None if sim_b is None else sim_b.detach()
+    losses, stats = be.match_softmax_fwd(U, I, inv_temperature, sw, sb, item_ids, ignore_in_batch, weight)
+    ctx.save_for_backward(U, I, item_ids, weight, sw, sb, stats, losses)
+    ctx.cfg = (inv_temperature, ignore_in_batch)
+    ctx.grads = grads
+    ctx.mark_non_differentiable(stats)
+    return losses[0], losses[1], stats
+
+  @staticmethod
+  def backward(ctx, g_ce, g_reg, _):
+    U, I, item_ids, weight, sw, sb, stats, losses = ctx.saved_tensors
+    inv_temperature, ignore_in_batch = ctx.cfg
+    table, acc, ret = None, True, (None, None)
+    if sw is not None:
+      table, acc, ret = _theta_grads(ctx, (sw, sb))
+    dU, dI = hip().match_softmax_bwd(U, I, inv_temperature, sw, sb, item_ids, ignore_in_batch, weight, stats, losses,
+                                     g_ce.reshape(1).contiguous(), g_reg.reshape(1).contiguous(), table, acc)
+    return (dU, dI, None, None, None, None, None) + ret
 
 
 class MMoEMixManyFn(torch.autograd.Function):

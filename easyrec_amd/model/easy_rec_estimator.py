@@ -100,6 +100,8 @@ class EasyRecEstimator(object):
     labels = OrderedDict((name, self.features.label(name)) for name in self.schema.label_fields)
     with context.use(self.ctx):
       model_cls = EasyRecModel.create_class(cfg.model_config.model_class)
+      if hasattr(model_cls, 'check_data_config'):
+        model_cls.check_data_config(cfg.data_config)  # (what the input pipeline would have to deliver: model/match_model.py)
       self.model = model_cls(cfg.model_config, self.feature_configs, self.features, labels,
                              is_training=is_training)
 

@@ -716,6 +716,57 @@ int er_senet_bwd(const float* x, const float* theta, const float* dy, int64_t B,
                  int32_t R, int skip, int ln, float* dx, float* partials, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8f The head of the two-tower retrieval models.  Replaces l2_normalize, MatMul, the scale, the in-batch
+ *     mask, Softmax, the diagonal GatherNd, Log, both weighted means and every gradient of them in
+ *     MatchModel model/match_model.py:50-69, :141-143, :213-234 and DSSM model/dssm.py:64-96.  fp32.
+ * er_match_normalize_fwd: y [R, D] = x * inv_norm, inv_norm [R] = 1 / sqrt(max(sum x^2, 1e-12)) per row
+ *   (tf.nn.l2_normalize, axis -1); any D.  er_match_normalize_bwd: dx = inv_norm * dy - inv_norm^3 *
+ *   (x . dy) * x, and inv_norm * dy for a row under the floor.
+ * The list-wise head.  U [B, D] users, I [M, D] items, M >= B: item i is user i's positive, rows B .. M - 1
+ *   are extra negatives.  logit z_ij = (U_i . I_j) * inv_temperature * |sim_w| + sim_b (sim_w, sim_b: device
+ *   scalars, both null for no scale).  Mask, for j < B and j != i: with ignore_in_batch every such entry,
+ *   else with item_ids [M] (int64, may be null) the entries with item_ids[j] == item_ids[i], become
+ *   z - 1e32; a masked entry adds exactly 0 to the row's softmax sum.  sample_weight [B] or null (ones).
+ * er_match_softmax_fwd: row_max, row_sum (sum of exp(z - row_max)), zdiag (z_ii), hit (softmax(z_i)[i]),
+ *   each [B]; partials [er_match_grid(B), 3]: per workgroup the sums of w log(hit + 1e-12), w relu(-U_i . I_i)
+ *   and w; losses [3] = cross_entropy_loss = -sum(w log(hit + 1e-12)) / sum(w), reg_pos_loss =
+ *   sum(w relu(-U_i . I_i)) / sum(w), and sum(w), by a second, single-workgroup launch in a fixed order.
+ * er_match_softmax_bwd: g_ce, g_reg [1]: the upstream gradients of the two losses.  Recomputes the logits.
+ *   With g_i = g_ce (w_i / sum w) hit_i / (hit_i + 1e-12): dz_ij = g_i (softmax_ij - [i == j]); the gradient
+ *   of the similarity is ds_ij = inv_temperature |sim_w| dz_ij - [i == j] [U_i . I_i < 0] g_reg w_i / sum w.
+ *   dU [B, D] = ds I (a launch with the users stationary), dI [M, D] = ds^T U (a launch with the items
+ *   stationary); partials [er_match_grid(B), 2] = per workgroup (sign(sim_w) inv_temperature sum dz_ij s_ij,
+ *   sum dz_ij), which er_theta_grad_reduce (K8e) sums with row_groups = 1 into sim_w's and sim_b's buffers.
+ *   No atomics anywhere: two runs and a graph replay give the same bits.
+ * er_match_rank_counts: c_in [B] = #{j < B, j != i: z_ij > z_ii, or z_ij == z_ii and j < i}, c_neg [B] =
+ *   #{j >= B: z_ij > z_ii} on the masked logits: the rank of the positive under tf.nn.top_k's tie rule (the
+ *   lower index wins) is c_in + c_neg in [0, M), c_in among the in-batch columns and c_neg in [pos, negatives].
+ * Envelope of the three streaming functions: 1 <= D <= 128, 1 <= B <= M.  er_match_lds_bytes(D) =
+ *   4 * (96 * (8 nk + 1) + 32 * 65 + 256) + 8 * 96 with nk = 4, 8, 16 for D <= 32, 64, 128 (0 outside): a
+ *   workgroup's 32 stationary and 64 streamed rows at an odd pitch, the backward's gradient tile, the row
+ *   statistics and the ids of both tiles.  This is the backward's footprint, the largest of the three: the
+ *   forward has no gradient tile (8320 bytes less) and the rank counts keep a 4096-byte count array in its
+ *   place, so the figure is an upper bound for every kernel.  er_match_grid(rows) = ceil(rows / 32).
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_match_lds_bytes(int32_t D);
+int32_t er_match_grid(int64_t rows);
+int er_match_normalize_fwd(const float* x, int64_t R, int32_t D, float* y, float* inv_norm, er_stream_t stream);
+int er_match_normalize_bwd(const float* x, const float* inv_norm, const float* dy, int64_t R, int32_t D, float* dx,
+                           er_stream_t stream);
+int er_match_softmax_fwd(const float* U, const float* I, int64_t B, int64_t M, int32_t D, float inv_temperature,
+                         const float* sim_w, const float* sim_b, const int64_t* item_ids, int ignore_in_batch,
+                         const float* sample_weight, float* row_max, float* row_sum, float* zdiag, float* hit,
+                         float* partials, float* losses, er_stream_t stream);
+int er_match_softmax_bwd(const float* U, const float* I, int64_t B, int64_t M, int32_t D, float inv_temperature,
+                         const float* sim_w, const float* sim_b, const int64_t* item_ids, int ignore_in_batch,
+                         const float* sample_weight, const float* row_max, const float* row_sum, const float* hit,
+                         const float* losses, const float* g_ce, const float* g_reg, float* dU, float* dI,
+                         float* partials, er_stream_t stream);
+int er_match_rank_counts(const float* U, const float* I, int64_t B, int64_t M, int32_t D, float inv_temperature,
+                         const float* sim_w, const float* sim_b, const int64_t* item_ids, int ignore_in_batch,
+                         int32_t* c_in, int32_t* c_neg, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed

@@ -1,0 +1,138 @@
+"""fp64 restatement of the reference's two-tower head and DSSM towers (easy_rec/python/model/match_model.py,
+model/dssm.py), in torch so that autograd gives every gradient: what the match kernels, the composed path and the
+model are checked against."""
+import numpy as np
+import torch
+
+BN_EPSILON = 1e-3
+
+
+def l2_normalize(x):
+  """tf.nn.l2_normalize(x, axis=-1): x * rsqrt(max(sum x^2, 1e-12))"""
+  return x * torch.rsqrt(torch.clamp((x * x).sum(dim=-1, keepdim=True), min=1e-12))
+
+
+def logits(user, item, inv_temperature=1.0, sim_w=None, sim_b=None, item_ids=None, ignore_in_batch=False):
+  """match_model.py:97, dssm.py:71-85 and _mask_in_batch (:50-69): [B, M]"""
+  B = user.shape[0]
+  z = (user @ item.t()) * inv_temperature
+  if sim_w is not None:
+    z = z * torch.abs(sim_w) + sim_b
+  eye = torch.eye(B, dtype=z.dtype)
+  if ignore_in_batch:
+    mask = 1 - eye
+  elif item_ids is not None:
+    mask = (item_ids[None, :B] == item_ids[:B, None]).to(z.dtype) - eye
+  else:
+    return z
+  return torch.cat([z[:, :B] - mask * 1e32, z[:, B:]], dim=1)
+
+
+def hit_prob(z):
+  B = z.shape[0]
+  return torch.diagonal(torch.softmax(z, dim=1)[:, :B])
+
+
+def list_wise_losses(user, item, inv_temperature=1.0, sim_w=None, sim_b=None, item_ids=None, ignore_in_batch=False,
+                     weight=None):
+  """(cross_entropy_loss, reg_pos_loss) of _build_list_wise_loss_graph (:213-234)"""
+  B = user.shape[0]
+  hit = hit_prob(logits(user, item, inv_temperature, sim_w, sim_b, item_ids, ignore_in_batch))
+  w = torch.ones_like(hit) if weight is None else weight
+  ce = -(torch.log(hit + 1e-12) * w).mean() / w.mean()
+  pos = (user * item[:B]).sum(dim=1)
+  return ce, (torch.relu(-pos) * w).mean() / w.mean()
+
+
+def point_wise_logits(user, item, inv_temperature=1.0, sim_w=None, sim_b=None):
+  y = (user * item).sum(dim=1) * inv_temperature
+  return y if sim_w is None else y * torch.abs(sim_w) + sim_b
+
+
+def sigmoid_ce(z, label, weight=None):
+  """tf.losses.sigmoid_cross_entropy: the weighted sum over the count of non-zero weights"""
+  per = torch.clamp(z, min=0) - z * label + torch.log1p(torch.exp(-torch.abs(z)))
+  if weight is None:
+    return per.mean()
+  return (per * weight).sum() / torch.clamp((weight != 0).sum(), min=1)
+
+
+def tower(x, var, name, training=True):
+  """dssm.py:42-62: dense -> BatchNorm (batch statistics) -> relu for all but the last layer, then a plain dense"""
+  n = len([k for k in var if k.startswith(name + '/dnn_') and k.endswith('/kernel')])
+  for i in range(n):
+    layer = '%s/dnn_%d' % (name, i)
+    x = x @ var[layer + '/kernel'] + var[layer + '/bias']
+    if i + 1 < n:
+      mean, v = x.mean(dim=0), x.var(dim=0, unbiased=False)
+      x = (x - mean) * torch.rsqrt(v + BN_EPSILON) * var[layer + '/bn/gamma'] + var[layer + '/bn/beta']
+      x = torch.relu(x)
+  return x
+
+
+def mse(y, label, weight=None):
+  """tf.losses.mean_squared_error: the weighted sum over the count of non-zero weights"""
+  per = (y - label) ** 2
+  if weight is None:
+    return per.mean()
+  return (per * weight).sum() / torch.clamp((weight != 0).sum(), min=1)
+
+
+def head_losses(head, loss_type, u, i, var, label=None, ids=None, weight=None, ignore_in_batch=False):
+  """The task losses from the two tower outputs on (dssm.py:64-96 / match_model.py:161-196, :207-279).  head: anything
+  with simi_func, temperature and scale_simi (the DSSM message or model_params); var: sim_w / sim_b by name.
+  -> (loss dict, prediction dict)"""
+  from easyrec_amd.protos.loss_pb2 import LossType
+  from easyrec_amd.protos.simi_pb2 import Similarity
+  inv_t = 1.0
+  if head.simi_func == Similarity.COSINE:
+    u, i, inv_t = l2_normalize(u), l2_normalize(i), 1.0 / head.temperature
+  sw, sb = (var['sim_w'], var['sim_b']) if head.scale_simi else (None, None)
+  pred = {'user_tower_emb': u, 'item_tower_emb': i}
+  if loss_type == LossType.SOFTMAX_CROSS_ENTROPY:
+    pred['logits'] = logits(u, i, inv_t, sw, sb, ids, ignore_in_batch)
+    pred['probs'] = torch.softmax(pred['logits'], dim=1)
+    ce, reg = list_wise_losses(u, i, inv_t, sw, sb, ids, ignore_in_batch, weight)
+    return {'cross_entropy_loss': ce, 'reg_pos_loss': reg}, pred
+  y = point_wise_logits(u, i, inv_t, sw, sb)
+  if loss_type == LossType.CLASSIFICATION:
+    pred['logits'], pred['probs'] = y, torch.sigmoid(y)
+    return {'cross_entropy_loss': sigmoid_ce(y, label, weight)}, pred
+  pred['y'] = y
+  return {'l2_loss': mse(y, label, weight)}, pred
+
+
+def dssm_losses(model_cfg, inputs, var, label, ids):
+  """fp64 restatement of one DSSM step's task losses from the towers' inputs on; var: leaves by variable name"""
+  d = model_cfg.dssm
+  u, i = tower(inputs['user'], var, 'user_dnn'), tower(inputs['item'], var, 'item_dnn')
+  return head_losses(d, model_cfg.loss_type, u, i, var, label, ids if d.item_id else None, None,
+                     d.ignore_in_batch_neg_sam)[0]
+
+
+def rank_counts(z):
+  """(c_in, c_neg) of each row's positive from a stable sort by descending logit (tf.nn.top_k: the lower index wins a
+  tie): its position among the in-batch columns, and how many extra negatives stand before it."""
+  z = np.asarray(z)
+  B, M = z.shape
+  c_in, c_neg = np.zeros(B, np.int64), np.zeros(B, np.int64)
+  for i in range(B):
+    order = np.argsort(-z[i], kind='stable')
+    before = order[:int(np.where(order == i)[0][0])]
+    c_in[i], c_neg[i] = int((before < B).sum()), int((before >= B).sum())
+  return c_in, c_neg
+
+
+def recall_at_k(z, k):
+  """The three metrics of _build_list_wise_metric_graph (:287-317) by sorting, each with the lower-index tie rule."""
+  z = np.asarray(z)
+  B = z.shape[0]
+
+  def rank(mat, label):
+    return np.array([int(np.where(np.argsort(-mat[i], kind='stable') == label[i])[0][0]) for i in range(B)])
+
+  idx = np.arange(B)
+  v2 = np.concatenate([z[idx, idx][:, None], z[:, B:]], axis=1)
+  return {'recall@%d' % k: float((rank(z, idx) < k).mean()),
+          'recall_neg_sam@%d' % k: float((rank(v2, np.zeros(B, np.int64)) < k).mean()),
+          'recall_in_batch@%d' % k: float((rank(z[:, :B], idx) < k).mean())}

@@ -332,6 +332,68 @@ def fibinet_taobao(bilinear_type='each', use_plus=True, **kw):
   ''' % (names, bilinear_type, 'true' if use_plus else 'false'))
 
 
+def dssm_taobao(in_batch=False, **kw):
+  """DSSM, the model section of samples/model_config/dssm_on_taobao.config: the user tower over the 8 user fields and
+  the two tag lists, the item tower over the 7 item fields, [256, 128, 64, 32] each, cosine similarity with scale_simi,
+  point-wise sigmoid cross-entropy; l2 1e-6, embedding l2 5e-5.  in_batch: the same towers list-wise instead -
+  SOFTMAX_CROSS_ENTROPY over the batch's own items, inner product, scale_simi, item_id adgroup_id, no sampler."""
+  cfg = taobao_base('tag', **kw)
+  cfg.model_dir = 'experiments/dssm%s_taobao_ckpt' % ('_inbatch' if in_batch else '')
+  cfg.data_config.label_fields.append('clk')
+  user = ' '.join("feature_names: '%s'" % n for n in TAOBAO_USER + ['tag_category_list', 'tag_brand_list'])
+  item = ' '.join("feature_names: '%s'" % n for n in TAOBAO_ITEM)
+  head = "simi_func: INNER_PRODUCT scale_simi: true item_id: 'adgroup_id'" if in_batch else ''
+  if in_batch:
+    del cfg.eval_config.metrics_set[:]
+    cfg.eval_config.metrics_set.add().recall_at_topk.topk = 10
+  return _model_text(cfg, '''
+    model_class: 'DSSM'
+    feature_groups { group_name: 'user' %s wide_deep: DEEP }
+    feature_groups { group_name: 'item' %s wide_deep: DEEP }
+    dssm {
+      user_tower { id: 'user_id' dnn { hidden_units: [256, 128, 64, 32] } }
+      item_tower { id: 'adgroup_id' dnn { hidden_units: [256, 128, 64, 32] } }
+      l2_regularization: 1e-6
+      %s
+    }
+    %s
+    embedding_regularization: 5e-5
+  ''' % (user, item, head, 'loss_type: SOFTMAX_CROSS_ENTROPY' if in_batch else ''))
+
+
+def dssm_backbone_taobao(**kw):
+  """MatchModel over a backbone, the model section of samples/model_config/dssm_on_taobao_backbone.config (two MLP
+  towers [128, 32] without a final BatchNorm or activation, cosine with temperature 0.01, in-batch softmax) without
+  its negative sampler."""
+  cfg = taobao_base('tag', **kw)
+  cfg.model_dir = 'experiments/dssm_backbone_taobao_ckpt'
+  cfg.data_config.label_fields.append('clk')
+  del cfg.eval_config.metrics_set[:]
+  cfg.eval_config.metrics_set.add().recall_at_topk.topk = 10
+  user = ' '.join("feature_names: '%s'" % n for n in TAOBAO_USER + ['tag_category_list', 'tag_brand_list'])
+  item = ' '.join("feature_names: '%s'" % n for n in TAOBAO_ITEM[:5])
+  tower = """blocks { name: '%s_tower' inputs { block_name: '%s' }
+               keras_layer { class_name: 'MLP'
+                             mlp { hidden_units: [128, 32] use_final_bn: false final_activation: 'linear' } } }"""
+  return _model_text(cfg, '''
+    model_name: 'DSSM'
+    model_class: 'MatchModel'
+    feature_groups { group_name: 'user' %s wide_deep: DEEP }
+    feature_groups { group_name: 'item' %s wide_deep: DEEP }
+    backbone {
+      blocks { name: 'user' inputs { feature_group_name: 'user' } input_layer { output_2d_tensor_and_feature_list: false } }
+      blocks { name: 'item' inputs { feature_group_name: 'item' } input_layer { output_2d_tensor_and_feature_list: false } }
+      %s
+      %s
+      output_blocks: ['user_tower', 'item_tower']
+    }
+    model_params { l2_regularization: 1e-4 user_tower_idx_in_output: 0 item_tower_idx_in_output: 1 scale_simi: false
+                   simi_func: COSINE temperature: 0.01 }
+    embedding_regularization: 5e-5
+    loss_type: SOFTMAX_CROSS_ENTROPY
+  ''' % (user, item, tower % ('user', 'user'), tower % ('item', 'item')))
+
+
 def mmoe_taobao(n_tasks=2, **kw):
   """MMoE, the shape of samples/model_config/mmoe_on_taobao.config (BASELINE config 5 uses 4 tasks)."""
   cfg = taobao_base('tag', **kw)
@@ -826,6 +888,8 @@ if __name__ == '__main__':
   write(bst_taobao(item_rows=10000000), 'bst_taobao_10m.config')
   write(autoint_taobao(item_rows=10000000), 'autoint_taobao_10m.config')
   write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
+  write(dssm_taobao(item_rows=10000000), 'dssm_taobao_10m.config')
+  write(dssm_taobao(in_batch=True, item_rows=10000000), 'dssm_inbatch_taobao_10m.config')
   write(mmoe_taobao(n_tasks=4, embedding_dim=64, batch_size=8192), 'mmoe_taobao_4task_d64.config')
   # BASELINE config 5 at full size (200 M embedding rows of 64 floats: 51 GB + Adam slots, row-sharded over 8 GPUs) and
   # the share one GPU owns of it (25 M rows) for single-GPU runs
