@@ -1546,6 +1546,10 @@ int er_reserve_scratch(int64_t floats) {
   return er::get_scratch(static_cast<size_t>(floats), &p);
 }
 
+int er_bn_row_chunks(int32_t B, int32_t N) { return er::choose_chunks(B, N); }
+
+int er_bn_apply_row_tiles(int32_t B) { return er::apply_tiles_per_block(B); }
+
 int er_bn_act_fwd(const float* x, const float* bias, const float* gamma, const float* beta, int32_t B, int32_t N,
                   int use_bn, float eps, float momentum, float* moving_mean, float* moving_var, int act, float* y,
                   float* save_mean, float* save_invstd, er_stream_t stream) {

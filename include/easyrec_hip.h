@@ -805,6 +805,12 @@ int er_bn_act_fwd(const float* x, const float* bias, const float* gamma, const f
                   int32_t B, int32_t N, int use_bn, float eps, float momentum,
                   float* moving_mean, float* moving_var, int act, float* y, float* save_mean,
                   float* save_invstd, er_stream_t stream);
+/* Host arithmetic of the launches above and below, for callers that size buffers or need to know the path taken (no device
+ * call): er_bn_row_chunks = the row chunks er_bn_act_fwd / er_bn_act_bwd* / er_dice_* / er_colsum* split B rows of N
+ * columns into (chunk c covers rows [c * ceil(B / chunks), ...): the last ones may be empty; more than 256 chunks take the
+ * merge launch first); er_bn_apply_row_tiles = the 16-row tiles one workgroup of the finalize + apply launches normalises. */
+int er_bn_row_chunks(int32_t B, int32_t N);
+int er_bn_apply_row_tiles(int32_t B);
 /* The same normalisation from ready-made column statistics: col_stats = `chunks` Welford triples per column
  * ([chunks][N][3]: count, mean, M2), e.g. written by er_gemm_*'s epilogue (chunks = er_gemm_row_tiles(B)).
  * One launch: every workgroup merges the partials of its 64 columns, then normalises its tile. */
