@@ -2216,6 +2216,79 @@ class HipBackend(object):
         bool(ignore_in_batch), _p(c_in), _p(c_neg), _stream()), 'er_match_rank_counts')
     return c_in, c_neg
 
+  # -- K8g MIND's capsule layer and label-aware attention (layers/capsule_layer.py, model/mind.py)
+  CAPSULE_MAX_K = 8
+  MIND_ATT_MAX_E = 128
+
+  def capsule_lds_bytes(self, S, D, E, K):
+    return int(self.lib.er_capsule_lds_bytes(int(S), int(D), int(E), int(K)))
+
+  def capsule_grid(self, B):
+    return int(self.lib.er_capsule_grid(int(B)))
+
+  def capsule_fwd(self, hist, seq_len, Smat, logits0, S, K, num_iters, scale, squash_pow, scale_ratio, const_caps):
+    """hist [B, L, D], seq_len [B] int32, Smat [D, E], logits0 [B, S, K] (per example) or [S, K] (shared) ->
+    (high_capsules [B, K, E], num_caps [B] int32, W [B, S, K]: the last iteration's routing weights)."""
+    B, L, D = hist.shape
+    E = Smat.shape[1]
+    assert Smat.shape == (D, E) and seq_len.dtype == torch.int32 and seq_len.shape == (B,)
+    assert logits0.shape in ((B, S, K), (S, K)) and logits0.is_contiguous() and logits0.dtype == torch.float32
+    stride = S * K if logits0.dim() == 3 else 0
+    high = torch.empty(B, K, E, dtype=torch.float32, device=hist.device)
+    ncaps = torch.empty(B, dtype=torch.int32, device=hist.device)
+    W = torch.empty(B, S, K, dtype=torch.float32, device=hist.device)
+    self._ck(self.lib.er_capsule_fwd(_p(_f32c(hist)), _p(seq_len), _p(_f32c(Smat)), _p(logits0), stride, B, L, S, D, E, K,
+                                     int(num_iters), float(scale), float(squash_pow), float(scale_ratio), bool(const_caps),
+                                     _p(high), _p(ncaps), _p(W), _stream()), 'er_capsule_fwd')
+    if self.op_log is not None:
+      self.op_log.append(('er::capsule_fwd_kernel', 2.0 * B * S * E * (D + K * (2 * num_iters - 1))))
+    return high, ncaps, W
+
+  def capsule_bwd(self, hist, seq_len, Smat, W, d_high, squash_pow, scale_ratio, const_caps, grads, dhist=None,
+                  acc_h=False, acc=True):
+    """-> dhist [B, L, D] (written, or added into with acc_h); capsule/S's gradient is added into (acc) or written to
+    `grads` (a ThetaGradTable of the one [D, E] buffer)."""
+    B, L, D = hist.shape
+    _, S, K = W.shape
+    E = Smat.shape[1]
+    assert d_high.shape == (B, K, E)
+    if dhist is None:
+      assert not acc_h
+      dhist = torch.empty_like(hist)
+    assert dhist.shape == hist.shape and dhist.is_contiguous()
+    rows = self.capsule_grid(B)
+    partials = torch.empty(rows * D * E, dtype=torch.float32, device=hist.device)
+    self._ck(self.lib.er_capsule_bwd(_p(_f32c(hist)), _p(seq_len), _p(_f32c(Smat)), _p(_f32c(W)), _p(_f32c(d_high)), B, L,
+                                     S, D, E, K, float(squash_pow), float(scale_ratio), bool(const_caps), _p(dhist),
+                                     bool(acc_h), _p(partials), _stream()), 'er_capsule_bwd')
+    self.theta_grad_reduce(partials, rows, grads, 1, acc)
+    if self.op_log is not None:
+      self.op_log.append(('er::capsule_bwd_kernel', 2.0 * B * S * E * (3 * D + 2 * K)))
+    return dhist
+
+  def mind_attention_fwd(self, interests, pos_item, num_caps, simi_pow):
+    """interests [B, K, E], pos_item [B, E], num_caps [B] int32 -> (user_emb [B, E], user_interests [B, K, E], weights
+    [B, K])."""
+    B, K, E = interests.shape
+    assert pos_item.shape == (B, E) and num_caps.dtype == torch.int32 and num_caps.shape == (B,)
+    emb = torch.empty(B, E, dtype=torch.float32, device=interests.device)
+    ui = torch.empty_like(interests)
+    w = torch.empty(B, K, dtype=torch.float32, device=interests.device)
+    self._ck(self.lib.er_mind_attention_fwd(_p(_f32c(interests)), _p(_f32c(pos_item)), _p(num_caps), B, K, E,
+                                            float(simi_pow), _p(emb), _p(ui), _p(w), _stream()), 'er_mind_attention_fwd')
+    return emb, ui, w
+
+  def mind_attention_bwd(self, interests, pos_item, num_caps, weights, d_emb, d_ui, simi_pow):
+    """-> (d_interests [B, K, E], d_pos_item [B, E]); d_ui: the gradient of user_interests, or None."""
+    B, K, E = interests.shape
+    assert d_emb.shape == (B, E) and (d_ui is None or d_ui.shape == (B, K, E))
+    di = torch.empty_like(interests)
+    dp = torch.empty_like(pos_item)
+    self._ck(self.lib.er_mind_attention_bwd(_p(_f32c(interests)), _p(_f32c(pos_item)), _p(num_caps), _p(weights),
+                                            _p(_f32c(d_emb)), None if d_ui is None else _p(_f32c(d_ui)), B, K, E,
+                                            float(simi_pow), _p(di), _p(dp), _stream()), 'er_mind_attention_bwd')
+    return di, dp
+
   # -- K1b hash-table (KV) embedding tables
   def kv_create(self, var_rows, capacity, seed, init_mean, init_stddev, filter_freq=0, steps_to_live=0, step=None):
     """The map of one KV table whose arena is `var_rows` ([capacity, dim] view of the table group's storage).
@@ -4211,6 +4284,64 @@ class MatchSoftmaxLossFn(torch.autograd.Function):
     dU, dI = hip().match_softmax_bwd(U, I, inv_temperature, sw, sb, item_ids, ignore_in_batch, weight, stats, losses,
                                      g_ce.reshape(1).contiguous(), g_reg.reshape(1).contiguous(), table, acc)
     return (dU, dI, None, None, None, None, None) + ret
+
+
+class CapsuleRoutingFn(torch.autograd.Function):
+  """reference layers/capsule_layer.py:60-176: apply(hist [B, L, D], seq_len [B] int32, logits0 ([B, S, K] or [S, K]),
+  cfg = (S, K, num_iters, routing_logits_scale, squash_pow, scale_ratio, const_caps_num), grads, Smat [D, E]) ->
+  (high_capsules [B, K, E], num_caps [B] int32) (er_capsule_*: one launch each way and a fixed-order reduce of capsule/S's
+  gradient).  Only the last iteration's routing weights W [B, S, K] are kept: every earlier iteration sits behind
+  stop_gradient, and the backward recomputes H = hist Smat and the pre-squash capsules from W.  With `grads` ([Smat's
+  gradient buffer]) the gradient is ADDED there and autograd gets nothing."""
+
+  @staticmethod
+  def forward(ctx, hist, seq_len, logits0, cfg, grads, Smat):
+    S, K, num_iters, scale, squash_pow, scale_ratio, const_caps = cfg
+    hist = hist if hist.is_contiguous() else hist.contiguous()
+    sm = Smat.detach()
+    sm = sm if sm.is_contiguous() else sm.contiguous()
+    high, ncaps, W = hip().capsule_fwd(hist, seq_len, sm, logits0, S, K, num_iters, scale, squash_pow, scale_ratio,
+                                       const_caps)
+    ctx.save_for_backward(hist, seq_len, sm, W)
+    ctx.cfg = (squash_pow, scale_ratio, const_caps)
+    ctx.grads = grads
+    ctx.mark_non_differentiable(ncaps)
+    return high, ncaps
+
+  @staticmethod
+  def backward(ctx, d_high, _):
+    hist, seq_len, sm, W = ctx.saved_tensors
+    squash_pow, scale_ratio, const_caps = ctx.cfg
+    table, acc, ret = _theta_grads(ctx, (sm,))
+    dhist = hip().capsule_bwd(hist, seq_len, sm, W, d_high.contiguous(), squash_pow, scale_ratio, const_caps, table,
+                              acc=acc)
+    return (dhist, None, None, None, None) + ret
+
+
+class MindAttentionFn(torch.autograd.Function):
+  """reference model/mind.py:168-200, the label-aware attention: apply(interests [B, K, E], pos_item [B, E], num_caps [B]
+  int32, simi_pow) -> (user_emb [B, E], user_interests [B, K, E]: the interests with the rows h >= num_caps zero)
+  (er_mind_attention_*; the forward keeps the [B, K] weights).  With simi_pow >= 100 the weights are the one-hot of the
+  argmax and carry no gradient."""
+
+  @staticmethod
+  def forward(ctx, interests, pos_item, num_caps, simi_pow):
+    interests = interests if interests.is_contiguous() else interests.contiguous()
+    pos_item = pos_item if pos_item.is_contiguous() else pos_item.contiguous()
+    emb, ui, w = hip().mind_attention_fwd(interests, pos_item, num_caps, simi_pow)
+    ctx.save_for_backward(interests, pos_item, num_caps, w)
+    ctx.simi_pow = simi_pow
+    ctx.set_materialize_grads(False)
+    return emb, ui
+
+  @staticmethod
+  def backward(ctx, d_emb, d_ui):
+    interests, pos_item, num_caps, w = ctx.saved_tensors
+    if d_emb is None:
+      d_emb = torch.zeros_like(pos_item)
+    di, dp = hip().mind_attention_bwd(interests, pos_item, num_caps, w, d_emb.contiguous(),
+                                      None if d_ui is None else d_ui.contiguous(), ctx.simi_pow)
+    return di, dp, None, None
 
 
 class MMoEMixManyFn(torch.autograd.Function):

@@ -1096,6 +1096,10 @@ class InputLayer(object):
     plain, plain_list = self._combined(features, group_name, plain_only=True)
     return seq_features, plain, list(plain_list)
 
+  def sequence_names(self, group_name):
+    """The raw feature names of a group's sequence columns, in the order is_combine=False returns them (after that call)."""
+    return [name for _, _, name in self._seq_plan[group_name]['cols']]
+
   def __call__(self, features, group_name, is_combine=True, is_dict=False):
     assert group_name in self._feature_groups, 'invalid group_name[%s], list: %s' % (
         group_name, ','.join(self._feature_groups))

@@ -767,6 +767,56 @@ int er_match_rank_counts(const float* U, const float* I, int64_t B, int64_t M, i
                          int32_t* c_in, int32_t* c_neg, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8g MIND's capsule layer and label-aware attention.  Replaces the pad / slice, Tensordot, l2_normalize,
+ *     SequenceMask, Minimum, Softmax, Mul, both Einsum, Pow / Sqrt of the squash and every gradient of
+ *     them in CapsuleLayer.__call__ layers/capsule_layer.py:60-176, and the Einsum, Minimum, Softmax,
+ *     ArgMax / OneHot, Einsum of MIND.build_predict_graph model/mind.py:168-200.  fp32.
+ * er_capsule_fwd: hist [B, L, D] (the group's sequence output), seq_len [B]; Smat [D, E] = capsule/S;
+ *   logits0 + b * logits_stride: the [S, K] initial routing logits of example b (stride S * K: per
+ *   example; 0: one table for the batch).  With len = min(max(seq_len, 0), S): rows s >= min(L, len)
+ *   contribute nothing (the reference's slice for L > S, its zero pad for L < S, its sequence mask).
+ *   num_caps = K with const_caps_num, else max(1, min(K, int(log(float(len))))) by the integer
+ *   thresholds len < 8 -> 1, < 21 -> 2, < 55 -> 3, < 149 -> 4, < 404 -> 5, < 1097 -> 6, < 2981 -> 7.
+ *   H = X Smat stays in LDS.  Each iteration: W = softmax over h < num_caps of the logits (0 for the
+ *   other h and for s >= len), c[h] = sum_s W[s, h] H[s].  All but the last: c = c * rsqrt(max(|c|^2,
+ *   1e-12)); logits[s, h] = routing_logits_scale * <H[s] * rsqrt(max(|H[s]|^2, 1e-12)), c[h]> with a
+ *   scale > 0, else <H[s], c[h]>.  The last: n = max(|c|^2, 1e-8), high_capsules [B, K, E] = c *
+ *   pow(n / (1 + n), squash_pow) * scale_ratio / sqrt(n), rows h >= num_caps zero; num_caps [B]; W
+ *   [B, S, K]: the last iteration's weights, all the backward needs of the routing.
+ * er_capsule_bwd: every earlier iteration sits behind stop_gradient, so with W constant: recomputes
+ *   H and c, dc through the squash (no gradient through n under its floor), dH = W dc, dhist [B, L, D]
+ *   (+)= dH Smat^T by `acc` (rows s >= min(L, len): nothing, or 0 without acc), and per-workgroup
+ *   partial sums of dSmat = X^T dH into partials [er_capsule_grid(B), D * E] (no atomics), which
+ *   er_theta_grad_reduce (K8e) sums with row_groups = 1 into capsule/S's buffer.
+ * Envelope: 1 <= S, D, E <= 128, 1 <= K <= 8, 1 <= num_iters <= 8, D * E < 65536.
+ *   er_capsule_lds_bytes(S, D, E, K) = 4 * (S * odd(D) + S * odd(E) + S * K + 2 * K * odd(E) + S)
+ *   (odd(n) = n | 1; 0 outside the envelope): one example's X, H, W, c, dc and row norms; one example
+ *   per workgroup at a time, at most 144,960 bytes of the CU's 160 KiB.
+ * er_mind_attention_fwd: interests [B, K, E], pos_item [B, E], num_caps [B]: simi[h] = <interests[h],
+ *   pos_item> * simi_pow for h < num_caps, weights [B, K] = softmax over those h (0 elsewhere), with
+ *   simi_pow >= 100 the one-hot of its argmax (the lowest index wins a tie); user_interests [B, K, E]
+ *   = interests with the rows h >= num_caps zero; user_emb [B, E] = sum_h weights[h] user_interests[h].
+ * er_mind_attention_bwd: d_user_interests may be null (zeros).  d_interests [B, K, E], d_pos_item
+ *   [B, E]; no gradient passes through the one-hot weights.  One wave per example, four examples per
+ *   workgroup round.  Envelope: 1 <= K <= 8, 1 <= E <= 128.
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_capsule_lds_bytes(int32_t S, int32_t D, int32_t E, int32_t K);
+int32_t er_capsule_grid(int64_t B);  /* rows of `partials` for a batch of B */
+int er_capsule_fwd(const float* hist, const int32_t* seq_len, const float* Smat, const float* logits0,
+                   int64_t logits_stride, int64_t B, int32_t L, int32_t S, int32_t D, int32_t E, int32_t K,
+                   int32_t num_iters, float routing_logits_scale, float squash_pow, float scale_ratio, int const_caps_num,
+                   float* high_capsules, int32_t* num_caps, float* W, er_stream_t stream);
+int er_capsule_bwd(const float* hist, const int32_t* seq_len, const float* Smat, const float* W, const float* d_high,
+                   int64_t B, int32_t L, int32_t S, int32_t D, int32_t E, int32_t K, float squash_pow, float scale_ratio,
+                   int const_caps_num, float* dhist, int acc, float* partials, er_stream_t stream);
+int er_mind_attention_fwd(const float* interests, const float* pos_item, const int32_t* num_caps, int64_t B, int32_t K,
+                          int32_t E, float simi_pow, float* user_emb, float* user_interests, float* weights,
+                          er_stream_t stream);
+int er_mind_attention_bwd(const float* interests, const float* pos_item, const int32_t* num_caps, const float* weights,
+                          const float* d_user_emb, const float* d_user_interests, int64_t B, int32_t K, int32_t E,
+                          float simi_pow, float* d_interests, float* d_pos_item, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed

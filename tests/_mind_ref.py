@@ -1,0 +1,150 @@
+"""fp64 restatement of the reference's MIND (easy_rec/python/layers/capsule_layer.py, model/mind.py) in torch: the
+capsule layer with dynamic routing, the label-aware attention, the towers and _build_interest_simi, with _match_ref's
+head behind them.  Every tf.stop_gradient is a .detach(), so autograd gives every gradient: what the capsule and
+attention kernels, the composed path and the model are checked against."""
+import numpy as np
+import torch
+
+import _match_ref as mref
+
+BN_EPSILON = 1e-3
+
+
+def sequence_mask(lens, n, dtype=torch.float64):
+  return (torch.arange(n)[None, :] < lens[:, None]).to(dtype)
+
+
+def num_capsules(seq_lens, S, K, const_caps_num):
+  """capsule_layer.py:106-115 on the host, in float32 as TensorFlow computes it"""
+  lens = np.minimum(np.asarray(seq_lens, dtype=np.int64), S)
+  if const_caps_num:
+    return torch.full((len(lens),), K, dtype=torch.int64)
+  with np.errstate(divide='ignore'):
+    logs = np.log(lens.astype(np.float32))
+  logs = np.where(lens > 0, logs, -1.0)  # (int(log(0)) is the most negative integer: max(1, .) takes it)
+  return torch.from_numpy(np.maximum(1, np.minimum(K, logs.astype(np.int32))).astype(np.int64))
+
+
+def squash(x, squash_pow, scale_ratio):
+  n = torch.clamp((x * x).sum(dim=-1, keepdim=True), min=1e-8)
+  return torch.pow(n / (1 + n), squash_pow) * scale_ratio / torch.sqrt(n) * x
+
+
+def capsule(seq_feas, seq_lens, Smat, logits0, S, K, num_iters=3, scale=20.0, squash_pow=1.0, scale_ratio=1.0,
+            const_caps_num=False):
+  """CapsuleLayer.__call__ (capsule_layer.py:60-176) -> (high_capsules [B, K, E], num_high_capsules [B])"""
+  B, L, _ = seq_feas.shape
+  if L > S:
+    seq_feas = seq_feas[:, :S]
+  elif L < S:
+    seq_feas = torch.nn.functional.pad(seq_feas, (0, 0, 0, S - L))
+  lens = torch.clamp(seq_lens.to(torch.int64), max=S)
+  r = logits0.detach()
+  if r.dim() == 2:
+    r = r[None].expand(B, S, K)
+  high = seq_feas @ Smat
+  high_stop = high.detach()
+  high_norm = mref.l2_normalize(high_stop)
+  ncaps = num_capsules(lens.numpy(), S, K, const_caps_num)
+  mask = sequence_mask(lens, S, seq_feas.dtype)
+  mask_cap = sequence_mask(ncaps, K, seq_feas.dtype)
+  thresh = ((mask_cap * 2 - 1) * 1e32)[:, None, :]
+  caps = None
+  for it in range(num_iters):
+    r = torch.softmax(torch.minimum(r, thresh), dim=2) * mask[:, :, None]
+    if it + 1 == num_iters:
+      caps = squash(torch.einsum('bse,bsh->bhe', high, r), squash_pow, scale_ratio)
+      break
+    caps = mref.l2_normalize(torch.einsum('bse,bsh->bhe', high_stop, r))
+    if scale > 0:
+      r = torch.einsum('bse,bhe->bsh', high_norm, caps) * scale
+    else:
+      r = torch.einsum('bse,bhe->bsh', high_stop, caps)
+  return caps * mask_cap[:, :, None], ncaps
+
+
+def attention(interests, pos_item, num_caps, simi_pow):
+  """mind.py:168-200 -> (user_tower_emb, masked user_interests, the weights)"""
+  K = interests.shape[1]
+  simi = torch.einsum('bhe,be->bh', interests, pos_item) * simi_pow
+  mask = sequence_mask(num_caps, K, interests.dtype)
+  user_interests = interests * mask[:, :, None]
+  simi = torch.softmax(torch.minimum(simi, (mask * 2 - 1) * 1e32), dim=1)
+  if simi_pow >= 100:
+    first = torch.from_numpy(np.argmax(simi.detach().numpy(), axis=1))  # (numpy: the first of the maxima, as tf.argmax)
+    simi = torch.nn.functional.one_hot(first, K).to(interests.dtype)
+  return torch.einsum('bhe,bh->be', user_interests, simi), user_interests, simi
+
+
+def interest_simi(user_interests, high_capsules, num):
+  """_build_interest_simi (mind.py:260-299) -> (avg_interest_simi, avg_capsule_simi)"""
+  K = user_interests.shape[1]
+  mask = sequence_mask(num, K, user_interests.dtype)[:, :, None]
+  div = torch.clamp((num * (num - 1)).to(user_interests.dtype), min=1.0)
+  multi = (num > 1).to(user_interests.dtype)
+  sum_div = torch.clamp(multi.sum(), min=1.0)
+  out = []
+  for x in (user_interests, high_capsules):
+    x = mref.l2_normalize(x) * mask
+    simi = ((x.sum(dim=1) ** 2) - (x * x).sum(dim=1)).sum(dim=1) / div
+    out.append(((simi + 1) * multi).sum() / 2.0 / sum_div)
+  return out[0], out[1]
+
+
+def batch_norm(x, var, name, training=True):
+  """tf.layers.batch_normalization: batch statistics while training, the moving ones otherwise"""
+  if training:
+    mean, v = x.mean(dim=0), x.var(dim=0, unbiased=False)
+  else:
+    mean, v = var[name + '/moving_mean'], var[name + '/moving_variance']
+  return (x - mean) * torch.rsqrt(v + BN_EPSILON) * var[name + '/gamma'] + var[name + '/beta']
+
+
+def dnn(x, var, name, last_plain=False, training=True):
+  """layers/dnn.py: dense -> BatchNorm -> relu per layer; last_plain: the last one is a plain dense"""
+  n = len([k for k in var if k.startswith(name + '/dnn_') and k.endswith('/kernel')])
+  for i in range(n):
+    layer = '%s/dnn_%d' % (name, i)
+    x = x @ var[layer + '/kernel'] + var[layer + '/bias']
+    if not (last_plain and i + 1 == n):
+      x = torch.relu(batch_norm(x, var, layer + '/bn', training))
+  return x
+
+
+def combine_hist(m, seqs, lens):
+  """mind.py:54-101 without pre_capsule_dnn: seqs {name: [B, L, d]} in group order -> the capsule layer's input"""
+  from easyrec_amd.protos.mind_pb2 import MIND
+  time = [v for k, v in seqs.items() if m.time_id_fea and m.time_id_fea in k]
+  feas = [v for k, v in seqs.items() if not (time and m.time_id_fea in k)]
+  hist = sum(feas) / len(feas) if m.user_seq_combine == MIND.SUM else torch.cat(feas, dim=2)
+  if time:
+    tmask = (sequence_mask(lens, time[0].shape[1], hist.dtype) * 2 - 1) * 1e32
+    hist = hist * torch.softmax(torch.minimum(time[0], tmask[:, :, None]), dim=1)
+  return hist
+
+
+def mind_forward(m, loss_type, hist, hist_len, user, item, var, logits0, label=None, ids=None, weight=None,
+                 training=True):
+  """MIND.build_predict_graph + build_loss_graph (mind.py:50-258) from the group outputs on.  m: the `mind` message (or
+  anything with its fields); hist: the combined sequence in front of the capsule layer [B, L, D] -> (losses, predictions)"""
+  from easyrec_amd.protos.simi_pb2 import Similarity
+  import types
+  c = m.capsule_config
+  caps, ncaps = capsule(hist, hist_len, var['capsule/S'], logits0, c.max_seq_len, c.max_k, c.num_iters,
+                        c.routing_logits_scale, c.squash_pow, c.scale_ratio, c.const_caps_num)
+  B, K, _ = caps.shape
+  u = dnn(batch_norm(user, var, 'user_fea_bn', training), var, 'user_dnn', training=training)
+  ui = torch.cat([caps, u[:, None, :].expand(B, K, u.shape[1])], dim=2).reshape(B * K, -1)
+  ui = dnn(ui, var, 'concat_dnn', last_plain=True, training=training).reshape(B, K, -1)
+  it = dnn(item, var, 'item_dnn', last_plain=True, training=training)
+  if m.simi_func == Similarity.COSINE:
+    it, ui = mref.l2_normalize(it), mref.l2_normalize(ui)
+  emb, ui, _ = attention(ui, it[:B], ncaps, m.simi_pow)
+  head = types.SimpleNamespace(simi_func=Similarity.INNER_PRODUCT, temperature=1.0, scale_simi=m.scale_simi)
+  losses, pred = mref.head_losses(head, loss_type, emb, it, var, label, ids if m.item_id else None, weight,
+                                  m.ignore_in_batch_neg_sam)
+  pred.update(high_capsules=caps, user_interests=ui, user_emb_num=ncaps)
+  pred['interests_simi'], pred['capsule_simi'] = interest_simi(ui, caps, ncaps)
+  if m.max_interests_simi < 1.0:
+    losses['reg_interest_simi'] = torch.relu(pred['interests_simi'] - m.max_interests_simi)
+  return losses, pred

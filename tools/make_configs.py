@@ -361,6 +361,38 @@ def dssm_taobao(in_batch=False, **kw):
   ''' % (user, item, head, 'loss_type: SOFTMAX_CROSS_ENTROPY' if in_batch else ''))
 
 
+def mind_taobao(list_wise=False, **kw):
+  """MIND, the model section of samples/model_config/mind_on_taobao.config: the `hist` group's two behaviour sequences
+  (their mean) through a capsule layer (max_k 5, max_seq_len 64, high_dim 64), user_dnn and item_dnn [256, 128, 64, 32],
+  concat_dnn [64, 32], cosine similarity with scale_simi, point-wise sigmoid cross-entropy; l2 1e-6, embedding l2 5e-5.
+  list_wise: the same towers with SOFTMAX_CROSS_ENTROPY over the batch's own items, item_id adgroup_id, no sampler."""
+  cfg = taobao_base('seq', **kw)
+  cfg.model_dir = 'experiments/mind%s_taobao_ckpt' % ('_inbatch' if list_wise else '')
+  cfg.data_config.label_fields.append('clk')
+  user = ' '.join("feature_names: '%s'" % n for n in TAOBAO_USER)
+  item = ' '.join("feature_names: '%s'" % n for n in TAOBAO_ITEM)
+  if list_wise:
+    del cfg.eval_config.metrics_set[:]
+    cfg.eval_config.metrics_set.add().recall_at_topk.topk = 10
+  return _model_text(cfg, '''
+    model_class: 'MIND'
+    feature_groups { group_name: 'hist' feature_names: 'tag_category_list' feature_names: 'tag_brand_list' }
+    feature_groups { group_name: 'user' %s wide_deep: DEEP }
+    feature_groups { group_name: 'item' %s wide_deep: DEEP }
+    mind {
+      user_dnn { hidden_units: [256, 128, 64, 32] }
+      item_dnn { hidden_units: [256, 128, 64, 32] }
+      concat_dnn { hidden_units: [64, 32] }
+      capsule_config { max_k: 5 max_seq_len: 64 high_dim: 64 }
+      l2_regularization: 1e-6
+      %s
+    }
+    %s
+    embedding_regularization: 5e-5
+  ''' % (user, item, "item_id: 'adgroup_id'" if list_wise else '',
+         'loss_type: SOFTMAX_CROSS_ENTROPY' if list_wise else ''))
+
+
 def dssm_backbone_taobao(**kw):
   """MatchModel over a backbone, the model section of samples/model_config/dssm_on_taobao_backbone.config (two MLP
   towers [128, 32] without a final BatchNorm or activation, cosine with temperature 0.01, in-batch softmax) without
@@ -890,6 +922,8 @@ if __name__ == '__main__':
   write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
   write(dssm_taobao(item_rows=10000000), 'dssm_taobao_10m.config')
   write(dssm_taobao(in_batch=True, item_rows=10000000), 'dssm_inbatch_taobao_10m.config')
+  write(mind_taobao(item_rows=10000000), 'mind_taobao_10m.config')
+  write(mind_taobao(list_wise=True, item_rows=10000000), 'mind_inbatch_taobao_10m.config')
   write(mmoe_taobao(n_tasks=4, embedding_dim=64, batch_size=8192), 'mmoe_taobao_4task_d64.config')
   # BASELINE config 5 at full size (200 M embedding rows of 64 floats: 51 GB + Adam slots, row-sharded over 8 GPUs) and
   # the share one GPU owns of it (25 M rows) for single-GPU runs
