@@ -390,24 +390,34 @@ __device__ __forceinline__ void gemm_bf16_block(const GemmArgs& g, int bx, int b
     }
   }
   const int col = n0 + wn * 32 + (lane & 31);
-  const float bv = (g.bias && g.splits == 1 && col < g.N) ? g.bias[col] : 0.f;
+  // (the fp32 block's epilogue form, er_gemm_core.h: values first, pinned, then the stores with nothing to wait for)
+  float bv = (g.bias && g.splits == 1) ? g.bias[col < g.N ? col : g.N - 1] : 0.f;
   const int khalf = lane >> 5;
+  const int row0 = m0 + wm * 32 + 4 * khalf;
+  const bool rows_all = m0 + BM <= g.M;
+  pin(bv);
+  float out[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) out[r] = acc[r] + bv;
   if (g.col_stats)
-    tile_col_stats(acc, bv, m0 + wm * 32, g.M, col, g.N, wm, wn, lane, reinterpret_cast<float*>(As),
+    tile_col_stats(out, m0 + wm * 32, g.M, col, g.N, wm, wn, lane, reinterpret_cast<float*>(As),
                    g.col_stats + static_cast<int64_t>(ty) * g.N * 3);
   if (col >= g.N) return;
   float* Cz = g.C + (g.splits > 1 ? static_cast<int64_t>(bz) * g.M * g.N : 0);
   const int ldc = g.splits > 1 ? g.N : g.ldc;
+  if (g.accumulate && g.splits == 1) {
+    float old[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-    if (row < g.M) {
-      float* p = Cz + static_cast<int64_t>(row) * ldc + col;
-      float v = acc[r] + bv;
-      if (g.accumulate && g.splits == 1) v = *p + v;
-      *p = v;
+    for (int r = 0; r < 16; ++r) {
+      int row = row0 + acc_row(r);
+      row = row < g.M ? row : g.M - 1;
+      old[r] = Cz[static_cast<int64_t>(row) * ldc + col];
     }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) out[r] = old[r] + out[r];
   }
+  pin(out);
+  store16(Cz + static_cast<int64_t>(row0) * ldc + col, ldc, row0, g.M, rows_all, out);
 }
 
 template <bool A_KC, bool B_KC>

@@ -124,6 +124,39 @@ __device__ __forceinline__ void tile_coords(int i, int gx, int gy, int& tx, int&
   ty = t / gx;
 }
 
+// The epilogues' stores.  On gfx9-family hardware a store counts in vmcnt like a load, and hipcc places an `s_waitcnt vmcnt(0)`
+// in front of the first use of a loaded value.  When that first use sits inside a per-element `if (row < M)` next to the store,
+// the wait cannot be proven done where the branches join and is repeated in EVERY branch - from the second on it waits for
+// the previous store's acknowledgement: a lane's 16 stores leave one round trip apart.  So every epilogue
+// (1) forms all of a lane's values first, (2) pins them (below): whatever they were computed from - the bias, old values of
+// C, the operands of an elementwise tail - has arrived BEFORE the first store, in straight-line code, and (3) stores them
+// with nothing left to wait for: without row predicates where the workgroup's 64 rows all exist (uniform), under them in the
+// last row tile.  No address is ever clamped into range: a store is issued for positions inside [0, M) x [0, N) only.
+// row of accumulator register r, relative to the lane's first row
+__device__ __forceinline__ constexpr int acc_row(int r) { return (r & 3) + 8 * (r >> 2); }
+// the value is in its register at this point of the program (an empty asm that "modifies" it: nothing is emitted, but the
+// definition cannot sink into a later branch and the waits for what it depends on are placed here)
+template <typename T>
+__device__ __forceinline__ void pin(T& v) { asm volatile("" : "+v"(v)); }
+template <typename T, int N_>
+__device__ __forceinline__ void pin(T (&v)[N_]) {
+#pragma unroll
+  for (int i = 0; i < N_; ++i) pin(v[i]);
+}
+// a lane's 16 values to p[acc_row(r) * ld], p = the position of its first row (row0) in its column; rows_all: uniform, the
+// workgroup's whole row tile lies inside M
+template <typename T>
+__device__ __forceinline__ void store16(T* __restrict__ p, int64_t ld, int row0, int M, bool rows_all, const T (&v)[16]) {
+  if (rows_all) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) p[acc_row(r) * ld] = v[r];
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (row0 + acc_row(r) < M) p[acc_row(r) * ld] = v[r];
+  }
+}
+
 // Per-row-tile column statistics of the OUTPUT (value = acc + bias), for a following BatchNorm: removes the
 // separate statistics pass over the GEMM output.  A lane holds 16 rows of one column; lanes l and l^32 hold the
 // other 16 rows; the two waves with wm = 0 / 1 cover the tile's 64 rows.  Welford/Chan merges in a fixed order.
@@ -137,7 +170,7 @@ __device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, flo
   n = tot;
 }
 
-__device__ __forceinline__ void tile_col_stats(const f32x16& acc, float bv, int row_base, int M, int col, int N, int wm,
+__device__ __forceinline__ void tile_col_stats(const float (&out)[16] /* acc + bias */, int row_base, int M, int col, int N, int wm,
                                                int wn, int lane, float* lds /* >= 2*32*3 floats */,
                                                float* __restrict__ out_tile /* [N][3] of this row tile */) {
   const int khalf = lane >> 5;
@@ -145,14 +178,14 @@ __device__ __forceinline__ void tile_col_stats(const f32x16& acc, float bv, int 
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-    if (row < M) { n += 1.f; s += acc[r] + bv; }
+    if (row < M) { n += 1.f; s += out[r]; }
   }
   float mean = n > 0.f ? s / n : 0.f;
   float m2 = 0.f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-    if (row < M) { const float d = (acc[r] + bv) - mean; m2 += d * d; }
+    if (row < M) { const float d = out[r] - mean; m2 += d * d; }
   }
   // the other 16 rows of this column live in lane ^ 32: lower half first so both lanes compute the same bits
   const float on = __shfl_xor(n, 32, 64), om = __shfl_xor(mean, 32, 64), o2 = __shfl_xor(m2, 32, 64);
@@ -178,9 +211,10 @@ __device__ __forceinline__ void tile_bn_bwd_partial(const f32x16& acc, const BnB
   float sg = 0.f, sgx = 0.f;
   const bool col_ok = col >= 0 && col < N;  // (col, N: the SOURCE column and width - BnBwdEpi.col0)
   if (col_ok) {
-    const float bv = e.zbias ? e.zbias[col] : 0.f;
-    const float mu = e.use_bn ? e.mean[col] : 0.f;
-    const float is = e.use_bn ? e.invstd[col] : 0.f;
+    float bv = e.zbias ? e.zbias[col] : 0.f;
+    float mu = e.use_bn ? e.mean[col] : 0.f;
+    float is = e.use_bn ? e.invstd[col] : 0.f;
+    pin(bv); pin(mu); pin(is);  // (waited for once, here, not inside each row's branch)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * khalf;
@@ -563,6 +597,12 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
   const bool a_vec = (g.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.A) & 15) == 0);
   const bool b_vec = (g.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.B) & 15) == 0);
   const bool rows_full = (m0 + BM <= g.M) && (n0 + BN <= g.N);
+  const bool rows_all = m0 + BM <= g.M;  // (uniform) every row of the tile exists: the epilogue's stores need no row predicate
+  // the lane's output column and its bias, requested HERE from a clamped column (like the operands): it has arrived long
+  // before the epilogue, which then has no load to wait for between its stores
+  const int col = n0 + wn * 32 + (lane & 31);
+  float bv = 0.f;
+  if (g.bias && g.splits == 1) bv = g.bias[col < g.N ? col : g.N - 1];
 
   f32x16 acc;
 #pragma unroll
@@ -675,10 +715,14 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
     }
   }
   // epilogue.  C/D map of the 32x32 tile: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-  const int col = n0 + wn * 32 + (lane & 31);
-  const float bv = (g.bias && g.splits == 1 && col < g.N) ? g.bias[col] : 0.f;
+  // Every path below forms the lane's 16 values, pins them and then stores them (store16, above): no wait between stores.
+  const int row0 = m0 + wm * 32 + 4 * khalf;  // the lane's first row: register r holds row0 + acc_row(r)
+  pin(bv);
+  float out[16];  // acc + bias
+#pragma unroll
+  for (int r = 0; r < 16; ++r) out[r] = acc[r] + bv;
   if (g.col_stats)  // (host guarantees splits == 1) every thread takes part: it synchronises the workgroup
-    tile_col_stats(acc, bv, m0 + wm * 32, g.M, col, g.N, wm, wn, lane, lds,
+    tile_col_stats(out, m0 + wm * 32, g.M, col, g.N, wm, wn, lane, lds,
                    g.col_stats + static_cast<int64_t>(ty) * g.N * 3);
   if (BN_EPI && g.bn.partial != nullptr) {
     tile_bn_bwd_partial(acc, g.bn, py, pz, m0 + wm * 32, g.M, col < g.N ? col - g.bn.col0 : -1, g.bn.n_src, wm, wn, lane, lds, ty);
@@ -686,15 +730,15 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
       if (col >= g.N) return;
       const float ga = g.bn.gamma ? g.bn.gamma[col] : 1.f;
       const float is = g.bn.invstd[col];
+      float dz[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-        if (row < g.M) {
-          float gg = acc[r] + bv;
-          if (g.bn.act == ER_ACT_RELU && !(py[r] > 0.f)) gg = 0.f;
-          g.C[static_cast<int64_t>(row) * g.ldc + col] = ga * is * gg;  // (bn_bwd_finalize_apply_body's frozen form)
-        }
+        float gg = out[r];
+        if (g.bn.act == ER_ACT_RELU && !(py[r] > 0.f)) gg = 0.f;
+        dz[r] = ga * is * gg;  // (bn_bwd_finalize_apply_body's frozen form)
       }
+      pin(dz);
+      store16(g.C + static_cast<int64_t>(row0) * g.ldc + col, g.ldc, row0, g.M, rows_all, dz);
       return;
     }
   }
@@ -713,22 +757,29 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
     __syncthreads();
     const int j = tid & 15, rg = tid >> 4;
     const int J = tx * 16 + j;
+    // the thread's 4 rows: q / h / old dh of all four requested together from clamped rows, then combined, then stored
+    float qv[4], hv[4], od[4], gh[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int row = m0 + rg * 4 + i;
+      row = row < g.M ? row : g.M - 1;
+      qv[i] = d.q[static_cast<int64_t>(din_div_L(d, row)) * d.ldq + J];
+      hv[i] = d.h[static_cast<int64_t>(row) * d.ldh + J];
+      od[i] = d.accumulate_dh ? d.dh[static_cast<int64_t>(row) * d.lddh + J] : 0.f;
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int rl = rg * 4 + i;
-      const int row = m0 + rl;
-      float e = 0.f;
-      if (row < g.M) {
-        const int b = din_div_L(d, row);
-        const float qv = d.q[static_cast<int64_t>(b) * d.ldq + J];
-        const float hv = d.h[static_cast<int64_t>(row) * d.ldh + J];
-        const float d0 = D[rl * kD + j], d1 = D[rl * kD + 16 + j], d2 = D[rl * kD + 32 + j], d3 = D[rl * kD + 48 + j];
-        const float gh = (d1 - d2) + qv * d3;
-        float* p = d.dh + static_cast<int64_t>(row) * d.lddh + J;
-        *p = d.accumulate_dh ? *p + gh : gh;
-        e = (d0 + d2) + hv * d3;
-      }
-      Es[rl * 16 + j] = e;
+      const float d0 = D[rl * kD + j], d1 = D[rl * kD + 16 + j], d2 = D[rl * kD + 32 + j], d3 = D[rl * kD + 48 + j];
+      const float t = (d1 - d2) + qv[i] * d3;
+      gh[i] = d.accumulate_dh ? od[i] + t : t;
+      Es[rl * 16 + j] = m0 + rl < g.M ? (d0 + d2) + hv[i] * d3 : 0.f;
+    }
+    pin(gh);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = m0 + rg * 4 + i;
+      if (row < g.M) d.dh[static_cast<int64_t>(row) * d.lddh + J] = gh[i];
     }
     __syncthreads();
     const int b0 = din_div_L(d, m0);
@@ -749,17 +800,18 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
     // x_{l+1} = x0 * (acc + b + diag * x_l) + x_l, in cross_v2_fwd_kernel's order; u keeps acc
     if (col >= g.N) return;
     const bool with_diag = xe->diag != 0.f;
+    float uv[16], xv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-      if (row < g.M) {
-        const int64_t rr = row;
-        if (xe->u) xe->u[rr * xe->ld_u + col] = acc[r];
-        float t = acc[r] + bv;
-        if (with_diag) t = t + xe->diag * qb[r];
-        g.C[rr * g.ldc + col] = qa[r] * t + qb[r];
-      }
+      uv[r] = acc[r];
+      float t = out[r];
+      if (with_diag) t = t + xe->diag * qb[r];
+      xv[r] = qa[r] * t + qb[r];
     }
+    pin(uv);
+    pin(xv);
+    if (xe->u) store16(xe->u + static_cast<int64_t>(row0) * xe->ld_u + col, xe->ld_u, row0, g.M, rows_all, uv);
+    store16(g.C + static_cast<int64_t>(row0) * g.ldc + col, g.ldc, row0, g.M, rows_all, xv);
     return;
   }
   if (XEPI == ER_EPI_CROSS_BWD) {
@@ -769,25 +821,43 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
     const float pb = (prev && xe->prev_bias && col < g.N) ? xe->prev_bias[col] : 0.f;
     float cs = 0.f;
     if (col < g.N) {
+      // C's old values (accumulate): the lane's 16 requested together from clamped rows
+      float cv[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-        if (row < g.M) {
-          const int64_t rr = row;
-          float v = acc[r] + bv + qa[r];
-          if (with_diag) v = v + xe->diag * qb[r];
-          float* p = g.C + rr * g.ldc + col;
-          *p = g.accumulate ? *p + v : v;
-          if (prev) {
-            const float du = v * qc[r];
-            float t = qd[r] + pb;
-            if (with_diag) t = t + xe->diag * qe[r];
-            const float a = v * t;
-            xe->dx0[rr * xe->ld_dx0 + col] = xe->accumulate_dx0 ? qf[r] + a : a;
-            if (xe->du_out) xe->du_out[rr * xe->ld_du_out + col] = du;
-            if (xe->du_out_bf16) xe->du_out_bf16[rr * xe->ld_du_out_bf16 + col] = static_cast<uint16_t>(f32_to_bf16_rne(du));
-            cs = cs + du;
-          }
+        int row = row0 + acc_row(r);
+        row = row < g.M ? row : g.M - 1;
+        cv[r] = g.accumulate ? g.C[static_cast<int64_t>(row) * g.ldc + col] : 0.f;
+      }
+      float v[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        v[r] = out[r] + qa[r];
+        if (with_diag) v[r] = v[r] + xe->diag * qb[r];
+        cv[r] = g.accumulate ? cv[r] + v[r] : v[r];
+      }
+      pin(cv);
+      store16(g.C + static_cast<int64_t>(row0) * g.ldc + col, g.ldc, row0, g.M, rows_all, cv);
+      if (prev) {
+        float du[16], dx[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          du[r] = v[r] * qc[r];
+          float t = qd[r] + pb;
+          if (with_diag) t = t + xe->diag * qe[r];
+          const float a = v[r] * t;
+          dx[r] = xe->accumulate_dx0 ? qf[r] + a : a;
+          if (row0 + acc_row(r) < g.M) cs = cs + du[r];
+        }
+        pin(dx);
+        pin(du);
+        store16(xe->dx0 + static_cast<int64_t>(row0) * xe->ld_dx0 + col, xe->ld_dx0, row0, g.M, rows_all, dx);
+        if (xe->du_out) store16(xe->du_out + static_cast<int64_t>(row0) * xe->ld_du_out + col, xe->ld_du_out, row0, g.M, rows_all, du);
+        if (xe->du_out_bf16) {
+          uint16_t dub[16];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dub[r] = static_cast<uint16_t>(f32_to_bf16_rne(du[r]));
+          store16(xe->du_out_bf16 + static_cast<int64_t>(row0) * xe->ld_du_out_bf16 + col, xe->ld_du_out_bf16, row0, g.M, rows_all, dub);
         }
       }
     }
@@ -812,18 +882,18 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
       g.fz_save[col] = mu;
       g.fz_save[g.N + col] = is;
     }
+    float yv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-      if (row < g.M) {
-        const float zv = acc[r] + bv;
-        g.C[static_cast<int64_t>(row) * g.ldc + col] = zv;
-        float v = ((zv + fb) - mu) * is;
-        v = v * ga + be;
-        if (g.bn.act == ER_ACT_RELU) v = v > 0.f ? v : 0.f;
-        g.fz_y[static_cast<int64_t>(row) * g.ldc + col] = v;
-      }
+      float v = ((out[r] + fb) - mu) * is;
+      v = v * ga + be;
+      if (g.bn.act == ER_ACT_RELU) v = v > 0.f ? v : 0.f;
+      yv[r] = v;
     }
+    pin(out);
+    pin(yv);
+    store16(g.C + static_cast<int64_t>(row0) * g.ldc + col, g.ldc, row0, g.M, rows_all, out);
+    store16(g.fz_y + static_cast<int64_t>(row0) * g.ldc + col, g.ldc, row0, g.M, rows_all, yv);
     return;
   }
   float* Cz = g.C + (g.splits > 1 ? static_cast<int64_t>(bz) * g.M * g.N : 0);
@@ -834,22 +904,18 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
     float old[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+      int row = row0 + acc_row(r);
       row = row < g.M ? row : g.M - 1;
       old[r] = Cz[static_cast<int64_t>(row) * ldc + col];
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-      if (row < g.M) Cz[static_cast<int64_t>(row) * ldc + col] = old[r] + (acc[r] + bv);
-    }
+    for (int r = 0; r < 16; ++r) old[r] = old[r] + out[r];
+    pin(old);
+    store16(Cz + static_cast<int64_t>(row0) * ldc + col, ldc, row0, g.M, rows_all, old);
     return;
   }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-    if (row < g.M) Cz[static_cast<int64_t>(row) * ldc + col] = acc[r] + bv;
-  }
+  pin(out);
+  store16(Cz + static_cast<int64_t>(row0) * ldc + col, ldc, row0, g.M, rows_all, out);
 }
 
 // Grouped launch: up to kMaxGroup independent problems of one layout in ONE grid (the weight gradients of all
