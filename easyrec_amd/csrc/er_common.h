@@ -38,6 +38,15 @@ inline hipStream_t as_stream(er_stream_t s) { return reinterpret_cast<hipStream_
 
 __host__ __device__ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// splitmix64 finaliser: the hash-table embeddings' home slot and row initialiser (er_kv.hip), the negative sampler's
+// round keys, round function and id-set home slot (er_sampler.hip)
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
 // fp32 -> bf16 bits, round to nearest even (NaN stays NaN): what every bf16 copy in the library holds
 __host__ __device__ inline uint16_t f32_to_bf16_bits(float f) {
   uint32_t u;

@@ -36,13 +36,6 @@ namespace er {
 constexpr int64_t kKvEmpty = -1;
 inline int blocks_for(int64_t n) { return static_cast<int>(ceil_div(n, kBlock)); }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
 // value of column c of the row of `key`: mean + stddev * z, z = ((u0 + u1) + (u2 + u3) - 2) * sqrt(3) with four
 // 24-bit uniforms (sum of four U(0,1): variance 1/3 -> unit variance, support +-3.46 sigma; fp32, this operation order:
 // oracle/kernel_ref.py kv_init_value restates it bit for bit)

@@ -215,13 +215,43 @@ class DeviceFeatures(object):
     self.seq_batch_max = {name: s['max_len'] for name, s in schema.seqs.items()}
     self.pad_to_batch_max = True
     self._use_device_hash = False
+    # negative_sampler_in_memory (input/neg_sampler.py): per attribute feature the extended buffers {'ids' | 'raw': [B + N]}
+    # (allocated once: fixed addresses), whose [0, B) the sampler copies from the batch's own column and whose [B, B + N)
+    # it draws; `sampling`: the step at hand drew, ids_of / raw of those features return the B + N views
+    self.sampler = None
+    self.extended = {}
+    self.sampling = False
 
   @property
   def batch_size(self):
     return self.schema.batch_size
 
+  def attach_sampler(self, sampler, extended):
+    self.sampler, self.extended = sampler, extended
+
+  def extended_rows(self, name):
+    """rows of feature `name`'s lookup source: B + N for an attribute feature of the sampler, else B"""
+    return self.batch_size + self.sampler.N if name in self.extended else self.batch_size
+
+  def lookup_ids(self, name):
+    """what the embedding lookup of an id feature reads: its extended buffer under a sampler, else its batch column"""
+    return self.extended[name]['ids'] if 'ids' in self.extended.get(name, ()) else self.batch_ids_of(name)
+
+  def lookup_raw(self, name):
+    return self.extended[name]['raw'] if 'raw' in self.extended.get(name, ()) else self.batch_raw(name)
+
   # -- dict-like views (the reference's parsed feature dict)
   def raw(self, name):
+    if self.sampling and 'raw' in self.extended.get(name, ()):
+      return self.extended[name]['raw']  # [B + N]
+    return self.batch_raw(name)
+
+  def ids_of(self, name):
+    if self.sampling and 'ids' in self.extended.get(name, ()):
+      return self.extended[name]['ids']  # [B + N]
+    return self.batch_ids_of(name)
+
+  def batch_raw(self, name):
     if name in self.raw_multi:
       return self.raw_multi[name]['values']  # [B, k]
     if name not in self.schema.raw:
@@ -232,7 +262,7 @@ class DeviceFeatures(object):
     blk = self.raw_block[r['row']:r['row'] + r['dim']]
     return blk[0] if r['dim'] == 1 else blk  # [B] or [dim, B]
 
-  def ids_of(self, name):
+  def batch_ids_of(self, name):
     if name in self.schema.hash_single:
       return self.hash_ids[self.schema.hash_single[name]['col']]
     if name in self.schema.int_single:

@@ -2216,6 +2216,34 @@ class HipBackend(object):
         bool(ignore_in_batch), _p(c_in), _p(c_neg), _stream()), 'er_match_rank_counts')
     return c_in, c_neg
 
+  # -- K1b negative_sampler_in_memory (input/neg_sampler.py)
+  NEG_SAMPLE_MAX_COLS = 32
+
+  def neg_sample_lds_bytes(self, B):
+    return int(self.lib.er_neg_sample_lds_bytes(int(B)))
+
+  def neg_sample(self, table_ids, batch_ids, N, step, step_offset, seed, columns, sel):
+    """The draw of easyrec_hip.h K1b at step *step + step_offset.  columns: [(table column [n], the batch's column [B],
+    its extended buffer [B + N])], int64 or fp32; sel: int32 [N]."""
+    n, B = table_ids.numel(), batch_ids.numel()
+    assert table_ids.dtype == torch.int64 and batch_ids.dtype == torch.int64 and step.dtype == torch.int64
+    assert table_ids.is_contiguous() and batch_ids.is_contiguous()
+    assert sel.dtype == torch.int32 and sel.numel() == N and sel.is_contiguous()
+    nc = len(columns)
+    tabs, bats, outs, sizes = [], [], [], []
+    for tab, bat, out in columns:
+      assert tab.dtype == bat.dtype == out.dtype and tab.dtype in (torch.int64, torch.float32), tab.dtype
+      assert tab.numel() == n and bat.numel() == B and out.numel() == B + N
+      assert tab.is_contiguous() and bat.is_contiguous() and out.is_contiguous()
+      tabs.append(tab.data_ptr())
+      bats.append(bat.data_ptr())
+      outs.append(out.data_ptr())
+      sizes.append(tab.element_size())
+    ptrs = ctypes.c_void_p * max(nc, 1)
+    self._ck(self.lib.er_neg_sample(
+        _p(table_ids), n, _p(batch_ids), B, int(N), _p(step), int(step_offset), int(seed) & 0xFFFFFFFFFFFFFFFF, ptrs(*tabs),
+        ptrs(*bats), ptrs(*outs), (ctypes.c_int32 * max(nc, 1))(*sizes), nc, _p(sel), _stream()), 'er_neg_sample')
+
   # -- K8g MIND's capsule layer and label-aware attention (layers/capsule_layer.py, model/mind.py)
   CAPSULE_MAX_K = 8
   MIND_ATT_MAX_E = 128

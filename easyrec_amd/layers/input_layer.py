@@ -172,9 +172,14 @@ class EmbeddingEngine(object):
     self.tables[var_name] = t
     return t
 
-  def declare_group(self, gkey, width, regularize):
+  def declare_group(self, gkey, width, regularize, n_rows=None):
+    """n_rows: a group whose features are all attribute fields of a negative sampler has batch_size + num_sample rows.
+    The fused single-GPU step (emb_front / emb_bwd_fused) takes plain groups of batch_size rows only: such a model runs
+    the general path."""
     assert gkey not in self.groups
-    B = self.batch_size
+    B = int(n_rows or self.batch_size)
+    if B != self.batch_size:
+      self._fused = False
     g = {
         'out': torch.zeros(B, width, dtype=torch.float32, device=self.device),
         'dout': torch.zeros(B, width, dtype=torch.float32, device=self.device),
@@ -1032,9 +1037,16 @@ class InputLayer(object):
     scope = self._next_scope()
     eng = self._engine
     B = eng.batch_size
+    # negative sampler: a group of attribute fields only has B + N rows; one that mixes them with other features has no
+    # row count (reference input.py:839-841 concatenates the sampled rows to the attribute columns alone)
+    sampled = [c.raw_name for c in columns if c.raw_name in getattr(features, 'extended', {})]
+    if sampled and len(sampled) != len(columns):
+      raise ValueError('feature group %s mixes attribute fields of the negative sampler (%s) with other features (%s)' % (
+          group_name, ', '.join(sampled), ', '.join(c.raw_name for c in columns if c.raw_name not in sampled)))
+    rows = features.extended_rows(sampled[0]) if sampled else B
     width = sum(c.dimension for c in columns)
     gkey = 'group:' + group_name + (':plain' if plain_only else '')
-    eng.declare_group(gkey, width, self._embedding_regularizer)
+    eng.declare_group(gkey, width, self._embedding_regularizer, n_rows=rows)
     col, cols, dims, numeric = 0, [], [], []
     for c in columns:
       if isinstance(c, NumericColumn):
@@ -1047,7 +1059,7 @@ class InputLayer(object):
       dims.append(c.dimension)
       col += c.dimension
     self._group_plan[(group_name, plain_only)] = {'gkey': gkey, 'columns': columns, 'cols': cols, 'dims': dims,
-                                                  'numeric': numeric}
+                                                  'numeric': numeric, 'rows': rows}
 
   def _declare_sequences(self, features, group_name):
     """The sequence columns of a group kept over time (`get_sequence_feature`, layers/input_layer.py:164-200): one
@@ -1135,8 +1147,10 @@ class InputLayer(object):
       for c, col in plan['numeric']:
         src = features.raw(c.key)
         src2 = src.view(-1, 1) if src.dim() == 1 else src
-        kernels.hip().axpy2d(src2, 1.0, g['out'][:, col:col + c.dimension], accumulate=False)
+        kernels.hip().axpy2d(src2, 1.0, g['out'][:src2.shape[0], col:col + c.dimension], accumulate=False)
       out = eng.group_tensor(plan['gkey'], requires_grad=self._is_training)
+    if plan['rows'] != eng.batch_size and not features.sampling:
+      out = out[:eng.batch_size]  # (a step that does not sample: the batch's own rows, as the reference's PREDICT mode)
     views = [out[:, c0:c0 + d] for c0, d in zip(plan['cols'], plan['dims'])]
     flist = FeatureList(views, base=out, col0=0, dims=plan['dims'])
     if is_dict:
@@ -1171,8 +1185,10 @@ def declare_lookup(eng, features, column, scope, gkey, col, n_out_rows, seq=Fals
       eng.add_lookup(gkey, table_name, rm['ids'], rm['offsets'], rm['values'].view(-1), col, column.combiner, B,
                      rm['ids'].numel(), fname)
     else:
-      eng.add_lookup(gkey, table_name, features.zero_ids, None, features.raw(fname), col, column.combiner, B, B,
-                     fname)
+      w = features.lookup_raw(fname)  # (under a negative sampler: the attribute's extended buffer)
+      n = w.numel()
+      zero_ids = features.zero_ids if n == B else torch.zeros(n, dtype=torch.int64, device=eng.device)
+      eng.add_lookup(gkey, table_name, zero_ids, None, w, col, column.combiner, n, n, fname)
     return
   if seq:
     s = features.seqs[fname]
@@ -1200,7 +1216,8 @@ def declare_lookup(eng, features, column, scope, gkey, col, n_out_rows, seq=Fals
     # sequence feature used as a plain (combined) column: sum/mean over the time axis
     s = features.seqs[fname]
     raise NotImplementedError('sequence feature %s as combined column' % fname)
-  ids = features.ids_of(fname)
+  ids = features.lookup_ids(fname)  # (under a negative sampler: the attribute's extended buffer of B + N ids)
+  B = ids.numel()
   if kv_capacity is not None:
     assert fname in schema.hash_single, 'ev_params on %s: hash-table embeddings cover hashed IdFeatures and TagFeatures' % fname
     rows_buf = torch.full((B,), -1, dtype=torch.int64, device=eng.device)  # arena rows of this step's ids

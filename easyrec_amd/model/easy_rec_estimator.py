@@ -38,7 +38,7 @@ class EasyRecEstimator(object):
   HYPER_SLOTS = 4096
 
   def __init__(self, pipeline_config, device='cuda', batch_size=None, seed=0, schema_kwargs=None,
-               is_training=True, overlap_sweep=False, dense_dtype=None, dense_sweep=None):
+               is_training=True, overlap_sweep=False, dense_dtype=None, dense_sweep=None, item_table=None):
     import_all_models()
     self.pipeline_config = config_util.get_configs_from_pipeline_file(pipeline_config) \
         if isinstance(pipeline_config, str) else pipeline_config
@@ -102,6 +102,15 @@ class EasyRecEstimator(object):
       model_cls = EasyRecModel.create_class(cfg.model_config.model_class)
       if hasattr(model_cls, 'check_data_config'):
         model_cls.check_data_config(cfg.data_config)  # (what the input pipeline would have to deliver: model/match_model.py)
+      # negative_sampler_in_memory: the item table goes to the device and the attribute features get their extended
+      # buffers before the model declares its groups (item_table: an input/neg_sampler.py ItemTable instead of input_path)
+      self.sampler = None
+      if cfg.data_config.WhichOneof('sampler') == 'negative_sampler_in_memory':
+        if not getattr(model_cls, 'supports_sampled_negatives', False):
+          raise NotImplementedError('data_config.negative_sampler_in_memory: %s takes no sampled negatives' %
+                                    cfg.model_config.model_class)
+        from easyrec_amd.input.neg_sampler import NegativeSampler
+        self.sampler = NegativeSampler(cfg.data_config, self.feature_configs, self.features, seed, item_table)
       self.model = model_cls(cfg.model_config, self.feature_configs, self.features, labels,
                              is_training=is_training)
 
@@ -272,6 +281,9 @@ class EasyRecEstimator(object):
     be.step_prologue(self.hyper_table, self.step_counter, self.hyper, history=self.lr_hist,
                      zero=self.varstore.flat_grad_all, decay_tables=self.decay_tables, hash_job=hash_job)
     self.features.transform(hashed=hash_job is not None)
+    if self.sampler is not None:
+      # the step's negatives, drawn on the device for step *step_counter - 1 (the prologue has advanced the counter)
+      self.sampler.run(self.step_counter, -1, sample=True)
     if self.is_training and self.overlap_sweep and self.opt_emb.kind == kernels.OPT_ADAM:
       self.engine.start_decay_sweep(self.hyper[0])
     with context.use(self.ctx):
@@ -376,11 +388,19 @@ class EasyRecEstimator(object):
 
   OVERFLOW_CHECK_EVERY = 256
 
-  def predict(self, batch=None):
+  def predict(self, batch=None, sample_negatives=False):
+    """sample_negatives: the evaluation mode of a config with a negative sampler - the item tower sees B + N rows, drawn
+    for the step the counter stands at; without it the batch's own B rows, as the reference's PREDICT mode."""
     assert self._built
     if batch is not None:
       self.features.load(batch)
     self.features.transform()
+    if self.sampler is not None:
+      if batch is None:
+        self.features.version += 1  # (the extended columns change: the lookups run again)
+      self.sampler.run(self.step_counter, 0, sample=bool(sample_negatives))
+    else:
+      assert not sample_negatives, 'predict(sample_negatives=True) needs data_config.negative_sampler_in_memory'
     # no row update follows these lookups: bring the tables current once, then look up without the catch-up
     # (running it here would re-apply the pending Adam decay on every call)
     self.engine.begin_inference()

@@ -10,8 +10,10 @@ form (:145-205).
 
 While training, the list-wise head never builds its [B, B] logits: build_predict_graph stops at the tower embeddings and
 build_loss_graph hands them to layers/match_head.py (one fused forward, the backward recomputing the logits).  Outside
-training `logits` and `probs` are composed of torch ops.  Item rows beyond the batch (negative samplers, hard negatives)
-are not produced by the input pipeline here: configs that ask for them are refused at build time.
+training `logits` and `probs` are composed of torch ops.  Item rows beyond the batch come from
+`negative_sampler_in_memory` alone (input/neg_sampler.py: N rows drawn on the device inside the step, the item group then
+has B + N rows and every head function here takes M = B + N columns); the graphlearn samplers and hard negatives are
+refused at build time.  predict() does not sample (the reference's PREDICT mode): the item tower sees the batch's B rows.
 """
 import logging
 
@@ -25,8 +27,7 @@ from easyrec_amd.model.easy_rec_model import EasyRecModel
 from easyrec_amd.protos.loss_pb2 import LossType
 from easyrec_amd.protos.simi_pb2 import Similarity
 
-_SAMPLERS = ('negative_sampler', 'negative_sampler_v2', 'hard_negative_sampler', 'hard_negative_sampler_v2',
-             'negative_sampler_in_memory')
+_REFUSED_SAMPLERS = ('negative_sampler', 'negative_sampler_v2', 'hard_negative_sampler', 'hard_negative_sampler_v2')
 
 
 class MatchModel(EasyRecModel):
@@ -48,6 +49,9 @@ class MatchModel(EasyRecModel):
       features.ids_of(self._item_id_name)  # (KeyError now rather than at the first step)
     ctx = context.current()
     self.check_supported(self._loss_type, getattr(ctx, 'dense_dtype', 'f32'), ctx.engine, type(self).__name__)
+    if getattr(features, 'sampler', None) is not None and self._is_point_wise:
+      raise ValueError('%s: a negative sampler needs a list-wise loss (SOFTMAX_CROSS_ENTROPY): the sampled rows have no '
+                       'labels for %s' % (type(self).__name__, LossType.Name(self._loss_type)))
     if 'hard_neg_indices' in features:
       raise NotImplementedError('%s: a batch with hard_neg_indices (hard negative examples) is not supported' %
                                 type(self).__name__)
@@ -62,12 +66,14 @@ class MatchModel(EasyRecModel):
     if loss_type not in (LossType.CLASSIFICATION, LossType.L2_LOSS, LossType.SOFTMAX_CROSS_ENTROPY):
       raise ValueError('invalid loss type: %s' % LossType.Name(loss_type))
 
+  supports_sampled_negatives = True
+
   @staticmethod
   def check_data_config(data_config):
-    """The estimator's build-time hook: the samplers give the item tower more rows than the user tower, which the
-    packed batch and the embedding stage do not carry."""
+    """The estimator's build-time hook: negative_sampler_in_memory is built (input/neg_sampler.py); the other four
+    delegate their draw to graphlearn (weighted, per-user, hard negatives), which nothing here restates."""
     sampler = data_config.WhichOneof('sampler')
-    if sampler in _SAMPLERS:
+    if sampler in _REFUSED_SAMPLERS:
       raise NotImplementedError('data_config.%s: negative sampling is not supported (the item tower sees the '
                                 "batch's own rows only)" % sampler)
 
@@ -100,6 +106,8 @@ class MatchModel(EasyRecModel):
 
   def _list_wise_sim(self, user_emb, item_emb):
     if self._is_predicting:
+      # (the exported model scores (user, item) pairs row by row: never a sampled step, the towers have the same rows)
+      assert user_emb.shape[0] == item_emb.shape[0], 'a predicting model does not sample negatives'
       return self._point_wise_sim(user_emb, item_emb)
     return user_emb @ item_emb.t()
 

@@ -817,6 +817,49 @@ int er_mind_attention_bwd(const float* interests, const float* pos_item, const i
                           float simi_pow, float* d_interests, float* d_pos_item, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K1b negative_sampler_in_memory on the device.  Replaces the tf.py_func around
+ *     NegativeSamplerInMemory._get_impl core/sampler.py:425-454 (np.random.choice without replacement,
+ *     the `rid not in ids` walk, the column gathers) and the tf.concat of input/input.py:823-845 that
+ *     appends the sampled rows to the batch's attribute columns.  One launch: one workgroup draws and
+ *     gathers, ceil(B / 1024) more copy the batch's own values meanwhile.
+ * The item table: n rows; table_ids [n] int64 are the rows' item ids as the embedding of the
+ *   item-id feature sees them (hashed into its buckets, or the identity column's clamped integer),
+ *   unique over the table; every attribute column is int64 [n] (ids) or float [n] (raw values),
+ *   converted once when the table is loaded.  batch_ids [B]: the batch's ids of the same feature.
+ * The draw at global step s (0 for the first step) with `seed`:
+ *   bits = max(2, bit_length(n - 1)), h = ceil(bits / 2), mask = 2^h - 1;
+ *   mix64(x): x ^= x >> 30, x *= 0xBF58476D1CE4E5B9, x ^= x >> 27, x *= 0x94D049BB133111EB,
+ *     x ^= x >> 31 on 64 bits (the splitmix64 finaliser);
+ *   base = mix64(seed ^ mix64(s)); key_r = mix64(base + r * 0xD1B54A32D192ED03) mod 2^64, r = 0..3;
+ *   P(k): x = k; split x into (L, R) = (x >> h, x & mask); four rounds (L, R) <- (R, L ^ (mix64(key_r
+ *     ^ R) & mask)), r = 0..3; x = (L << h) | R; the four rounds again from this x until x < n (cycle
+ *     walking).  P is a bijection on [0, n), so the candidates P(0), P(1), .., P(B + N - 1) are
+ *     distinct rows, as np.random.choice(n, B + N, replace=False) gives distinct rows.
+ *   The candidates are walked in order of k; one is kept unless table_ids[P(k)] equals one of the B
+ *   batch ids; the walk stops after N kept.  With unique table ids at most B are dropped, so N are
+ *   always found (a table that breaks the rule gets row 0 in the places left over).  sel [N] = the
+ *   kept rows in order of k.  The result depends only on (seed, s, n, the SET of batch ids, the
+ *   table): not on how membership is tested, the launch shape or the thread order.  The reference's
+ *   np.random stream cannot be reproduced: the two agree in distribution (uniform over the eligible
+ *   rows, without replacement), not draw by draw.
+ * s = *step + step_offset, read on the device: inside a training step (after er_step_prologue_hash
+ *   has advanced the counter) step_offset is -1; a replayed graph draws fresh rows every step.
+ * Every column c of the ncols <= 32 (HOST arrays of device pointers and of element sizes, 8 for
+ *   int64 and 4 for float; they travel in the kernel arguments, nothing is built on the device):
+ *   out_c [B + N]: [0, B) = batch_c [B] (the tf.concat's first operand), [B, B + N) = table_c[sel[j]].
+ * Envelope: 1 <= B <= 4096, 1 <= N, B + N <= n < 2^31.  er_neg_sample_lds_bytes(B) = 8 * cap + 128
+ *   with cap = max(64, the power of two >= 2 B): the batch ids as an open-addressing set (home slot
+ *   mix64(id) & (cap - 1), linear probing) and the 16 wave counts of the in-order compaction; 0
+ *   outside the envelope, where (and on a CPU backend) easyrec_amd/input/neg_sampler.py composes the
+ *   same draw of torch / numpy operations.
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_neg_sample_lds_bytes(int32_t B);
+int er_neg_sample(const int64_t* table_ids, int64_t n, const int64_t* batch_ids, int32_t B, int32_t N,
+                  const int64_t* step, int64_t step_offset, uint64_t seed, const void* const* table_cols_host,
+                  const void* const* batch_cols_host, void* const* out_cols_host, const int32_t* elem_bytes_host,
+                  int32_t ncols, int32_t* sel, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed

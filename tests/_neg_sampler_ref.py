@@ -1,0 +1,75 @@
+"""numpy-uint64 restatement of the negative sampler's draw, written from the text of include/easyrec_hip.h (K1b) and not
+from the product's composition: what er_neg_sample and easyrec_amd/input/neg_sampler.py are checked against.
+
+  bits = max(2, bit_length(n - 1)), h = ceil(bits / 2), mask = 2^h - 1
+  mix64: the splitmix64 finaliser; base = mix64(seed ^ mix64(s)); key_r = mix64(base + r * 0xD1B54A32D192ED03)
+  P(k): x = k; (L, R) = (x >> h, x & mask); four rounds (L, R) <- (R, L ^ (mix64(key_r ^ R) & mask)); x = (L << h) | R;
+        again from this x until x < n
+  walk P(0), P(1), ..: keep a row unless its id is one of the batch's; stop after N kept."""
+import numpy as np
+
+U64 = np.uint64
+GOLDEN = 0xD1B54A32D192ED03
+M64 = (1 << 64) - 1
+
+
+def mix64(v):
+  with np.errstate(over='ignore'):
+    v = np.array(v, dtype=U64)
+    v = v ^ (v >> U64(30))
+    v = v * U64(0xBF58476D1CE4E5B9)
+    v = v ^ (v >> U64(27))
+    v = v * U64(0x94D049BB133111EB)
+    return v ^ (v >> U64(31))
+
+
+def round_keys(seed, step):
+  base = int(mix64((seed & M64) ^ int(mix64(step & M64))))
+  return [U64(int(mix64((base + r * GOLDEN) & M64))) for r in range(4)]
+
+
+def half_bits(n):
+  bits = max(2, (n - 1).bit_length())
+  return -(-bits // 2)
+
+
+def feistel(x, keys, h):
+  """one pass of the four rounds over a uint64 array"""
+  mask = U64((1 << h) - 1)
+  left, right = x >> U64(h), x & mask
+  for key in keys:
+    left, right = right, left ^ (mix64(key ^ right) & mask)
+  return (left << U64(h)) | right
+
+
+def perm(seed, step, n, ks=None):
+  """P(k) for every k of `ks` (default: all of [0, n)) -> int64 array"""
+  keys, h = round_keys(seed, step), half_bits(n)
+  x = np.arange(n, dtype=U64) if ks is None else np.asarray(ks, dtype=U64)
+  x = feistel(x, keys, h)
+  outside = x >= U64(n)
+  while outside.any():
+    x = np.where(outside, feistel(x, keys, h), x)
+    outside = x >= U64(n)
+  return x.astype(np.int64)
+
+
+def draw(seed, step, table_ids, batch_ids, N):
+  """sel [N] int64: the kept rows in order of k"""
+  table_ids = np.asarray(table_ids, dtype=np.int64)
+  n, B = len(table_ids), len(batch_ids)
+  excluded = set(int(v) for v in np.asarray(batch_ids).tolist())
+  sel = []
+  for row in perm(seed, step, n, np.arange(B + N)).tolist():
+    if int(table_ids[row]) not in excluded:
+      sel.append(row)
+      if len(sel) == N:
+        break
+  assert len(sel) == N, 'unique table ids leave at least N of B + N candidates'
+  return np.asarray(sel, dtype=np.int64)
+
+
+def extended(batch_col, table_col, sel):
+  """[0, B) the batch's values, [B, B + N) table_col[sel]"""
+  table_col = np.asarray(table_col)
+  return np.concatenate([np.asarray(batch_col).astype(table_col.dtype), table_col[np.asarray(sel)]])
