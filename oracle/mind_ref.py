@@ -1,11 +1,11 @@
 """fp64 restatement of the reference's MIND (easy_rec/python/layers/capsule_layer.py, model/mind.py) in torch: the
-capsule layer with dynamic routing, the label-aware attention, the towers and _build_interest_simi, with _match_ref's
+capsule layer with dynamic routing, the label-aware attention, the towers and _build_interest_simi, with match_ref's
 head behind them.  Every tf.stop_gradient is a .detach(), so autograd gives every gradient: what the capsule and
 attention kernels, the composed path and the model are checked against."""
 import numpy as np
 import torch
 
-import _match_ref as mref
+from oracle import match_ref as mref
 
 BN_EPSILON = 1e-3
 
@@ -111,12 +111,15 @@ def dnn(x, var, name, last_plain=False, training=True):
   return x
 
 
-def combine_hist(m, seqs, lens):
-  """mind.py:54-101 without pre_capsule_dnn: seqs {name: [B, L, d]} in group order -> the capsule layer's input"""
+def combine_hist(m, seqs, lens, pre_capsule_dnn=None):
+  """mind.py:54-101: seqs {name: [B, L, d]} in group order -> the capsule layer's input; pre_capsule_dnn: the configured
+  DNN as a callable over the combined [B, L, D] sequence (:82-91, in front of the time weighting)"""
   from easyrec_amd.protos.mind_pb2 import MIND
   time = [v for k, v in seqs.items() if m.time_id_fea and m.time_id_fea in k]
   feas = [v for k, v in seqs.items() if not (time and m.time_id_fea in k)]
   hist = sum(feas) / len(feas) if m.user_seq_combine == MIND.SUM else torch.cat(feas, dim=2)
+  if pre_capsule_dnn is not None:
+    hist = pre_capsule_dnn(hist)
   if time:
     tmask = (sequence_mask(lens, time[0].shape[1], hist.dtype) * 2 - 1) * 1e32
     hist = hist * torch.softmax(torch.minimum(time[0], tmask[:, :, None]), dim=1)
@@ -124,9 +127,11 @@ def combine_hist(m, seqs, lens):
 
 
 def mind_forward(m, loss_type, hist, hist_len, user, item, var, logits0, label=None, ids=None, weight=None,
-                 training=True):
+                 training=True, dnn=dnn, batch_norm=batch_norm):
   """MIND.build_predict_graph + build_loss_graph (mind.py:50-258) from the group outputs on.  m: the `mind` message (or
-  anything with its fields); hist: the combined sequence in front of the capsule layer [B, L, D] -> (losses, predictions)"""
+  anything with its fields); hist: the combined sequence in front of the capsule layer [B, L, D]; var: anything that
+  gives a variable by name; dnn / batch_norm: the layers, this module's unless the caller brings its own (the model
+  oracle: its DNN with the regulariser and the moving statistics) -> (losses, predictions)"""
   from easyrec_amd.protos.simi_pb2 import Similarity
   import types
   c = m.capsule_config

@@ -16,6 +16,14 @@ to /root/reference/easy_rec/python) and TF's documented op semantics (SURVEY.md 
   FiBiNet        layers/keras/fibinet.py (BiLinear's pair terms: oracle/fibinet_ref.py), the input-layer block's
                  do_batch_norm layers/common_layers.py:142-191
   MMoE           model/mmoe.py:35-70, layers/mmoe.py:62-83, model/multi_task_model.py:33-141
+  DSSM           model/dssm.py:41-106 (towers :42-62); the head model/match_model.py:50-69, :71-143, :213-279
+                 (oracle/match_ref.py)
+  MatchModel     model/match_model.py:145-205 over the backbone's output_blocks (layers/backbone.py:327-334)
+  MIND           model/mind.py:50-299, layers/capsule_layer.py:60-176 (oracle/mind_ref.py); the `hist` sequences
+                 layers/input_layer.py:164-200, :268-278.  The initial routing logits are an INPUT
+                 (OracleTrainer.routing_logits): capsule_layer.py:83-85 draws them from TensorFlow's generator
+  negative_sampler_in_memory  the draw of include/easyrec_hip.h K1b (oracle/neg_sampler_ref.py; the reference's
+                 core/sampler.py:321-473 draws with np.random.choice (:431): parity in distribution only)
   loss           model/rank_model.py:105-111,213-332, builders/loss_builder.py:35-39
   regularisation model/easy_rec_estimator.py:166-184, compat/regularizers.py:76-108
   optimizer      builders/optimizer_builder.py:61-66 (tf.train.AdamOptimizer, dense-decay sparse
@@ -32,7 +40,10 @@ no bias) / CIN / DotInteraction (layers/keras/interaction.py), layers/dnn.py DNN
 keras MLP (layers/keras/blocks.py, configured through the reference's Parameter), keras DIN (layers/keras/din.py),
 layers/sequence_feature_layer.py target_attention, layers/mmoe.py MMOE, model/dcn.py _cross_net,
 core/learning_schedules.py exponential_decay_with_burnin; hashing by TensorFlow's documented vectors; the embedding
-lookup by embed_test's vectors.  The assembly of the model classes (build_predict_graph of eleven classes), the
+lookup by embed_test's vectors; the two-tower head and DSSM's towers (match_ref) and MIND from its group outputs on
+(mind_ref) by tests/golden/match_vectors.npz and mind_vectors.npz, the outputs of the reference's own match_model.py,
+dssm.py, capsule_layer.py and mind.py (tests/test_match_pins.py, tests/test_mind_pins.py).  The assembly of the model
+classes (build_predict_graph of eleven classes; DSSM, MatchModel and MIND in front of those fixtures' inputs), the
 backbone DAG, keras MMoE / SENet and the FeatureColumnParser are pinned THROUGH THE PRODUCT (its model classes,
 backbone, layers and parser are held to the reference's outputs; this oracle is held to the product by
 tests/test_host_logic.py).  "Parity unpinned" (the reference's tests hold no numeric expectation, the code is
@@ -46,7 +57,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from oracle import autoint_ref, bst_ref, fibinet_ref, hashing
+from oracle import autoint_ref, bst_ref, fibinet_ref, hashing, match_ref, mind_ref, neg_sampler_ref
 
 F32 = np.float32
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
@@ -124,10 +135,22 @@ class Vars(object):
     return self.used[name]
 
 
+class _ByName(object):
+  """V.get as a mapping: what the restatements that take their variables by name read"""
+
+  def __init__(self, V):
+    self.V = V
+
+  def __getitem__(self, name):
+    return self.V.get(name)
+
+
 class OracleTrainer(object):
 
-  def __init__(self, cfg, state, batch_size, dtype=torch.float32, compact_ids=None):
-    """compact_ids: {embedding table name: ascending int64 ids}: `state[name]` (and the slots handed to resume()) hold
+  def __init__(self, cfg, state, batch_size, dtype=torch.float32, compact_ids=None, item_table=None, sampler_seed=None):
+    """item_table, sampler_seed: what data_config.negative_sampler_in_memory draws from - anything with `.ids` and
+    `.columns[name]['ids' | 'raw']` as numpy arrays, and the seed of the draw (oracle/neg_sampler_ref.py).
+    compact_ids: {embedding table name: ascending int64 ids}: `state[name]` (and the slots handed to resume()) hold
     ONLY those rows - every id the batches of this trainer's life will look up must be among them.  Rows that no lookup
     reads cannot influence a loss, and TF-Adam's every-row decay acts on each row independently, so the losses and the
     listed rows are exactly those of the full tables: what makes the 200 M-row table of BASELINE config 5 (51 GB, 153 GB
@@ -176,6 +199,11 @@ class OracleTrainer(object):
         if oc[0].HasField('embedding_learning_rate_multiplier') else 1.0
     self.model_class = cfg.model_config.model_class
     self.last_bst = []  # MultiTowerBST: the BST towers' block outputs of the last forward pass
+    self.item_table, self.sampler_seed = item_table, sampler_seed
+    # MIND: the initial routing logits [B, max_seq_len, max_k] of the NEXT training step.  The reference draws them from
+    # TensorFlow's generator and the product from the device's (parity in distribution only, layers/capsule_layer.py), so
+    # the caller sets what the product drew; forward() consumes them
+    self.routing_logits = None
 
   def resume(self, global_step, slots):
     """Continue from a training state taken elsewhere: `global_step` finished steps (LR schedule position, Adam's beta
@@ -457,7 +485,7 @@ class OracleTrainer(object):
       elif fc.feature_type == fc.RawFeature:
         if dim == 0:
           v = torch.as_tensor(raws[n], dtype=self.dtype)
-          outs.append((v.reshape(self.B, -1), False))
+          outs.append((v.reshape(len(raws[n]), -1), False))
           continue
         table = V.get(self._column_var_name(scope, fc, wide))
         if fc.raw_input_dim > 1:
@@ -466,7 +494,7 @@ class OracleTrainer(object):
           e = self._lookup_ragged(table, ids, np.arange(self.B + 1) * k, raws[n].reshape(-1),
                                   'sum' if wide else fc.combiner)
         else:
-          e = self._lookup_dense(table, np.zeros(self.B, dtype=np.int64), raws[n])
+          e = self._lookup_dense(table, np.zeros(len(raws[n]), dtype=np.int64), raws[n])
         outs.append((e, True))
       elif fc.feature_type == fc.IdFeature or (fc.feature_type == fc.ComboFeature and (n in ints or n in hashed)):
         # (crossed ComboFeature: CrossedColumn under an EmbeddingColumn, the id comes from the input stage)
@@ -855,6 +883,86 @@ class OracleTrainer(object):
     out = self.dense(V, x.reshape(B, -1), mc.num_class, 'output', 0.0)
     return {'logits': out.squeeze(1)}
 
+  # ------------------------------------------------------------------ two-tower models (MatchModel)
+  def _match_inputs(self, batch, head):
+    """What the head of model/match_model.py:161-279 reads beside the tower outputs -> (the label, the item ids of
+    `item_id` - B + N of them under the sampler - or None, the sample weights where the batch carries them or None)"""
+    if len(self.cfg.model_config.kd) > 0:
+      raise NotImplementedError('oracle: model_config.kd (knowledge distillation) on a two-tower model is not restated')
+    label = torch.as_tensor(np.asarray(batch['labels'])[0], dtype=self.dtype)
+    item_id = getattr(head, 'item_id', '')  # (model_params has no such field: match_model.py:35-48)
+    ids = torch.as_tensor(self._categorical_ids(batch, None, item_id), dtype=torch.int64) if item_id else None
+    weight = torch.as_tensor(batch['sample_weight'], dtype=self.dtype) if 'sample_weight' in batch else None
+    return label, ids, weight
+
+  def _dssm(self, V, batch):
+    """model/dssm.py:41-106: the `user` and `item` groups (both input-layer calls first) through their towers - a DNN
+    whose last layer is a plain dense (:42-62) - then the head (oracle/match_ref.py) -> (task losses, predictions)"""
+    mc = self.cfg.model_config
+    l2 = self._l2_of(mc)
+    user, _ = self.input_layer(V, batch, 'user', 'input_layer')
+    item, _ = self.input_layer(V, batch, 'item', 'input_layer_1')
+    u = self.dnn(V, user, mc.dssm.user_tower.dnn, 'user_dnn', l2, last_no_act=True, last_no_bn=True)
+    i = self.dnn(V, item, mc.dssm.item_tower.dnn, 'item_dnn', l2, last_no_act=True, last_no_bn=True)
+    return match_ref.head_losses(mc.dssm, mc.loss_type, u, i, _ByName(V), *self._match_inputs(batch, mc.dssm),
+                                 ignore_in_batch=mc.dssm.ignore_in_batch_neg_sam)
+
+  def _match_model_backbone(self, V, batch):
+    """model/match_model.py:145-205 (model_class MatchModel): two of the backbone's output_blocks are the towers;
+    model_params has neither item_id nor ignore_in_batch_neg_sam."""
+    mc = self.cfg.model_config
+    mp = mc.model_params
+    out = self._backbone(V, batch)
+    return match_ref.head_losses(mp, mc.loss_type, out[mp.user_tower_idx_in_output], out[mp.item_tower_idx_in_output],
+                                 _ByName(V), *self._match_inputs(batch, mp))
+
+  def _mind(self, V, batch):
+    """model/mind.py:50-258: the `hist` group's sequences one by one (then `user`, then `item`: the constructor's
+    input-layer calls), combined (oracle/mind_ref.py combine_hist, pre_capsule_dnn inside), and mind_forward over this
+    oracle's DNN and BatchNorm: the capsule layer on self.routing_logits, user_fea_bn -> user_dnn, concat_dnn and
+    item_dnn with a plain last layer, the label-aware attention, MatchModel's head, reg_interest_simi."""
+    mc = self.cfg.model_config
+    m = mc.mind
+    l2 = self._l2_of(mc)
+    seqs, lens, plain = self._seq_features(V, batch, 'hist')
+    scopes = iter(['input_layer', 'input_layer_1', 'input_layer_2'])
+    if plain:  # (is_combine=False evaluates the group's plain columns too; MIND does not read them)
+      self.input_layer(V, batch, 'hist', next(scopes), only=plain)
+    user, _ = self.input_layer(V, batch, 'user', next(scopes))
+    item, _ = self.input_layer(V, batch, 'item', next(scopes))
+    if self.routing_logits is None:
+      raise NotImplementedError('oracle: a MIND training step needs the initial routing logits the product drew '
+                                '(OracleTrainer.routing_logits): they come from the device generator, in distribution only')
+    logits0, self.routing_logits = torch.as_tensor(self.routing_logits, dtype=self.dtype), None
+
+    def dnn(x, var, name, last_plain=False, training=True):
+      return self.dnn(V, x, getattr(m, name), name, l2, last_no_act=last_plain, last_no_bn=last_plain)
+    pre = None
+    if len(m.pre_capsule_dnn.hidden_units) > 0:
+      pre = lambda h: dnn(h.reshape(-1, h.shape[2]), None, 'pre_capsule_dnn').reshape(h.shape[0], h.shape[1], -1)
+    lens = torch.as_tensor(lens, dtype=torch.int64)
+    hist = mind_ref.combine_hist(m, seqs, lens, pre)
+    return mind_ref.mind_forward(m, mc.loss_type, hist, lens, user, item, _ByName(V), logits0, *self._match_inputs(batch, m),
+                                 dnn=dnn, batch_norm=lambda x, var, name, training=True: self.batch_norm(V, x, name))
+
+  def _sampled_negatives(self, batch):
+    """data_config.negative_sampler_in_memory (oracle/neg_sampler_ref.py): at step s the draw of N table rows that hold
+    none of the batch's item ids; every attribute feature's column - ids and raw values alike - becomes the batch's B
+    values followed by the drawn rows'.  The groups of those features then have B + N rows."""
+    ns = self.cfg.data_config.negative_sampler_in_memory
+    if self.item_table is None or self.sampler_seed is None:
+      raise NotImplementedError('oracle: data_config.negative_sampler_in_memory needs the item table and the seed of the '
+                                'draw (OracleTrainer(item_table=, sampler_seed=))')
+    hashed, raws, ints = self._cache
+    feats = {field: [n for n, f in self.fc_by_name.items() if list(f.input_names) == [field]]
+             for field in list(ns.attr_fields) + [ns.item_id_field]}
+    batch_ids = self._categorical_ids(batch, None, feats[ns.item_id_field][0])
+    sel = neg_sampler_ref.draw(self.sampler_seed, self.global_step, self.item_table.ids, batch_ids, ns.num_sample)
+    for name in [n for field in ns.attr_fields for n in feats[field]]:
+      for cols, kind in ((hashed, 'ids'), (ints, 'ids'), (raws, 'raw')):
+        if name in cols:
+          cols[name] = neg_sampler_ref.extended(cols[name], self.item_table.columns[name][kind], sel)
+
   def _mmoe_layer(self, V, x, expert_cfgs, num_task, l2, name='mmoe', training=False):
     """layers/mmoe.py:62-83: expert DNNs stacked on axis 1, per task a softmax gate over the experts, the mixture.
     The model classes build the layer without is_training (model/mmoe.py:37-47, model/dbmtl.py:66-70; the layer's
@@ -1015,23 +1123,30 @@ class OracleTrainer(object):
     """input_layer { output_seq_and_normal_feature } (layers/common_layers.py:119-131, layers/input_layer.py:164-200):
     sequence columns under `input_layer/<column>` (time axis kept, batch-max padded), then the plain columns through a
     regular input-layer call; embedding L2 on both."""
+    seqs, seq_len, plain_names = self._seq_features(V, batch, group_name)
+    target = None
+    if plain_names:
+      target, _ = self.input_layer(V, batch, group_name, scope, only=plain_names)
+    return torch.cat(list(seqs.values()), dim=-1), seq_len, target
+
+  def _seq_features(self, V, batch, group_name):
+    """The sequence columns of a group kept over time, one by one (layers/input_layer.py:164-200, :268-278): tables
+    `input_layer/<column>/embedding_weights`, batch-max padded, embedding L2 on each.
+    -> ({name: [B, L, dim]} in group order, the first one's lengths, the names of the group's plain columns)"""
     g = [x for x in self.cfg.model_config.feature_groups if x.group_name == group_name][0]
     lam = self.cfg.model_config.embedding_regularization
-    seqs, seq_len, plain_names = [], None, []
+    seqs, seq_len, plain_names = OrderedDict(), None, []
     for n in g.feature_names:
       fc = self.fc_by_name[n]
       if fc.feature_type == fc.SequenceFeature:
         e, lens = self._seq_lookup(V, 'input_layer/%s/embedding_weights' % n, batch, n)
         if lam > 0:
           self._reg = self._reg + lam * 0.5 * (e * e).sum()
-        seqs.append(e)
+        seqs[n] = e
         seq_len = lens if seq_len is None else seq_len
       else:
         plain_names.append(n)
-    target = None
-    if plain_names:
-      target, _ = self.input_layer(V, batch, group_name, scope, only=plain_names)
-    return torch.cat(seqs, dim=-1), seq_len, target
+    return seqs, seq_len, plain_names
 
   def _keras_cin(self, V, x0, hidden_sizes, name):
     """keras CIN (layers/keras/interaction.py:370-409): per layer the outer product of x_k and x_0 along the field
@@ -1294,6 +1409,8 @@ class OracleTrainer(object):
     if not concat:  # no concat_blocks / output_blocks: every leaf block, in config order (backbone.py:187-196)
       used = {getattr(node, node.WhichOneof('name')) for blk in bb.blocks for node in blk.inputs}
       concat = [blk.name for blk in bb.blocks if blk.name not in used]
+    if len(bb.output_blocks) > 0:  # (backbone.py:327-334: the named blocks' outputs as a list, nothing merged)
+      return [outs[n] for n in bb.output_blocks]
     # merge_inputs (backbone.py:532-550): one output is handed on as it is (a list stays a list)
     out = torch.cat([outs[n] for n in concat], dim=-1) if len(concat) > 1 else outs[concat[0]]
     if bb.HasField('top_mlp'):
@@ -1320,6 +1437,8 @@ class OracleTrainer(object):
     self._moving = {}
     self._touched = {}
     self._cache = (self._hashed_ids(batch), self._raw_values(batch), self._int_ids(batch))
+    if self.cfg.data_config.WhichOneof('sampler') == 'negative_sampler_in_memory':
+      self._sampled_negatives(batch)
     labels_np = np.asarray(batch['labels'], dtype=np.float32)
     def ce_of(z, y):
       # tf.nn.sigmoid_cross_entropy_with_logits as TensorFlow writes it - relu and -|z| through `where(z >= 0, ...)` - so
@@ -1393,6 +1512,11 @@ class OracleTrainer(object):
           key = (entry.loss_name + ('' if plain else suffix)) if entry.loss_name else name + suffix
           losses[key] = li = li * first
           ce = ce + li
+    elif self.model_class in ('DSSM', 'MatchModel', 'MIND'):
+      fn = {'DSSM': self._dssm, 'MatchModel': self._match_model_backbone, 'MIND': self._mind}[self.model_class]
+      task, pred = fn(V, batch)
+      losses.update(task)
+      ce = sum(task.values())
     else:
       if self.model_class == 'DeepFM':
         pred = self._deepfm(V, batch)

@@ -1,6 +1,8 @@
-"""Test infrastructure shared by the -m gpu model tests (tests/test_models_gpu.py, test_bst_gpu.py, test_autoint_gpu.py,
-test_fibinet_gpu.py): a model's first training steps against the CPU oracle, the two-runs-and-a-hipGraph-replay bit
-identity check of a kernel sequence, and the max-error-over-max-value comparison."""
+"""Test infrastructure shared by the model tests (-m gpu: tests/test_models_gpu.py, test_bst_gpu.py,
+test_autoint_gpu.py, test_fibinet_gpu.py, test_match_gpu.py, test_mind_gpu.py, test_neg_sampler_gpu.py; on the CPU
+stand-in: test_match_pins.py, test_mind_pins.py, test_neg_sampler_pins.py): a model's first training steps against the
+CPU oracle, the two-runs-and-a-hipGraph-replay bit identity check of a kernel sequence, and the
+max-error-over-max-value comparison."""
 import numpy as np
 import torch
 
@@ -22,28 +24,38 @@ def close(got, want, tol, what, scale=None):
 
 
 def first_steps(cfg, B, seed, steps=2, step0_tol=1e-5, device='cuda:0', grad_views=True, skip_bn_shadowed_bias=True,
-                coverage=None):
+                coverage=None, oracle_dtype=torch.float32, est_kw=None, oracle_kw=None, after_step=None):
   """`steps` training steps of the product and of the oracle from the same state on the same synthetic batches: every
   loss within step0_tol (first step) / 1e-4 (later steps) relative; after the first step the logits (1e-4) and the
   gradient of every variable, read back as Adam's first moment, within 2e-4 of the tensor's gradient scale.
   grad_views: autograd accumulated in place into the flat gradient buffer; skip_bn_shadowed_bias: a dense bias under
   BatchNorm has a zero gradient (rounding noise) and is not compared; coverage(names, cfg): the caller's own assertions
-  on the list of compared variables."""
-  est = EasyRecEstimator(cfg, device=device, batch_size=B, seed=seed).build()
-  orc = OracleTrainer(cfg, est.state_dict(), batch_size=B)
+  on the list of compared variables.  oracle_dtype: the oracle's forward and backward pass; est_kw / oracle_kw: further
+  constructor arguments (an item table, the sampler's seed); after_step(est, orc, step, batch): called between the
+  product's step and the oracle's (MIND: hands the routing logits the product drew to the oracle).  A list-wise
+  two-tower model never builds its logits while training: the two tower embeddings they are the product of are
+  compared instead."""
+  est = EasyRecEstimator(cfg, device=device, batch_size=B, seed=seed, **(est_kw or {})).build()
+  orc = OracleTrainer(cfg, est.state_dict(), batch_size=B, dtype=oracle_dtype, **(oracle_kw or {}))
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 100)
   for step in range(steps):
     b = gen.next_batch()
     est.train_step(b)
+    if after_step is not None:
+      after_step(est, orc, step, b)
     got, exp = est.loss_values(), orc.train_step(b)
+    assert sorted(got) == sorted(exp)
     for k in exp:
       assert abs(got[k] - exp[k]) <= (step0_tol if step == 0 else 1e-4) * max(1e-3, abs(exp[k])), (step, k, got[k], exp[k])
     if step > 0:
       continue
-    for k, ref in orc.last_pred.items():
-      if k.startswith('logits'):
-        got_l = est.model._prediction_dict[k].detach().cpu().numpy()
-        assert np.allclose(got_l, ref, rtol=1e-4, atol=1e-5), k
+    got_pred = est.model._prediction_dict
+    keys = [k for k in orc.last_pred if k.startswith('logits')]
+    if keys == ['logits'] and 'logits' not in got_pred:  # (a list-wise two-tower model while training)
+      keys = ['user_tower_emb', 'item_tower_emb']
+    for k in keys:
+      got_l, ref = got_pred[k].detach().cpu().numpy(), orc.last_pred[k]
+      assert np.allclose(got_l, ref, rtol=1e-4, atol=1e-5), k
     if grad_views:
       est.varstore.check_grad_views()
     st = est.state_dict(slots=True)
@@ -64,6 +76,16 @@ def first_steps(cfg, B, seed, steps=2, step0_tol=1e-5, device='cuda:0', grad_vie
     if coverage is not None:
       coverage(compared, cfg)
   return est
+
+
+def covers(names, cfg, dense, groups=('user', 'item')):
+  """a coverage callback's body: the compared variables hold `dense` and an embedding table of each of `groups` (a plain
+  column's `<scope>/<feature>_embedding`, a sequence kept over time's `input_layer/<feature>`)"""
+  assert set(dense) <= set(names), set(dense) - set(names)
+  for g in cfg.model_config.feature_groups:
+    if g.group_name in groups:
+      assert any(n.endswith('/%s_embedding/embedding_weights' % f) or n == 'input_layer/%s/embedding_weights' % f
+                 for n in names for f in g.feature_names), g.group_name
 
 
 def assert_runs_and_replay_bit_identical(run):

@@ -1,5 +1,5 @@
 """The two-tower head on the GPU: the fused kernels (csrc/er_match.hip) against fp64 autograd of the restatement
-(tests/_match_ref.py) on shapes that cross the tiles' edges in rows (32), columns (64) and depth (32 / 64 / 128), every
+(oracle/match_ref.py) on shapes that cross the tiles' edges in rows (32), columns (64) and depth (32 / 64 / 128), every
 mask and weight option, the rank counts against a sort, bit identity of runs and graph replays, and both DSSM configs'
 first steps.  Tolerances: tests/_oracle_steps.close, 1e-5 forward and 1e-4 gradients."""
 import os
@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-import _match_ref as ref
-from _oracle_steps import assert_runs_and_replay_bit_identical, close
+from oracle import match_ref as ref
+from _oracle_steps import assert_runs_and_replay_bit_identical, close, first_steps
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -236,58 +236,14 @@ def _configs():
 
 @pytest.mark.parametrize('in_batch', [False, True])
 def test_model_first_steps(built_lib, in_batch):
-  """Two steps of a DSSM config at small table sizes, B = 67, against the fp64 restatement run from the product's own
-  tower inputs (the input layer has its tests; the model oracle does not know DSSM): every task loss within 1e-5
-  (first step) / 1e-4 (second); after the first step every dense variable's gradient, read back as Adam's first moment,
-  within 2e-4 of its scale."""
-  from easyrec_amd.input.synthetic import SyntheticBatches
-  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
-  B = 67
-  cfg = _configs().dssm_taobao(in_batch=in_batch, batch_size=B, scale=0.01)
-  est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=5).build()
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
-  seen = {}
-  group = est.model._group
-
-  def recording(name):
-    out = group(name)
-    seen[name] = out[0].detach().double().cpu()
-    return out
-  est.model._group = recording
-  for step in range(2):
-    state = est.state_dict()
-    est.train_step(gen.next_batch())
-    got = est.loss_values()
-    dense = [n for n in est.varstore.trainable_names()]
-    var = {n: torch.from_numpy(np.asarray(state[n], dtype=np.float64)).requires_grad_(True) for n in dense}
-    label = est.features.label('clk').double().cpu()
-    ids = est.features.ids_of('adgroup_id').cpu()
-    want = ref.dssm_losses(cfg.model_config, seen, var, label, ids)
-    assert set(want) <= set(got)
-    for k, v in want.items():
-      v = float(v.detach())
-      assert abs(got[k] - v) <= (1e-5 if step == 0 else 1e-4) * max(1e-3, abs(v)), (step, k, got[k], v)
-    if step > 0:
-      continue
-    grads = dict(zip(dense, torch.autograd.grad(sum(want.values()), [var[n] for n in dense], allow_unused=True)))
-    st = est.state_dict(slots=True)
-    exp = {}
-    for n in dense:
-      g = grads[n] if grads[n] is not None else torch.zeros_like(var[n])
-      exp[n] = (0.1 * (g + est.varstore.l2_of(n) * var[n].detach())).numpy()  # Adam's m after one step, beta1 0.9
-    gmax = max(float(np.abs(v).max()) for v in exp.values())
-    compared = []
-    for n in dense:
-      if n.endswith('/bias') and (n[:-len('/bias')] + '/bn/gamma') in var:
-        continue  # d(loss)/d(bias) == 0 under BatchNorm: rounding noise
-      d, scale = float(np.abs(st[n + '/m'] - exp[n]).max()), float(np.abs(exp[n]).max())
-      assert d <= 2e-4 * scale + 2e-6 * gmax, (n, d, scale)
-      compared.append(n)
-    assert {'sim_w', 'sim_b', 'user_dnn/dnn_3/kernel', 'item_dnn/dnn_0/kernel', 'user_dnn/dnn_1/bn/gamma'} <= set(compared)
+  """Two steps of a DSSM config at small table sizes, B = 67, against the fp64 model oracle from the batch on
+  (tests/_oracle_steps.first_steps: every loss, the tower embeddings or logits, every variable's first moment)."""
+  first_steps(_configs().dssm_taobao(in_batch=in_batch, batch_size=67, scale=0.01), 67, seed=5, oracle_dtype=torch.float64,
+              coverage=pins.dssm_coverage)
 
 
 # ---------------------------------------------------------------------------------------- the reference's own outputs
-import test_match_pins as pins  # noqa: E402  (the fixture readers and the step loop shared with the CPU tests)
+import test_match_pins as pins  # noqa: E402  (the fixture readers, configs and coverage sets shared with the CPU tests)
 
 LIST_WISE_GOLD = [t for t in pins.GOLD_CASES if pins.gold_case(t)[0]['loss'] == 'SOFTMAX_CROSS_ENTROPY']
 
@@ -320,7 +276,6 @@ def test_fixture_cases_through_the_kernels(built_lib, tag):
 
 @pytest.mark.parametrize('kind', ['backbone', 'l2'])
 def test_backbone_and_l2_first_steps(built_lib, kind):
-  """MatchModel over a backbone (fused list-wise head, temperature 0.01) and the point-wise L2 head on the device:
-  the task losses against the restatement from the tower outputs on, first_steps' bars."""
-  cfg = pins.backbone_cfg(67) if kind == 'backbone' else pins.l2_cfg(67)
-  pins._step_against_the_restatement(cfg, 67, pins.record_finish, device=DEV, seed=5)
+  """MatchModel over a backbone (fused list-wise head, temperature 0.01) and the point-wise L2 head on the device."""
+  cfg, coverage = (pins.backbone_cfg(67), pins.backbone_coverage) if kind == 'backbone' else (pins.l2_cfg(67), pins.dssm_coverage)
+  first_steps(cfg, 67, seed=5, oracle_dtype=torch.float64, coverage=coverage)

@@ -9,8 +9,9 @@ import numpy as np
 import pytest
 import torch
 
-import _match_ref as ref
+from _oracle_steps import covers, first_steps
 from easyrec_amd.layers import match_head
+from oracle import match_ref as ref
 from easyrec_amd.utils import load_class
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,36 +106,31 @@ def test_lds_formula_is_the_library_s(built_lib):
   assert match_head.lds_bytes(0) == 0 == match_head.lds_bytes(129)
 
 
+def dssm_coverage(names, cfg):
+  covers(names, cfg, {'sim_w', 'sim_b', 'user_dnn/dnn_3/kernel', 'item_dnn/dnn_0/kernel', 'user_dnn/dnn_1/bn/gamma'})
+
+
+def backbone_coverage(names, cfg):
+  covers(names, cfg, {'user_tower/layer_1/dense/kernel', 'item_tower/layer_0/dense/kernel', 'user_tower/layer_0/bn/gamma'})
+
+
 @pytest.mark.parametrize('in_batch', [False, True])
 def test_model_builds_and_steps_on_the_stand_in(ref_backend, built_lib, in_batch):
-  """Two steps; every task loss equals the fp64 restatement run from the product's own tower inputs."""
+  """Two steps against the fp64 model oracle from the batch on (tests/_oracle_steps.first_steps)."""
   from easyrec_amd.input.synthetic import SyntheticBatches
-  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
   B = 16
   cfg = dssm_cfg(in_batch, B)
-  est = EasyRecEstimator(cfg, device='cpu', batch_size=B, seed=4).build()
+
+  def initial_values(est, orc, step, batch):
+    if step == 0:  # (the oracle still holds the state the estimator was built with)
+      assert float(orc.state['sim_w'][0]) == 1.0 and float(orc.state['sim_b'][0]) == 0.0
+  est = first_steps(cfg, B, seed=4, device='cpu', oracle_dtype=torch.float64, coverage=dssm_coverage, after_step=initial_values)
   st = est.state_dict()
   for tower in ('user_dnn', 'item_dnn'):
     assert st[tower + '/dnn_3/kernel'].shape == (64, 32) and tower + '/dnn_3/bn/gamma' not in st
     assert tower + '/dnn_2/bn/gamma' in st and est.varstore.l2_of(tower + '/dnn_3/kernel') == pytest.approx(1e-6)
-  assert float(st['sim_w'][0]) == 1.0 and float(st['sim_b'][0]) == 0.0 and est.varstore.l2_of('sim_w') == 0.0
+  assert est.varstore.l2_of('sim_w') == 0.0
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=44)
-  seen, group = {}, est.model._group
-
-  def recording(name):
-    out = group(name)
-    seen[name] = out[0].detach().double()
-    return out
-  est.model._group = recording
-  for step in range(2):
-    state = est.state_dict()
-    est.train_step(gen.next_batch())
-    got = est.loss_values()
-    var = {n: torch.from_numpy(np.asarray(state[n], dtype=np.float64)) for n in est.varstore.trainable_names()}
-    want = ref.dssm_losses(cfg.model_config, seen, var, est.features.label('clk').double(), est.features.ids_of('adgroup_id'))
-    assert set(got) == set(want) | {'regularization_loss', 'total_loss'}
-    for k, v in want.items():
-      assert abs(got[k] - float(v)) <= (1e-5 if step == 0 else 1e-4) * max(1e-3, abs(float(v))), (step, k, got[k], float(v))
   # evaluation: the list-wise metrics from the rank counts, the point-wise auc
   est.model._is_training = est.ctx.is_training = False
   pred = est.predict(gen.next_batch())
@@ -279,40 +275,6 @@ def test_product_host_path_matches_the_reference(tag):
     assert np.array_equal(c_in.numpy(), want_in) and np.array_equal(c_neg.numpy(), want_neg)
 
 
-def _step_against_the_restatement(cfg, B, towers_of, device='cpu', seed=4):
-  """Two steps of `cfg`; the task losses against ref.head_losses run from the tower outputs towers_of(model) recorded,
-  1e-5 on the first step and 1e-4 on the second.  -> the estimator"""
-  from easyrec_amd.input.synthetic import SyntheticBatches
-  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
-  est = EasyRecEstimator(cfg, device=device, batch_size=B, seed=seed).build()
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 40)
-  mc = cfg.model_config
-  head = mc.dssm if mc.WhichOneof('model') == 'dssm' else mc.model_params
-  for step in range(2):
-    state = est.state_dict()
-    seen = towers_of(est.model)
-    est.train_step(gen.next_batch())
-    got = est.loss_values()
-    var = {n: torch.from_numpy(np.asarray(state[n], dtype=np.float64)) for n in ('sim_w', 'sim_b') if n in state}
-    want, _ = ref.head_losses(head, mc.loss_type, seen['user'], seen['item'], var,
-                              est.features.label('clk').double().cpu(), None, None, False)
-    assert set(got) == set(want) | {'regularization_loss', 'total_loss'}
-    for k, v in want.items():
-      assert abs(got[k] - float(v)) <= (1e-5 if step == 0 else 1e-4) * max(1e-3, abs(float(v))), (step, k, got[k], float(v))
-  return est
-
-
-def record_finish(model):
-  """the raw tower outputs as the model hands them to MatchModel._finish_predict_graph"""
-  seen, finish = {}, model._finish_predict_graph
-
-  def recording(user, item, *args):
-    seen['user'], seen['item'] = user.detach().double().cpu(), item.detach().double().cpu()
-    return finish(user, item, *args)
-  model._finish_predict_graph = recording
-  return seen
-
-
 def backbone_cfg(B=16):
   return _make_configs().dssm_backbone_taobao(batch_size=B, scale=0.01)
 
@@ -329,7 +291,7 @@ def l2_cfg(B=16):
 def test_backbone_form_builds_and_steps(ref_backend, built_lib):
   """MatchModel over a backbone (model_params): the reference's dssm_on_taobao_backbone model section, no sampler."""
   cfg = backbone_cfg()
-  est = _step_against_the_restatement(cfg, 16, record_finish)
+  est = first_steps(cfg, 16, seed=4, device='cpu', oracle_dtype=torch.float64, coverage=backbone_coverage)
   st = est.state_dict()
   assert 'user_tower/layer_1/dense/kernel' in st and 'sim_w' not in st and st['item_tower/layer_1/dense/kernel'].shape == (128, 32)
   est.model._is_training = est.ctx.is_training = False
@@ -341,7 +303,7 @@ def test_backbone_form_builds_and_steps(ref_backend, built_lib):
 
 def test_l2_loss_head_builds_and_steps(ref_backend, built_lib):
   cfg = l2_cfg()
-  est = _step_against_the_restatement(cfg, 16, record_finish)
+  est = first_steps(cfg, 16, seed=4, device='cpu', oracle_dtype=torch.float64, coverage=dssm_coverage)
   est.model._is_training = est.ctx.is_training = False
   pred = est.predict()
   assert pred['y'].shape == (16,) and est.model.get_outputs()[0] == 'y'

@@ -1,5 +1,5 @@
 """MIND on the GPU: the capsule-routing and label-aware attention kernels (csrc/er_capsule.hip) against fp64 autograd of
-the restatement (tests/_mind_ref.py) over the envelope's edges, bit identity of runs and graph replays, the composed path
+the restatement (oracle/mind_ref.py) over the envelope's edges, bit identity of runs and graph replays, the composed path
 outside the envelope, and both MIND configs' first steps.  Tolerances: tests/_oracle_steps.close, 1e-5 forward and 1e-4
 gradients."""
 import os
@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-import _mind_ref as ref
-from _oracle_steps import assert_runs_and_replay_bit_identical, close
+from oracle import mind_ref as ref
+from _oracle_steps import assert_runs_and_replay_bit_identical, close, first_steps
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -253,70 +253,22 @@ def _configs():
 
 @pytest.mark.parametrize('list_wise', [False, True])
 def test_model_first_steps(built_lib, list_wise):
-  """Two steps of a MIND config at small table sizes, B = 67, against the fp64 restatement run from the product's own
-  group outputs and the routing logits each step drew: every task loss within 1e-5 (first step) / 1e-4 (second); after
-  the first step every dense variable's gradient, read back as Adam's first moment, within 2e-4 of its scale
-  (test_match_gpu.test_model_first_steps' bars).  Then the step as a hipGraph: each replay draws fresh routing noise."""
+  """Two steps of a MIND config at small table sizes, B = 67, against the fp64 model oracle from the batch on, run on
+  the routing logits each step drew (tests/_oracle_steps.first_steps: every loss, the tower embeddings or logits, every
+  variable's first moment).  Then the step as a hipGraph: each replay draws fresh routing noise."""
   from easyrec_amd.input.synthetic import SyntheticBatches
-  from easyrec_amd.layers import capsule_layer
-  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
   B = 67
   cfg = _configs().mind_taobao(list_wise=list_wise, batch_size=B, scale=0.01)
-  est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=5).build()
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
-  seen = {}
-  group, hist_sequence = est.model._group, est.model._hist_sequence
-
-  def recording(name):
-    out = group(name)
-    seen[name] = out[0].detach().double().cpu()
-    return out
-
-  def recording_hist():
-    hist, n = hist_sequence()
-    seen['hist'], seen['hist_len'] = hist.detach().double().cpu(), n.detach().cpu()
-    assert capsule_layer.capsule_fits(hist, 64, 64, 5, 3)
-    return hist, n
-  est.model._group, est.model._hist_sequence = recording, recording_hist
   noise = []
-  for step in range(2):
-    state = est.state_dict()
-    est.train_step(gen.next_batch())
-    got = est.loss_values()
-    noise.append(est.model._capsule_layer.last_routing_logits.detach().clone())
-    assert noise[-1].shape == (B, 64, 5) and float(noise[-1].abs().max()) <= 2.0
-    dense = [n for n in est.varstore.trainable_names()]
-    var = {n: torch.from_numpy(np.asarray(state[n], dtype=np.float64)).requires_grad_(True) for n in dense}
-    label = est.features.label('clk').double().cpu()
-    ids = est.features.ids_of('adgroup_id').cpu()
-    want, _ = ref.mind_forward(cfg.model_config.mind, cfg.model_config.loss_type, seen['hist'], seen['hist_len'],
-                               seen['user'], seen['item'], var, noise[-1].double().cpu(), label, ids)
-    assert set(want) <= set(got)
-    for k, v in want.items():
-      v = float(v.detach())
-      print('model list_wise=%s step %d %s: got %r want %r' % (list_wise, step, k, got[k], v))
-      assert abs(got[k] - v) <= (1e-5 if step == 0 else 1e-4) * max(1e-3, abs(v)), (step, k, got[k], v)
-    if step > 0:
-      continue
-    grads = dict(zip(dense, torch.autograd.grad(sum(want.values()), [var[n] for n in dense], allow_unused=True)))
-    st = est.state_dict(slots=True)
-    exp = {}
-    for n in dense:
-      g = grads[n] if grads[n] is not None else torch.zeros_like(var[n])
-      exp[n] = (0.1 * (g + est.varstore.l2_of(n) * var[n].detach())).numpy()  # Adam's m after one step, beta1 0.9
-    gmax = max(float(np.abs(v).max()) for v in exp.values())
-    compared = []
-    for n in dense:
-      if n.endswith('/bias') and (n[:-len('/bias')] + '/bn/gamma') in var:
-        continue  # d(loss)/d(bias) == 0 under BatchNorm: rounding noise
-      d, scale = float(np.abs(st[n + '/m'] - exp[n]).max()), float(np.abs(exp[n]).max())
-      print('model list_wise=%s gradient %s: error %.3g scale %.3g' % (list_wise, n, d, scale))
-      assert d <= 2e-4 * scale + 2e-6 * gmax, (n, d, scale)
-      compared.append(n)
-    assert {'capsule/S', 'concat_dnn/dnn_0/kernel', 'user_dnn/dnn_0/kernel', 'sim_w'} <= set(compared)
-  assert not torch.equal(noise[0], noise[1])
+  est = first_steps(cfg, B, seed=5, oracle_dtype=torch.float64, coverage=pins.mind_coverage,
+                    after_step=pins.hand_over_routing_logits(noise))
+  assert all(n.shape == (B, 64, 5) and float(np.abs(n).max()) <= 2.0 for n in noise)
+  assert not np.array_equal(noise[0], noise[1])
+  from easyrec_amd.layers import capsule_layer
+  width = est.state_dict()['capsule/S'].shape[0]  # (an operand of the model's: the steps above ran the kernels)
+  assert capsule_layer.capsule_fits(torch.empty(B, 64, width, device=DEV), 64, 64, 5, 3)
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
   # the captured step: a replay must draw fresh noise
-  est.model._group, est.model._hist_sequence = group, hist_sequence
   est.capture()
   replayed = []
   for _ in range(2):

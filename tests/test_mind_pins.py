@@ -1,4 +1,4 @@
-"""MIND on the CPU: the class resolves, the restatement (tests/_mind_ref.py) and the product's composed capsule layer,
+"""MIND on the CPU: the class resolves, the restatement (oracle/mind_ref.py) and the product's composed capsule layer,
 attention and interest similarity hold the reference's own outputs (tests/golden/mind_vectors.npz, written by
 tests/golden/make_mind_vectors.py) to 1e-6 of their scale in fp64, the evaluation routing table is the seeded numpy draw,
 the capsule count is int(log(float32(len))) for every length, both committed configs train on the stand-in backend with
@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 import torch
 
-import _mind_ref as ref
+from _oracle_steps import covers, first_steps
 from easyrec_amd.layers import capsule_layer
+from oracle import mind_ref as ref
 from easyrec_amd.utils import load_class
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -202,48 +203,37 @@ def test_committed_configs_are_the_generated_ones(name, list_wise):
   assert mc.loss_type == (LossType.SOFTMAX_CROSS_ENTROPY if list_wise else LossType.CLASSIFICATION)
 
 
+def mind_coverage(names, cfg):
+  covers(names, cfg, {'capsule/S', 'concat_dnn/dnn_0/kernel', 'user_dnn/dnn_0/kernel', 'item_dnn/dnn_0/kernel', 'sim_w'},
+         groups=('hist', 'user', 'item'))
+
+
+def hand_over_routing_logits(seen=None):
+  """first_steps' after_step for MIND: the oracle runs the step on the routing logits the product drew (kept in `seen`)"""
+  def after_step(est, orc, step, batch):
+    orc.routing_logits = est.model._capsule_layer.last_routing_logits.detach().cpu().numpy()
+    if seen is not None:
+      seen.append(orc.routing_logits.copy())
+  return after_step
+
+
 @pytest.mark.parametrize('list_wise', [False, True])
 def test_model_builds_and_steps_on_the_stand_in(ref_backend, built_lib, list_wise):
-  """Two steps; every task loss equals the fp64 restatement run from the product's own group outputs and the routing
-  logits the step drew."""
+  """Two steps against the fp64 model oracle from the batch on, run on the routing logits each step drew
+  (tests/_oracle_steps.first_steps)."""
   from easyrec_amd.input.synthetic import SyntheticBatches
-  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
   B = 16
   cfg = mind_cfg(list_wise, B)
-  est = EasyRecEstimator(cfg, device='cpu', batch_size=B, seed=4).build()
+  noise = []
+  est = first_steps(cfg, B, seed=4, device='cpu', oracle_dtype=torch.float64, coverage=mind_coverage,
+                    after_step=hand_over_routing_logits(noise))
   st = est.state_dict()
   assert st['capsule/S'].shape == (16, 64) and est.varstore.l2_of('capsule/S') == 0.0
   assert st['concat_dnn/dnn_0/kernel'].shape == (96, 64) and st['concat_dnn/dnn_1/kernel'].shape == (64, 32)
   assert 'concat_dnn/dnn_1/bn/gamma' not in st and 'item_dnn/dnn_3/bn/gamma' not in st and 'user_dnn/dnn_3/bn/gamma' in st
-  assert 'user_fea_bn/gamma' in st and float(st['sim_w'][0]) == 1.0
+  assert 'user_fea_bn/gamma' in st and 'sim_w' in st
+  assert noise[0].shape == (B, 64, 5) and not np.array_equal(noise[0], noise[1])
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=44)
-  seen = {}
-  group, hist_sequence = est.model._group, est.model._hist_sequence
-
-  def recording(name):
-    out = group(name)
-    seen[name] = out[0].detach().double()
-    return out
-
-  def recording_hist():
-    hist, n = hist_sequence()
-    seen['hist'], seen['hist_len'] = hist.detach().double(), n.detach()
-    return hist, n
-  est.model._group, est.model._hist_sequence = recording, recording_hist
-  noise = []
-  for step in range(2):
-    state = est.state_dict()
-    est.train_step(gen.next_batch())
-    got = est.loss_values()
-    noise.append(est.model._capsule_layer.last_routing_logits.clone())
-    var = {n: torch.from_numpy(np.asarray(state[n], dtype=np.float64)) for n in est.varstore.trainable_names()}
-    want, _ = ref.mind_forward(cfg.model_config.mind, cfg.model_config.loss_type, seen['hist'], seen['hist_len'],
-                               seen['user'], seen['item'], var, noise[-1].double(), est.features.label('clk').double(),
-                               est.features.ids_of('adgroup_id'))
-    assert set(got) == set(want) | {'regularization_loss', 'total_loss'}
-    for k, v in want.items():
-      assert abs(got[k] - float(v)) <= (1e-5 if step == 0 else 1e-4) * max(1e-3, abs(float(v))), (step, k, got[k], float(v))
-  assert noise[0].shape == (B, 64, 5) and not torch.equal(noise[0], noise[1])
   # evaluation: the shared table, the interest metrics beside MatchModel's
   est.model._is_training = est.ctx.is_training = False
   pred = est.predict(gen.next_batch())

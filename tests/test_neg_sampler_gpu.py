@@ -1,5 +1,5 @@
 """negative_sampler_in_memory on the GPU: er_neg_sample (csrc/er_sampler.hip) against the numpy restatement
-(tests/_neg_sampler_ref.py) bit for bit - sel and every extended column - over table sizes at and above B + N, the
+(oracle/neg_sampler_ref.py) bit for bit - sel and every extended column - over table sizes at and above B + N, the
 largest envelope batch, repeated runs, a captured graph replayed over three steps, the composed path outside the
 envelope; DSSM's and MIND's first steps with sampled negatives against their fp64 restatements at the bars of
 tests/test_match_gpu.py and tests/test_mind_gpu.py; the recall metrics over B + N columns."""
@@ -7,10 +7,12 @@ import numpy as np
 import pytest
 import torch
 
-import _match_ref as mref
-import _mind_ref as mind_ref
-import _neg_sampler_ref as ref
+import test_match_pins
+import test_mind_pins
 import test_neg_sampler_pins as pins
+from _oracle_steps import first_steps
+from oracle import match_ref as mref
+from oracle import neg_sampler_ref as ref
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -137,43 +139,23 @@ def _estimator(model):
   return cfg, table, est, gen
 
 
-def _record_groups(est, seen):
-  group = est.model._group
+def _first_steps(model, coverage, after_step=None):
+  """first_steps of a config with the sampler (seed 5, the fp64 oracle drawing from the same table); after each of the
+  product's steps: the item group had B + N rows, the draw and - after the first - the trained rows are the restatement's"""
+  cfg = pins.negsam_cfg(B, N, ROWS, model=model)
+  table = pins.item_table_for(cfg, ROWS)
 
-  def recording(name):
-    out = group(name)
-    seen[name] = out[0].detach().double().cpu()
-    return out
-  est.model._group = recording
-
-
-def _check_losses(got, want, step, tag):
-  assert set(want) <= set(got)
-  for k, v in want.items():
-    v = float(v.detach())
-    print('%s step %d %s: got %r want %r' % (tag, step, k, got[k], v))
-    assert abs(got[k] - v) <= (1e-5 if step == 0 else 1e-4) * max(1e-3, abs(v)), (step, k, got[k], v)
-
-
-def _check_first_moments(est, var, want, dense, must, tag):
-  """Adam's first moments after one step against fp64 autograd: 2e-4 * scale + 2e-6 * gmax"""
-  grads = dict(zip(dense, torch.autograd.grad(sum(want.values()), [var[n] for n in dense], allow_unused=True)))
-  st = est.state_dict(slots=True)
-  exp = {}
-  for n in dense:
-    g = grads[n] if grads[n] is not None else torch.zeros_like(var[n])
-    exp[n] = (0.1 * (g + est.varstore.l2_of(n) * var[n].detach())).numpy()  # Adam's m after one step, beta1 0.9
-  gmax = max(float(np.abs(v).max()) for v in exp.values())
-  compared = []
-  for n in dense:
-    if n.endswith('/bias') and (n[:-len('/bias')] + '/bn/gamma') in var:
-      continue  # d(loss)/d(bias) == 0 under BatchNorm: rounding noise
-    d, scale = float(np.abs(st[n + '/m'] - exp[n]).max()), float(np.abs(exp[n]).max())
-    print('%s gradient %s: error %.3g scale %.3g' % (tag, n, d, scale))
-    assert d <= 2e-4 * scale + 2e-6 * gmax, (n, d, scale)
-    compared.append(n)
-  assert must <= set(compared)
-  return st
+  def check(est, orc, step, batch):
+    assert est.sampler.uses_kernel()
+    pd = est.model._prediction_dict
+    assert pd['item_tower_emb'].shape[0] == B + N and pd['user_tower_emb'].shape[0] == B
+    assert est.features.ids_of('adgroup_id').shape == (B + N,)
+    _check_the_draw_and_the_trained_rows(cfg, table, est, batch, step, est.state_dict(slots=True) if step == 0 else None)
+    if after_step is not None:
+      after_step(est, orc, step, batch)
+  est = first_steps(cfg, B, seed=5, oracle_dtype=torch.float64, coverage=coverage, est_kw=dict(item_table=table),
+                    oracle_kw=dict(item_table=table, sampler_seed=5), after_step=check)
+  return cfg, table, est
 
 
 def _check_the_draw_and_the_trained_rows(cfg, table, est, batch, step, st=None):
@@ -201,65 +183,18 @@ def _check_the_draw_and_the_trained_rows(cfg, table, est, batch, step, st=None):
 
 def test_dssm_first_steps_with_sampled_negatives(built_lib):
   """tests/test_match_gpu.py test_model_first_steps with the sampler: B = 67, N = 40, a 301-row table, two steps."""
-  cfg, table, est, gen = _estimator('dssm')
-  seen = {}
-  _record_groups(est, seen)
-  for step in range(2):
-    state = est.state_dict()
-    batch = gen.next_batch()
-    est.train_step(batch)
-    got = est.loss_values()
-    assert seen['item'].shape == (B + N, 7 * 16) and seen['user'].shape[0] == B
-    dense = [n for n in est.varstore.trainable_names()]
-    var = {n: torch.from_numpy(np.asarray(state[n], dtype=np.float64)).requires_grad_(True) for n in dense}
-    ids = est.features.ids_of('adgroup_id').cpu()
-    assert ids.shape == (B + N,)
-    want = mref.dssm_losses(cfg.model_config, seen, var, est.features.label('clk').double().cpu(), ids)
-    _check_losses(got, want, step, 'dssm')
-    st = None
-    if step == 0:
-      st = _check_first_moments(est, var, want, dense, {'sim_w', 'sim_b', 'user_dnn/dnn_3/kernel', 'item_dnn/dnn_0/kernel',
-                                                       'user_dnn/dnn_1/bn/gamma'}, 'dssm')
-    _check_the_draw_and_the_trained_rows(cfg, table, est, batch, step, st)
+  _first_steps('dssm', test_match_pins.dssm_coverage)
 
 
 def test_mind_first_steps_with_sampled_negatives(built_lib, monkeypatch):
   """tests/test_mind_gpu.py test_model_first_steps (list-wise) with the sampler, then the step as a hipGraph: each
   replay draws the next step's negatives."""
+  from easyrec_amd.input.synthetic import SyntheticBatches
   from easyrec_amd.layers import capsule_layer
   monkeypatch.setattr(capsule_layer, 'fused_capsule', True)
-  cfg, table, est, gen = _estimator('mind')
-  seen = {}
-  _record_groups(est, seen)
-  group, hist_sequence = est.model._group, est.model._hist_sequence
-
-  def recording_hist():
-    hist, n = hist_sequence()
-    seen['hist'], seen['hist_len'] = hist.detach().double().cpu(), n.detach().cpu()
-    return hist, n
-  est.model._hist_sequence = recording_hist
-  for step in range(2):
-    state = est.state_dict()
-    batch = gen.next_batch()
-    est.train_step(batch)
-    got = est.loss_values()
-    noise = est.model._capsule_layer.last_routing_logits.detach().clone()
-    assert seen['item'].shape[0] == B + N
-    dense = [n for n in est.varstore.trainable_names()]
-    var = {n: torch.from_numpy(np.asarray(state[n], dtype=np.float64)).requires_grad_(True) for n in dense}
-    ids = est.features.ids_of('adgroup_id').cpu()
-    want, _ = mind_ref.mind_forward(cfg.model_config.mind, cfg.model_config.loss_type, seen['hist'], seen['hist_len'],
-                                    seen['user'], seen['item'], var, noise.double().cpu(),
-                                    est.features.label('clk').double().cpu(), ids)
-    _check_losses(got, want, step, 'mind')
-    st = None
-    if step == 0:
-      st = _check_first_moments(est, var, want, dense, {'capsule/S', 'concat_dnn/dnn_0/kernel', 'user_dnn/dnn_0/kernel',
-                                                       'item_dnn/dnn_0/kernel', 'sim_w'}, 'mind')
-    _check_the_draw_and_the_trained_rows(cfg, table, est, batch, step, st)
+  cfg, table, est = _first_steps('mind', test_mind_pins.mind_coverage, test_mind_pins.hand_over_routing_logits())
   # the captured step (capture() warms up over three steps: 2, 3, 4; the replays are steps 5 and 6)
-  est.model._hist_sequence = hist_sequence
-  del est.model.__dict__['_group']
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
   est.capture()
   for step in (5, 6):
     batch = gen.next_batch()

@@ -1,5 +1,5 @@
 """negative_sampler_in_memory on the CPU: the restated permutation is a bijection, the product's composed draw
-(easyrec_amd/input/neg_sampler.py) equals the restatement (tests/_neg_sampler_ref.py, written from include/easyrec_hip.h
+(easyrec_amd/input/neg_sampler.py) equals the restatement (oracle/neg_sampler_ref.py, written from include/easyrec_hip.h
 K1b) bit for bit, its properties, its uniformity, the item table's loading and build-time refusals, and a DSSM config
 with the sampler training on the stand-in backend with the fp64 restatement's losses over B + N item rows."""
 import os
@@ -9,8 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-import _match_ref as mref
-import _neg_sampler_ref as ref
+import test_match_pins
+from _oracle_steps import first_steps
+from oracle import match_ref as mref
+from oracle import neg_sampler_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 1234
@@ -391,43 +393,30 @@ def test_committed_configs_are_the_generated_ones():
 
 
 def test_dssm_with_the_sampler_steps_on_the_stand_in(ref_backend, built_lib):
-  """tests/test_match_pins.py's step test with the sampler: two steps; every task loss equals the fp64 restatement run
-  from the recorded group outputs, the item group's being [B + N, W]; then predict() without and with negatives."""
+  """tests/test_match_pins.py's step test with the sampler: two steps against the fp64 model oracle drawing from the
+  same table (tests/_oracle_steps.first_steps), the item group's rows being B + N; then predict() without and with
+  negatives."""
   from easyrec_amd.input.synthetic import SyntheticBatches
-  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
   B, N, rows = 16, 8, 301
   cfg = negsam_cfg(B, N, rows)
   table = item_table_for(cfg, rows)
-  est = EasyRecEstimator(cfg, device='cpu', batch_size=B, seed=4, item_table=table).build()
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=44)
-  seen, group = {}, est.model._group
 
-  def recording(name):
-    out = group(name)
-    seen[name] = out[0].detach().double()
-    return out
-  est.model._group = recording
-  for step in range(2):
-    state = est.state_dict()
-    batch = gen.next_batch()
-    est.train_step(batch)
-    got = est.loss_values()
-    assert seen['user'].shape[0] == B and seen['item'].shape == (B + N, 7 * 16)
+  def check(est, orc, step, batch):
+    assert est.model._prediction_dict['item_tower_emb'].shape == (B + N, 32)
+    assert est.model._prediction_dict['user_tower_emb'].shape == (B, 32)
     ids = est.features.ids_of('adgroup_id')
     batch_ids = batch['hash_ids'][est.schema.hash_single['adgroup_id']['col']]
     sel = ref.draw(4, step, table.ids, batch_ids, N)
     assert np.array_equal(est.sampler.sel.numpy(), sel.astype(np.int32))
     assert np.array_equal(ids.numpy(), ref.extended(batch_ids, table.columns['adgroup_id']['ids'], sel))
     assert np.array_equal(est.features.ids_of('price').numpy()[B:], table.columns['price']['ids'][sel])
-    var = {n: torch.from_numpy(np.asarray(state[n], dtype=np.float64)) for n in est.varstore.trainable_names()}
-    want = mref.dssm_losses(cfg.model_config, seen, var, est.features.label('clk').double(), ids)
-    assert set(got) == set(want) | {'regularization_loss', 'total_loss'}
-    for k, v in want.items():
-      assert abs(got[k] - float(v)) <= (1e-5 if step == 0 else 1e-4) * max(1e-3, abs(float(v))), (step, k, got[k], float(v))
+  est = first_steps(cfg, B, seed=4, device='cpu', oracle_dtype=torch.float64, coverage=test_match_pins.dssm_coverage,
+                    est_kw=dict(item_table=table), oracle_kw=dict(item_table=table, sampler_seed=4), after_step=check)
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=44)
   # predict() does not sample; predict(sample_negatives=True) is the evaluation mode
   est.model._is_training = est.ctx.is_training = False
   pred = est.predict(gen.next_batch())
-  assert pred['item_tower_emb'].shape == (B, 32) and pred['logits'].shape == (B, B) and seen['item'].shape[0] == B
+  assert pred['item_tower_emb'].shape == (B, 32) and pred['logits'].shape == (B, B)
   assert est.features.ids_of('adgroup_id').shape == (B,)
   pred = est.predict(sample_negatives=True)
   assert pred['item_tower_emb'].shape == (B + N, 32) and pred['logits'].shape == (B, B + N)

@@ -33,7 +33,11 @@ def main():
           fc.num_buckets = 2000
         for dr in fc.ListFields():
           pass
-      est = EasyRecEstimator(cfg, device='cpu', batch_size=16, seed=1).build()
+      table = None
+      if cfg.data_config.WhichOneof('sampler') == 'negative_sampler_in_memory':
+        from easyrec_amd.input.neg_sampler import ItemTable
+        table = ItemTable.load(cfg.data_config, list(cfg.feature_configs) or list(cfg.feature_config.features))
+      est = EasyRecEstimator(cfg, device='cpu', batch_size=16, seed=1, item_table=table).build()
       gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=16, seed=2)
       batches = [gen.next_batch() for _ in range(2)]
       state = est.state_dict()
@@ -41,10 +45,13 @@ def main():
       no_product += 1
       continue
     try:
-      orc = OracleTrainer(cfg, state, batch_size=16)
+      orc = OracleTrainer(cfg, state, batch_size=16, item_table=table, sampler_seed=1)
       worst = 0.0
       for b in batches:
         est.train_step(b)
+        capsule = getattr(est.model, '_capsule_layer', None)
+        if capsule is not None:  # MIND: the oracle runs the step on the routing logits the product drew
+          orc.routing_logits = capsule.last_routing_logits.detach().cpu().numpy()
         got, exp = est.loss_values(), orc.train_step(b)
         assert sorted(got) == sorted(exp), (sorted(got), sorted(exp))
         worst = max(worst, max(abs(got[k] - exp[k]) / max(1.0, abs(exp[k])) for k in exp))
