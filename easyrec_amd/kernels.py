@@ -2244,6 +2244,55 @@ class HipBackend(object):
         _p(table_ids), n, _p(batch_ids), B, int(N), _p(step), int(step_offset), int(seed) & 0xFFFFFFFFFFFFFFFF, ptrs(*tabs),
         ptrs(*bats), ptrs(*outs), (ctypes.c_int32 * max(nc, 1))(*sizes), nc, _p(sel), _stream()), 'er_neg_sample')
 
+  # -- K9k full-corpus top-K search and hit count (core/knn.py, core/hit_rate.py)
+  def knn_lds_bytes(self, D, K):
+    return int(self.lib.er_knn_lds_bytes(int(D), int(K)))
+
+  def knn_workspace_bytes(self, nq, K, slices=0):
+    return int(self.lib.er_knn_workspace_bytes(int(nq), int(K), int(slices)))
+
+  def knn_norms(self, items):
+    """items [n, D] -> xx [n]: the fmaf chain over x_d^2 of every row."""
+    n, D = items.shape
+    xx = torch.empty(n, dtype=torch.float32, device=items.device)
+    self._ck(self.lib.er_knn_norms(_p(_f32c(items)), n, D, _p(xx), _stream()), 'er_knn_norms')
+    return xx
+
+  def knn_search(self, queries, items, xx, table_ids, K, metric, slices=0):
+    """The search of easyrec_hip.h K9k -> (ids int64 [nq, K], rows int32 [nq, K], dist fp32 [nq, K])."""
+    nq, D = queries.shape
+    n = items.shape[0]
+    assert items.shape == (n, D) and items.dtype == torch.float32 and items.is_contiguous()
+    assert table_ids.dtype == torch.int64 and table_ids.shape == (n,) and table_ids.is_contiguous()
+    assert metric == 1 or (xx is not None and xx.shape == (n,) and xx.dtype == torch.float32 and xx.is_contiguous())
+    nbytes = self.knn_workspace_bytes(nq, K, slices)
+    if nbytes <= 0:
+      raise RuntimeError('er_knn_search: nq %d, K %d, slices %d outside the envelope' % (nq, K, slices))
+    dev = queries.device
+    work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    ids = torch.empty(nq, K, dtype=torch.int64, device=dev)
+    rows = torch.empty(nq, K, dtype=torch.int32, device=dev)
+    dist = torch.empty(nq, K, dtype=torch.float32, device=dev)
+    self._ck(self.lib.er_knn_search(
+        _p(_f32c(queries)), _p(items), None if xx is None else _p(xx), _p(table_ids), nq, n, D, int(K), int(metric),
+        int(slices), _p(work), _p(ids), _p(rows), _p(dist), _stream()), 'er_knn_search')
+    if self.op_log is not None:
+      self.op_log.append(('er::knn_scan_kernel', 2.0 * nq * n * D))
+    return ids, rows, dist
+
+  def knn_hits(self, ids, user_emb_num, gt_offsets, gt_ids):
+    """ids int64 [U, I, K], user_emb_num int32 [U], gt_offsets int64 [U + 1], gt_ids int64 -> (hits, gt_count) int32 [U]"""
+    U, I, K = ids.shape
+    assert ids.dtype == torch.int64 and ids.is_contiguous()
+    assert user_emb_num.dtype == torch.int32 and user_emb_num.shape == (U,) and user_emb_num.is_contiguous()
+    assert gt_offsets.dtype == torch.int64 and gt_offsets.shape == (U + 1,) and gt_offsets.is_contiguous()
+    assert gt_ids.dtype == torch.int64 and gt_ids.is_contiguous()
+    hits = torch.empty(U, dtype=torch.int32, device=ids.device)
+    gt_count = torch.empty(U, dtype=torch.int32, device=ids.device)
+    self._ck(self.lib.er_knn_hits(_p(ids), _p(user_emb_num), _p(gt_offsets), _p(gt_ids), U, I, K, _p(hits),
+                                  _p(gt_count), _stream()), 'er_knn_hits')
+    return hits, gt_count
+
   # -- K8g MIND's capsule layer and label-aware attention (layers/capsule_layer.py, model/mind.py)
   CAPSULE_MAX_K = 8
   MIND_ATT_MAX_E = 128

@@ -481,6 +481,68 @@ class EasyRecEstimator(object):
       self.model._is_training, self.ctx.is_training = was
     return {name + suf: m.result() for (name, suf), (_, _, m) in acc.items()}
 
+  def _predict_eval(self, batches):
+    """predict over `batches` with is_training=False, as evaluate runs it -> (batch, prediction dict) pairs"""
+    assert self._built
+    if getattr(self.engine, 'kv_tables', None):
+      self.engine.check_overflow()
+    was = (self.model._is_training, self.ctx.is_training)
+    self.model._is_training, self.ctx.is_training = False, False
+    try:
+      for batch in batches:
+        yield batch, self.predict(batch)
+    finally:
+      self.model._is_training, self.ctx.is_training = was
+
+  def _require_retrieval(self, what):
+    from easyrec_amd.model.match_model import MatchModel
+    if not isinstance(self.model, MatchModel):
+      raise NotImplementedError('%s: %s is no retrieval model (DSSM, MIND)' % (what, type(self.model).__name__))
+
+  def item_embeddings(self, batches, id_field):
+    """The item corpus of a retrieval model: `batches` are host batches whose item side holds the corpus (the user side
+    is ignored) -> (raw ids int64 [n] of input `id_field`, item_tower_emb fp32 [n, D] on the device).  The model runs
+    with is_training=False; the batch's own B rows of item_tower_emb are taken (no sampled negatives)."""
+    from easyrec_amd.input.features import host_key_column
+    self._require_retrieval('item_embeddings')
+    ids, embs = [], []
+    for batch, pred in self._predict_eval(batches):
+      key = host_key_column(self.features.schema, batch, id_field)
+      ids.append(np.array([int(k) for k in key], dtype=np.int64))
+      embs.append(pred['item_tower_emb'][:self.batch_size].detach().to(torch.float32).clone())
+    if not ids:
+      raise ValueError('item_embeddings: no item batches')
+    return np.concatenate(ids), torch.cat(embs, dim=0)
+
+  def hit_rate(self, item_batches, user_batches, gt_items, top_k, knn_metric=1, id_field=None):
+    """The full-corpus hit rate of the reference's tools/hit_rate_ds.py: the items of `item_batches` are embedded and
+    indexed (core/knn.py) under the raw ids of input `id_field` (default: the model's `item_id`, else the negative
+    sampler's item_id_field), every user vector of `user_batches` - DSSM: user_tower_emb as one interest, MIND: user_interests with
+    user_emb_num valid ones - recalls its top_k items, and the ground-truth items found are counted
+    (core/hit_rate.py).  gt_items: per user batch a list of B lists of item ids.  ->
+    {'hitrate': hits / gt_count, 'hits': .., 'gt_count': ..}"""
+    from easyrec_amd.core import hit_rate as hit_rate_lib
+    from easyrec_amd.core import knn
+    self._require_retrieval('hit_rate')
+    if id_field is None:
+      from easyrec_amd.input.features import feature_name_of
+      by_name = {feature_name_of(fc): fc.input_names[0] for fc in self.feature_configs if len(fc.input_names) == 1}
+      id_field = by_name.get(self.model._item_id_name) or \
+          self.pipeline_config.data_config.negative_sampler_in_memory.item_id_field
+    if not id_field:
+      raise ValueError('hit_rate: the model config names no item_id and there is no negative sampler: pass id_field')
+    ids, emb = self.item_embeddings(item_batches, id_field)
+    acc = hit_rate_lib.HitRate(knn.ItemIndex(ids, emb, knn_metric, self.device), top_k)
+    user_batches = list(user_batches)
+    if len(user_batches) != len(gt_items):
+      raise ValueError('hit_rate: %d user batches for %d ground-truth batches' % (len(user_batches), len(gt_items)))
+    for (batch, pred), gt in zip(self._predict_eval(user_batches), gt_items):
+      if 'user_interests' in pred:
+        acc.update(pred['user_interests'].detach(), pred['user_emb_num'], gt)
+      else:
+        acc.update(pred['user_tower_emb'].detach(), None, gt)
+    return {'hitrate': acc.result(), 'hits': acc.total_hits, 'gt_count': acc.total_gt_count}
+
   def capture(self, warmup=3):
     """Capture the device part of the step into one hipGraph (replayed by train_step)."""
     assert self._built and self.graph is None

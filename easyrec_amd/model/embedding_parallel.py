@@ -297,6 +297,13 @@ class EmbeddingParallelEstimator(EasyRecEstimator):
       self.engine.check_overflow()
     return self.losses
 
+  def item_embeddings(self, batches, id_field):
+    raise NotImplementedError('item_embeddings / hit_rate: the full-corpus search runs on the single-GPU engine only (the '
+                              'embedding-parallel engine holds a shard of every table and of every batch per rank)')
+
+  def hit_rate(self, item_batches, user_batches, gt_items, top_k, knn_metric=1, id_field=None):
+    self.item_embeddings(item_batches, id_field)
+
   def evaluate(self, batches, eval_config=None):
     self.engine.check_overflow()
     return super(EmbeddingParallelEstimator, self).evaluate(batches, eval_config)

@@ -860,6 +860,64 @@ int er_neg_sample(const int64_t* table_ids, int64_t n, const int64_t* batch_ids,
                   int32_t ncols, int32_t* sel, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K9k Full-corpus hit rate: exact top-K item search and the hit count.  Replaces g.search (graphlearn's
+ *     KNN index, a faiss flat index) and batch_hitrate of utils/hit_rate_utils.py:37-94, :148-220 as
+ *     tools/hit_rate_ds.py drives them.  ("K9" alone is the MLP section below.)  fp32.
+ * Scores of query q [D] and table row r, x = items[r]:
+ *   s(q, r) = the fp32 chain acc = fmaf(q_d, x_d, acc) over d = 0 .. D - 1 in ascending d from acc = 0:
+ *     what v_mfma_f32_32x32x2_f32 fed two columns at a time and a VALU fmaf loop both produce, bit
+ *     for bit.  A -0 result counts and is reported as +0.
+ *   metric 1 (inner product): larger is better; the reported distance is s.
+ *   metric 0 (L2): dist = max(0, (qq + xx[r]) - 2 s), qq = the chain acc = fmaf(q_d, q_d, acc), xx[r] =
+ *     the chain acc = fmaf(x_d, x_d, acc) (er_knn_norms, once per index); smaller is better; the
+ *     reported distance is dist, the SQUARED distance: the faiss flat-index convention.  This project
+ *     states the convention; graphlearn's source is not part of the reference.
+ * Order: a strict total order on (score, row): the better score first, on equal scores the lower ROW
+ *   first.  The top K of a query are the first min(K, n) rows in that order, reported in that order:
+ *   out_ids [nq, K] = table_ids[row] (int64), out_rows [nq, K] = row (int32; may be null), out_dist
+ *   [nq, K].  Places past n hold id -1, row -1 and distance -inf (metric 1) / +inf (metric 0).  The
+ *   result depends on nothing else: not on the launch shape, the slice count or the thread order;
+ *   two runs, every `slices` and a graph replay give the same bits.  NaN scores are not ordered.
+ * er_knn_search: Q [nq, D], items [n, D], xx [n] (null with metric 1), table_ids [n].  Envelope: 1 <= D
+ *   <= 128, 1 <= K <= 128, 1 <= n < 2^31, 1 <= nq < 2^33, 0 <= slices <= 64.  Launch one, grid = ceil(nq / 32)
+ *   query tiles x S item slices (slice s = rows [s L, min(n, (s + 1) L)), L = ceil(n / S)); S = slices,
+ *   or with slices = 0: min(ceil(512 / ceil(nq / 32)), floor(n / 2048), 64), at least 1.  A workgroup
+ *   keeps its 32 queries in LDS, streams its slice in tiles of 128 rows through the fp32 MFMA and keeps
+ *   per query a candidate list in LDS behind the query's threshold (the score of its current K-th
+ *   best): a score strictly better than the threshold is appended (LDS atomic counter; rows arrive
+ *   in ascending order, so an equal score always loses its tie); a list that has grown past cap - 128
+ *   is cut to its best K by the total order and the threshold tightened.  It leaves [S, nq, K] sorted
+ *   partial lists in `workspace`; launch two merges them per query by the same order and gathers
+ *   table_ids.  No global atomics, no host synchronisation: the call can be captured.
+ * er_knn_query_tile() = 32, er_knn_item_tile() = 128: the two tile heights.
+ * er_knn_lds_bytes(D, K) = 4 * 160 * P + 768 + 256 * cap (0 outside the envelope): the 32 + 128 rows
+ *   of both tiles at the even pitch P = D rounded up to even, + 2 if P / 2 is even (8-byte staging
+ *   stores; the dword operand reads of the MFMAs, served in groups of 32 lanes over 32 banks at row
+ *   * P + const, reach 16 banks: a 2-way bank conflict), the tile's xx, the thresholds and counters,
+ *   and 32 lists of cap = min(128 + max(2 K, 64), (152 KiB - 4 * 160 * P - 768) / 256, 384) 8-byte
+ *   keys; at most 155,648 of the CU's 163,840 bytes (D = 128, K = 128: cap 280).
+ * er_knn_workspace_bytes(nq, K, slices) = 8 * S * nq * K, S = slices or with slices = 0 the most
+ *   er_knn_search picks for nq: min(ceil(512 / ceil(nq / 32)), 64); 0 outside the envelope.
+ * er_knn_hits: out_ids [U, I, K] (the search's ids of U users x I interests), user_emb_num [U], the
+ *   ground-truth lists gt_ids[gt_offsets[u] .. gt_offsets[u + 1]).  Interest h of user u counts iff
+ *   h < user_emb_num[u]; hits [U] = the number of DISTINCT values of u's list that occur in any
+ *   counted interest's K ids; gt_count [U] = the length of the list, duplicates included (an empty
+ *   list: 0 / 0).  One wave per user; no atomics.  A lane tests one list element: it rescans the
+ *   elements before it for a duplicate, then the counted ids: len^2 / 2 + len * I * K reads per user
+ *   in all, meant for lists of tens of ids (a sort-based form would suit thousands).
+ * -------------------------------------------------------------------------------------------- */
+int32_t er_knn_query_tile(void);  /* 32: queries of a workgroup */
+int32_t er_knn_item_tile(void);   /* 128: item rows of a tile */
+int64_t er_knn_lds_bytes(int32_t D, int32_t K);
+int64_t er_knn_workspace_bytes(int64_t nq, int32_t K, int32_t slices);
+int er_knn_norms(const float* items, int64_t n, int32_t D, float* xx, er_stream_t stream);
+int er_knn_search(const float* Q, const float* items, const float* xx, const int64_t* table_ids, int64_t nq, int64_t n,
+                  int32_t D, int32_t K, int32_t metric, int32_t slices, void* workspace, int64_t* out_ids,
+                  int32_t* out_rows, float* out_dist, er_stream_t stream);
+int er_knn_hits(const int64_t* out_ids, const int32_t* user_emb_num, const int64_t* gt_offsets, const int64_t* gt_ids,
+                int64_t U, int32_t I, int32_t K, int32_t* hits, int32_t* gt_count, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed
