@@ -9,131 +9,58 @@ library has not been built or no MI355X is visible - there is no CPU fallback in
 import ctypes
 import threading
 import os
-import re
 from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 import torch
 
-
-class KvJob(ctypes.Structure):
-  """er_kv_job (include/easyrec_hip.h)"""
-  _fields_ = [('ids', ctypes.c_void_p), ('n', ctypes.c_int64), ('map_keys', ctypes.c_void_p), ('map_rows', ctypes.c_void_p),
-              ('map_slots', ctypes.c_int64), ('next_row', ctypes.c_void_p), ('var', ctypes.c_void_p), ('seed', ctypes.c_uint64),
-              ('rows_out', ctypes.c_void_p), ('overflow', ctypes.c_void_p), ('capacity', ctypes.c_int32), ('dim', ctypes.c_int32),
-              ('init_mean', ctypes.c_float), ('init_stddev', ctypes.c_float), ('n_limit', ctypes.c_void_p),
-              ('freq', ctypes.c_void_p), ('version', ctypes.c_void_p), ('n_keys', ctypes.c_void_p), ('step', ctypes.c_void_p),
-              ('filter_freq', ctypes.c_int32), ('table_ld', ctypes.c_int32)]
-
-
-class KvRouteJob(ctypes.Structure):
-  """er_kv_route_job (include/easyrec_hip.h)"""
-  _fields_ = [('ids', ctypes.c_void_p), ('n', ctypes.c_int64), ('n_limit', ctypes.c_void_p), ('rows_out', ctypes.c_void_p),
-              ('slot', ctypes.c_void_p), ('send_off', ctypes.c_int64)]
-
-
-class CastDesc(ctypes.Structure):
-  """er_cast_desc (include/easyrec_hip.h)"""
-  _fields_ = [('src', ctypes.c_void_p), ('dst', ctypes.c_void_p), ('rows', ctypes.c_int64), ('cols', ctypes.c_int32),
-              ('ld_src', ctypes.c_int32), ('ld_dst', ctypes.c_int32), ('transpose', ctypes.c_int32)]
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# EASYREC_AMD_LIB: another build of the same ABI (same-box A/B of a kernel change, tools/gpu_ab.sh)
-LIB_PATH = os.environ.get('EASYREC_AMD_LIB') or os.path.join(_HERE, 'csrc', 'libeasyrec_hip.so')
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'easyrec_hip.h')
-
-# C scalar types of the header -> ctypes; every pointer (and er_stream_t) is c_void_p, which also takes an int address,
-# None, bytes, a ctypes array and byref()
-_C_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint32_t': ctypes.c_uint32,
-              'uint64_t': ctypes.c_uint64, 'uint8_t': ctypes.c_uint8, 'float': ctypes.c_float, 'double': ctypes.c_double,
-              'er_stream_t': ctypes.c_void_p}
-
-
-def _ctype(decl, what, ret=False):
-  decl = ' '.join(decl.replace('*', ' * ').split())
-  if '*' in decl:
-    return ctypes.c_char_p if ret and decl == 'const char *' else ctypes.c_void_p
-  if decl not in _C_SCALARS:
-    raise RuntimeError('easyrec_amd: %s: no ctypes type for %r (%s)' % (what, decl, HEADER_PATH))
-  return _C_SCALARS[decl]
+from easyrec_amd import abi
+from easyrec_amd.abi import HEADER_PATH, LIB_PATH
 
 
 def load_library(path=LIB_PATH):
-  """Open libeasyrec_hip.so and bind it (bind_library)."""
-  if not os.path.exists(path):
-    raise RuntimeError(
-        'easyrec_amd: %s not found. Build it with `python -c "import __graft_entry__ as g; '
-        'g.build()"` or `make -C easyrec_amd/csrc`; there is no CPU fallback.' % path)
-  return bind_library(ctypes.CDLL(path))
+  """Open libeasyrec_hip.so and bind it to this module's HEADER_PATH (abi.load_library)."""
+  return abi.load_library(path, HEADER_PATH)
 
 
 def bind_library(lib):
-  """Give every function include/easyrec_hip.h declares argtypes / restype on `lib` (a ctypes.CDLL of
-  libeasyrec_hip.so), so that ctypes converts (and type-checks) each argument as the header says: plain Python ints /
-  floats / bools for scalars, an address, None, bytes, a ctypes array or byref() for pointers.  Returns lib."""
-  with open(HEADER_PATH) as f:
-    text = re.sub(r'/\*.*?\*/', ' ', f.read(), flags=re.S)
-  text = re.sub(r'^\s*#.*$', '', text, flags=re.M)  # (preprocessor lines)
-  for ret, name, params in re.findall(r'([\w\s*]+?)\b(er_\w+)\s*\(([^()]*)\)\s*;', text):
-    params = ' '.join(params.split())
-    decls = [] if params in ('', 'void') else [re.sub(r'\w+$', '', p) for p in params.split(',')]
-    if not hasattr(lib, name):
-      raise RuntimeError('easyrec_amd: %s declares %s, %s does not export it' % (HEADER_PATH, name, lib._name))
-    fn = getattr(lib, name)
-    fn.restype = _ctype(ret, name + ' return type', ret=True)
-    fn.argtypes = [_ctype(d, '%s argument %d' % (name, i + 1)) for i, d in enumerate(decls)]
-  return lib
+  """abi.bind_library with this module's HEADER_PATH."""
+  return abi.bind_library(lib, HEADER_PATH)
 
-COMBINER_SUM, COMBINER_MEAN, COMBINER_SQRTN = 0, 1, 2
+
+# Everything below is READ from include/easyrec_hip.h (abi.py): the header is the only place a record or a constant is
+# stated.  The records, under the names the package uses:
+LookupDesc = abi.RECORDS['er_lookup_desc']
+OptHyper = abi.RECORDS['er_opt_hyper']
+GradTerm = abi.RECORDS['er_grad_term']
+GradGroup = abi.RECORDS['er_grad_group']  # (its `lambda` is `lam` here)
+KvJob = abi.RECORDS['er_kv_job']
+KvRouteJob = abi.RECORDS['er_kv_route_job']
+CeHead = abi.RECORDS['er_ce_head']
+TailJob = abi.RECORDS['er_tail_job']
+LossTailJob = abi.RECORDS['er_loss_tail_job']
+DenseOptJob = abi.RECORDS['er_dense_opt_job']
+GemmProblem = abi.RECORDS['er_gemm_problem']
+BnLayer = abi.RECORDS['er_bn_layer']
+CastDesc = abi.RECORDS['er_cast_desc']
+GemmEpilogue = abi.RECORDS['er_gemm_epilogue']
+ColsumJob = abi.RECORDS['er_colsum_job']
+DenseApplyDesc = abi.RECORDS['er_dense_apply_desc']
+(COMBINER_SUM, COMBINER_MEAN, COMBINER_SQRTN, OPT_SGD, OPT_ADAM, OPT_LAZY_ADAM, OPT_ADAGRAD, ACT_NONE, ACT_RELU,
+ BN_NONE, BN_BATCH, BN_FROZEN, GEMM_NN, GEMM_NT, GEMM_TN, EPI_PLAIN, EPI_STATS, EPI_BN_BWD, EPI_CROSS_FWD, EPI_CROSS_BWD,
+ GRAD_TERM_ROWSUM, GRAD_TERM_FM, FRONT_SKIP_ONE_ROW, FRONT_DEFER_CATCH_UP, ABI_VERSION) = (
+     abi.CONSTANTS['ER_' + name] for name in (
+         'COMBINER_SUM', 'COMBINER_MEAN', 'COMBINER_SQRTN', 'OPT_SGD', 'OPT_ADAM', 'OPT_LAZY_ADAM', 'OPT_ADAGRAD', 'ACT_NONE',
+         'ACT_RELU', 'BN_NONE', 'BN_BATCH', 'BN_FROZEN', 'GEMM_NN', 'GEMM_NT', 'GEMM_TN', 'EPI_PLAIN', 'EPI_STATS',
+         'EPI_BN_BWD', 'EPI_CROSS_FWD', 'EPI_CROSS_BWD', 'GRAD_TERM_ROWSUM', 'GRAD_TERM_FM', 'FRONT_SKIP_ONE_ROW',
+         'FRONT_DEFER_CATCH_UP', 'ABI_VERSION'))
 COMBINERS = {'sum': COMBINER_SUM, 'mean': COMBINER_MEAN, 'sqrtn': COMBINER_SQRTN}
-OPT_SGD, OPT_ADAM, OPT_LAZY_ADAM, OPT_ADAGRAD = 0, 1, 2, 3
-ACT_NONE, ACT_RELU = 0, 1
-BN_NONE, BN_BATCH, BN_FROZEN = 0, 1, 2  # er_bn_act_fwd / _bwd use_bn (include/easyrec_hip.h)
-GEMM_NN, GEMM_NT, GEMM_TN = 0, 1, 2
-
-
-class GemmEpilogue(ctypes.Structure):  # = er_gemm_epilogue
-  _fields_ = [('kind', ctypes.c_int32), ('diag', ctypes.c_float), ('col_stats', ctypes.c_void_p),
-              ('bn_z', ctypes.c_void_p), ('bn_zbias', ctypes.c_void_p), ('bn_y', ctypes.c_void_p), ('bn_mean', ctypes.c_void_p),
-              ('bn_invstd', ctypes.c_void_p), ('bn_partial', ctypes.c_void_p),
-              ('bn_ld', ctypes.c_int32), ('bn_use_bn', ctypes.c_int32), ('bn_act', ctypes.c_int32), ('bn_col0', ctypes.c_int32),
-              ('bn_n_src', ctypes.c_int32),
-              ('ld_x0', ctypes.c_int32), ('ld_xl', ctypes.c_int32), ('ld_u', ctypes.c_int32), ('ld_dout', ctypes.c_int32),
-              ('ld_du_in', ctypes.c_int32), ('ld_prev_u', ctypes.c_int32), ('ld_dx0', ctypes.c_int32),
-              ('ld_du_out', ctypes.c_int32), ('ld_du_out_bf16', ctypes.c_int32), ('accumulate_dx0', ctypes.c_int32),
-              ('x0', ctypes.c_void_p), ('xl', ctypes.c_void_p), ('u', ctypes.c_void_p), ('dout', ctypes.c_void_p),
-              ('du_in', ctypes.c_void_p), ('prev_u', ctypes.c_void_p), ('prev_bias', ctypes.c_void_p), ('dx0', ctypes.c_void_p),
-              ('du_out', ctypes.c_void_p), ('du_out_bf16', ctypes.c_void_p), ('partial', ctypes.c_void_p)]
-
-
-EPI_PLAIN, EPI_STATS, EPI_BN_BWD, EPI_CROSS_FWD, EPI_CROSS_BWD = 0, 1, 2, 3, 4
-
-
-class LookupDesc(ctypes.Structure):
-  """Mirror of `er_lookup_desc` (include/easyrec_hip.h)."""
-  _fields_ = [
-      ('table', ctypes.c_void_p),
-      ('ids', ctypes.c_void_p),
-      ('offsets', ctypes.c_void_p),
-      ('weights', ctypes.c_void_p),
-      ('out', ctypes.c_void_p),
-      ('rows', ctypes.c_int64),
-      ('key_base', ctypes.c_int64),
-      ('dim', ctypes.c_int32),
-      ('out_stride', ctypes.c_int32),
-      ('out_col', ctypes.c_int32),
-      ('combiner', ctypes.c_int32),
-      ('n_rows', ctypes.c_int32),
-      ('max_nnz', ctypes.c_int32),
-      ('table_ld', ctypes.c_int32),
-  ]
-
-
-# er_opt_hyper: 16 floats
-HYPER_FLOATS = 16
-HYPER_LR, HYPER_LR_T, HYPER_BETA1, HYPER_BETA2, HYPER_OMB1, HYPER_OMB2, HYPER_EPS, HYPER_GSCALE = range(8)
-HYPER_CLIP = 8  # er_opt_hyper.clip_scale: 0 = no clipping
+# er_opt_hyper as the flat float array the host writes: its length and the index of each field
+HYPER_FLOATS = ctypes.sizeof(OptHyper) // 4
+HYPER_LR, HYPER_LR_T, HYPER_BETA1, HYPER_BETA2, HYPER_OMB1, HYPER_OMB2, HYPER_EPS, HYPER_GSCALE, HYPER_CLIP = (
+    getattr(OptHyper, f).offset // 4 for f in ('lr', 'lr_t', 'beta1', 'beta2', 'one_minus_beta1', 'one_minus_beta2', 'eps',
+                                               'grad_scale', 'clip_scale'))
 
 
 _wgrad_tls = threading.local()
@@ -321,81 +248,7 @@ def bn_source_of(x):
   return src
 
 
-class GemmProblem(ctypes.Structure):  # = er_gemm_problem
-  _fields_ = [('M', ctypes.c_int32), ('N', ctypes.c_int32), ('K', ctypes.c_int32), ('A', ctypes.c_void_p),
-              ('lda', ctypes.c_int32), ('B', ctypes.c_void_p), ('ldb', ctypes.c_int32), ('C', ctypes.c_void_p),
-              ('ldc', ctypes.c_int32), ('bias', ctypes.c_void_p), ('accumulate', ctypes.c_int32),
-              ('col_stats', ctypes.c_void_p),
-              ('bn_z', ctypes.c_void_p), ('bn_zbias', ctypes.c_void_p), ('bn_y', ctypes.c_void_p),
-              ('bn_mean', ctypes.c_void_p), ('bn_invstd', ctypes.c_void_p), ('bn_ld', ctypes.c_int32),
-              ('bn_use_bn', ctypes.c_int32), ('bn_act', ctypes.c_int32), ('bn_partial', ctypes.c_void_p),
-              ('fz_bias', ctypes.c_void_p), ('fz_gamma', ctypes.c_void_p), ('fz_beta', ctypes.c_void_p),
-              ('fz_mean', ctypes.c_void_p), ('fz_var', ctypes.c_void_p), ('fz_eps', ctypes.c_float), ('fz_act', ctypes.c_int32),
-              ('fz_y', ctypes.c_void_p), ('fz_save', ctypes.c_void_p), ('bn_gamma', ctypes.c_void_p), ('bn_dz_out', ctypes.c_int32)]
-
-
-class BnLayer(ctypes.Structure):  # = er_bn_layer
-  _fields_ = [('x', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('gamma', ctypes.c_void_p), ('beta', ctypes.c_void_p),
-              ('moving_mean', ctypes.c_void_p), ('moving_var', ctypes.c_void_p), ('col_stats', ctypes.c_void_p),
-              ('chunks', ctypes.c_int32), ('B', ctypes.c_int32), ('N', ctypes.c_int32), ('use_bn', ctypes.c_int32),
-              ('act', ctypes.c_int32), ('eps', ctypes.c_float), ('momentum', ctypes.c_float), ('y', ctypes.c_void_p),
-              ('save_mean', ctypes.c_void_p), ('save_invstd', ctypes.c_void_p), ('y_in', ctypes.c_void_p),
-              ('dy', ctypes.c_void_p), ('dy_ld', ctypes.c_int32), ('partial', ctypes.c_void_p), ('dx', ctypes.c_void_p),
-              ('dbias', ctypes.c_void_p), ('dgamma', ctypes.c_void_p), ('dbeta', ctypes.c_void_p),
-              ('accumulate', ctypes.c_int32)]
-
-
-class CeHead(ctypes.Structure):  # = er_ce_head
-  _fields_ = [('logits', ctypes.c_void_p), ('labels', ctypes.c_void_p), ('weights', ctypes.c_void_p), ('B', ctypes.c_int32),
-              ('loss_scale', ctypes.c_float), ('loss_out', ctypes.c_void_p), ('dlogits', ctypes.c_void_p),
-              ('probs_out', ctypes.c_void_p)]
-
-
 CROSS_HASH_KEY = 0xDECAFCAFFE  # tf.sparse.cross_hashed's default hash_key (crossed_column(hash_key=None))
-
-
-class TailJob(ctypes.Structure):  # = er_tail_job
-  _fields_ = [('partial', ctypes.c_void_p), ('dst', ctypes.c_void_p), ('n_parts', ctypes.c_int32), ('n_cols', ctypes.c_int32),
-              ('ld', ctypes.c_int32)]
-
-
-class ColsumJob(ctypes.Structure):  # = er_colsum_job
-  _fields_ = [('x', ctypes.c_void_p), ('rows', ctypes.c_int32), ('cols', ctypes.c_int32), ('x_stride', ctypes.c_int32),
-              ('out', ctypes.c_void_p)]
-
-
-class LossTailJob(ctypes.Structure):  # = er_loss_tail_job
-  _fields_ = [('emb_partials', ctypes.c_void_p), ('n_partials', ctypes.c_int32), ('emb_scale', ctypes.c_float),
-              ('dense_partials', ctypes.c_void_p), ('n_dense', ctypes.c_int32),
-              ('losses', ctypes.c_void_p), ('report', ctypes.c_void_p), ('loss_parts', ctypes.c_void_p),
-              ('loss_scales', ctypes.c_void_p), ('loss_divs', ctypes.c_void_p), ('loss_values', ctypes.c_void_p),
-              ('n_losses', ctypes.c_int32), ('jobs', ctypes.c_void_p), ('n_jobs', ctypes.c_int32),
-              ('reg_out', ctypes.c_void_p), ('total_out', ctypes.c_void_p)]
-
-
-class DenseOptJob(ctypes.Structure):  # = er_dense_opt_job
-  _fields_ = [('w', ctypes.c_void_p), ('m', ctypes.c_void_p), ('v', ctypes.c_void_p), ('grad', ctypes.c_void_p),
-              ('l2coef', ctypes.c_void_p), ('n', ctypes.c_int64), ('opt_kind', ctypes.c_int32), ('hyper', ctypes.c_void_p),
-              ('l2_partials', ctypes.c_void_p)]
-
-
-class GradTerm(ctypes.Structure):  # = er_grad_term
-  _fields_ = [('kind', ctypes.c_int32), ('col0', ctypes.c_int32), ('width', ctypes.c_int32), ('dim', ctypes.c_int32),
-              ('g', ctypes.c_void_p), ('g_ld', ctypes.c_int32), ('pad_', ctypes.c_int32), ('saved', ctypes.c_void_p)]
-
-
-class GradGroup(ctypes.Structure):  # = er_grad_group
-  _fields_ = [('dout', ctypes.c_void_p), ('out', ctypes.c_void_p), ('ld', ctypes.c_int32), ('batch', ctypes.c_int32),
-              ('width', ctypes.c_int32), ('has_base', ctypes.c_int32), ('n_terms', ctypes.c_int32),
-              ('lam', ctypes.c_float), ('terms', GradTerm * 4)]
-
-
-GRAD_TERM_ROWSUM, GRAD_TERM_FM = 0, 1
-
-
-class DenseApplyDesc(ctypes.Structure):  # = er_dense_apply_desc
-  _fields_ = [('var', ctypes.c_void_p), ('m', ctypes.c_void_p), ('v', ctypes.c_void_p), ('dense', ctypes.c_void_p),
-              ('ld', ctypes.c_int32), ('dim', ctypes.c_int32), ('rows', ctypes.c_int64), ('table_ld', ctypes.c_int64)]
 
 
 def same_lookup_keys(group, leader):
@@ -555,15 +408,37 @@ class Bf16Shadows(object):
     return dst
 
 
+class _CheckedCalls(object):
+  """`ck.er_NAME(...)` calls `lib.er_NAME(...)` and hands a non-zero return code to `fail(rc, 'er_NAME')`: the name in
+  the error is the name of the function that was called.  For the entry points that return 0 or an error; those that
+  return a value or a code the caller interprets are called through `lib`."""
+
+  def __init__(self, lib, fail):
+    self._lib, self._fail = lib, fail
+
+  def __getattr__(self, name):  # (the first use of a name only: the callable then is an attribute of its own)
+    fn, fail = getattr(self._lib, name), self._fail
+
+    def call(*args):
+      rc = fn(*args)
+      if rc != 0:
+        fail(rc, name)
+    setattr(self, name, call)
+    return call
+
+
 class HipBackend(object):
   """Tensor-level wrappers.  Every method launches asynchronously on torch's current stream."""
 
   name = 'hip'
 
   def __init__(self):
-    self._lib = load_library(LIB_PATH)
-    if self.lib.er_abi_version() != 1:
+    self._adopt(load_library(LIB_PATH))
+    if self.lib.er_abi_version() != ABI_VERSION:
       raise RuntimeError('easyrec_amd: ABI version mismatch in %s' % LIB_PATH)
+
+  def _adopt(self, bound_lib):
+    self._lib, self.ck = bound_lib, _CheckedCalls(bound_lib, self._ck)
 
   @property
   def lib(self):
@@ -573,12 +448,12 @@ class HipBackend(object):
   def lib(self, lib):
     # a library opened elsewhere (a host-only backend made without __init__) is bound here: every wrapper passes plain
     # Python values, which an unbound CDLL would truncate to C ints
-    self._lib = bind_library(lib)
+    self._adopt(bind_library(lib))
 
   # -- measurement hook (bench.py): with `op_log` a list, every contraction appends (kernel name as rocprof prints it,
   # flops): one eager step gives the algorithmic work behind each GEMM kernel of the step's profile
   op_log = None
-  _LAYOUT_TPL = {0: '<true, false>', 1: '<true, true>', 2: '<false, false>'}
+  _LAYOUT_TPL = {GEMM_NN: '<true, false>', GEMM_NT: '<true, true>', GEMM_TN: '<false, false>'}
 
   def _log_gemm(self, kernel, layout, M, N, K):
     if self.op_log is not None:
@@ -598,39 +473,39 @@ class HipBackend(object):
                          '(there is no CPU fallback).')
 
   def reserve_scratch(self, floats):
-    self._ck(self.lib.er_reserve_scratch(int(floats)), 'er_reserve_scratch')
+    self.ck.er_reserve_scratch(int(floats))
 
   def config_set(self, key, value):
-    self._ck(self.lib.er_config_set(key.encode(), int(value)), 'er_config_set')
+    self.ck.er_config_set(key.encode(), int(value))
 
   def device_info(self):
     cu, wave = ctypes.c_int(0), ctypes.c_int(0)
     buf = ctypes.create_string_buffer(64)
-    self._ck(self.lib.er_device_info(ctypes.byref(cu), ctypes.byref(wave), buf, 64), 'er_device_info')
+    self.ck.er_device_info(ctypes.byref(cu), ctypes.byref(wave), buf, 64)
     return {'cu_count': cu.value, 'wave_size': wave.value, 'arch': buf.value.decode()}
 
   # -- K14 sharded embedding checkpoint files (host code)
   def save_dense_embed(self, ckpt_path, var_name, task_index, task_num, vals_np):
     vals_np = np.ascontiguousarray(vals_np, dtype=np.float32)
     rows, dim = vals_np.shape
-    self._ck(self.lib.er_save_dense_embed(ckpt_path.encode(), var_name.encode(), task_index, task_num,
-                                          _np(vals_np), rows, dim), 'er_save_dense_embed')
+    self.ck.er_save_dense_embed(ckpt_path.encode(), var_name.encode(), task_index, task_num,
+                                _np(vals_np), rows, dim)
 
   def load_dense_embed(self, ckpt_path, var_name, task_index, task_num, embed_dim, embed_part_size):
     out = np.empty((embed_part_size, embed_dim), dtype=np.float32)
     n = ctypes.c_int64(0)
-    self._ck(self.lib.er_load_dense_embed(ckpt_path.encode(), var_name.encode(), task_index, task_num, embed_dim,
-                                          embed_part_size, _np(out), ctypes.byref(n)), 'er_load_dense_embed')
+    self.ck.er_load_dense_embed(ckpt_path.encode(), var_name.encode(), task_index, task_num, embed_dim,
+                                embed_part_size, _np(out), ctypes.byref(n))
     return out
 
   def load_kv_embed(self, ckpt_path, var_name, task_index, task_num, embed_dim):
     n = ctypes.c_int64(0)
     args = (ckpt_path.encode(), var_name.encode(), task_index, task_num, embed_dim)
-    self._ck(self.lib.er_load_kv_embed(*args, 0, None, None, ctypes.byref(n)), 'er_load_kv_embed')
+    self.ck.er_load_kv_embed(*args, 0, None, None, ctypes.byref(n))
     keys = np.empty(n.value, dtype=np.int64)
     vals = np.empty((n.value, embed_dim), dtype=np.float32)
     if n.value:
-      self._ck(self.lib.er_load_kv_embed(*args, n.value, _np(keys), _np(vals), ctypes.byref(n)), 'er_load_kv_embed')
+      self.ck.er_load_kv_embed(*args, n.value, _np(keys), _np(vals), ctypes.byref(n))
     return keys, vals
 
   # -- K1 hashing
@@ -664,15 +539,14 @@ class HipBackend(object):
     if text.size == 0:
       return 0, 0, ints, flts, empty, begin, length
     if int(threads) == 1:
-      self._ck(self.lib.er_decode_csv_host(_np(text), text.size, sep_b[0], F,
-                                           _np(kinds), int(max_rows), _np(ints), _np(flts), _np(empty),
-                                           _np(begin), _np(length), ctypes.byref(n_rows), ctypes.byref(consumed)),
-               'er_decode_csv_host')
+      self.ck.er_decode_csv_host(_np(text), text.size, sep_b[0], F,
+                                 _np(kinds), int(max_rows), _np(ints), _np(flts), _np(empty),
+                                 _np(begin), _np(length), ctypes.byref(n_rows), ctypes.byref(consumed))
     else:
-      self._ck(self.lib.er_decode_csv_host_mt(_np(text), text.size, sep_b[0], F,
-                                              _np(kinds), int(max_rows), int(pitch), _np(ints),
-                                              _np(flts), _np(empty), _np(begin), _np(length), ctypes.byref(n_rows),
-                                              ctypes.byref(consumed), int(threads)), 'er_decode_csv_host_mt')
+      self.ck.er_decode_csv_host_mt(_np(text), text.size, sep_b[0], F,
+                                    _np(kinds), int(max_rows), int(pitch), _np(ints),
+                                    _np(flts), _np(empty), _np(begin), _np(length), ctypes.byref(n_rows),
+                                    ctypes.byref(consumed), int(threads))
     return n_rows.value, consumed.value, ints, flts, empty, begin, length
 
   def pack_cells_host(self, text, begin, length):
@@ -683,8 +557,8 @@ class HipBackend(object):
     n = len(begin)
     out = np.empty(max(int(length.sum(dtype=np.int64)), 1), dtype=np.uint8)
     offsets = np.empty(n + 1, dtype=np.int64)
-    self._ck(self.lib.er_pack_cells_host(_np(text if text.size else out), _np(begin), _np(length), n,
-                                         _np(out), _np(offsets)), 'er_pack_cells_host')
+    self.ck.er_pack_cells_host(_np(text if text.size else out), _np(begin), _np(length), n,
+                               _np(out), _np(offsets))
     return out[:int(offsets[-1])], offsets
 
   def split_cells_host(self, text, begin, length, seps, keep_empty=False, max_tokens=0):
@@ -698,9 +572,8 @@ class HipBackend(object):
     tb, tl = np.empty(cap, dtype=np.int64), np.empty(cap, dtype=np.int32)
     offs = np.empty(n + 1, dtype=np.int64)
     sb = np.frombuffer(seps if isinstance(seps, bytes) else seps.encode('utf-8'), dtype=np.uint8)
-    self._ck(self.lib.er_split_cells_host(_np(text if text.size else tb), _np(begin), _np(length), n, _np(sb),
-                                          len(sb), keep_empty, int(max_tokens), _np(tb), _np(tl), cap, _np(offs)),
-             'er_split_cells_host')
+    self.ck.er_split_cells_host(_np(text if text.size else tb), _np(begin), _np(length), n, _np(sb),
+                                len(sb), keep_empty, int(max_tokens), _np(tb), _np(tl), cap, _np(offs))
     T = int(offs[-1])
     return tb[:T], tl[:T], offs
 
@@ -710,7 +583,7 @@ class HipBackend(object):
     n = values.size
     out = np.empty(max(20 * n, 1), dtype=np.uint8)
     offsets = np.empty(n + 1, dtype=np.int64)
-    self._ck(self.lib.er_pack_int_decimal_host(_np(values), n, _np(out), _np(offsets)), 'er_pack_int_decimal_host')
+    self.ck.er_pack_int_decimal_host(_np(values), n, _np(out), _np(offsets))
     return out[:int(offsets[-1])], offsets
 
   def sparse_cross_hashed_host(self, bytes_np, offsets_np, n_rows, n_cols, num_buckets, hash_key=None):
@@ -722,8 +595,8 @@ class HipBackend(object):
     if bytes_np.size == 0:
       bytes_np = np.zeros(1, dtype=np.uint8)
     key = CROSS_HASH_KEY if hash_key is None else int(hash_key)
-    self._ck(self.lib.er_sparse_cross_hashed_host(_np(bytes_np), _np(offsets_np), int(n_rows), int(n_cols), int(num_buckets),
-                                                  key, _np(out)), 'er_sparse_cross_hashed_host')
+    self.ck.er_sparse_cross_hashed_host(_np(bytes_np), _np(offsets_np), int(n_rows), int(n_cols), int(num_buckets),
+                                        key, _np(out))
     return out
 
   def hash_bucket_fast_host(self, bytes_np, offsets_np, n_per_col, num_buckets, drop_empty):
@@ -735,26 +608,24 @@ class HipBackend(object):
     out = np.empty(n, dtype=np.int64)
     if bytes_np.size == 0:
       bytes_np = np.zeros(1, dtype=np.uint8)
-    self._ck(self.lib.er_hash_bucket_fast_host(_np(bytes_np), _np(offsets_np), n, int(n_per_col), _np(nb), int(drop_empty),
-                                               _np(out)), 'er_hash_bucket_fast_host')
+    self.ck.er_hash_bucket_fast_host(_np(bytes_np), _np(offsets_np), n, int(n_per_col), _np(nb), int(drop_empty),
+                                     _np(out))
     return out
 
   def hash_bucket_fast(self, bytes_t, offsets_t, n_per_col, num_buckets_t, drop_empty, out=None):
     n = offsets_t.numel() - 1
     if out is None:
       out = torch.empty(n, dtype=torch.int64, device=bytes_t.device)
-    self._ck(
-        self.lib.er_hash_bucket_fast(_p(bytes_t), _p(offsets_t), n, int(n_per_col), _p(num_buckets_t), int(drop_empty),
-                                     _p(out), _stream()), 'er_hash_bucket_fast')
+    self.ck.er_hash_bucket_fast(_p(bytes_t), _p(offsets_t), n, int(n_per_col), _p(num_buckets_t), int(drop_empty),
+                                _p(out), _stream())
     return out
 
   def hash_bucket_fast_int64(self, values_t, n_per_col, num_buckets_t, out=None):
     n = values_t.numel()
     if out is None:
       out = torch.empty(n, dtype=torch.int64, device=values_t.device)
-    self._ck(
-        self.lib.er_hash_bucket_fast_int64(_p(values_t), n, int(n_per_col),
-                                           _p(num_buckets_t), _p(out), _stream()), 'er_hash_bucket_fast_int64')
+    self.ck.er_hash_bucket_fast_int64(_p(values_t), n, int(n_per_col),
+                                      _p(num_buckets_t), _p(out), _stream())
     return out
 
   # -- K2 / K3 / K4 embeddings
@@ -780,8 +651,7 @@ class HipBackend(object):
 
   def emb_plan_create(self, specs):
     plan = ctypes.c_void_p(0)
-    self._ck(self.lib.er_emb_plan_create(self._descs(specs), len(specs), ctypes.byref(plan)),
-             'er_emb_plan_create')
+    self.ck.er_emb_plan_create(self._descs(specs), len(specs), ctypes.byref(plan))
     nblk = self.lib.er_emb_plan_num_blocks(plan)
     return {'handle': plan, 'specs': list(specs), 'num_blocks': nblk}
 
@@ -789,13 +659,12 @@ class HipBackend(object):
     self.lib.er_emb_plan_destroy(plan['handle'])
 
   def emb_fwd(self, plan, sumsq_partials=None):
-    self._ck(self.lib.er_emb_fwd(plan['handle'], _p(sumsq_partials), _stream()), 'er_emb_fwd')
+    self.ck.er_emb_fwd(plan['handle'], _p(sumsq_partials), _stream())
 
   def emb_group_create(self, specs, dim, total_rows, var, m, v, bitmap):
     grp = ctypes.c_void_p(0)
-    self._ck(
-        self.lib.er_emb_group_create(self._descs(specs), len(specs), dim, total_rows, _p(var), _p(m), _p(v), _p(bitmap),
-                                     ctypes.byref(grp)), 'er_emb_group_create')
+    self.ck.er_emb_group_create(self._descs(specs), len(specs), dim, total_rows, _p(var), _p(m), _p(v), _p(bitmap),
+                                ctypes.byref(grp))
     n_ent = self.lib.er_emb_group_num_entries(grp)
     group = {'handle': grp, 'specs': list(specs), 'dim': dim, 'total_rows': total_rows, 'var': var,
              'm': m, 'v': v, 'bitmap': bitmap, 'num_entries': n_ent, 'last_step': None}
@@ -812,15 +681,13 @@ class HipBackend(object):
     assert var.dim() != 2 or var.stride(1) == 1
     ls_ld = 1 if ls is None else (ls.stride(0) if ls.numel() > 1 else 1)
     if ld != group['dim'] or ls_ld != 1:
-      self._ck(self.lib.er_emb_group_set_row_pitch(group['handle'], ld, ls_ld),
-               'er_emb_group_set_row_pitch')
+      self.ck.er_emb_group_set_row_pitch(group['handle'], ld, ls_ld)
 
   def emb_group_destroy(self, group):
     self.lib.er_emb_group_destroy(group['handle'])
 
   def emb_bwd_update(self, group, opt_kind, hyper):
-    self._ck(self.lib.er_emb_bwd_update(group['handle'], opt_kind, _p(hyper), _stream()),
-             'er_emb_bwd_update')
+    self.ck.er_emb_bwd_update(group['handle'], opt_kind, _p(hyper), _stream())
 
   def emb_bwd_reduce(self, group, out=None):
     """out: a (keys, grads, n_unique) triple from an earlier call to reuse (fixed addresses for hipGraphs)."""
@@ -832,13 +699,12 @@ class HipBackend(object):
       n_unique = torch.zeros(1, dtype=torch.int32, device=dev)
     else:
       keys, grads, n_unique = out
-    self._ck(self.lib.er_emb_bwd_reduce(group['handle'], _p(keys), _p(grads), _p(n_unique), _stream()),
-             'er_emb_bwd_reduce')
+    self.ck.er_emb_bwd_reduce(group['handle'], _p(keys), _p(grads), _p(n_unique), _stream())
     return keys, grads, n_unique
 
   # -- K13 GEMM on the matrix cores
   def gemm_reserve(self, floats):
-    self._ck(self.lib.er_gemm_reserve(int(floats)), 'er_gemm_reserve')
+    self.ck.er_gemm_reserve(int(floats))
 
   def gemm_row_tiles(self, M):
     return int(self.lib.er_gemm_row_tiles(int(M)))
@@ -852,11 +718,10 @@ class HipBackend(object):
     mean = torch.empty(N, dtype=torch.float32, device=x.device)
     invstd = torch.empty(N, dtype=torch.float32, device=x.device)
     yb = bf16_state.new_copy(y) if bf16_state is not None else None
-    self._ck(
-        self.lib.er_bn_apply_from_stats_b16(_p(_f32c(x)), _p(bias), _p(col_stats), int(chunks), _p(gamma), _p(beta), B,
-                                            N, eps, momentum, _p(moving_mean), _p(moving_var), int(act), _p(y),
-                                            _p(mean), _p(invstd), _p(yb), 0 if yb is None else yb.stride(0),
-                                            _stream()), 'er_bn_apply_from_stats')
+    self.ck.er_bn_apply_from_stats_b16(_p(_f32c(x)), _p(bias), _p(col_stats), int(chunks), _p(gamma), _p(beta), B,
+                                       N, eps, momentum, _p(moving_mean), _p(moving_var), int(act), _p(y),
+                                       _p(mean), _p(invstd), _p(yb), 0 if yb is None else yb.stride(0),
+                                       _stream())
     return y, mean, invstd
 
   def gemm(self, layout, a, b, out=None, bias=None, accumulate=False, bf16=False, col_stats=None):
@@ -880,11 +745,11 @@ class HipBackend(object):
     if layout == GEMM_NN and not bf16 and not accumulate and col_stats is None and self.gemv_ok(a, M, N, K):
       return self._gemv(a, None, b, bias, out)
     self._log_gemm('gemm_bf16_kernel' if bf16 else 'gemm_f32_kernel', layout, M, N, K)
-    fn = self.lib.er_gemm_bf16 if bf16 else self.lib.er_gemm_f32
+    fn = self.ck.er_gemm_bf16 if bf16 else self.ck.er_gemm_f32
     if col_stats is not None:
       assert col_stats.numel() >= self.gemm_row_tiles(M) * N * 3 and col_stats.dtype == torch.float32
-    self._ck(fn(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), _p(bias), accumulate,
-                _p(col_stats), _stream()), 'er_gemm')
+    fn(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out), out.stride(0), _p(bias), accumulate,
+       _p(col_stats), _stream())
     return out
 
   # -- bf16 operands in HBM (dense_dtype 'bf16'): er_gemm_bf16_nt
@@ -896,7 +761,7 @@ class HipBackend(object):
 
   def bf16_enable(self, varstore):
     """Called by the estimator (dense_dtype 'bf16') once the dense variables are packed; outside graph capture."""
-    self._ck(self.lib.er_gemm_bf16_nt_prepare(), 'er_gemm_bf16_nt_prepare')
+    self.ck.er_gemm_bf16_nt_prepare()
     states = [s for s in getattr(self, '_bf16_states', []) if s.alive()]
     st = Bf16Shadows(self, varstore)
     states.append(st)
@@ -920,7 +785,7 @@ class HipBackend(object):
       rows, cols = src.shape
       assert dst.shape[0] == (cols if tr else rows) and dst.stride(0) >= (rows if tr else cols)
       arr[i] = CastDesc(src.data_ptr(), dst.data_ptr(), rows, cols, src.stride(0), dst.stride(0), 1 if tr else 0)
-    self._ck(self.lib.er_cast_bf16(arr, n, _stream()), 'er_cast_bf16')
+    self.ck.er_cast_bf16(arr, n, _stream())
 
   def gemm_bf16_nt(self, a, bt, M, N, K, out=None, out_bf16=None, bias=None, accumulate=False, epi=None):
     """out[M, N] (+)= a[M, K] . bt[N, K]^T (+ bias): bf16 operands with leading dimensions that are multiples of 8,
@@ -929,13 +794,12 @@ class HipBackend(object):
     assert a.shape[0] >= M and bt.shape[0] >= N
     Kp = (K + 7) // 8 * 8  # (the k-tail up to the padded width reads zeros: Bf16Shadows pads with zeros)
     assert a.stride(0) >= Kp and bt.stride(0) >= Kp and a.stride(0) % 8 == 0 and bt.stride(0) % 8 == 0
-    kind = 0 if epi is None else int(epi.kind)
+    kind = EPI_PLAIN if epi is None else int(epi.kind)
     self._log_gemm('gemm_bf16_nt_kernel<4, %d>' % kind, None, M, N, K)
-    self._ck(self.lib.er_gemm_bf16_nt_epi(M, N, Kp, _p(a), a.stride(0), _p(bt), bt.stride(0), _p(out),
-                                          0 if out is None else out.stride(0), _p(out_bf16),
-                                          0 if out_bf16 is None else out_bf16.stride(0), _p(bias), accumulate,
-                                          None if epi is None else ctypes.byref(epi), _stream()),
-             'er_gemm_bf16_nt')
+    self.ck.er_gemm_bf16_nt_epi(M, N, Kp, _p(a), a.stride(0), _p(bt), bt.stride(0), _p(out),
+                                0 if out is None else out.stride(0), _p(out_bf16),
+                                0 if out_bf16 is None else out_bf16.stride(0), _p(bias), accumulate,
+                                None if epi is None else ctypes.byref(epi), _stream())
     return out
 
   @staticmethod
@@ -1001,21 +865,20 @@ class HipBackend(object):
       assert partial.numel() >= self.gemm_row_tiles(M) * n_src * 2
       self._log_gemm('gemm_f32_bn_bwd_kernel', layout, M, N, K)
       out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-      self._ck(self.lib.er_gemm_f32_bn_bwd_cols(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out),
-                                                out.stride(0), _p(src.z), _p(src.zbias), _p(src.y), _p(src.mean),
-                                                _p(src.invstd), src.y.stride(0), int(src.mean is not None),
-                                                int(src.act), _p(partial), int(col0), n_src, _stream()),
-               'er_gemm_f32_bn_bwd_cols')
+      self.ck.er_gemm_f32_bn_bwd_cols(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out),
+                                      out.stride(0), _p(src.z), _p(src.zbias), _p(src.y), _p(src.mean),
+                                      _p(src.invstd), src.y.stride(0), int(src.mean is not None),
+                                      int(src.act), _p(partial), int(col0), n_src, _stream())
       return out
     assert K == K2 and src.z.shape == (M, N) and src.y.shape == (M, N) and src.y.stride() == src.z.stride()
     assert partial.numel() >= self.gemm_row_tiles(M) * N * 2
     self._log_gemm('gemm_f32_bn_bwd_kernel', layout, M, N, K)
     out = torch.empty(M, N, dtype=torch.float32, device=a.device)
     use_bn = src.mean is not None
-    self._ck(self.lib.er_gemm_f32_bn_bwd(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out),
-                                         out.stride(0), _p(src.z), _p(src.zbias), _p(src.y), _p(src.mean),
-                                         _p(src.invstd), src.y.stride(0), int(use_bn), int(src.act), _p(partial),
-                                         _stream()), 'er_gemm_f32_bn_bwd')
+    self.ck.er_gemm_f32_bn_bwd(layout, M, N, K, _p(a), a.stride(0), _p(b), b.stride(0), _p(out),
+                               out.stride(0), _p(src.z), _p(src.zbias), _p(src.y), _p(src.mean),
+                               _p(src.invstd), src.y.stride(0), int(use_bn), int(src.act), _p(partial),
+                               _stream())
     return out
 
   # the same-depth layers of parallel stacks (MMoE's experts, task towers) as one grouped launch: layers/dnn.py run_parallel
@@ -1047,7 +910,7 @@ class HipBackend(object):
         q.col_stats, q.chunks = l['col_stats'].data_ptr(), self.gemm_row_tiles(B)
       q.y, q.save_mean, q.save_invstd = y.data_ptr(), _p(mean), _p(invstd)
       outs.append((y, mean, invstd))
-    self._ck(self.lib.er_bn_fwd_multi(arr, len(layers), _stream()), 'er_bn_fwd_multi')
+    self.ck.er_bn_fwd_multi(arr, len(layers), _stream())
     return outs
 
   def bn_bwd_multi(self, layers):
@@ -1084,7 +947,7 @@ class HipBackend(object):
       q.dx, q.dbias, q.dgamma, q.dbeta = (None if dx_done else dx.data_ptr()), _p(dbias), _p(dgamma), _p(dbeta)
       q.accumulate = int(into is not None)
       outs.append((dx, None, None, None) if into is not None else (dx, dbias, dgamma, dbeta))
-    self._ck(self.lib.er_bn_bwd_multi(arr, len(layers), _stream()), 'er_bn_bwd_multi')
+    self.ck.er_bn_bwd_multi(arr, len(layers), _stream())
     return outs
 
   def gemm_grouped(self, layout, problems, bf16=False):
@@ -1092,9 +955,9 @@ class HipBackend(object):
     bf16: operands rounded to bf16 while staged (er_gemm_grouped_bf16)."""
     arr = self._gemm_problems(layout, problems, bf16)
     if bf16:
-      self._ck(self.lib.er_gemm_grouped_bf16(layout, arr, len(problems), _stream()), 'er_gemm_grouped_bf16')
+      self.ck.er_gemm_grouped_bf16(layout, arr, len(problems), _stream())
     else:
-      self._ck(self.lib.er_gemm_grouped_f32(layout, arr, len(problems), _stream()), 'er_gemm_grouped_f32')
+      self.ck.er_gemm_grouped_f32(layout, arr, len(problems), _stream())
 
   def _gemm_problems(self, layout, problems, bf16=False, log_as=None):
     """The er_gemm_problem array of a grouped launch (log_as: the kernel the op log books the contractions under)."""
@@ -1204,8 +1067,7 @@ class HipBackend(object):
     for q, (x, out) in zip(arr, jobs):
       assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == torch.float32 and out.is_contiguous() and out.numel() == x.shape[1]
       q.x, q.rows, q.cols, q.x_stride, q.out = x.data_ptr(), x.shape[0], x.shape[1], x.stride(0), out.data_ptr()
-    self._ck(self.lib.er_colsum_narrow_multi(arr, len(jobs), accumulate, _stream()),
-             'er_colsum_narrow_multi')
+    self.ck.er_colsum_narrow_multi(arr, len(jobs), accumulate, _stream())
 
   def colsum_partials_multi(self, jobs, accumulate=True):
     """jobs: [(partial [P, ld], dst [n_cols], n_cols)]: dst[j] (+)= sum_p partial[p, j], all jobs in one launch."""
@@ -1213,8 +1075,7 @@ class HipBackend(object):
     for q, (partial, d, n_cols) in zip(arr, jobs):
       assert partial.dim() == 2 and partial.stride(1) == 1 and d.is_contiguous() and d.numel() == n_cols
       q.partial, q.dst, q.n_parts, q.n_cols, q.ld = partial.data_ptr(), d.data_ptr(), partial.shape[0], int(n_cols), partial.stride(0)
-    self._ck(self.lib.er_colsum_partials_multi(arr, len(jobs), accumulate, _stream()),
-             'er_colsum_partials_multi')
+    self.ck.er_colsum_partials_multi(arr, len(jobs), accumulate, _stream())
 
   # the step's tail in one grid (er_emb_bwd_fused_wgrad); A/B switch, and the workgroups its contraction's k-splits aim at
   # (0: the stand-alone launch's 512 - bit-identical to the unfused tail; same-box 256 -> 54.5 us, 512 -> 60, 1024 -> 66)
@@ -1229,37 +1090,36 @@ class HipBackend(object):
   # -- K12 embedding-parallel routing (include/easyrec_hip.h)
   def emb_group_set_routing(self, group, world, shard_stride, local_base):
     arr = (ctypes.c_int64 * len(local_base))(*[int(x) for x in local_base])
-    self._ck(self.lib.er_emb_group_set_routing(group['handle'], world, shard_stride, arr),
-             'er_emb_group_set_routing')
+    self.ck.er_emb_group_set_routing(group['handle'], world, shard_stride, arr)
     group['world'], group['shard_stride'], group['local_base'] = world, shard_stride, list(local_base)
 
   def emb_group_set_active(self, group, n_rows):
-    self._ck(self.lib.er_emb_group_set_active(group['handle'], int(n_rows)), 'er_emb_group_set_active')
+    self.ck.er_emb_group_set_active(group['handle'], int(n_rows))
     group['n_active'] = int(n_rows)
 
   def emb_group_share_sort(self, group, leader):
     """True when `group` now reuses `leader`'s per-step sort (identical ids and table geometry), else False."""
     if not same_lookup_keys(group, leader):
       return False
-    self._ck(self.lib.er_emb_group_share_sort(group['handle'], leader['handle']), 'er_emb_group_share_sort')
+    self.ck.er_emb_group_share_sort(group['handle'], leader['handle'])
     group['sort_leader'] = leader
     return True
 
   def emb_route(self, group, unique_keys, n_unique, entry_unique_index, owner_counts):
     if unique_keys is None:  # follower of a shared sort: the outputs are the leader's
       assert group.get('sort_leader') is not None and n_unique is None and entry_unique_index is None
-      self._ck(self.lib.er_emb_route(group['handle'], None, None, None, None, _stream()), 'er_emb_route')
+      self.ck.er_emb_route(group['handle'], None, None, None, None, _stream())
       return
     assert unique_keys.dtype == torch.int32 and n_unique.dtype == torch.int32
     assert entry_unique_index is None or entry_unique_index.dtype == torch.int64
     assert owner_counts is None or owner_counts.dtype == torch.int32
-    self._ck(self.lib.er_emb_route(group['handle'], _p(unique_keys), _p(n_unique), _p(entry_unique_index),
-                                   _p(owner_counts), _stream()), 'er_emb_route')
+    self.ck.er_emb_route(group['handle'], _p(unique_keys), _p(n_unique), _p(entry_unique_index),
+                         _p(owner_counts), _stream())
 
   def emb_bwd_reduce_routed(self, group, unique_grads):
     assert unique_grads.dtype == torch.float32 and unique_grads.dim() == 2 and unique_grads.stride(1) == 1
-    self._ck(self.lib.er_emb_bwd_reduce_routed(group['handle'], _p(unique_grads), unique_grads.stride(0),
-                                               _stream()), 'er_emb_bwd_reduce_routed')
+    self.ck.er_emb_bwd_reduce_routed(group['handle'], _p(unique_grads), unique_grads.stride(0),
+                                     _stream())
 
   # the embedding-parallel requester's local reductions + the step's weight gradients + the loss tail as two launches
   # (er_emb_reduce_local_tail); A/B switch: '0' = one launch per reduction kind and dim group, the grouped wgrad launch apart
@@ -1284,36 +1144,33 @@ class HipBackend(object):
       pr = self._gemm_problems(GEMM_TN, wgrads, log_as='emb_reduce_local_wgrad_kernel')
       lt = self._deferred_loss_tail
       self._deferred_loss_tail = None
-    self._ck(self.lib.er_emb_reduce_local_tail(gh, modes, outs, ld, n, pr, len(wgrads) if wgrads else 0,
-                                               int(self.tail_wgrad_blocks) if wgrads else 0,
-                                               ctypes.byref(lt[0]) if lt is not None else None, _stream()),
-             'er_emb_reduce_local_tail')
+    self.ck.er_emb_reduce_local_tail(gh, modes, outs, ld, n, pr, len(wgrads) if wgrads else 0,
+                                     int(self.tail_wgrad_blocks) if wgrads else 0,
+                                     ctypes.byref(lt[0]) if lt is not None else None, _stream())
 
   def gather_rows(self, table, keys, n, key_sub, out):
     assert keys.dtype == torch.int32 and table.dim() == 2 and table.stride(1) == 1
-    self._ck(self.lib.er_gather_rows_ld(_p(table), table.stride(0), table.shape[0], table.shape[1], _p(keys), int(n),
-                                        int(key_sub), _p(out), _stream()), 'er_gather_rows_ld')
+    self.ck.er_gather_rows_ld(_p(table), table.stride(0), table.shape[0], table.shape[1], _p(keys), int(n),
+                              int(key_sub), _p(out), _stream())
 
   def scatter_unique(self, keys, grads, n_unique, capacity, dim, dense):
     assert dense.dim() == 2 and dense.stride(1) == 1
-    self._ck(self.lib.er_scatter_unique(_p(keys), _p(grads), _p(n_unique), int(capacity),
-                                        dim, _p(dense), dense.stride(0), _stream()),
-             'er_scatter_unique')
+    self.ck.er_scatter_unique(_p(keys), _p(grads), _p(n_unique), int(capacity),
+                              dim, _p(dense), dense.stride(0), _stream())
 
   def emb_owner_merge(self, group, run_counts):
     """Owner side: the received keys are len(run_counts) ascending duplicate-free runs; merge instead of sort."""
     n = len(run_counts)
     rc = (ctypes.c_int32 * n)(*[int(x) for x in run_counts])
-    self._ck(self.lib.er_emb_owner_merge(group['handle'], rc, n, _stream()), 'er_emb_owner_merge')
+    self.ck.er_emb_owner_merge(group['handle'], rc, n, _stream())
 
   def emb_group_set_peer_capacity(self, group, peer_cap, count_header=True):
-    self._ck(self.lib.er_emb_group_set_peer_capacity(group['handle'], int(peer_cap), 1 if count_header else 0),
-             'er_emb_group_set_peer_capacity')
+    self.ck.er_emb_group_set_peer_capacity(group['handle'], int(peer_cap), 1 if count_header else 0)
     group['peer_cap'], group['peer_hdr'] = int(peer_cap), bool(count_header)
 
   def emb_route_overflow(self, group):
     out = ctypes.c_int32(0)
-    self._ck(self.lib.er_emb_route_overflow(group['handle'], ctypes.byref(out)), 'er_emb_route_overflow')
+    self.ck.er_emb_route_overflow(group['handle'], ctypes.byref(out))
     return bool(out.value)
 
   def emb_owner_ids(self, recv_keys, counts, n_runs, peer_cap, key_sub, ids, counts_out):
@@ -1322,8 +1179,8 @@ class HipBackend(object):
     assert recv_keys.dtype == torch.int32 and ids.dtype == torch.int64 and counts_out.dtype == torch.int32
     assert recv_keys.numel() >= n_runs * (peer_cap + hdr) and ids.numel() >= n_runs * peer_cap and counts_out.numel() >= n_runs
     assert counts is None or (counts.dtype == torch.int32 and counts.numel() >= n_runs)
-    self._ck(self.lib.er_emb_owner_ids(_p(recv_keys), None if counts is None else _p(counts), n_runs, int(peer_cap),
-                                       int(key_sub), _p(ids), _p(counts_out), _stream()), 'er_emb_owner_ids')
+    self.ck.er_emb_owner_ids(_p(recv_keys), None if counts is None else _p(counts), n_runs, int(peer_cap),
+                             int(key_sub), _p(ids), _p(counts_out), _stream())
 
   # owner ids + entry build + merge (+ the serve launch's lag-1 replay table) as one launch - A/B switch
   ep_owner_fused = os.environ.get('EASYREC_AMD_EP_OWNER_FUSED', '1') != '0'
@@ -1332,14 +1189,13 @@ class HipBackend(object):
     """er_emb_owner_ids_merge: emb_owner_ids (runs with their count in front) + emb_owner_merge_padded in one launch."""
     assert recv_keys.dtype == torch.int32 and ids.dtype == torch.int64 and counts_out.dtype == torch.int32
     assert recv_keys.numel() >= n_runs * (peer_cap + 1) and ids.numel() >= n_runs * peer_cap and counts_out.numel() >= n_runs
-    self._ck(self.lib.er_emb_owner_ids_merge(group['handle'], _p(recv_keys), None, n_runs, int(peer_cap), int(key_sub),
-                                             _p(ids), _p(counts_out), 1 if build_tables else 0, _stream()),
-             'er_emb_owner_ids_merge')
+    self.ck.er_emb_owner_ids_merge(group['handle'], _p(recv_keys), None, n_runs, int(peer_cap), int(key_sub),
+                                   _p(ids), _p(counts_out), 1 if build_tables else 0, _stream())
 
   def emb_owner_merge_padded(self, group, counts, n_runs, peer_cap):
     assert counts.dtype == torch.int32 and counts.numel() >= n_runs
-    self._ck(self.lib.er_emb_owner_merge_padded(group['handle'], _p(counts), n_runs,
-                                                int(peer_cap), _stream()), 'er_emb_owner_merge_padded')
+    self.ck.er_emb_owner_merge_padded(group['handle'], _p(counts), n_runs,
+                                      int(peer_cap), _stream())
 
   def emb_owner_serve(self, groups, rows_out, hyper):
     """Catch up (lazy dense decay) and reply the received rows of up to 4 owner groups in one launch."""
@@ -1349,8 +1205,7 @@ class HipBackend(object):
       assert o.stride(1) == 1 and o.dtype == torch.float32 and o.shape[1] == g['dim']
     op = (ctypes.c_void_p * n)(*[o.data_ptr() for o in rows_out])
     ld = (ctypes.c_int32 * n)(*[o.stride(0) for o in rows_out])
-    self._ck(self.lib.er_emb_owner_serve(gh, op, ld, n, None if hyper is None else _p(hyper), _stream()),
-             'er_emb_owner_serve')
+    self.ck.er_emb_owner_serve(gh, op, ld, n, None if hyper is None else _p(hyper), _stream())
 
   def emb_bwd_reduce_dense(self, groups, dense):
     """Per-row gradient sums of the groups straight into their dense [rows, dim + 1] buffers (count in the last
@@ -1361,7 +1216,7 @@ class HipBackend(object):
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
     dp = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dense])
     ld = (ctypes.c_int32 * n)(*[d.stride(0) for d in dense])
-    self._ck(self.lib.er_emb_bwd_reduce_dense(gh, dp, ld, n, _stream()), 'er_emb_bwd_reduce_dense')
+    self.ck.er_emb_bwd_reduce_dense(gh, dp, ld, n, _stream())
 
   def emb_dense_apply(self, tables, opt_kind, hyper):
     """tables: [(var, m, v, dense)] - one pass over each replicated table after the all-reduce of `dense`."""
@@ -1372,25 +1227,23 @@ class HipBackend(object):
       assert all(t is None or t.stride() == var.stride() for t in (m, v))
       descs[i] = DenseApplyDesc(var.data_ptr(), None if m is None else m.data_ptr(), None if v is None else v.data_ptr(),
                                 dense.data_ptr(), dense.stride(0), var.shape[1], var.shape[0], var.stride(0))
-    self._ck(self.lib.er_emb_dense_apply(descs, n, opt_kind, _p(hyper), _stream()), 'er_emb_dense_apply')
+    self.ck.er_emb_dense_apply(descs, n, opt_kind, _p(hyper), _stream())
 
   def emb_mark_touched(self, group):
-    self._ck(self.lib.er_emb_mark_touched(group['handle'], _stream()), 'er_emb_mark_touched')
+    self.ck.er_emb_mark_touched(group['handle'], _stream())
 
   def emb_sweep_untouched(self, group, hyper):
-    self._ck(self.lib.er_emb_sweep_untouched(group['handle'], _p(hyper), _stream()), 'er_emb_sweep_untouched')
+    self.ck.er_emb_sweep_untouched(group['handle'], _p(hyper), _stream())
 
   def stream_copy(self, src, dst):
     nbytes = src.numel() * src.element_size()
     assert dst.numel() * dst.element_size() >= nbytes
-    self._ck(self.lib.er_stream_copy(_p(src), _p(dst), nbytes, _stream()), 'er_stream_copy')
+    self.ck.er_stream_copy(_p(src), _p(dst), nbytes, _stream())
 
   def adam_decay_sweep(self, var, m, v, bitmap, total_rows, dim, hyper):
     ld = var.stride(0) if var.dim() == 2 else dim
     assert var.dim() != 2 or (m.stride() == var.stride() and v.stride() == var.stride() and var.stride(1) == 1)
-    self._ck(
-        self.lib.er_adam_decay_sweep_ld(_p(var), _p(m), _p(v), _p(bitmap), total_rows, dim, ld, _p(hyper), _stream()),
-        'er_adam_decay_sweep_ld')
+    self.ck.er_adam_decay_sweep_ld(_p(var), _p(m), _p(v), _p(bitmap), total_rows, dim, ld, _p(hyper), _stream())
 
   # -- K5 FM / wide
   def fm_fwd(self, x, F, D):
@@ -1398,16 +1251,15 @@ class HipBackend(object):
     B = x.shape[0]
     fm = torch.empty(B, D, dtype=torch.float32, device=x.device)
     S = torch.empty(B, D, dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_fm_fwd(_p(x), B, F, D, x.stride(0), _p(fm), _p(S), _stream()), 'er_fm_fwd')
+    self.ck.er_fm_fwd(_p(x), B, F, D, x.stride(0), _p(fm), _p(S), _stream())
     return fm, S
 
   def fm_bwd(self, x, S, g, F, D, into=None, accumulate=False):
     B = x.shape[0]
     dx = torch.empty(B, F * D, dtype=torch.float32, device=x.device) if into is None else into
     assert dx.shape == (B, F * D) and dx.stride(1) == 1
-    self._ck(
-        self.lib.er_fm_bwd(_p(x), _p(S), _p(_f32c(g)), B, F, D, x.stride(0), _p(dx), dx.stride(0), int(accumulate),
-                           _stream()), 'er_fm_bwd')
+    self.ck.er_fm_bwd(_p(x), _p(S), _p(_f32c(g)), B, F, D, x.stride(0), _p(dx), dx.stride(0), int(accumulate),
+                      _stream())
     return dx
 
   def auc_update(self, probs, labels, weights, thresholds, counts):
@@ -1416,8 +1268,8 @@ class HipBackend(object):
     assert probs.numel() == labels.numel() and counts.dtype == torch.int64 and counts.is_contiguous()
     assert counts.numel() == 2 * (thresholds.numel() + 1)
     w = None if weights is None else _f32c(weights.reshape(-1))
-    self._ck(self.lib.er_auc_update(_p(probs), _p(labels), _p(w), probs.numel(), _p(thresholds),
-                                    thresholds.numel(), _p(counts), _stream()), 'er_auc_update')
+    self.ck.er_auc_update(_p(probs), _p(labels), _p(w), probs.numel(), _p(thresholds),
+                          thresholds.numel(), _p(counts), _stream())
 
   def grouped_auc(self, keys, preds, labels, reduction):
     """gAUC / session AUC of the accumulated rows (int64 keys, fp32 predictions, labels != 0 positive) -> (sum of
@@ -1432,8 +1284,8 @@ class HipBackend(object):
       order = by_pred[torch.sort(keys.reshape(-1)[by_pred], stable=True).indices]
       k, p, y = keys.reshape(-1)[order].contiguous(), preds[order].contiguous(), labels[order].contiguous()
       work = torch.zeros(3 * n, dtype=torch.float64, device=keys.device)
-      self._ck(self.lib.er_grouped_auc(_p(k), _p(p), _p(y), n, int(reduction), _p(work), _p(out),
-                                       _stream()), 'er_grouped_auc')
+      self.ck.er_grouped_auc(_p(k), _p(p), _p(y), n, int(reduction), _p(work), _p(out),
+                             _stream())
     return tuple(float(x) for x in out.cpu().tolist())
 
   def dot_interaction_fwd(self, x, F, D, self_interaction):
@@ -1441,23 +1293,22 @@ class HipBackend(object):
     B = x.shape[0]
     P = F * (F - 1) // 2 + (F if self_interaction else 0)
     out = torch.empty(B, P, dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_dot_interaction_fwd(_p(x), B, F, D, x.stride(0), self_interaction, _p(out),
-                                             out.stride(0), _stream()), 'er_dot_interaction_fwd')
+    self.ck.er_dot_interaction_fwd(_p(x), B, F, D, x.stride(0), self_interaction, _p(out),
+                                   out.stride(0), _stream())
     return out
 
   def dot_interaction_bwd(self, x, g, F, D, self_interaction):
     B = x.shape[0]
     dx = torch.empty(B, F * D, dtype=torch.float32, device=x.device)
     g = _f32c(g)
-    self._ck(self.lib.er_dot_interaction_bwd(_p(x), _p(g), B, F, D, x.stride(0), self_interaction,
-                                             g.stride(0), _p(dx), dx.stride(0), 0, _stream()),
-             'er_dot_interaction_bwd')
+    self.ck.er_dot_interaction_bwd(_p(x), _p(g), B, F, D, x.stride(0), self_interaction,
+                                   g.stride(0), _p(dx), dx.stride(0), 0, _stream())
     return dx
 
   def rowsum_fwd(self, x, n):
     B = x.shape[0]
     out = torch.empty(B, 1, dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_rowsum_fwd(_p(x), B, n, x.stride(0), _p(out), _stream()), 'er_rowsum_fwd')
+    self.ck.er_rowsum_fwd(_p(x), B, n, x.stride(0), _p(out), _stream())
     return out
 
   fused_wide_fm = os.environ.get('EASYREC_AMD_FUSED_WIDE_FM', '1') != '0'  # A/B switch
@@ -1469,8 +1320,8 @@ class HipBackend(object):
     width = 1 + D + n_d
     out = torch.empty(B, (width + 3) // 4 * 4, dtype=torch.float32, device=wide.device)[:, :width]
     S = torch.empty(B, D, dtype=torch.float32, device=wide.device)
-    self._ck(self.lib.er_wide_fm_concat(_p(wide), n_w, wide.stride(0), _p(fm_x), F, D, fm_x.stride(0), _p(deep), n_d,
-                                        deep.stride(0), B, _p(out), out.stride(0), _p(S), _stream()), 'er_wide_fm_concat')
+    self.ck.er_wide_fm_concat(_p(wide), n_w, wide.stride(0), _p(fm_x), F, D, fm_x.stride(0), _p(deep), n_d,
+                              deep.stride(0), B, _p(out), out.stride(0), _p(S), _stream())
     return out, S
 
   def bn_apply_wide_fm(self, pend, wide, fm_x, F, D):
@@ -1497,12 +1348,11 @@ class HipBackend(object):
     """the deferred BatchNorm finalize + apply as the launch of its own it would have been"""
     z = pend['z']
     B, N = z.shape
-    self._ck(self.lib.er_bn_apply_from_stats_b16(_p(z), None, _p(pend['stats']), int(pend['chunks']),
-                                                 _p(pend['gamma']), _p(pend['beta']), B, N, pend['eps'],
-                                                 pend['momentum'], _p(pend['moving_mean']),
-                                                 _p(pend['moving_var']), int(pend['act']), _p(pend['y']), _p(pend['mean']),
-                                                 _p(pend['invstd']), None, 0, _stream()),
-             'er_bn_apply_from_stats')
+    self.ck.er_bn_apply_from_stats_b16(_p(z), None, _p(pend['stats']), int(pend['chunks']),
+                                       _p(pend['gamma']), _p(pend['beta']), B, N, pend['eps'],
+                                       pend['momentum'], _p(pend['moving_mean']),
+                                       _p(pend['moving_var']), int(pend['act']), _p(pend['y']), _p(pend['mean']),
+                                       _p(pend['invstd']), None, 0, _stream())
 
   # the last BatchNorm apply of DeepFM's deep tower inside the [sum(wide) | FM | deep] launch (er_bn_apply_wide_fm) - A/B switch
   defer_bn_apply = os.environ.get('EASYREC_AMD_DEFER_BN_APPLY', '1') != '0'
@@ -1545,11 +1395,11 @@ class HipBackend(object):
       self.op_log.append(('er::gemv_bna_kernel<%d>' % N, 2.0 * M * N * K))
     bn = pend is not None
     y = pend['y'] if bn else None
-    self._ck(self.lib.er_gemv_f32_bn_a(M, N, K, _p(x), x.stride(0), _p(pend['mean']) if bn else None,
-                                       _p(pend['invstd']) if bn else None, _p(pend['gamma']) if bn else None,
-                                       _p(pend['beta']) if bn else None, int(pend['act']) if bn else 0, _p(y),
-                                       y.stride(0) if bn else 0, _p(w), w.stride(0), _p(out),
-                                       out.stride(0), _p(bias), _stream()), 'er_gemv_f32_bn_a')
+    self.ck.er_gemv_f32_bn_a(M, N, K, _p(x), x.stride(0), _p(pend['mean']) if bn else None,
+                             _p(pend['invstd']) if bn else None, _p(pend['gamma']) if bn else None,
+                             _p(pend['beta']) if bn else None, int(pend['act']) if bn else ACT_NONE, _p(y),
+                             y.stride(0) if bn else 0, _p(w), w.stride(0), _p(out),
+                             out.stride(0), _p(bias), _stream())
     return out
 
   def wgrad_tall_narrow_ok(self, x, dz):
@@ -1567,9 +1417,9 @@ class HipBackend(object):
     scratch = torch.empty(513 * (K + 1) * N, dtype=torch.float32, device=x.device)
     if self.op_log is not None:
       self.op_log.append(('er::wgrad_narrow_partial_kernel<%d>' % N, 2.0 * rows * N * K))
-    self._ck(self.lib.er_wgrad_tall_narrow(rows, K, N, _p(x), x.stride(0), _p(dz), dz.stride(0),
-                                           _p(out), out.stride(0), _p(bias_grad), accumulate, _p(scratch),
-                                           scratch.numel(), _stream()), 'er_wgrad_tall_narrow')
+    self.ck.er_wgrad_tall_narrow(rows, K, N, _p(x), x.stride(0), _p(dz), dz.stride(0),
+                                 _p(out), out.stride(0), _p(bias_grad), accumulate, _p(scratch),
+                                 scratch.numel(), _stream())
     return out
 
   def gemm_bn_a(self, pend, w, bias, col_stats=None):
@@ -1579,35 +1429,34 @@ class HipBackend(object):
     z, y = pend['z'], pend['y']
     M, K = z.shape
     N = w.shape[1]
-    self._ck(self.lib.er_bn_finalize_from_stats(_p(pend['stats']), int(pend['chunks']), M, K,
-                                                pend['eps'], pend['momentum'],
-                                                _p(pend['moving_mean']), _p(pend['moving_var']), _p(pend['mean']),
-                                                _p(pend['invstd']), _stream()), 'er_bn_finalize_from_stats')
+    self.ck.er_bn_finalize_from_stats(_p(pend['stats']), int(pend['chunks']), M, K,
+                                      pend['eps'], pend['momentum'],
+                                      _p(pend['moving_mean']), _p(pend['moving_var']), _p(pend['mean']),
+                                      _p(pend['invstd']), _stream())
     if col_stats is None and self.gemv_ok(z, M, N, K):
       return self._gemv(z, pend, w, bias)
     out = torch.empty(M, N, dtype=torch.float32, device=z.device)
     if col_stats is not None:
       assert col_stats.numel() >= self.gemm_row_tiles(M) * N * 3 and col_stats.dtype == torch.float32
     self._log_gemm('gemm_f32_bna_kernel', None, M, N, K)
-    self._ck(self.lib.er_gemm_f32_bn_a(M, N, K, _p(z), z.stride(0), _p(pend['mean']), _p(pend['invstd']),
-                                       _p(pend['gamma']), _p(pend['beta']), int(pend['act']), _p(y),
-                                       y.stride(0), _p(w), w.stride(0), _p(out),
-                                       out.stride(0), _p(bias), _p(col_stats), _stream()), 'er_gemm_f32_bn_a')
+    self.ck.er_gemm_f32_bn_a(M, N, K, _p(z), z.stride(0), _p(pend['mean']), _p(pend['invstd']),
+                             _p(pend['gamma']), _p(pend['beta']), int(pend['act']), _p(y),
+                             y.stride(0), _p(w), w.stride(0), _p(out),
+                             out.stride(0), _p(bias), _p(col_stats), _stream())
     return out
 
   def rowsum_bwd(self, g, n, into=None, accumulate=False):
     B = g.shape[0]
     dx = torch.empty(B, n, dtype=torch.float32, device=g.device) if into is None else into
     assert dx.shape == (B, n) and dx.stride(1) == 1
-    self._ck(self.lib.er_rowsum_bwd(_p(_f32c(g)), B, n, _p(dx), dx.stride(0), int(accumulate), _stream()),
-             'er_rowsum_bwd')
+    self.ck.er_rowsum_bwd(_p(_f32c(g)), B, n, _p(dx), dx.stride(0), int(accumulate), _stream())
     return dx
 
   def group_grad_finish(self, groups):
     """groups: [(dout, out, lambda, has_base, [terms])], term = ('rowsum', g, col0, width) | ('fm', g, saved, col0,
     width, dim); g: [B] / [B, 1] / [B, dim] with unit inner stride.  One launch (er_group_grad_finish)."""
     arr, _keep = self._grad_groups(groups)
-    self._ck(self.lib.er_group_grad_finish(arr, len(groups), _stream()), 'er_group_grad_finish')
+    self.ck.er_group_grad_finish(arr, len(groups), _stream())
 
   # the fused single-GPU embedding step: er_emb_front (build + sort + heads [+ decay table] in one launch, catch-up from
   # the heads) and er_emb_bwd_fused (finish + reduce + row update in one launch) - A/B switch
@@ -1621,7 +1470,7 @@ class HipBackend(object):
     must then be emb_fwd_lazy."""
     n = len(groups)
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
-    flags = (1 if skip_one_row else 0) | (2 if defer else 0)
+    flags = (FRONT_SKIP_ONE_ROW if skip_one_row else 0) | (FRONT_DEFER_CATCH_UP if defer else 0)
     rc = self.lib.er_emb_front(gh, n, flags, _p(hyper), _stream())
     if rc == 3:
       return False
@@ -1632,15 +1481,15 @@ class HipBackend(object):
     """emb_fwd whose lookups into the lazily decaying `groups` catch their rows up in registers (after emb_front(defer))."""
     n = len(groups)
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
-    self._ck(self.lib.er_emb_fwd_lazy(plan['handle'], gh, n, _p(hyper), _p(sumsq_partials), _stream()), 'er_emb_fwd_lazy')
+    self.ck.er_emb_fwd_lazy(plan['handle'], gh, n, _p(hyper), _p(sumsq_partials), _stream())
 
   def emb_front_fwd(self, groups, plan, hyper, skip_one_row, sumsq_partials=None):
     """emb_front(defer=True) + emb_fwd_lazy in one call (one launch when the prologue builds the replay table).
     -> False when the groups need the general path (nothing launched)."""
     n = len(groups)
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
-    rc = self.lib.er_emb_front_fwd(gh, n, (1 if skip_one_row else 0) | 2, plan['handle'], _p(hyper),
-                                   _p(sumsq_partials), _stream())
+    flags = (FRONT_SKIP_ONE_ROW if skip_one_row else 0) | FRONT_DEFER_CATCH_UP
+    rc = self.lib.er_emb_front_fwd(gh, n, flags, plan['handle'], _p(hyper), _p(sumsq_partials), _stream())
     if rc == 3:
       return False
     self._ck(rc, 'er_emb_front_fwd')
@@ -1650,15 +1499,15 @@ class HipBackend(object):
   prologue_tables = os.environ.get('EASYREC_AMD_PROLOGUE_TABLES', '1') != '0'
 
   def decay_tables_set_prologue_build(self, tabs, on):
-    self._ck(self.lib.er_decay_tables_set_prologue_build(tabs['handle'], on), 'er_decay_tables_set_prologue_build')
+    self.ck.er_decay_tables_set_prologue_build(tabs['handle'], on)
     tabs['prologue_build'] = bool(on)
 
   def decay_tables_sync(self, tabs):
-    self._ck(self.lib.er_decay_tables_sync(tabs['handle'], _stream()), 'er_decay_tables_sync')
+    self.ck.er_decay_tables_sync(tabs['handle'], _stream())
 
   def decay_tables_error(self, tabs):
     flag = ctypes.c_int32(0)
-    self._ck(self.lib.er_decay_tables_error(tabs['handle'], ctypes.byref(flag)), 'er_decay_tables_error')
+    self.ck.er_decay_tables_error(tabs['handle'], ctypes.byref(flag))
     return bool(flag.value)
 
   def emb_bwd_fused(self, groups, finish, opt_kind, hyper, wgrads=None, dense_opt=None):
@@ -1680,18 +1529,16 @@ class HipBackend(object):
       if dense_opt is not None:
         w, m, v, grad, l2coef, kind, hyp, l2p = dense_opt
         oj = DenseOptJob(_p(w), _p(m), _p(v), _p(grad), _p(l2coef), w.numel(), int(kind), _p(hyp), _p(l2p))
-      self._ck(self.lib.er_emb_bwd_fused_tail(gh, n, arr, len(finish), opt_kind, _p(hyper), pr, len(wgrads),
-                                              int(self.tail_wgrad_blocks),
-                                              ctypes.byref(lt[0]) if lt is not None else None,
-                                              ctypes.byref(oj) if oj is not None else None, _stream()),
-               'er_emb_bwd_fused_tail')
+      self.ck.er_emb_bwd_fused_tail(gh, n, arr, len(finish), opt_kind, _p(hyper), pr, len(wgrads),
+                                    int(self.tail_wgrad_blocks),
+                                    ctypes.byref(lt[0]) if lt is not None else None,
+                                    ctypes.byref(oj) if oj is not None else None, _stream())
       if oj is not None:
         st = self._bf16_state_of(dense_opt[0])
         if st is not None:
           st.refresh()  # (a bf16 step whose dense optimizer ran in the tail: the weights' bf16 shadows follow the masters)
       return oj is not None
-    self._ck(self.lib.er_emb_bwd_fused(gh, n, arr, len(finish), opt_kind, _p(hyper), _stream()),
-             'er_emb_bwd_fused')
+    self.ck.er_emb_bwd_fused(gh, n, arr, len(finish), opt_kind, _p(hyper), _stream())
     return False
 
   # the riders of the fused tail (er_emb_bwd_fused_tail); A/B switch
@@ -1728,9 +1575,8 @@ class HipBackend(object):
     """y (+)= alpha * x on 2-D views with unit inner stride."""
     rows, cols = x.shape
     assert x.stride(1) == 1 and y.stride(1) == 1 and y.shape == x.shape
-    self._ck(
-        self.lib.er_axpy2d(_p(x), x.stride(0), alpha, _p(y), y.stride(0), rows, cols,
-                           int(accumulate), _stream()), 'er_axpy2d')
+    self.ck.er_axpy2d(_p(x), x.stride(0), alpha, _p(y), y.stride(0), rows, cols,
+                      int(accumulate), _stream())
 
   # -- K6 / K7 cross
   def cross_v1_fwd(self, x0, w, b):
@@ -1738,8 +1584,8 @@ class HipBackend(object):
     L = w.shape[0]
     out = torch.empty_like(x0)
     dots = torch.empty(B, L, dtype=torch.float32, device=x0.device)
-    self._ck(self.lib.er_cross_v1_fwd(_p(_f32c(x0)), _p(_f32c(w)), _p(_f32c(b)), B, d, L, _p(out), _p(dots),
-                                      _stream()), 'er_cross_v1_fwd')
+    self.ck.er_cross_v1_fwd(_p(_f32c(x0)), _p(_f32c(w)), _p(_f32c(b)), B, d, L, _p(out), _p(dots),
+                            _stream())
     return out, dots
 
   def cross_v1_bwd(self, x0, w, b, dots, dout):
@@ -1749,9 +1595,8 @@ class HipBackend(object):
     dx0 = torch.empty_like(x0)
     dwp = torch.empty(npart, L * d, dtype=torch.float32, device=x0.device)
     dbp = torch.empty(npart, L * d, dtype=torch.float32, device=x0.device)
-    self._ck(
-        self.lib.er_cross_v1_bwd(_p(x0), _p(w), _p(b), _p(dots), _p(_f32c(dout)), B, d, L, _p(dx0), _p(dwp),
-                                 _p(dbp), _stream()), 'er_cross_v1_bwd')
+    self.ck.er_cross_v1_bwd(_p(x0), _p(w), _p(b), _p(dots), _p(_f32c(dout)), B, d, L, _p(dx0), _p(dwp),
+                            _p(dbp), _stream())
     dw = self.colsum(dwp).view(L, d)
     db = self.colsum(dbp).view(L, d)
     return dx0, dw, db
@@ -1759,19 +1604,15 @@ class HipBackend(object):
   def cross_v2_fwd(self, x0, x, u, bias, diag_scale):
     B, d = x0.shape
     out = torch.empty_like(x0)
-    self._ck(
-        self.lib.er_cross_v2_epilogue_fwd(_p(_f32c(x0)), _p(_f32c(x)), _p(_f32c(u)), _p(bias),
-                                          diag_scale, B, d, _p(out), _stream()),
-        'er_cross_v2_epilogue_fwd')
+    self.ck.er_cross_v2_epilogue_fwd(_p(_f32c(x0)), _p(_f32c(x)), _p(_f32c(u)), _p(bias),
+                                     diag_scale, B, d, _p(out), _stream())
     return out
 
   def cross_v2_bwd(self, x0, x, u, bias, diag_scale, dout):
     B, d = x0.shape
     dx0, dx, du = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
-    self._ck(
-        self.lib.er_cross_v2_epilogue_bwd(_p(x0), _p(x), _p(u), _p(bias), diag_scale,
-                                          _p(_f32c(dout)), B, d, _p(dx0), 0, _p(dx), _p(du), _stream()),
-        'er_cross_v2_epilogue_bwd')
+    self.ck.er_cross_v2_epilogue_bwd(_p(x0), _p(x), _p(u), _p(bias), diag_scale,
+                                     _p(_f32c(dout)), B, d, _p(dx0), 0, _p(dx), _p(du), _stream())
     return dx0, dx, du
 
   # The DCN-v2 cross layer as ONE launch forward and one or two backward (north_star: "DCN-cross ... as fused HIP kernels";
@@ -1806,9 +1647,9 @@ class HipBackend(object):
       self.gemm_bf16_nt(st.act(x, cache=True), t, B, d, d, out=out, out_bf16=st.new_copy(out), bias=bias, epi=epi)
     else:
       self._log_gemm('gemm_f32_cross_kernel<true, false, 3>', None, B, d, d)
-      self._ck(self.lib.er_gemm_f32_cross(GEMM_NN, B, d, d, _p(x), x.stride(0), _p(w),
-                                          w.stride(0), _p(out), out.stride(0), _p(bias), 0,
-                                          ctypes.byref(epi), _stream()), 'er_gemm_f32_cross')
+      self.ck.er_gemm_f32_cross(GEMM_NN, B, d, d, _p(x), x.stride(0), _p(w),
+                                w.stride(0), _p(out), out.stride(0), _p(bias), 0,
+                                ctypes.byref(epi), _stream())
     return out, u
 
   def cross_bwd_top(self, x0, x, u, bias, diag, dout, dx0, acc0, bf16, w):
@@ -1822,9 +1663,9 @@ class HipBackend(object):
     if st:
       dub = torch.empty(B, st.pad8(d), dtype=torch.bfloat16, device=x0.device)  # (the kernel zeroes the k-tail columns)
       st.register(du, dub)
-    self._ck(self.lib.er_cross_v2_bwd_top(_p(x0), _p(x), _p(u), _p(bias), diag, _p(dout), dout.stride(0), B, d, _p(dx0),
-                                          dx0.stride(0), acc0, _p(du), _p(dub), 0 if dub is None else dub.stride(0),
-                                          _p(partial), _stream()), 'er_cross_v2_bwd_top')
+    self.ck.er_cross_v2_bwd_top(_p(x0), _p(x), _p(u), _p(bias), diag, _p(dout), dout.stride(0), B, d, _p(dx0),
+                                dx0.stride(0), acc0, _p(du), _p(dub), 0 if dub is None else dub.stride(0),
+                                _p(partial), _stream())
     return du, partial
 
   def cross_dgrad_fused(self, du, w, dout, diag, bf16, dst, acc, prev=None):
@@ -1859,8 +1700,8 @@ class HipBackend(object):
       self.gemm_bf16_nt(st.act(du), plain, B, d, d, out=dst, accumulate=acc, epi=epi)
     else:
       self._log_gemm('gemm_f32_cross_kernel<true, true, 4>', None, B, d, d)
-      self._ck(self.lib.er_gemm_f32_cross(GEMM_NT, B, d, d, _p(du), du.stride(0), _p(w), w.stride(0), _p(dst),
-                                          dst.stride(0), None, acc, ctypes.byref(epi), _stream()), 'er_gemm_f32_cross')
+      self.ck.er_gemm_f32_cross(GEMM_NT, B, d, d, _p(du), du.stride(0), _p(w), w.stride(0), _p(dst),
+                                dst.stride(0), None, acc, ctypes.byref(epi), _stream())
     return du_prev, partial
 
   def cross_v2_bwd_acc(self, x0, x, u, bias, diag_scale, dout, dx0, acc0, dx, accx):
@@ -1870,18 +1711,17 @@ class HipBackend(object):
     du = torch.empty_like(x0)
     assert dx0.stride(1) == 1 and (dx is None or dx.stride(1) == 1)
     assert dout.dim() == 2 and dout.stride(1) == 1 and dout.dtype == torch.float32
-    self._ck(self.lib.er_cross_v2_epilogue_bwd_acc(_p(x0), _p(x), _p(u), _p(bias), diag_scale, _p(dout),
-                                                   dout.stride(0), B, d, _p(dx0), dx0.stride(0), acc0, _p(dx),
-                                                   dx.stride(0) if dx is not None else 0, accx,
-                                                   _p(du), _stream()), 'er_cross_v2_epilogue_bwd_acc')
+    self.ck.er_cross_v2_epilogue_bwd_acc(_p(x0), _p(x), _p(u), _p(bias), diag_scale, _p(dout),
+                                         dout.stride(0), B, d, _p(dx0), dx0.stride(0), acc0, _p(dx),
+                                         dx.stride(0) if dx is not None else 0, accx,
+                                         _p(du), _stream())
     return du
 
   # -- K8 DIN
   def din_concat_fwd(self, q, h):
     B, L, E = h.shape
     out = torch.empty(B, L, 4 * E, dtype=torch.float32, device=h.device)
-    self._ck(self.lib.er_din_concat_fwd(_p(_f32c(q)), _p(_f32c(h)), B, L, E, _p(out), _stream()),
-             'er_din_concat_fwd')
+    self.ck.er_din_concat_fwd(_p(_f32c(q)), _p(_f32c(h)), B, L, E, _p(out), _stream())
     return out
 
   def din_concat_bwd(self, q, h, dout, dh=None, acc_h=False):
@@ -1892,9 +1732,7 @@ class HipBackend(object):
       assert not acc_h
       dh = torch.empty_like(h)
     assert dh.shape == h.shape and dh.is_contiguous()
-    self._ck(
-        self.lib.er_din_concat_bwd(_p(q), _p(h), _p(_f32c(dout)), B, L, E, _p(dq), 0, _p(dh), acc_h, _stream()),
-        'er_din_concat_bwd')
+    self.ck.er_din_concat_bwd(_p(q), _p(h), _p(_f32c(dout)), B, L, E, _p(dq), 0, _p(dh), acc_h, _stream())
     return dq, dh
 
   # DIN's first attention layer on the GENERATED [q, h, q - h, q * h] operand (er_din_gemm_*): the [B, L, 4E] block exists
@@ -1917,8 +1755,8 @@ class HipBackend(object):
     N = w.shape[1]
     z = torch.empty(B * L, N, dtype=torch.float32, device=h.device)
     self._log_gemm('gemm_f32_din_kernel<true, false, 1>', None, B * L, N, 4 * E)
-    self._ck(self.lib.er_din_gemm_fwd(_p(q), q.stride(0), _p(h), E, B, L, E, _p(w), w.stride(0), N, _p(bias), _p(z), N,
-                                      _p(col_stats), _stream()), 'er_din_gemm_fwd')
+    self.ck.er_din_gemm_fwd(_p(q), q.stride(0), _p(h), E, B, L, E, _p(w), w.stride(0), N, _p(bias), _p(z), N,
+                            _p(col_stats), _stream())
     return z
 
   def din_gemm_wgrad(self, q, h, dz, out, accumulate=True):
@@ -1927,8 +1765,8 @@ class HipBackend(object):
     N = dz.shape[1]
     assert dz.shape[0] == B * L and dz.stride(1) == 1 and out.shape == (4 * E, N) and out.stride(1) == 1
     self._log_gemm('gemm_f32_din_kernel<false, false, 1>', None, 4 * E, N, B * L)
-    self._ck(self.lib.er_din_gemm_wgrad(_p(q), q.stride(0), _p(h), E, B, L, E, _p(dz), dz.stride(0), N, _p(out),
-                                        out.stride(0), accumulate, _stream()), 'er_din_gemm_wgrad')
+    self.ck.er_din_gemm_wgrad(_p(q), q.stride(0), _p(h), E, B, L, E, _p(dz), dz.stride(0), N, _p(out),
+                              out.stride(0), accumulate, _stream())
     return out
 
   def din_gemm_dgrad(self, dz, w, q, h, dh=None, acc_h=False):
@@ -1944,17 +1782,16 @@ class HipBackend(object):
     n_part = int(self.lib.er_din_dq_partial_floats(B, L, E))
     partial = torch.empty(n_part, dtype=torch.float32, device=h.device)
     self._log_gemm('gemm_f32_din_kernel<true, true, 2>', None, B * L, 4 * E, N)
-    self._ck(self.lib.er_din_gemm_dgrad(_p(dz), dz.stride(0), N, _p(w), w.stride(0), _p(q), q.stride(0), _p(h), E, B, L,
-                                        E, _p(dq), E, _p(dh), E, acc_h, _p(partial), _stream()), 'er_din_gemm_dgrad')
+    self.ck.er_din_gemm_dgrad(_p(dz), dz.stride(0), N, _p(w), w.stride(0), _p(q), q.stride(0), _p(h), E, B, L,
+                              E, _p(dq), E, _p(dh), E, acc_h, _p(partial), _stream())
     return dq, dh
 
   def din_pool_fwd(self, scores, hist, seq_len, scale=1.0):
     B, L, E = hist.shape
     probs = torch.empty(B, L, dtype=torch.float32, device=hist.device)
     out = torch.empty(B, E, dtype=torch.float32, device=hist.device)
-    self._ck(
-        self.lib.er_din_pool_fwd(_p(_f32c(scores)), _p(_f32c(hist)), _p(seq_len), B, L, E, scale,
-                                 _p(probs), _p(out), _stream()), 'er_din_pool_fwd')
+    self.ck.er_din_pool_fwd(_p(_f32c(scores)), _p(_f32c(hist)), _p(seq_len), B, L, E, scale,
+                            _p(probs), _p(out), _stream())
     return out, probs
 
   def din_pool_bwd(self, probs, hist, seq_len, dout, scale=1.0, dhist=None, acc_h=False):
@@ -1964,17 +1801,16 @@ class HipBackend(object):
       assert not acc_h
       dhist = torch.empty_like(hist)
     assert dhist.shape == hist.shape and dhist.is_contiguous()
-    self._ck(
-        self.lib.er_din_pool_bwd(_p(probs), _p(hist), _p(seq_len), _p(_f32c(dout)), B, L, E,
-                                 scale, _p(dscores), _p(dhist), acc_h, _stream()), 'er_din_pool_bwd')
+    self.ck.er_din_pool_bwd(_p(probs), _p(hist), _p(seq_len), _p(_f32c(dout)), B, L, E,
+                            scale, _p(dscores), _p(dhist), acc_h, _stream())
     return dscores, dhist
 
   # -- K8e the gradient reduce of the blocks with packed parameters (K8b, K8d)
   def theta_grad_reduce(self, partials, rows, grads, row_groups, acc):
     """`grads` (a ThetaGradTable) (+)= the sum over the rows of partials [rows, P]; row_groups (1 or 8) is the
     summation order easyrec_hip.h states."""
-    self._ck(self.lib.er_theta_grad_reduce(_p(partials), rows, partials.numel() // rows, grads.lens, len(grads.grads),
-                                           grads.table, row_groups, bool(acc), _stream()), 'er_theta_grad_reduce')
+    self.ck.er_theta_grad_reduce(_p(partials), rows, partials.numel() // rows, grads.lens, len(grads.grads),
+                                 grads.table, row_groups, bool(acc), _stream())
 
   # -- K8b BST transformer block (model/multi_tower_bst.py)
   BST_MAX_T = 64
@@ -2000,8 +1836,8 @@ class HipBackend(object):
     B, L, E = hist.shape
     assert key.shape == (B, E) and seq_len.dtype == torch.int32
     out = torch.empty(B, T * E, dtype=torch.float32, device=hist.device)
-    self._ck(self.lib.er_bst_fwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), B, L, T,
-                                 E, H, _p(out), _stream()), 'er_bst_fwd')
+    self.ck.er_bst_fwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), B, L, T,
+                       E, H, _p(out), _stream())
     if self.op_log is not None:
       self.op_log.append(('er::bst_fwd_kernel', self._bst_flops(B, T, E, H)))
     return out
@@ -2017,8 +1853,8 @@ class HipBackend(object):
     assert dhist.shape == hist.shape and dhist.is_contiguous()
     rows = self.bst_grid(B)
     partials = torch.empty(rows * self.bst_param_count(E, H), dtype=torch.float32, device=hist.device)
-    self._ck(self.lib.er_bst_bwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), _p(_f32c(dout)), B, L,
-                                 T, E, H, _p(dkey), _p(dhist), acc_h, _p(partials), _stream()), 'er_bst_bwd')
+    self.ck.er_bst_bwd(_p(_f32c(key)), _p(_f32c(hist)), _p(seq_len), _p(_f32c(theta)), _p(_f32c(dout)), B, L,
+                       T, E, H, _p(dkey), _p(dhist), acc_h, _p(partials), _stream())
     self.theta_grad_reduce(partials, rows, grads, 1, True)
     if self.op_log is not None:
       self.op_log.append(('er::bst_bwd_kernel', 2.0 * self._bst_flops(B, T, E, H)))
@@ -2038,8 +1874,8 @@ class HipBackend(object):
     din, d = wq.shape
     assert all(w.shape == (din, d) for w in (wk, wv, wr))
     out = torch.empty(din, 4 * d, dtype=torch.float32, device=wq.device)
-    self._ck(self.lib.er_autoint_pack(_p(_f32c(wq)), _p(_f32c(wk)), _p(_f32c(wv)), _p(_f32c(wr)), din, d, _p(out),
-                                      _stream()), 'er_autoint_pack')
+    self.ck.er_autoint_pack(_p(_f32c(wq)), _p(_f32c(wk)), _p(_f32c(wv)), _p(_f32c(wr)), din, d, _p(out),
+                            _stream())
     return out
 
   def autoint_attn_fwd(self, qkvr, F, H, ds):
@@ -2049,8 +1885,7 @@ class HipBackend(object):
     assert w == 4 * d and rows % F == 0
     B = rows // F
     y = torch.empty(rows, d, dtype=torch.float32, device=qkvr.device)
-    self._ck(self.lib.er_autoint_attn_fwd(_p(_f32c(qkvr)), B, F, H, ds, _p(y), _stream()),
-             'er_autoint_attn_fwd')
+    self.ck.er_autoint_attn_fwd(_p(_f32c(qkvr)), B, F, H, ds, _p(y), _stream())
     if self.op_log is not None:
       self.op_log.append(('er::autoint_attn_fwd_kernel', 4.0 * B * F * F * d))
     return y
@@ -2061,8 +1896,8 @@ class HipBackend(object):
     B = rows // F
     assert y.shape == dy.shape == (rows, H * ds)
     dq = torch.empty_like(qkvr)
-    self._ck(self.lib.er_autoint_attn_bwd(_p(_f32c(qkvr)), _p(_f32c(y)), _p(_f32c(dy)), B, F, H, ds,
-                                          _p(dq), _stream()), 'er_autoint_attn_bwd')
+    self.ck.er_autoint_attn_bwd(_p(_f32c(qkvr)), _p(_f32c(y)), _p(_f32c(dy)), B, F, H, ds,
+                                _p(dq), _stream())
     if self.op_log is not None:
       self.op_log.append(('er::autoint_attn_bwd_kernel', 12.0 * B * F * F * H * ds))
     return dq
@@ -2084,8 +1919,8 @@ class HipBackend(object):
     assert x.shape == (B, F * D) and theta.numel() == self.bilinear_param_count(F, D, each)
     pairs = F * (F - 1) // 2
     out = torch.empty(B, pairs if plus else pairs * D, dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_bilinear_fwd(_p(_f32c(x)), _p(_f32c(theta)), B, F, D, bool(each), bool(plus), _p(out),
-                                      _stream()), 'er_bilinear_fwd')
+    self.ck.er_bilinear_fwd(_p(_f32c(x)), _p(_f32c(theta)), B, F, D, bool(each), bool(plus), _p(out),
+                            _stream())
     if self.op_log is not None:
       self.op_log.append(('er::bilinear_fwd_kernel', 2.0 * B * ((F - 1) * D * D + pairs * D)))
     return out
@@ -2099,8 +1934,8 @@ class HipBackend(object):
     dx = torch.empty_like(x)
     rows = int(self.lib.er_bilinear_grid(B, F, D, bool(each)))
     partials = torch.empty(rows * theta.numel(), dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_bilinear_bwd(_p(_f32c(x)), _p(_f32c(theta)), _p(_f32c(dout)), B, F, D, bool(each), bool(plus),
-                                      _p(dx), _p(partials), _stream()), 'er_bilinear_bwd')
+    self.ck.er_bilinear_bwd(_p(_f32c(x)), _p(_f32c(theta)), _p(_f32c(dout)), B, F, D, bool(each), bool(plus),
+                            _p(dx), _p(partials), _stream())
     self.theta_grad_reduce(partials, rows, grads, 8, acc)
     if self.op_log is not None:
       self.op_log.append(('er::bilinear_bwd_kernel', 6.0 * B * ((F - 1) * D * D + pairs * D)))
@@ -2122,8 +1957,8 @@ class HipBackend(object):
     assert x.shape == (B, F * D) and theta.numel() == self.senet_param_count(F, D, G, R, ln)
     y = torch.empty_like(x)
     a1 = torch.empty(B, R, dtype=torch.float32, device=x.device) if want_a1 else None
-    self._ck(self.lib.er_senet_fwd(_p(_f32c(x)), _p(_f32c(theta)), B, F, D, G, R, bool(skip), bool(ln), _p(y),
-                                   None if a1 is None else _p(a1), _stream()), 'er_senet_fwd')
+    self.ck.er_senet_fwd(_p(_f32c(x)), _p(_f32c(theta)), B, F, D, G, R, bool(skip), bool(ln), _p(y),
+                         None if a1 is None else _p(a1), _stream())
     if self.op_log is not None:
       self.op_log.append(('er::senet_fwd_kernel', 2.0 * B * R * (2 * F * G + F * D)))
     return (y, a1) if want_a1 else y
@@ -2135,8 +1970,8 @@ class HipBackend(object):
     dx = torch.empty_like(x)
     rows = int(self.lib.er_senet_grid(B, F, D, G, R, bool(ln)))
     partials = torch.empty(rows * theta.numel(), dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_senet_bwd(_p(_f32c(x)), _p(_f32c(theta)), _p(_f32c(dy)), B, F, D, G, R, bool(skip), bool(ln),
-                                   _p(dx), _p(partials), _stream()), 'er_senet_bwd')
+    self.ck.er_senet_bwd(_p(_f32c(x)), _p(_f32c(theta)), _p(_f32c(dy)), B, F, D, G, R, bool(skip), bool(ln),
+                         _p(dx), _p(partials), _stream())
     self.theta_grad_reduce(partials, rows, grads, 8, acc)
     if self.op_log is not None:
       self.op_log.append(('er::senet_bwd_kernel', 6.0 * B * R * (2 * F * G + F * D)))
@@ -2153,15 +1988,14 @@ class HipBackend(object):
     R, D = x.shape
     y = torch.empty_like(x)
     inv = torch.empty(R, dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_match_normalize_fwd(_p(_f32c(x)), R, D, _p(y), _p(inv), _stream()), 'er_match_normalize_fwd')
+    self.ck.er_match_normalize_fwd(_p(_f32c(x)), R, D, _p(y), _p(inv), _stream())
     return y, inv
 
   def match_normalize_bwd(self, x, inv, dy):
     R, D = x.shape
     assert dy.shape == x.shape
     dx = torch.empty_like(x)
-    self._ck(self.lib.er_match_normalize_bwd(_p(_f32c(x)), _p(inv), _p(_f32c(dy)), R, D, _p(dx), _stream()),
-             'er_match_normalize_bwd')
+    self.ck.er_match_normalize_bwd(_p(_f32c(x)), _p(inv), _p(_f32c(dy)), R, D, _p(dx), _stream())
     return dx
 
   @staticmethod
@@ -2180,10 +2014,10 @@ class HipBackend(object):
     stats = torch.empty(4, B, dtype=torch.float32, device=U.device)
     partials = torch.empty(int(self.lib.er_match_grid(B)) * 3, dtype=torch.float32, device=U.device)
     losses = torch.empty(3, dtype=torch.float32, device=U.device)
-    self._ck(self.lib.er_match_softmax_fwd(
+    self.ck.er_match_softmax_fwd(
         _p(_f32c(U)), _p(_f32c(I)), B, M, D, float(inv_temperature), _p(sim_w), _p(sim_b), _p(item_ids),
         bool(ignore_in_batch), None if weight is None else _p(_f32c(weight)), _p(stats[0]), _p(stats[1]), _p(stats[2]),
-        _p(stats[3]), _p(partials), _p(losses), _stream()), 'er_match_softmax_fwd')
+        _p(stats[3]), _p(partials), _p(losses), _stream())
     if self.op_log is not None:
       self.op_log.append(('er::match_fwd_kernel', 2.0 * B * M * D))
     return losses, stats
@@ -2196,10 +2030,10 @@ class HipBackend(object):
     dU, dI = torch.empty_like(U), torch.empty_like(I)
     rows = int(self.lib.er_match_grid(B))
     partials = torch.empty(rows * 2, dtype=torch.float32, device=U.device)
-    self._ck(self.lib.er_match_softmax_bwd(
+    self.ck.er_match_softmax_bwd(
         _p(_f32c(U)), _p(_f32c(I)), B, M, D, float(inv_temperature), _p(sim_w), _p(sim_b), _p(item_ids),
         bool(ignore_in_batch), None if weight is None else _p(_f32c(weight)), _p(stats[0]), _p(stats[1]), _p(stats[3]),
-        _p(losses), _p(_f32c(g_ce)), _p(_f32c(g_reg)), _p(dU), _p(dI), _p(partials), _stream()), 'er_match_softmax_bwd')
+        _p(losses), _p(_f32c(g_ce)), _p(_f32c(g_reg)), _p(dU), _p(dI), _p(partials), _stream())
     if grads is not None:
       self.theta_grad_reduce(partials, rows, grads, 1, acc)
     if self.op_log is not None:
@@ -2211,9 +2045,9 @@ class HipBackend(object):
     B, M, D = self._match_operands(U, I, item_ids, None)
     c_in = torch.empty(B, dtype=torch.int32, device=U.device)
     c_neg = torch.empty(B, dtype=torch.int32, device=U.device)
-    self._ck(self.lib.er_match_rank_counts(
+    self.ck.er_match_rank_counts(
         _p(_f32c(U)), _p(_f32c(I)), B, M, D, float(inv_temperature), _p(sim_w), _p(sim_b), _p(item_ids),
-        bool(ignore_in_batch), _p(c_in), _p(c_neg), _stream()), 'er_match_rank_counts')
+        bool(ignore_in_batch), _p(c_in), _p(c_neg), _stream())
     return c_in, c_neg
 
   # -- K1b negative_sampler_in_memory (input/neg_sampler.py)
@@ -2240,9 +2074,9 @@ class HipBackend(object):
       outs.append(out.data_ptr())
       sizes.append(tab.element_size())
     ptrs = ctypes.c_void_p * max(nc, 1)
-    self._ck(self.lib.er_neg_sample(
+    self.ck.er_neg_sample(
         _p(table_ids), n, _p(batch_ids), B, int(N), _p(step), int(step_offset), int(seed) & 0xFFFFFFFFFFFFFFFF, ptrs(*tabs),
-        ptrs(*bats), ptrs(*outs), (ctypes.c_int32 * max(nc, 1))(*sizes), nc, _p(sel), _stream()), 'er_neg_sample')
+        ptrs(*bats), ptrs(*outs), (ctypes.c_int32 * max(nc, 1))(*sizes), nc, _p(sel), _stream())
 
   # -- K9k full-corpus top-K search and hit count (core/knn.py, core/hit_rate.py)
   def knn_lds_bytes(self, D, K):
@@ -2255,7 +2089,7 @@ class HipBackend(object):
     """items [n, D] -> xx [n]: the fmaf chain over x_d^2 of every row."""
     n, D = items.shape
     xx = torch.empty(n, dtype=torch.float32, device=items.device)
-    self._ck(self.lib.er_knn_norms(_p(_f32c(items)), n, D, _p(xx), _stream()), 'er_knn_norms')
+    self.ck.er_knn_norms(_p(_f32c(items)), n, D, _p(xx), _stream())
     return xx
 
   def knn_search(self, queries, items, xx, table_ids, K, metric, slices=0):
@@ -2273,9 +2107,9 @@ class HipBackend(object):
     ids = torch.empty(nq, K, dtype=torch.int64, device=dev)
     rows = torch.empty(nq, K, dtype=torch.int32, device=dev)
     dist = torch.empty(nq, K, dtype=torch.float32, device=dev)
-    self._ck(self.lib.er_knn_search(
+    self.ck.er_knn_search(
         _p(_f32c(queries)), _p(items), None if xx is None else _p(xx), _p(table_ids), nq, n, D, int(K), int(metric),
-        int(slices), _p(work), _p(ids), _p(rows), _p(dist), _stream()), 'er_knn_search')
+        int(slices), _p(work), _p(ids), _p(rows), _p(dist), _stream())
     if self.op_log is not None:
       self.op_log.append(('er::knn_scan_kernel', 2.0 * nq * n * D))
     return ids, rows, dist
@@ -2289,8 +2123,8 @@ class HipBackend(object):
     assert gt_ids.dtype == torch.int64 and gt_ids.is_contiguous()
     hits = torch.empty(U, dtype=torch.int32, device=ids.device)
     gt_count = torch.empty(U, dtype=torch.int32, device=ids.device)
-    self._ck(self.lib.er_knn_hits(_p(ids), _p(user_emb_num), _p(gt_offsets), _p(gt_ids), U, I, K, _p(hits),
-                                  _p(gt_count), _stream()), 'er_knn_hits')
+    self.ck.er_knn_hits(_p(ids), _p(user_emb_num), _p(gt_offsets), _p(gt_ids), U, I, K, _p(hits),
+                        _p(gt_count), _stream())
     return hits, gt_count
 
   # -- K8g MIND's capsule layer and label-aware attention (layers/capsule_layer.py, model/mind.py)
@@ -2314,9 +2148,9 @@ class HipBackend(object):
     high = torch.empty(B, K, E, dtype=torch.float32, device=hist.device)
     ncaps = torch.empty(B, dtype=torch.int32, device=hist.device)
     W = torch.empty(B, S, K, dtype=torch.float32, device=hist.device)
-    self._ck(self.lib.er_capsule_fwd(_p(_f32c(hist)), _p(seq_len), _p(_f32c(Smat)), _p(logits0), stride, B, L, S, D, E, K,
-                                     int(num_iters), float(scale), float(squash_pow), float(scale_ratio), bool(const_caps),
-                                     _p(high), _p(ncaps), _p(W), _stream()), 'er_capsule_fwd')
+    self.ck.er_capsule_fwd(_p(_f32c(hist)), _p(seq_len), _p(_f32c(Smat)), _p(logits0), stride, B, L, S, D, E, K,
+                           int(num_iters), float(scale), float(squash_pow), float(scale_ratio), bool(const_caps),
+                           _p(high), _p(ncaps), _p(W), _stream())
     if self.op_log is not None:
       self.op_log.append(('er::capsule_fwd_kernel', 2.0 * B * S * E * (D + K * (2 * num_iters - 1))))
     return high, ncaps, W
@@ -2335,9 +2169,9 @@ class HipBackend(object):
     assert dhist.shape == hist.shape and dhist.is_contiguous()
     rows = self.capsule_grid(B)
     partials = torch.empty(rows * D * E, dtype=torch.float32, device=hist.device)
-    self._ck(self.lib.er_capsule_bwd(_p(_f32c(hist)), _p(seq_len), _p(_f32c(Smat)), _p(_f32c(W)), _p(_f32c(d_high)), B, L,
-                                     S, D, E, K, float(squash_pow), float(scale_ratio), bool(const_caps), _p(dhist),
-                                     bool(acc_h), _p(partials), _stream()), 'er_capsule_bwd')
+    self.ck.er_capsule_bwd(_p(_f32c(hist)), _p(seq_len), _p(_f32c(Smat)), _p(_f32c(W)), _p(_f32c(d_high)), B, L,
+                           S, D, E, K, float(squash_pow), float(scale_ratio), bool(const_caps), _p(dhist),
+                           bool(acc_h), _p(partials), _stream())
     self.theta_grad_reduce(partials, rows, grads, 1, acc)
     if self.op_log is not None:
       self.op_log.append(('er::capsule_bwd_kernel', 2.0 * B * S * E * (3 * D + 2 * K)))
@@ -2351,8 +2185,8 @@ class HipBackend(object):
     emb = torch.empty(B, E, dtype=torch.float32, device=interests.device)
     ui = torch.empty_like(interests)
     w = torch.empty(B, K, dtype=torch.float32, device=interests.device)
-    self._ck(self.lib.er_mind_attention_fwd(_p(_f32c(interests)), _p(_f32c(pos_item)), _p(num_caps), B, K, E,
-                                            float(simi_pow), _p(emb), _p(ui), _p(w), _stream()), 'er_mind_attention_fwd')
+    self.ck.er_mind_attention_fwd(_p(_f32c(interests)), _p(_f32c(pos_item)), _p(num_caps), B, K, E,
+                                  float(simi_pow), _p(emb), _p(ui), _p(w), _stream())
     return emb, ui, w
 
   def mind_attention_bwd(self, interests, pos_item, num_caps, weights, d_emb, d_ui, simi_pow):
@@ -2361,9 +2195,9 @@ class HipBackend(object):
     assert d_emb.shape == (B, E) and (d_ui is None or d_ui.shape == (B, K, E))
     di = torch.empty_like(interests)
     dp = torch.empty_like(pos_item)
-    self._ck(self.lib.er_mind_attention_bwd(_p(_f32c(interests)), _p(_f32c(pos_item)), _p(num_caps), _p(weights),
-                                            _p(_f32c(d_emb)), None if d_ui is None else _p(_f32c(d_ui)), B, K, E,
-                                            float(simi_pow), _p(di), _p(dp), _stream()), 'er_mind_attention_bwd')
+    self.ck.er_mind_attention_bwd(_p(_f32c(interests)), _p(_f32c(pos_item)), _p(num_caps), _p(weights),
+                                  _p(_f32c(d_emb)), None if d_ui is None else _p(_f32c(d_ui)), B, K, E,
+                                  float(simi_pow), _p(di), _p(dp), _stream())
     return di, dp
 
   # -- K1b hash-table (KV) embedding tables
@@ -2407,7 +2241,7 @@ class HipBackend(object):
     assert ids.dtype == torch.int64 and rows_out.dtype == torch.int64 and ids.is_contiguous() and rows_out.is_contiguous()
     assert ids.numel() == rows_out.numel()
     job = self._kv_job(kv, ids, rows_out)
-    self._ck(self.lib.er_kv_translate_job(ctypes.byref(job), insert, _stream()), 'er_kv_translate_job')
+    self.ck.er_kv_translate_job(ctypes.byref(job), insert, _stream())
 
   def kv_jobs_create(self, jobs):
     """jobs: [(kv, ids, rows_out[, n_limit])] -> the device-resident descriptor table of er_kv_translate_multi (built
@@ -2430,8 +2264,8 @@ class HipBackend(object):
   def kv_translate_multi(self, handle, insert):
     if handle['blocks'] == 0:
       return
-    self._ck(self.lib.er_kv_translate_multi(_p(handle['table']), _p(handle['blk_start']), handle['n'], handle['blocks'],
-                                            insert, _stream()), 'er_kv_translate_multi')
+    self.ck.er_kv_translate_multi(_p(handle['table']), _p(handle['blk_start']), handle['n'], handle['blocks'],
+                                  insert, _stream())
 
   def kv_route_create(self, jobs, world):
     """Embedding-parallel hash tables: jobs [(ids, rows_out[, n_limit])] -> the buffers and descriptor table of
@@ -2461,13 +2295,13 @@ class HipBackend(object):
 
   def kv_bucket(self, h):
     if h['blocks']:
-      self._ck(self.lib.er_kv_bucket(_p(h['table']), _p(h['blk_start']), h['n'], h['blocks'], h['world'], h['C'],
-                                     _p(h['send']), _p(h['counts']), _stream()), 'er_kv_bucket')
+      self.ck.er_kv_bucket(_p(h['table']), _p(h['blk_start']), h['n'], h['blocks'], h['world'], h['C'],
+                           _p(h['send']), _p(h['counts']), _stream())
 
   def kv_unbucket(self, h):
     if h['blocks']:
-      self._ck(self.lib.er_kv_unbucket(_p(h['table']), _p(h['blk_start']), h['n'], h['blocks'], h['world'],
-                                       h['C'], _p(h['back']), _stream()), 'er_kv_unbucket')
+      self.ck.er_kv_unbucket(_p(h['table']), _p(h['blk_start']), h['n'], h['blocks'], h['world'],
+                             h['C'], _p(h['back']), _stream())
 
   def kv_export(self, kv):
     """(keys ascending, arena rows) of the table's materialised ids (host sync)."""
@@ -2475,8 +2309,8 @@ class HipBackend(object):
     keys = torch.empty(n_max, dtype=torch.int64, device=kv['keys'].device)
     rows = torch.empty(n_max, dtype=torch.int32, device=kv['keys'].device)
     count = torch.zeros(1, dtype=torch.int32, device=kv['keys'].device)
-    self._ck(self.lib.er_kv_export(_p(kv['keys']), _p(kv['rows']), kv['keys'].numel(), _p(keys), _p(rows),
-                                   _p(count), _stream()), 'er_kv_export')
+    self.ck.er_kv_export(_p(kv['keys']), _p(kv['rows']), kv['keys'].numel(), _p(keys), _p(rows),
+                         _p(count), _stream())
     n = int(count.item())
     keys, rows = keys[:n], rows[:n]
     order = torch.argsort(keys)
@@ -2491,9 +2325,8 @@ class HipBackend(object):
     keys = torch.empty(n_max, dtype=torch.int64, device=dev)
     rows, freq, version = (torch.empty(n_max, dtype=torch.int32, device=dev) for _ in range(3))
     count = torch.zeros(1, dtype=torch.int32, device=dev)
-    self._ck(self.lib.er_kv_export_all(_p(kv['keys']), _p(kv['rows']), _p(kv['freq']), _p(kv['version']),
-                                       slots, _p(keys), _p(rows), _p(freq), _p(version), _p(count), _stream()),
-             'er_kv_export_all')
+    self.ck.er_kv_export_all(_p(kv['keys']), _p(kv['rows']), _p(kv['freq']), _p(kv['version']),
+                             slots, _p(keys), _p(rows), _p(freq), _p(version), _p(count), _stream())
     n = int(count.item())
     order = torch.argsort(keys[:n])
     return keys[:n][order], rows[:n][order].to(torch.int64), freq[:n][order], version[:n][order]
@@ -2512,10 +2345,10 @@ class HipBackend(object):
     if kv['version'] is not None:
       kv['version'].zero_()
       version = None if version is None else version.to(dev, torch.int32).contiguous()
-    self._ck(self.lib.er_kv_rebuild(_p(keys), _p(rows32), _p(freq) if kv['freq'] is not None else None,
-                                    _p(version) if kv['version'] is not None else None, keys.numel(),
-                                    _p(kv['keys']), _p(kv['rows']), _p(kv['freq']), _p(kv['version']),
-                                    kv['keys'].numel(), _p(kv['overflow']), _stream()), 'er_kv_rebuild')
+    self.ck.er_kv_rebuild(_p(keys), _p(rows32), _p(freq) if kv['freq'] is not None else None,
+                          _p(version) if kv['version'] is not None else None, keys.numel(),
+                          _p(kv['keys']), _p(kv['rows']), _p(kv['freq']), _p(kv['version']),
+                          kv['keys'].numel(), _p(kv['overflow']), _stream())
     kv['next_row'].fill_(int((rows32 >= 0).sum().item()))
     if kv['n_keys'] is not None:
       kv['n_keys'].fill_(keys.numel())
@@ -2525,27 +2358,26 @@ class HipBackend(object):
     """z[(b, d), h * H0 + m] = xi[b, h, d] * x0[b, m, d]; xi addressed by strides = (stride_b, stride_h, stride_d)."""
     B, H0, D = x0.shape
     assert z.shape == (B * D, H * H0) and z.is_contiguous() and x0.is_contiguous()
-    self._ck(self.lib.er_cin_outer_fwd(_p(xi), strides[0], strides[1], strides[2], H, _p(x0), H0, D, B, _p(z),
-                                       _stream()), 'er_cin_outer_fwd')
+    self.ck.er_cin_outer_fwd(_p(xi), strides[0], strides[1], strides[2], H, _p(x0), H0, D, B, _p(z),
+                             _stream())
 
   def cin_act_pool_fwd(self, c, bias, B, D, pooled, col0):
     """c [B * D, N] <- relu(c + bias) in place; pooled[:, col0 : col0 + N] = its sum over d."""
     N = c.shape[1]
     assert c.is_contiguous() and pooled.stride(1) == 1
-    self._ck(self.lib.er_cin_act_pool_fwd(_p(c), _p(bias), B, D, N, _p(pooled), pooled.stride(0), col0, _stream()),
-             'er_cin_act_pool_fwd')
+    self.ck.er_cin_act_pool_fwd(_p(c), _p(bias), B, D, N, _p(pooled), pooled.stride(0), col0, _stream())
 
   def cin_act_pool_bwd(self, fm, dpooled, col0, dnext, B, D, dc):
     N = fm.shape[1]
     assert fm.is_contiguous() and dc.is_contiguous() and dpooled.stride(1) == 1 and (dnext is None or dnext.is_contiguous())
-    self._ck(self.lib.er_cin_act_pool_bwd(_p(fm), _p(dpooled), dpooled.stride(0), col0, _p(dnext), B, D, N, _p(dc),
-                                          _stream()), 'er_cin_act_pool_bwd')
+    self.ck.er_cin_act_pool_bwd(_p(fm), _p(dpooled), dpooled.stride(0), col0, _p(dnext), B, D, N, _p(dc),
+                                _stream())
 
   def cin_outer_bwd(self, dz, xi, strides, H, x0, dxi, add_xi, dx0):
     B, H0, D = x0.shape
     assert dz.shape == (B * D, H * H0) and dz.is_contiguous() and dx0.is_contiguous()
-    self._ck(self.lib.er_cin_outer_bwd(_p(dz), _p(xi), strides[0], strides[1], strides[2], H, _p(x0), H0, D, B, _p(dxi),
-                                       add_xi, _p(dx0), _stream()), 'er_cin_outer_bwd')
+    self.ck.er_cin_outer_bwd(_p(dz), _p(xi), strides[0], strides[1], strides[2], H, _p(x0), H0, D, B, _p(dxi),
+                             add_xi, _p(dx0), _stream())
 
   # -- K9 MLP pieces
   def bn_act_fwd(self, x, bias, gamma, beta, use_bn, eps, momentum, moving_mean, moving_var, act):
@@ -2553,10 +2385,9 @@ class HipBackend(object):
     y = torch.empty_like(x)
     mean = torch.empty(N, dtype=torch.float32, device=x.device) if use_bn else None
     invstd = torch.empty(N, dtype=torch.float32, device=x.device) if use_bn else None
-    self._ck(
-        self.lib.er_bn_act_fwd(_p(_f32c(x)), _p(bias), _p(gamma), _p(beta), B, N, int(use_bn),
-                               eps, momentum, _p(moving_mean), _p(moving_var),
-                               int(act), _p(y), _p(mean), _p(invstd), _stream()), 'er_bn_act_fwd')
+    self.ck.er_bn_act_fwd(_p(_f32c(x)), _p(bias), _p(gamma), _p(beta), B, N, int(use_bn),
+                          eps, momentum, _p(moving_mean), _p(moving_var),
+                          int(act), _p(y), _p(mean), _p(invstd), _stream())
     return y, mean, invstd
 
   def copy_multi(self, pairs):
@@ -2567,7 +2398,7 @@ class HipBackend(object):
     srcs = (ctypes.c_void_p * n)(*[s_.data_ptr() for _, s_ in pairs])
     dsts = (ctypes.c_void_p * n)(*[d.data_ptr() for d, _ in pairs])
     nb = (ctypes.c_int64 * n)(*[s_.numel() * s_.element_size() for _, s_ in pairs])
-    self._ck(self.lib.er_copy_multi(srcs, dsts, nb, n, _stream()), 'er_copy_multi')
+    self.ck.er_copy_multi(srcs, dsts, nb, n, _stream())
 
   concat_pitch = os.environ.get('EASYREC_AMD_CONCAT_PITCH', '1') != '0'  # A/B switch
 
@@ -2594,9 +2425,8 @@ class HipBackend(object):
       pp = (ctypes.c_void_p * len(chunk))(*[t.data_ptr() for t in chunk])
       ww = (ctypes.c_int32 * len(chunk))(*[t.shape[1] for t in chunk])
       ll = (ctypes.c_int32 * len(chunk))(*[t.stride(0) for t in chunk])
-      self._ck(self.lib.er_concat_cols_b16(pp, ww, ll, len(chunk), B, _p(dst), out.stride(0), _p(outb),
-                                           0 if outb is None else outb.stride(0), _stream()),
-               'er_concat_cols')
+      self.ck.er_concat_cols_b16(pp, ww, ll, len(chunk), B, _p(dst), out.stride(0), _p(outb),
+                                 0 if outb is None else outb.stride(0), _stream())
     return out
 
   def bn_act_bwd(self, x, bias, gamma, y, mean, invstd, dy, use_bn, act, need_bias, need_affine, into=None,
@@ -2619,17 +2449,14 @@ class HipBackend(object):
       dbeta = torch.empty(N, dtype=torch.float32, device=dev) if need_affine else None
     assert dy.dim() == 2 and dy.stride(1) == 1 and dy.dtype == torch.float32
     if partial is not None:
-      self._ck(
-          self.lib.er_bn_act_bwd_from_partials_ld_b16(_p(x), _p(bias), _p(gamma), _p(y), _p(mean), _p(invstd), _p(dy),
-                                                      dy.stride(0), B, N, int(use_bn), int(act), _p(partial),
-                                                      self.gemm_row_tiles(B), _p(dx), _p(dbias), _p(dgamma),
-                                                      _p(dbeta), int(acc), _p(dxb), ldb, _stream()),
-          'er_bn_act_bwd_from_partials_ld')
+      self.ck.er_bn_act_bwd_from_partials_ld_b16(_p(x), _p(bias), _p(gamma), _p(y), _p(mean), _p(invstd), _p(dy),
+                                                 dy.stride(0), B, N, int(use_bn), int(act), _p(partial),
+                                                 self.gemm_row_tiles(B), _p(dx), _p(dbias), _p(dgamma),
+                                                 _p(dbeta), int(acc), _p(dxb), ldb, _stream())
     else:  # (dy may be a column block of a wider gradient - ConcatFn's backward -: read in place)
-      self._ck(
-          self.lib.er_bn_act_bwd_ld_b16(_p(x), _p(bias), _p(gamma), _p(y), _p(mean), _p(invstd), _p(dy),
-                                        dy.stride(0), B, N, int(use_bn), int(act), _p(dx), _p(dbias),
-                                        _p(dgamma), _p(dbeta), int(acc), _p(dxb), ldb, _stream()), 'er_bn_act_bwd_ld')
+      self.ck.er_bn_act_bwd_ld_b16(_p(x), _p(bias), _p(gamma), _p(y), _p(mean), _p(invstd), _p(dy),
+                                   dy.stride(0), B, N, int(use_bn), int(act), _p(dx), _p(dbias),
+                                   _p(dgamma), _p(dbeta), int(acc), _p(dxb), ldb, _stream())
     if acc:
       return dx, None, None, None
     return dx, dbias, dgamma, dbeta
@@ -2640,8 +2467,7 @@ class HipBackend(object):
     if out is None:
       assert not accumulate
       out = torch.empty(cols, dtype=torch.float32, device=x.device)
-    self._ck(self.lib.er_colsum_acc(_p(x), rows, cols, x.stride(0), _p(out), accumulate, _stream()),
-             'er_colsum_acc')
+    self.ck.er_colsum_acc(_p(x), rows, cols, x.stride(0), _p(out), accumulate, _stream())
     return out
 
   def dice_fwd(self, x, alpha, eps, momentum, moving_mean, moving_var):
@@ -2649,19 +2475,16 @@ class HipBackend(object):
     y = torch.empty_like(x)
     mean = torch.empty(N, dtype=torch.float32, device=x.device)
     invstd = torch.empty(N, dtype=torch.float32, device=x.device)
-    self._ck(
-        self.lib.er_dice_fwd(_p(_f32c(x)), _p(alpha), B, N, eps, momentum,
-                             _p(moving_mean), _p(moving_var), _p(y), _p(mean), _p(invstd), _stream()),
-        'er_dice_fwd')
+    self.ck.er_dice_fwd(_p(_f32c(x)), _p(alpha), B, N, eps, momentum,
+                        _p(moving_mean), _p(moving_var), _p(y), _p(mean), _p(invstd), _stream())
     return y, mean, invstd
 
   def dice_bwd(self, x, alpha, mean, invstd, dy):
     B, N = x.shape
     dx = torch.empty_like(x)
     dalpha = torch.empty(N, dtype=torch.float32, device=x.device)
-    self._ck(
-        self.lib.er_dice_bwd(_p(x), _p(alpha), _p(mean), _p(invstd), _p(_f32c(dy)), B, N, _p(dx), _p(dalpha),
-                             _stream()), 'er_dice_bwd')
+    self.ck.er_dice_bwd(_p(x), _p(alpha), _p(mean), _p(invstd), _p(_f32c(dy)), B, N, _p(dx), _p(dalpha),
+                        _stream())
     return dx, dalpha
 
   # -- K10 loss / scalars
@@ -2672,10 +2495,8 @@ class HipBackend(object):
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     dlogits = torch.empty(B, dtype=torch.float32, device=dev)
     probs = torch.empty(B, dtype=torch.float32, device=dev)
-    self._ck(
-        self.lib.er_sigmoid_ce_fwd_bwd(_p(_f32c(logits)), _p(_f32c(labels)), _p(weights), B,
-                                       loss_scale, _p(loss), _p(dlogits), _p(probs), _stream()),
-        'er_sigmoid_ce_fwd_bwd')
+    self.ck.er_sigmoid_ce_fwd_bwd(_p(_f32c(logits)), _p(_f32c(labels)), _p(weights), B,
+                                  loss_scale, _p(loss), _p(dlogits), _p(probs), _stream())
     return loss, dlogits, probs
 
   def sigmoid_ce_multi(self, heads):
@@ -2692,15 +2513,14 @@ class HipBackend(object):
       q.loss_out, q.dlogits, q.probs_out = loss.data_ptr(), dz.data_ptr(), None
       outs.append((loss, dz))
       keep.append((z, y))
-    self._ck(self.lib.er_sigmoid_ce_multi(arr, len(heads), _stream()), 'er_sigmoid_ce_multi')
+    self.ck.er_sigmoid_ce_multi(arr, len(heads), _stream())
     return outs
 
   def total_loss(self, reg_emb, reg_dense, losses, reports, reg_out, total_out):
     n = len(losses)
     src = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in losses])
     dst = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in reports])
-    self._ck(self.lib.er_total_loss(_p(reg_emb), _p(reg_dense), src, dst, n, _p(reg_out), _p(total_out), _stream()),
-             'er_total_loss')
+    self.ck.er_total_loss(_p(reg_emb), _p(reg_dense), src, dst, n, _p(reg_out), _p(total_out), _stream())
 
   def reg_total_loss(self, emb_partials, emb_scale, dense_partials, losses, reports, reg_out, total_out):
     """reg_out = emb_scale * sum(emb_partials) + sum(dense_partials); total_out = reg_out + sum(losses); reports[i] =
@@ -2711,8 +2531,8 @@ class HipBackend(object):
     dst = (ctypes.c_void_p * max(n, 1))(*[t.data_ptr() for t in reports])
     n_part = 0 if emb_partials is None else emb_partials.numel()
     n_dense = 0 if dense_partials is None else dense_partials.numel()
-    self._ck(self.lib.er_reg_total_loss(_p(emb_partials), n_part, emb_scale, _p(dense_partials), n_dense, src, dst, n,
-                                        _p(reg_out), _p(total_out), _stream()), 'er_reg_total_loss')
+    self.ck.er_reg_total_loss(_p(emb_partials), n_part, emb_scale, _p(dense_partials), n_dense, src, dst, n,
+                              _p(reg_out), _p(total_out), _stream())
 
   # the binary head of a rank model (dense(K -> 1) + sigmoid cross entropy + their gradients) as ONE launch, its dW / db
   # partial sums folded into the loss tail's launch: layers/dnn.py dense(head=True), builders/loss_builder.py
@@ -2734,10 +2554,10 @@ class HipBackend(object):
       assert src.y is not None and src.y.data_ptr() == x.data_ptr() and src.zbias is None
       out['bn_partials'] = f(T, K, 2)
       sz, smean, sinv, sld, sact = src.z, src.mean, src.invstd, src.z.stride(0), src.act
-    self._ck(self.lib.er_head_sigmoid_ce(_p(x), x.stride(0), _p(w), _p(b), _p(_f32c(labels)), B, K, loss_scale,
-                                         _p(out['logits']), _p(out['probs']), _p(out['dlogits']), _p(out['dx']),
-                                         _p(out['loss_partials']), _p(out['wb_partials']), _p(sz), sld, _p(smean),
-                                         _p(sinv), int(sact), _p(out['bn_partials']), _stream()), 'er_head_sigmoid_ce')
+    self.ck.er_head_sigmoid_ce(_p(x), x.stride(0), _p(w), _p(b), _p(_f32c(labels)), B, K, loss_scale,
+                               _p(out['logits']), _p(out['probs']), _p(out['dlogits']), _p(out['dx']),
+                               _p(out['loss_partials']), _p(out['wb_partials']), _p(sz), sld, _p(smean),
+                               _p(sinv), int(sact), _p(out['bn_partials']), _stream())
     return out
 
   def loss_tail(self, emb_partials, emb_scale, dense_partials, losses, reports, reg_out, total_out, jobs=(), defer=False):
@@ -2776,9 +2596,9 @@ class HipBackend(object):
       self._deferred_loss_tail = (job, (src, dst, parts, scales, divs, values, arr, emb_partials, dense_partials, list(losses),
                                         list(reports), reg_out, total_out, list(jobs)))
       return
-    self._ck(self.lib.er_loss_tail(_p(emb_partials), n_part, emb_scale, _p(dense_partials),
-                                   n_dense, src, dst, parts, scales, divs, values, n, arr,
-                                   len(jobs), _p(reg_out), _p(total_out), _stream()), 'er_loss_tail')
+    self.ck.er_loss_tail(_p(emb_partials), n_part, emb_scale, _p(dense_partials),
+                         n_dense, src, dst, parts, scales, divs, values, n, arr,
+                         len(jobs), _p(reg_out), _p(total_out), _stream())
 
   # the deferred loss tail is per THREAD: the embedding-parallel tests run their ranks as threads over this one backend
   _tail_tls = threading.local()
@@ -2803,25 +2623,22 @@ class HipBackend(object):
       return
     self._deferred_loss_tail = None
     j = pending[0]
-    self._ck(self.lib.er_loss_tail(j.emb_partials, j.n_partials, j.emb_scale, j.dense_partials, j.n_dense, j.losses,
-                                   j.report, j.loss_parts, j.loss_scales, j.loss_divs, j.loss_values, j.n_losses, j.jobs,
-                                   j.n_jobs, j.reg_out, j.total_out, _stream()), 'er_loss_tail')
+    self.ck.er_loss_tail(j.emb_partials, j.n_partials, j.emb_scale, j.dense_partials, j.n_dense, j.losses,
+                         j.report, j.loss_parts, j.loss_scales, j.loss_divs, j.loss_values, j.n_losses, j.jobs,
+                         j.n_jobs, j.reg_out, j.total_out, _stream())
 
   def l2_partials(self, w, coef, partials):
     """partials[b] = sum over weights [256 b, 256 b + 256) of 0.5 * coef * w^2 (what dense_opt_step(l2_partials=) keeps
     current from then on)."""
     assert partials.numel() == (w.numel() + 255) // 256
-    self._ck(self.lib.er_l2_partials(_p(w), _p(coef), w.numel(), _p(partials), _stream()),
-             'er_l2_partials')
+    self.ck.er_l2_partials(_p(w), _p(coef), w.numel(), _p(partials), _stream())
 
   def reduce_sum(self, partials, scale, out, accumulate=False):
-    self._ck(
-        self.lib.er_reduce_sum(_p(partials), partials.numel(), scale, _p(out), int(accumulate),
-                               _stream()), 'er_reduce_sum')
+    self.ck.er_reduce_sum(_p(partials), partials.numel(), scale, _p(out), int(accumulate),
+                          _stream())
 
   def l2_loss(self, w, coef, out, accumulate=False):
-    self._ck(self.lib.er_l2_loss(_p(w), _p(coef), w.numel(), _p(out), int(accumulate), _stream()),
-             'er_l2_loss')
+    self.ck.er_l2_loss(_p(w), _p(coef), w.numel(), _p(out), int(accumulate), _stream())
 
   # -- K11 MMoE
   def mmoe_mix_fwd(self, experts, gate_logits):
@@ -2829,9 +2646,8 @@ class HipBackend(object):
     T = gate_logits.shape[0]
     gates = torch.empty_like(gate_logits)
     out = torch.empty(T, B, H, dtype=torch.float32, device=experts.device)
-    self._ck(
-        self.lib.er_mmoe_mix_fwd(_p(_f32c(experts)), _p(_f32c(gate_logits)), T, E, B, H, _p(gates), _p(out),
-                                 _stream()), 'er_mmoe_mix_fwd')
+    self.ck.er_mmoe_mix_fwd(_p(_f32c(experts)), _p(_f32c(gate_logits)), T, E, B, H, _p(gates), _p(out),
+                            _stream())
     return out, gates
 
   def mmoe_mix_bwd(self, experts, gates, dout):
@@ -2839,18 +2655,16 @@ class HipBackend(object):
     T = gates.shape[0]
     dexperts = torch.empty_like(experts)
     dlogits = torch.empty_like(gates)
-    self._ck(
-        self.lib.er_mmoe_mix_bwd(_p(experts), _p(gates), _p(_f32c(dout)), T, E, B, H, _p(dexperts), _p(dlogits),
-                                 _stream()), 'er_mmoe_mix_bwd')
+    self.ck.er_mmoe_mix_bwd(_p(experts), _p(gates), _p(_f32c(dout)), T, E, B, H, _p(dexperts), _p(dlogits),
+                            _stream())
     return dexperts, dlogits
 
   def hyper_select(self, table, counter, out, history=None, history_index=HYPER_LR_T):
     """history: fp32 [2 * capacity]: value of step s at [s], the running maximum of the values at [capacity + s]."""
     n_slots = table.shape[0]
     cap = 0 if history is None else history.numel() // 2
-    self._ck(self.lib.er_hyper_select(_p(table), _p(counter), n_slots, table[0].numel(), _p(out), _p(history),
-                                      cap, history_index, _stream()),
-             'er_hyper_select')
+    self.ck.er_hyper_select(_p(table), _p(counter), n_slots, table[0].numel(), _p(out), _p(history),
+                            cap, history_index, _stream())
 
   def step_prologue(self, table, counter, out, history=None, zero=None, history_index=HYPER_LR_T, decay_tables=None,
                     hash_job=None):
@@ -2868,10 +2682,10 @@ class HipBackend(object):
       hb, ho, hpc, hk, hdrop, hout = hash_job
       hn = ho.numel() - 1
       assert hout.dtype == torch.int64 and hout.numel() >= hn
-    self._ck(self.lib.er_step_prologue_hash(_p(table), _p(counter), n_slots, table[0].numel(), _p(out), _p(history),
-                                            cap, history_index, _p(zero), nz,
-                                            decay_tables['handle'] if decay_tables else None, _p(hb), _p(ho), hn,
-                                            int(hpc), _p(hk), int(hdrop), _p(hout), _stream()), 'er_step_prologue_hash')
+    self.ck.er_step_prologue_hash(_p(table), _p(counter), n_slots, table[0].numel(), _p(out), _p(history),
+                                  cap, history_index, _p(zero), nz,
+                                  decay_tables['handle'] if decay_tables else None, _p(hb), _p(ho), hn,
+                                  int(hpc), _p(hk), int(hdrop), _p(hout), _stream())
 
   # -- closed-form replay of TF-Adam's decay-only steps (csrc/er_decay.h)
   def decay_tables_create(self, lr_hist, step_counter, beta1, beta2):
@@ -2883,9 +2697,8 @@ class HipBackend(object):
     nbytes = int(self.lib.er_decay_tables_bytes(cap))
     buf = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=lr_hist.device)
     handle = ctypes.c_void_p()
-    self._ck(self.lib.er_decay_tables_create(_p(buf), cap, _p(lr_hist), _p(step_counter),
-                                             beta1, beta2, ctypes.byref(handle)),
-             'er_decay_tables_create')
+    self.ck.er_decay_tables_create(_p(buf), cap, _p(lr_hist), _p(step_counter),
+                                   beta1, beta2, ctypes.byref(handle))
     return {'handle': handle, 'buffer': buf, 'lr_hist': lr_hist, 'step_counter': step_counter,
             'betas': (float(beta1), float(beta2))}
 
@@ -2895,19 +2708,17 @@ class HipBackend(object):
       tabs['handle'] = None
 
   def emb_group_set_decay_tables(self, group, tabs):
-    self._ck(self.lib.er_emb_group_set_decay_tables(group['handle'], tabs['handle'] if tabs else None),
-             'er_emb_group_set_decay_tables')
+    self.ck.er_emb_group_set_decay_tables(group['handle'], tabs['handle'] if tabs else None)
     group['decay_tables'] = tabs
 
   # -- TF-exact Adam without the sweep (lazy dense decay)
   def emb_group_enable_lazy_decay(self, group, last_step, lr_hist, step_counter):
     """lr_hist: the [2 * capacity] history buffer of hyper_select (values | running maxima)."""
     assert last_step.dtype == torch.int32 and lr_hist.dtype == torch.float32 and step_counter.dtype == torch.int64
-    self._ck(self.lib.er_emb_group_enable_lazy_decay(group['handle'], _p(last_step), _p(lr_hist), _p(step_counter)),
-             'er_emb_group_enable_lazy_decay')
+    self.ck.er_emb_group_enable_lazy_decay(group['handle'], _p(last_step), _p(lr_hist), _p(step_counter))
     cap = lr_hist.numel() // 2
     if True:  # (the absorbed regime of the replay)
-      self._ck(self.lib.er_emb_group_set_lr_max(group['handle'], _p(lr_hist[cap:])), 'er_emb_group_set_lr_max')
+      self.ck.er_emb_group_set_lr_max(group['handle'], _p(lr_hist[cap:]))
     group['last_step'], group['lr_hist'], group['step_counter'] = last_step, lr_hist, step_counter
     self._set_row_pitch(group)
 
@@ -2916,12 +2727,10 @@ class HipBackend(object):
     variant that runs concurrently with the step (after its catch-up, on another stream)."""
     n = len(groups)
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
-    self._ck(self.lib.er_emb_flush_window(gh, n, int(n_windows), int(lag), int(max_blocks), _p(hyper), _stream()),
-             'er_emb_flush_window')
+    self.ck.er_emb_flush_window(gh, n, int(n_windows), int(lag), int(max_blocks), _p(hyper), _stream())
 
   def emb_catch_up(self, group, unique_keys, n_unique, hyper):
-    self._ck(self.lib.er_emb_catch_up(group['handle'], _p(unique_keys), _p(n_unique), _p(hyper), _stream()),
-             'er_emb_catch_up')
+    self.ck.er_emb_catch_up(group['handle'], _p(unique_keys), _p(n_unique), _p(hyper), _stream())
 
   def emb_catch_up_multi(self, groups, unique_keys, n_unique, hyper):
     """er_emb_catch_up for several table groups in one launch (same results)."""
@@ -2929,14 +2738,13 @@ class HipBackend(object):
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
     uk = (ctypes.c_void_p * n)(*[t.data_ptr() for t in unique_keys])
     nu = (ctypes.c_void_p * n)(*[t.data_ptr() for t in n_unique])
-    self._ck(self.lib.er_emb_catch_up_multi(gh, uk, nu, n, _p(hyper), _stream()), 'er_emb_catch_up_multi')
+    self.ck.er_emb_catch_up_multi(gh, uk, nu, n, _p(hyper), _stream())
 
   def emb_bwd_update_multi(self, groups, opt_kind, hyper):
     """er_emb_bwd_update for several table groups: one tile launch and one fix launch for all (same results)."""
     n = len(groups)
     gh = (ctypes.c_void_p * n)(*[g['handle'] for g in groups])
-    self._ck(self.lib.er_emb_bwd_update_multi(gh, n, opt_kind, _p(hyper), _stream()),
-             'er_emb_bwd_update_multi')
+    self.ck.er_emb_bwd_update_multi(gh, n, opt_kind, _p(hyper), _stream())
 
   # the end of an embedding-parallel step - owner fix | replicated apply | dense optimizer - as one launch - A/B switch
   ep_update_tail = os.environ.get('EASYREC_AMD_EP_UPDATE_TAIL', '1') != '0'
@@ -2954,14 +2762,14 @@ class HipBackend(object):
                                 dense.data_ptr(), dense.stride(0), var.shape[1], var.shape[0], var.stride(0))
     w, m, v, grad, l2coef, kind, hyp, l2p = dense_opt
     oj = DenseOptJob(_p(w), _p(m), _p(v), _p(grad), _p(l2coef), w.numel(), int(kind), _p(hyp), _p(l2p))
-    self._ck(self.lib.er_emb_owner_update_tail(gh, n, opt_kind, _p(hyper), descs if nt else None, nt,
-                                               ctypes.byref(oj), _stream()), 'er_emb_owner_update_tail')
+    self.ck.er_emb_owner_update_tail(gh, n, opt_kind, _p(hyper), descs if nt else None, nt,
+                                     ctypes.byref(oj), _stream())
     st = self._bf16_state_of(w)
     if st is not None:
       st.refresh()  # the weights' bf16 shadows follow the masters (one launch)
 
   def emb_flush_decay(self, group, hyper):
-    self._ck(self.lib.er_emb_flush_decay(group['handle'], _p(hyper), _stream()), 'er_emb_flush_decay')
+    self.ck.er_emb_flush_decay(group['handle'], _p(hyper), _stream())
 
   # -- gradient clipping by global norm (compat/optimizers.py:365-376, 453-481)
   def gradsq_rows(self, x, cols, weight, acc, accumulate, counts=None, seg_stride=None):
@@ -2972,33 +2780,31 @@ class HipBackend(object):
     n_seg = 0 if counts is None else counts.numel()
     assert counts is None or counts.dtype == torch.int32
     stride = rows if seg_stride is None else int(seg_stride)
-    self._ck(self.lib.er_gradsq_rows(_p(x), rows, int(cols), x.stride(0), _p(counts), n_seg, max(stride, 1), weight,
-                                     _p(acc), accumulate, _stream()), 'er_gradsq_rows')
+    self.ck.er_gradsq_rows(_p(x), rows, int(cols), x.stride(0), _p(counts), n_seg, max(stride, 1), weight,
+                           _p(acc), accumulate, _stream())
 
   def gradsq_dense(self, w, grad, l2coef, hyper, acc, accumulate=False):
     """acc[0] (+)= sum (hyper.grad_scale * grad + l2coef * w)^2: the dense gradient as er_dense_opt_step sees it."""
-    self._ck(self.lib.er_gradsq_dense(_p(w), _p(grad), _p(l2coef), w.numel(), _p(hyper), _p(acc),
-                                      accumulate, _stream()), 'er_gradsq_dense')
+    self.ck.er_gradsq_dense(_p(w), _p(grad), _p(l2coef), w.numel(), _p(hyper), _p(acc),
+                            accumulate, _stream())
 
   def clip_scale(self, normsq, clip_norm, records, norm_out=None):
     """records [n, HYPER_FLOATS] (device): records[:, HYPER_CLIP] = clip_norm * min(1 / norm, 1 / clip_norm)."""
     assert records.dim() == 2 and records.shape[1] == HYPER_FLOATS and records.is_contiguous()
-    self._ck(self.lib.er_clip_scale(_p(normsq), clip_norm, _p(records), records.shape[0],
-                                    _p(norm_out), _stream()), 'er_clip_scale')
+    self.ck.er_clip_scale(_p(normsq), clip_norm, _p(records), records.shape[0],
+                          _p(norm_out), _stream())
 
   def emb_apply_unique(self, group, keys, grads, n_unique, opt_kind, hyper):
     """The row-wise optimizer of emb_bwd_update on ready-made de-duplicated row sums (emb_bwd_reduce[_routed])."""
     assert keys.dtype == torch.int32 and n_unique.dtype == torch.int32 and grads.dim() == 2 and grads.stride(1) == 1
-    self._ck(self.lib.er_emb_apply_unique(group['handle'], _p(keys), _p(grads), grads.stride(0),
-                                          _p(n_unique), opt_kind, _p(hyper), _stream()), 'er_emb_apply_unique')
+    self.ck.er_emb_apply_unique(group['handle'], _p(keys), _p(grads), grads.stride(0),
+                                _p(n_unique), opt_kind, _p(hyper), _stream())
 
   # -- dense optimizer
   def dense_opt_step(self, w, m, v, grad, l2coef, opt_kind, hyper, l2_partials=None):
     """l2_partials: left holding the per-256-weight sums of 0.5 * l2coef * w_new^2 (the next step's kernel-L2 loss)."""
-    self._ck(
-        self.lib.er_dense_opt_step_l2(_p(w), _p(m), _p(v), _p(grad), _p(l2coef), w.numel(),
-                                      opt_kind, _p(hyper), _p(l2_partials), _stream()),
-        'er_dense_opt_step_l2')
+    self.ck.er_dense_opt_step_l2(_p(w), _p(m), _p(v), _p(grad), _p(l2coef), w.numel(),
+                                 opt_kind, _p(hyper), _p(l2_partials), _stream())
     st = self._bf16_state_of(w)
     if st is not None:
       st.refresh()  # the weights' bf16 shadows follow the masters (one launch)

@@ -72,13 +72,56 @@ def test_every_declared_function_is_bound_to_its_header_signature(built_lib):
 
 
 def test_binder_refuses_unknown_types_and_missing_exports(built_lib, monkeypatch, tmp_path):
-  from easyrec_amd import kernels
-  for proto, what in (('int er_abi_version(long x);', 'no ctypes type'), ('int er_not_exported(void);', 'does not export')):
+  """What the header's readers cannot represent stops them: a signature (load_library), a record field or a constant
+  (abi.parse_header) is never skipped."""
+  from easyrec_amd import abi, kernels
+
+  def bind(header):
+    monkeypatch.setattr(kernels, 'HEADER_PATH', header)
+    kernels.load_library(built_lib)
+
+  for read, proto, what in (
+      (bind, 'int er_abi_version(long x);', 'no ctypes type'), (bind, 'int er_not_exported(void);', 'does not export'),
+      (abi.parse_header, 'typedef struct { int32_t n; long x; } er_bad;', "er_bad field `long x`: no ctypes type for 'long'"),
+      (abi.parse_header, 'typedef struct er_bad { int32_t n; int32_t flag : 1; } er_bad;', 'er_bad field `int32_t flag : 1`'),
+      (abi.parse_header, 'typedef struct { int32_t n; union { float f; int32_t i; } u; } er_bad;', 'er_bad field `union'),
+      (abi.parse_header, 'typedef struct { int32_t n; struct { float f; } s; } er_bad;', 'er_bad field `struct'),
+      (abi.parse_header, 'typedef struct { int32_t n; int (*fn)(int32_t); } er_bad;', r'er_bad field `int \(\*fn\)\(int32_t\)`'),
+      (abi.parse_header, 'typedef struct __attribute__((packed)) { int32_t n; } er_bad;', '0 records built from 1'),
+      (abi.parse_header, 'struct er_bad { int32_t n; };', '`struct er_bad {` defines a struct or union'),
+      (abi.parse_header, 'typedef union { float f; int32_t i; } er_bad;', '`union {` defines a struct or union'),
+      (abi.parse_header, '#define ER_X (1 << 2)', "#define ER_X: '\\(1 << 2\\)' is not an integer literal"),
+      (abi.parse_header, 'enum { ER_Y = ER_X + 1 };', 'enum ER_Y')):
     header = tmp_path / 'easyrec_hip.h'
     header.write_text('/* int er_commented_out(void); */\n' + proto + '\n')
-    monkeypatch.setattr(kernels, 'HEADER_PATH', str(header))
     with pytest.raises(RuntimeError, match=what):
-      kernels.load_library(built_lib)
+      read(str(header))
+  header.write_text('typedef struct er_opaque er_opaque;\ntypedef struct { int32_t a, b; float* p; } er_ok;\nenum { ER_A, ER_B };\n')
+  records, constants = abi.parse_header(str(header))  # (and what it can represent, it reads)
+  assert [(n, t.__name__) for n, t in records['er_ok']._fields_] == [('a', 'c_int'), ('b', 'c_int'), ('p', 'c_void_p')]
+  assert list(records) == ['er_ok'] and constants == {'ER_A': 0, 'ER_B': 1}
+
+
+def test_a_failed_call_is_reported_under_the_name_of_the_function_called(built_lib, tmp_path):
+  """HipBackend.ck.er_NAME(...) raises for a non-zero return code, naming er_NAME itself and quoting er_last_error().
+  er_load_dense_embed fails on the host (no such checkpoint folder) before anything touches a device."""
+  from easyrec_amd import kernels
+  be = kernels.HipBackend.__new__(kernels.HipBackend)  # (a host-only backend)
+  be.lib = ctypes.CDLL(built_lib)
+  with pytest.raises(RuntimeError) as err:
+    be.load_dense_embed(str(tmp_path / 'nope'), 'var', 0, 1, 4, 8)
+  reason = be.lib.er_last_error().decode()
+  assert 'cannot list' in reason and str(tmp_path) in reason
+  rc = be.lib.er_load_dense_embed(str(tmp_path / 'nope').encode(), b'var', 0, 1, 4, 8, None, None)
+  assert rc != 0 and str(err.value) == 'er_load_dense_embed failed (rc=%d): %s' % (rc, reason)
+  first = be.ck.er_load_dense_embed
+  assert be.ck.er_load_dense_embed is first  # (built once per name)
+  be.lib = ctypes.CDLL(built_lib)  # another library handed over: the checked calls are built again, for that library
+  assert be.ck.er_load_dense_embed is not first
+  with pytest.raises(RuntimeError, match=r'^er_save_dense_embed failed \(rc=\d+\): er_save_dense_embed: '):
+    be.ck.er_save_dense_embed(None, None, 0, 1, None, 0, 0)
+  with pytest.raises(AttributeError):
+    be.ck.er_no_such_function
 
 
 def _library_calls():
@@ -126,6 +169,24 @@ def test_struct_layout_matches_header(built_lib):
   assert kernels.HYPER_FLOATS == 16
 
 
+def test_constants_read_from_the_header_have_the_values_the_library_was_built_with():
+  """kernels.py takes every constant from include/easyrec_hip.h; these are the values, stated by hand, that the kernels
+  switch on."""
+  from easyrec_amd import kernels as k
+  assert (k.COMBINER_SUM, k.COMBINER_MEAN, k.COMBINER_SQRTN) == (0, 1, 2)
+  assert k.COMBINERS == {'sum': 0, 'mean': 1, 'sqrtn': 2}
+  assert (k.OPT_SGD, k.OPT_ADAM, k.OPT_LAZY_ADAM, k.OPT_ADAGRAD) == (0, 1, 2, 3)
+  assert (k.ACT_NONE, k.ACT_RELU) == (0, 1)
+  assert (k.BN_NONE, k.BN_BATCH, k.BN_FROZEN) == (0, 1, 2)
+  assert (k.GEMM_NN, k.GEMM_NT, k.GEMM_TN) == (0, 1, 2)
+  assert (k.EPI_PLAIN, k.EPI_STATS, k.EPI_BN_BWD, k.EPI_CROSS_FWD, k.EPI_CROSS_BWD) == (0, 1, 2, 3, 4)
+  assert (k.GRAD_TERM_ROWSUM, k.GRAD_TERM_FM) == (0, 1)
+  assert (k.HYPER_LR, k.HYPER_LR_T, k.HYPER_BETA1, k.HYPER_BETA2, k.HYPER_OMB1, k.HYPER_OMB2, k.HYPER_EPS,
+          k.HYPER_GSCALE) == tuple(range(8))
+  assert k.HYPER_CLIP == 8
+  assert (k.FRONT_SKIP_ONE_ROW, k.FRONT_DEFER_CATCH_UP, k.ABI_VERSION) == (1, 2, 1)
+
+
 def test_product_does_not_import_the_oracle():
   """easyrec_amd/ must never import oracle/ (the product path has no CPU fallback)."""
   bad = []
@@ -146,36 +207,32 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     kernels.HipBackend()
 
 
-MIRRORS = {  # ctypes class in easyrec_amd/kernels.py -> the C struct it mirrors
-    'GemmEpilogue': 'er_gemm_epilogue', 'LookupDesc': 'er_lookup_desc', 'KvJob': 'er_kv_job', 'KvRouteJob': 'er_kv_route_job', 'CastDesc': 'er_cast_desc',
-    'GemmProblem': 'er_gemm_problem', 'BnLayer': 'er_bn_layer', 'CeHead': 'er_ce_head', 'TailJob': 'er_tail_job',
-    'LossTailJob': 'er_loss_tail_job', 'DenseOptJob': 'er_dense_opt_job', 'GradTerm': 'er_grad_term',
-    'GradGroup': 'er_grad_group', 'DenseApplyDesc': 'er_dense_apply_desc', 'ColsumJob': 'er_colsum_job',
-}
-
-
-RENAMED = {('GradGroup', 'lam'): 'lambda'}  # (a Python keyword on the C side)
+RENAMED = {'lam': 'lambda'}  # (a Python keyword on the C side)
 
 
 def test_every_ctypes_mirror_has_the_size_and_field_offsets_of_its_c_struct(tmp_path):
-  """The host side hands the library arrays of records: a ctypes mirror that drifts from include/easyrec_hip.h (a field
-  dropped on one side only) would corrupt every call silently.  The header is compiled as C (gcc) into a probe that prints
-  sizeof and every field's offsetof; the mirrors must agree field by field, in order."""
+  """The host side hands the library arrays of records: a ctypes record that differs from include/easyrec_hip.h (a field
+  dropped, reordered or of another width) would corrupt every call silently.  abi.py lays each class out from the field
+  list it parsed; here the header is compiled as C (gcc) into a probe that prints sizeof and every field's offsetof and
+  size: every record the header defines must agree, field by field - padding and reserved fields included."""
   import shutil
   import subprocess
-  from easyrec_amd import kernels
+  from easyrec_amd import abi, kernels
   if shutil.which('gcc') is None:
     import pytest
     pytest.skip('no gcc')
+  assert len(abi.RECORDS) == 16 and abi.RECORDS['er_opt_hyper'] is kernels.OptHyper
+  assert abi.RECORDS['er_grad_group'].terms.size == 4 * ctypes.sizeof(kernels.GradTerm)
+  assert dict(abi.RECORDS['er_grad_group']._fields_)['terms']._type_ is kernels.GradTerm  # (ONE class per C struct)
+  assert {name for name, v in vars(kernels).items() if isinstance(v, type) and issubclass(v, ctypes.Structure)} == {
+      'GemmEpilogue', 'LookupDesc', 'KvJob', 'KvRouteJob', 'CastDesc', 'GemmProblem', 'BnLayer', 'CeHead', 'TailJob',
+      'LossTailJob', 'DenseOptJob', 'GradTerm', 'GradGroup', 'DenseApplyDesc', 'ColsumJob', 'OptHyper'}
   lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "easyrec_hip.h"', 'int main(void) {']
-  for cls_name, c_name in MIRRORS.items():
-    cls = getattr(kernels, cls_name)
-    lines.append('  printf("%s size %%zu\\n", sizeof(%s));' % (c_name, c_name))
-    for field in cls._fields_:
-      fname = field[0]
-      if fname.endswith('_') and fname.startswith('pad'):
-        continue
-      lines.append('  printf("%s %s %%zu\\n", offsetof(%s, %s));' % (c_name, fname, c_name, RENAMED.get((cls_name, fname), fname)))
+  for c_name, cls in abi.RECORDS.items():
+    lines.append('  printf("%s size %%zu 0\\n", sizeof(%s));' % (c_name, c_name))
+    for fname, _ in cls._fields_:
+      lines.append('  printf("%s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' %
+                   (c_name, fname, c_name, RENAMED.get(fname, fname), c_name, RENAMED.get(fname, fname)))
   lines += ['  return 0;', '}']
   src = tmp_path / 'probe.c'
   src.write_text('\n'.join(lines))
@@ -184,12 +241,12 @@ def test_every_ctypes_mirror_has_the_size_and_field_offsets_of_its_c_struct(tmp_
   out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
   got = {}
   for ln in out.splitlines():
-    c_name, key, val = ln.split()
-    got[(c_name, key)] = int(val)
-  for cls_name, c_name in MIRRORS.items():
-    cls = getattr(kernels, cls_name)
-    assert ctypes.sizeof(cls) == got[(c_name, 'size')], (cls_name, ctypes.sizeof(cls), got[(c_name, 'size')])
-    for field in cls._fields_:
-      fname = field[0]
-      if (c_name, fname) in got:
-        assert getattr(cls, fname).offset == got[(c_name, fname)], (cls_name, fname)
+    c_name, key, val, size = ln.split()
+    got[(c_name, key)] = (int(val), int(size))
+  n_fields = 0
+  for c_name, cls in abi.RECORDS.items():
+    assert ctypes.sizeof(cls) == got[(c_name, 'size')][0], (c_name, ctypes.sizeof(cls), got[(c_name, 'size')])
+    for fname, _ in cls._fields_:
+      n_fields += 1
+      assert (getattr(cls, fname).offset, getattr(cls, fname).size) == got[(c_name, fname)], (c_name, fname)
+  assert n_fields == len(got) - len(abi.RECORDS) and n_fields > 200
