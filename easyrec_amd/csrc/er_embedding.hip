@@ -1806,82 +1806,91 @@ __device__ __forceinline__ void seg_cmpx(C& a, C& b, bool up) {
 }
 
 // The NARROW composites (rel << log2 P | position) by a stable LSD radix sort on the `rel` bits alone - the positions start
-// in ascending order, so a stable sort by rel IS the composite order, and the padding (all ones) sorts last.  5-bit digits:
-// a 1 M-row table takes 4 passes, a one-row table (every entry `missing`) one - where the bitonic network below always runs
-// its 78 compare-exchange stages (P = 4096), ~1300 VALU instructions per thread on ONE compute unit per lookup: the sort
-// workgroups were VALU-issue-bound, 20 us, and the whole front launch waited for them (SQ_WAIT_INST_ANY / SQ_INSTS_VALU of
-// emb_front_fwd_kernel, profiles/r06_s6_sq_counters_by_kernel.json).
-// Per pass every wave ranks its own 64 E keys (striped: round e holds keys e * 64 + lane of the wave's chunk, so the key
-// order is (wave, round, lane)): the lanes holding the same digit are found with 5 ballots, rank = the wave's count of that
-// digit in earlier rounds (an LDS counter only the group's first lane advances) + the same-digit lanes below; one exclusive
-// scan over the [digit][wave] counters places every (digit, wave) group; the keys are scattered into the other LDS buffer.
-// Composites are distinct, so the result is the bitonic network's, bit for bit.
+// in ascending order, so a stable sort by rel IS the composite order, and the padding (all ones) sorts last.  A table of
+// 10^6 rows (20 key bits: a missing id sorts as rel == rows) takes four passes, a one-row table one - where the bitonic
+// network below always runs its 78 compare-exchange stages (P = 4096), ~1300 VALU instructions per thread on ONE compute
+// unit per lookup.
+// Every wave ranks its own 64 E keys, STRIPED: round e holds the key at position e * 64 + lane of the wave's chunk, so the
+// key order is (wave, round, lane).  The wave's running digit histogram lives in registers - lane l counts digit l.  A
+// round's kRadixBits ballots are wave-uniform, so lane l forms from them the mask of the lanes that hold digit l: its
+// popcount advances the histogram.  A key's rank is the histogram of ITS digit before this round plus the same-digit
+// lanes below it - both read from the lane that owns the digit with cross-lane reads (the mask there
+// IS the key's same-digit mask).  No LDS cell is written and read again inside a round.  Once per pass the wave stores its
+// histogram to cnt[wave][digit]; behind ONE barrier every wave derives the offsets of its own (digit, wave) groups itself -
+// a lane sums its digits' columns of cnt, one scan across the lanes orders the digits - and scatters its keys into the
+// other LDS buffer: two barriers per pass.  Composites are distinct, so the result is the bitonic network's, bit for bit.
+// In: key[e] = the composite at position wave * 64 E + e * 64 + lane.  Out: the sorted composite at that position; the
+// whole sorted array stands in the returned LDS buffer (a barrier behind the last scatter has been passed).
+// Digit width (profiles/r08_front_sort_lookup_probe.txt, DeepFM's 20-bit keys): 5 bits 9.5 us for the four passes, 6 bits
+// 10.2 (one more ballot per round for the same four passes), 7 bits with a two-register histogram 14.6 for three.
 constexpr int kRadixBits = 5;
+constexpr int64_t kFrontDbgOffset = 4096 * 16;  // er_debug_stamps: the fused front launch's stamps stand behind the backward launch's
 template <int E>
-__device__ __forceinline__ void seg_radix_sort_narrow(uint32_t (&x)[E], uint32_t* buf /* [2 P] */, int P, int logP, uint32_t rel_max) {
+__device__ __forceinline__ const uint32_t* seg_radix_sort_narrow(uint32_t (&key)[E], uint32_t* buf /* [2 P] */, int P, int logP,
+                                                                 uint32_t rel_max, unsigned long long* dbg) {
   constexpr int NB = 1 << kRadixBits;
   constexpr int kMaxWaves = kSegSortMax / 8 / 64;
-  __shared__ uint32_t cnt[NB * kMaxWaves];  // [digit][wave]
-  __shared__ uint32_t wtot[kMaxWaves];
+  static_assert(kRadixBits >= 1 && kRadixBits <= 6, "one histogram register per lane: at most 64 digits");
+  __shared__ uint32_t cnt[kMaxWaves * NB];  // [wave][digit]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nW = static_cast<int>(blockDim.x >> 6);
-  const int n_cnt = NB * nW;  // <= blockDim.x / 2
+  // the rows of waves that do not exist read as zero (no wave writes them; the first pass's barrier orders this)
+  for (int i = nW * NB + t; i < kMaxWaves * NB; i += static_cast<int>(blockDim.x)) cnt[i] = 0u;
   uint32_t* A = buf;
   uint32_t* B = buf + P;
-#pragma unroll
-  for (int e = 0; e < E; ++e) A[t * E + e] = x[e];
-  __syncthreads();
   const int key_bits = 32 - __clz(static_cast<int>(rel_max | 1u));
   const int chunk = wave * 64 * E;
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
-  uint32_t key[E];
+  uint32_t inv[kRadixBits];  // all ones where bit b of the lane's digit is CLEAR: ballot ^ inv = the lanes that agree with it in bit b
 #pragma unroll
-  for (int e = 0; e < E; ++e) key[e] = A[chunk + e * 64 + lane];
-  for (int shift = logP; shift < logP + key_bits; shift += kRadixBits) {
-    if (t < n_cnt) cnt[t] = 0u;
-    __syncthreads();
-    uint32_t rank[E], slot[E];
+  for (int b = 0; b < kRadixBits; ++b) inv[b] = ((lane >> b) & 1) != 0 ? 0u : ~0u;
+  int pass = 0;
+  for (int shift = logP; shift < logP + key_bits; shift += kRadixBits, ++pass) {
+    uint32_t hist = 0u, rank[E], dig[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const uint32_t d = (key[e] >> shift) & static_cast<uint32_t>(NB - 1);
-      unsigned long long m = ~0ull;
+      uint32_t lo = ~0u, hi = ~0u;  // the lanes of this round that hold digit `lane` (lanes >= NB repeat lane & (NB - 1))
 #pragma unroll
       for (int b = 0; b < kRadixBits; ++b) {
-        const bool bit = ((d >> b) & 1u) != 0u;
-        const unsigned long long bal = __ballot(bit);
-        m &= bit ? bal : ~bal;
+        const unsigned long long bal = __ballot(((d >> b) & 1u) != 0u);
+        lo &= static_cast<uint32_t>(bal) ^ inv[b];
+        hi &= static_cast<uint32_t>(bal >> 32) ^ inv[b];
       }
-      const uint32_t lower = static_cast<uint32_t>(__popcll(m & lt_mask));
-      const int sl = static_cast<int>(d) * nW + wave;
-      const uint32_t prior = cnt[sl];
-      rank[e] = prior + lower;
-      slot[e] = static_cast<uint32_t>(sl);
-      if (lower == 0u) cnt[sl] = prior + static_cast<uint32_t>(__popcll(m));
+      // from the lane that owns the key's digit: the digit's count before this round and its lanes of this round
+      const int src = static_cast<int>(d);
+      const uint32_t prior = static_cast<uint32_t>(__shfl(static_cast<int>(hist), src, 64));
+      const uint32_t own_lo = static_cast<uint32_t>(__shfl(static_cast<int>(lo), src, 64));
+      const uint32_t own_hi = static_cast<uint32_t>(__shfl(static_cast<int>(hi), src, 64));
+      rank[e] = prior + __builtin_amdgcn_mbcnt_hi(own_hi, __builtin_amdgcn_mbcnt_lo(own_lo, 0u));
+      dig[e] = d;
+      hist += static_cast<uint32_t>(__popc(lo)) + static_cast<uint32_t>(__popc(hi));
     }
+    if (lane < NB) cnt[wave * NB + lane] = hist;
     __syncthreads();
-    // exclusive scan of the n_cnt counters in index order (digit-major): wave-inclusive scans, then the wave totals
-    uint32_t v = 0u, inc = 0u;
-    if (t < n_cnt) v = cnt[t];
-    inc = v;
+    // this wave's offsets: digit-major exclusive scan of cnt, by every wave for itself (integers: any order is exact)
+    uint32_t tot = 0u, pre = 0u;
 #pragma unroll
-    for (int dd = 1; dd < 64; dd <<= 1) {
+    for (int w = 0; w < kMaxWaves; ++w) {
+      const uint32_t v = cnt[w * NB + (lane & (NB - 1))];
+      pre = w == wave ? tot : pre;
+      tot += v;
+    }
+    uint32_t inc = tot;
+#pragma unroll
+    for (int dd = 1; dd < NB; dd <<= 1) {
       const uint32_t o = __shfl_up(inc, dd, 64);
       if (lane >= dd) inc += o;
     }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0u;
-    for (int w = 0; w < wave; ++w) before += wtot[w];
-    if (t < n_cnt) cnt[t] = before + inc - v;
-    __syncthreads();
+    const uint32_t base = inc - tot + pre;  // (lanes < NB)
 #pragma unroll
-    for (int e = 0; e < E; ++e) B[cnt[slot[e]] + rank[e]] = key[e];
+    for (int e = 0; e < E; ++e)
+      B[static_cast<uint32_t>(__shfl(static_cast<int>(base), static_cast<int>(dig[e]), 64)) + rank[e]] = key[e];
     __syncthreads();
     uint32_t* T = A; A = B; B = T;
 #pragma unroll
     for (int e = 0; e < E; ++e) key[e] = A[chunk + e * 64 + lane];
+    if (dbg && t == 0 && pass < 8) dbg[8 + pass] = wall_clock64();
   }
-#pragma unroll
-  for (int e = 0; e < E; ++e) x[e] = A[t * E + e];
+  return A;
 }
 
 // HEADS: also emit, per sorted position, the run-head flag and the number of heads before it INSIDE the lookup, and
@@ -1904,7 +1913,8 @@ __device__ __forceinline__ void seg_sort_body(int lk, const uint32_t* __restrict
                         uint32_t* __restrict__ vals_out, uint32_t* __restrict__ flags_out,
                         uint32_t* __restrict__ hidx_out, uint32_t* __restrict__ seg_count, int skip_one_row,
                         unsigned long long* sk_raw, uint32_t* __restrict__ ukeys_seg = nullptr,
-                        int64_t n_limit = INT64_MAX) {  // (entries at positions >= n_limit do not exist: chunks of an owner group)
+                        int64_t n_limit = INT64_MAX,  // (entries at positions >= n_limit do not exist: chunks of an owner group)
+                        unsigned long long* dbg = nullptr) {  // probe hook (er_debug_stamps), or nullptr
   typedef typename std::conditional<NARROW, uint32_t, unsigned long long>::type C;
   C* sk = reinterpret_cast<C*>(sk_raw);
   constexpr int L = E == 8 ? 3 : (E == 4 ? 2 : 1);
@@ -1940,43 +1950,78 @@ __device__ __forceinline__ void seg_sort_body(int lk, const uint32_t* __restrict
     }
     return static_cast<uint32_t>(static_cast<unsigned long long>(c) >> 32);
   };
+  // the positions a thread holds: E consecutive ones for the bitonic network, STRIPED for the radix sort (position
+  // e * 64 + lane of the wave's 64 E: the order its rounds rank in, and a wave's loads and stores are contiguous)
+  const int lane = t & 63, wave = t >> 6;
+  auto pos = [&](int e) -> int { return NARROW ? wave * 64 * E + e * 64 + lane : i0 + e; };
+  // every input of the thread is requested before the first is used: a load inside a per-element branch is waited for
+  // inside it.  Positions past the end read the last entry and drop it.
   C x[E];
+  if (INLINE) {
+    const er_lookup_desc& d = descs[lk];
+    const bool pruned = d.weights != nullptr && d.combiner != ER_COMBINER_SUM;
+    int64_t id[E];
+    float w[E];
 #pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int i = i0 + e;
-    if (i >= cnt) {
-      x[e] = static_cast<C>(~0ull);
-    } else if (INLINE) {
-      const er_lookup_desc& d = descs[lk];
-      const int64_t id = d.ids[i];
-      bool ok = !(id < 0 || id >= d.rows);
-      if (d.weights != nullptr && d.combiner != ER_COMBINER_SUM && !(d.weights[i] > 0.f)) ok = false;
+    for (int e = 0; e < E; ++e) {
+      id[e] = 0;
+      w[e] = 1.f;
+    }
+    if (cnt > 0) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) id[e] = d.ids[pos(e) < cnt ? pos(e) : cnt - 1];
+      if (pruned) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) w[e] = d.weights[pos(e) < cnt ? pos(e) : cnt - 1];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int i = pos(e);
+      bool ok = !(id[e] < 0 || id[e] >= d.rows);
+      if (pruned && !(w[e] > 0.f)) ok = false;
       if (skip_one_row && d.rows == 1) ok = false;
       if (NARROW) {
-        const uint32_t rel = ok ? static_cast<uint32_t>(id) : static_cast<uint32_t>(d.rows);
+        const uint32_t rel = ok ? static_cast<uint32_t>(id[e]) : static_cast<uint32_t>(d.rows);
         x[e] = static_cast<C>((rel << logP) | static_cast<uint32_t>(i));
       } else {
-        const uint32_t key = ok ? static_cast<uint32_t>(d.key_base + id) : kInvalidKey;
+        const uint32_t key = ok ? static_cast<uint32_t>(d.key_base + id[e]) : kInvalidKey;
         x[e] = static_cast<C>((static_cast<unsigned long long>(key) << 32) | static_cast<unsigned>(base + i));
       }
-    } else if (NARROW) {
-      const uint32_t key = keys_in[base + i];
-      uint32_t rel = rows;
-      if (key != kInvalidKey) {
-        if (routed) {
-          const uint32_t owner = key / stride;
-          rel = owner * srows + (key - owner * stride - key_base);
-        } else {
-          rel = key - key_base;
+      if (i >= cnt) x[e] = static_cast<C>(~0ull);
+    }
+  } else {
+    uint32_t key[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) key[e] = kInvalidKey;
+    if (cnt > 0) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) key[e] = keys_in[base + (pos(e) < cnt ? pos(e) : cnt - 1)];
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int i = pos(e);
+      if (NARROW) {
+        uint32_t rel = rows;
+        if (key[e] != kInvalidKey) {
+          if (routed) {
+            const uint32_t owner = key[e] / stride;
+            rel = owner * srows + (key[e] - owner * stride - key_base);
+          } else {
+            rel = key[e] - key_base;
+          }
         }
+        x[e] = static_cast<C>((rel << logP) | static_cast<uint32_t>(i));
+      } else {
+        x[e] = static_cast<C>((static_cast<unsigned long long>(key[e]) << 32) | static_cast<unsigned>(base + i));
       }
-      x[e] = static_cast<C>((rel << logP) | static_cast<uint32_t>(i));
-    } else {
-      x[e] = static_cast<C>((static_cast<unsigned long long>(keys_in[base + i]) << 32) | static_cast<unsigned>(base + i));
+      if (i >= cnt) x[e] = static_cast<C>(~0ull);
     }
   }
+  if (dbg && t == 0) dbg[2] = wall_clock64();
+  const uint32_t* sorted = nullptr;  // NARROW: the sorted composites in LDS
   if constexpr (NARROW) {
-    seg_radix_sort_narrow<E>(x, reinterpret_cast<uint32_t*>(sk_raw), P, logP, rows);
+    sorted = seg_radix_sort_narrow<E>(x, reinterpret_cast<uint32_t*>(sk_raw), P, logP, rows, dbg);
   } else
   for (int k = 2; k <= P; k <<= 1) {
     int j = k >> 1;
@@ -2038,60 +2083,100 @@ __device__ __forceinline__ void seg_sort_body(int lk, const uint32_t* __restrict
     kk[e] = key_of(x[e]);
     ow[e] = routed ? kk[e] / stride : 0u;
   }
+  if (dbg && t == 0) dbg[3] = wall_clock64();
 #pragma unroll
   for (int e = 0; e < E; ++e) {
-    const int i = i0 + e;
+    const int i = pos(e);
     if (i < cnt) {
       keys_out[base + i] = kk[e];
       vals_out[base + i] = NARROW ? static_cast<uint32_t>(base) + (static_cast<uint32_t>(x[e]) & static_cast<uint32_t>(P - 1))
                                   : static_cast<uint32_t>(static_cast<unsigned long long>(x[e]) & 0xFFFFFFFFu);
     }
   }
+  if (dbg && t == 0) dbg[4] = wall_clock64();
   if (HEADS) {
-    __shared__ uint32_t wave_sum[kSegSortMax / 8 / 64];
-    uint32_t* k32 = reinterpret_cast<uint32_t*>(sk_raw);  // [P] sorted keys, to look one position back
-    __syncthreads();                                      // every thread has taken its composites out of sk
+    constexpr int kMaxWaves = kSegSortMax / 8 / 64;
+    __shared__ __attribute__((aligned(16))) uint32_t wave_sum[kMaxWaves];
+    const int n_waves = blockDim.x >> 6;
+    uint32_t f[E], run[E], total = 0;
+    if constexpr (NARROW) {
+      // the sorted composites stand in LDS: a position's predecessor is read there, a head is a valid key whose `rel`
+      // differs from it (key_of is one-to-one on rel < rows), and a round's flags are one ballot - a position's number
+      // of heads before it inside the wave is a popcount, not a scan
+      const unsigned long long lt_mask = (1ull << lane) - 1ull;
+      uint32_t prev[E], heads = 0;
 #pragma unroll
-    for (int e = 0; e < E; ++e) k32[i0 + e] = kk[e];
-    __syncthreads();
-    uint32_t prev = i0 > 0 ? k32[i0 - 1] : kInvalidKey;
-    uint32_t f[E], c = 0;
+      for (int e = 0; e < E; ++e) prev[e] = sorted[pos(e) > 0 ? pos(e) - 1 : 0];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const bool head = kk[e] != kInvalidKey && (pos(e) == 0 || (prev[e] >> logP) != (x[e] >> logP));
+        const unsigned long long bal = __ballot(head);
+        f[e] = head ? 1u : 0u;
+        run[e] = heads + static_cast<uint32_t>(__popcll(bal & lt_mask));
+        heads += static_cast<uint32_t>(__popcll(bal));
+      }
+      if (t < kMaxWaves && t >= n_waves) wave_sum[t] = 0u;
+      if (lane == 0) wave_sum[wave] = heads;
+      __syncthreads();
+      uint32_t before = 0;
+#pragma unroll
+      for (int q = 0; q < kMaxWaves / 4; ++q) {
+        const uint4 v = reinterpret_cast<const uint4*>(wave_sum)[q];
+        total += (v.x + v.y) + (v.z + v.w);
+        before += (q * 4 + 0 < wave ? v.x : 0u) + (q * 4 + 1 < wave ? v.y : 0u) + (q * 4 + 2 < wave ? v.z : 0u) +
+                  (q * 4 + 3 < wave ? v.w : 0u);
+      }
+#pragma unroll
+      for (int e = 0; e < E; ++e) run[e] += before;
+    } else {
+      uint32_t* k32 = reinterpret_cast<uint32_t*>(sk_raw);  // [P] sorted keys, to look one position back
+      __syncthreads();                                      // every thread has taken its composites out of sk
+#pragma unroll
+      for (int e = 0; e < E; ++e) k32[i0 + e] = kk[e];
+      __syncthreads();
+      uint32_t prev = i0 > 0 ? k32[i0 - 1] : kInvalidKey;
+      uint32_t c = 0;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const uint32_t key = kk[e];
+        f[e] = (key != kInvalidKey && (i0 + e == 0 || prev != key)) ? 1u : 0u;
+        c += f[e];
+        prev = key;
+      }
+      // exclusive scan of c over the workgroup: inclusive scan inside the wave, then the wave totals
+      uint32_t inc = c;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+      }
+      if (lane == 63) wave_sum[wave] = inc;
+      __syncthreads();
+      uint32_t before = 0;
+      for (int w = 0; w < n_waves; ++w) {
+        const uint32_t ws = wave_sum[w];
+        if (w < wave) before += ws;
+        total += ws;
+      }
+      uint32_t r = before + inc - c;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        run[e] = r;
+        r += f[e];
+      }
+    }
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-      const uint32_t key = kk[e];
-      f[e] = (key != kInvalidKey && (i0 + e == 0 || prev != key)) ? 1u : 0u;
-      c += f[e];
-      prev = key;
-    }
-    // exclusive scan of c over the workgroup: inclusive scan inside the wave, then the wave totals
-    const int lane = t & 63, wave = t >> 6, n_waves = blockDim.x >> 6;
-    uint32_t inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += o;
-    }
-    if (lane == 63) wave_sum[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (int w = 0; w < n_waves; ++w) {
-      const uint32_t ws = wave_sum[w];
-      if (w < wave) before += ws;
-      total += ws;
-    }
-    uint32_t run = before + inc - c;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int i = i0 + e;
+      const int i = pos(e);
       if (i < cnt) {
         flags_out[base + i] = f[e];
-        hidx_out[base + i] = run;
+        hidx_out[base + i] = run[e];
         // (the fused front: the lookup's distinct keys, compact inside its own segment - er_emb_front's catch-up reads
         // [base, base + seg_count[lookup]) of it, no cross-lookup scan and no launch for one)
-        if (ukeys_seg != nullptr && f[e]) ukeys_seg[base + run] = kk[e];
+        if (ukeys_seg != nullptr && f[e]) ukeys_seg[base + run[e]] = kk[e];
       }
-      run += f[e];
     }
+    if (dbg && t == 0) dbg[5] = wall_clock64();
     if (!routed) {
       if (t == 0) seg_count[lk] = total;
     } else {
@@ -2148,23 +2233,33 @@ emb_front_sort_kernel(const int64_t* __restrict__ ent_base, const er_lookup_desc
 // lanes each, fill the rest of the chip meanwhile - blockDim / kBlock of them per workgroup behind the sort's.  Possible
 // once nothing in the launch produces what another part of it consumes: the lag-1 replay table the lazy lookup reads is
 // built one launch earlier, by the step prologue (er_decay_tables_set_prologue_build).
+// Two of the 1024-thread workgroups per compute unit need eight waves per SIMD, i.e. at most 64 VGPRs: held as a launch
+// bound for the four-per-thread geometry (55 today; a first form of the register-histogram sort took the kernel to 65-69,
+// one workgroup per compute unit).  `dbg_all`: the probe hook's stamps (er_debug_stamps), or nullptr.
 template <int E, bool NARROW>
-__global__ void __launch_bounds__(kSegSortMax / 8)
+__global__ void __launch_bounds__(kSegSortMax / 8, E == 4 ? 8 : 4)
 emb_front_fwd_kernel(const int64_t* __restrict__ ent_base, const er_lookup_desc* __restrict__ descs, int n_lookups, int P,
                      uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out, uint32_t* __restrict__ flags_out,
                      uint32_t* __restrict__ hidx_out, uint32_t* __restrict__ seg_count, int skip_one_row,
                      uint32_t* __restrict__ ukeys_seg, const er_lookup_desc* __restrict__ fwd_descs,
                      const int32_t* __restrict__ fwd_blk_start, int fwd_lookups, int fwd_blocks,
-                     float* __restrict__ sumsq_partials, FwdLazy lz) {
+                     float* __restrict__ sumsq_partials, FwdLazy lz, unsigned long long* dbg_all) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long sk_raw[];  // [P] composites (sort workgroups)
+  unsigned long long* dbg = dbg_all ? dbg_all + static_cast<int64_t>(blockIdx.x) * 16 : nullptr;
+  if (dbg && threadIdx.x == 0) dbg[0] = wall_clock64();
   if (static_cast<int>(blockIdx.x) < n_lookups) {
     seg_sort_body<E, true, NARROW, true>(blockIdx.x, nullptr, ent_base, descs, P, Route{1, 0, nullptr}, keys_out, vals_out,
-                                         flags_out, hidx_out, seg_count, skip_one_row, sk_raw, ukeys_seg);
+                                         flags_out, hidx_out, seg_count, skip_one_row, sk_raw, ukeys_seg, INT64_MAX, dbg);
+    if (dbg && threadIdx.x == 0) dbg[1] = wall_clock64();
     return;
   }
   __shared__ float red[kSegSortMax / 8 / 64];
   const int per_wg = static_cast<int>(blockDim.x) / kBlock;
-  const int vb = (static_cast<int>(blockIdx.x) - n_lookups) * per_wg + static_cast<int>(threadIdx.x) / kBlock;
+  // a block is four whole waves, so its index is wave-uniform - said to the compiler, the block's search of blk_start
+  // (six dependent loads) and its lookup record become scalar loads into SGPRs as in the lookup launch, where the block
+  // index is blockIdx.x; left as a function of threadIdx.x they were vector loads of every lane, one round trip each
+  const int vb = __builtin_amdgcn_readfirstlane((static_cast<int>(blockIdx.x) - n_lookups) * per_wg +
+                                                static_cast<int>(threadIdx.x) / kBlock);
   const int vt = static_cast<int>(threadIdx.x) % kBlock;
   float ss = 0.f;
   if (vb < fwd_blocks) ss = fwd_rows<true>(vb, vt, fwd_descs, fwd_blk_start, fwd_lookups, &lz);
@@ -2178,6 +2273,7 @@ emb_front_fwd_kernel(const int64_t* __restrict__ ent_base, const er_lookup_desc*
       sumsq_partials[vb] = (red[w0] + red[w0 + 1]) + (red[w0 + 2] + red[w0 + 3]);
     }
   }
+  if (dbg && (threadIdx.x & 63) == 0) atomicMax(dbg + 1, static_cast<unsigned long long>(wall_clock64()));  // (every wave's end)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3956,6 +4052,12 @@ struct FrontFwd {
 static int fwd_lazy_prepare(er_emb_plan* p, er_emb_group* const* groups, int n, const er_opt_hyper* hyper, hipStream_t s,
                             er::FwdLazy* lz);
 
+// probe hook: 16 wall-clock stamps (100 MHz) per workgroup of the next er_emb_bwd_fused launches into `p` (nullptr: off),
+// and behind them (er::kFrontDbgOffset words on) of the next fused front launches; tools/own_probe.py and
+// tools/front_probe.py read them.  Not part of the product path.
+static unsigned long long* g_own_dbg = nullptr;
+int er_debug_stamps(unsigned long long* p) { g_own_dbg = p; return 0; }
+
 static int emb_front_impl(er_emb_group* const* groups, int n, int flags, const er_opt_hyper* hyper, hipStream_t s,
                           FrontFwd* ff) {
   ER_REQUIRE(groups && n >= 1 && n <= er::kMaxMulti, "er_emb_front: bad arguments (1 <= n <= %d)", er::kMaxMulti);
@@ -4019,10 +4121,12 @@ static int emb_front_impl(er_emb_group* const* groups, int n, int flags, const e
       er_emb_plan* pl = ff->plan;
       const int per_wg = threads / er::kBlock;
       const int fwd_wgs = static_cast<int>(er::ceil_div(pl->n_blocks, per_wg));
+      unsigned long long* fdbg = g_own_dbg && g->n + fwd_wgs <= 4096 ? g_own_dbg + er::kFrontDbgOffset : nullptr;
 #define ER_FRONT_FWD(EE, NRW)                                                                                             \
   hipLaunchKernelGGL((er::emb_front_fwd_kernel<EE, NRW>), dim3(g->n + fwd_wgs), dim3(threads), lds, s, g->d_ent_base,      \
                      g->d_descs, g->n, P, g->keys_out, g->vals_out, g->head_flags, g->head_index, g->seg_count,          \
-                     skip_one_row ? 1 : 0, g->keys_in, pl->d_descs, pl->d_blk_start, pl->n, pl->n_blocks, ff->sumsq, ff->lz)
+                     skip_one_row ? 1 : 0, g->keys_in, pl->d_descs, pl->d_blk_start, pl->n, pl->n_blocks, ff->sumsq, ff->lz, \
+                     fdbg)
       if (E == 8) { if (g->seg_narrow) ER_FRONT_FWD(8, true); else ER_FRONT_FWD(8, false); }
       else { if (g->seg_narrow) ER_FRONT_FWD(4, true); else ER_FRONT_FWD(4, false); }
 #undef ER_FRONT_FWD
@@ -4088,11 +4192,6 @@ static int emb_front_impl(er_emb_group* const* groups, int n, int flags, const e
 int er_emb_front(er_emb_group* const* groups, int n, int flags, const er_opt_hyper* hyper, er_stream_t stream) {
   return emb_front_impl(groups, n, flags, hyper, er::as_stream(stream), nullptr);
 }
-
-// probe hook: 16 wall-clock stamps (100 MHz) per workgroup of the next er_emb_bwd_fused launches into `p` (nullptr: off);
-// tools/own_probe.py reads them.  Not part of the product path.
-static unsigned long long* g_own_dbg = nullptr;
-int er_debug_stamps(unsigned long long* p) { g_own_dbg = p; return 0; }
 
 static int emb_bwd_fused_impl(er_emb_group* const* groups, int n, const er_grad_group* finish, int n_finish, int opt_kind,
                               const er_opt_hyper* hyper, const er_gemm_problem* wgrads, int n_wgrads, int wgrad_blocks,

@@ -15,11 +15,11 @@ bs = [gen.next_batch() for _ in range(6)]
 for b in bs[:5]: est.train_step(b)
 torch.cuda.synchronize()
 be = kernels.hip()
-buf = torch.zeros(4096 * 16, dtype=torch.int64, device='cuda:0')
+buf = torch.zeros(2 * 4096 * 16, dtype=torch.int64, device='cuda:0')  # (second half: the front launch's, tools/front_probe.py)
 be.lib.er_debug_stamps(buf.data_ptr())
 est.train_step(bs[5]); torch.cuda.synchronize()
 be.lib.er_debug_stamps(None)
-full = buf.cpu().numpy().reshape(-1, 16)
+full = buf[:4096 * 16].cpu().numpy().reshape(-1, 16)
 used = full[:, 0] > 0
 idx = np.where(used)[0]
 t0 = full[used, 0].min()
