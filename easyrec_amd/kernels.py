@@ -1902,6 +1902,99 @@ class HipBackend(object):
       self.op_log.append(('er::autoint_attn_bwd_kernel', 12.0 * B * F * F * H * ds))
     return dq
 
+  # -- K8f BERT-style encoder pieces (layers/multihead_cross_attention.py)
+  MHA_LDS_BUDGET = 81920  # bytes per workgroup (csrc/er_mha.hip)
+  MHA_MAX_DS = 128
+  ADD_LN_MAX_W = 4096
+
+  def mha_lds_bytes(self, F, T, ds, bwd=True):
+    return int(self.lib.er_mha_lds_bytes(int(F), int(T), int(ds), bool(bwd)))
+
+  def mha_pack(self, ws, bs):
+    """[w_0 | w_1 (| w_2)] ([din, d] each) -> [din, n d] and the biases side by side [n d]: one launch."""
+    n = len(ws)
+    din, d = ws[0].shape
+    assert n in (2, 3) and len(bs) == n and all(w.shape == (din, d) for w in ws) and all(b.shape == (d,) for b in bs)
+    w = torch.empty(din, n * d, dtype=torch.float32, device=ws[0].device)
+    bias = torch.empty(n * d, dtype=torch.float32, device=ws[0].device)
+    ws = [_f32c(t) for t in ws] + [None] * (3 - n)
+    bs = [_f32c(t) for t in bs] + [None] * (3 - n)
+    self.ck.er_mha_pack(_p(ws[0]), _p(ws[1]), _p(ws[2]), _p(bs[0]), _p(bs[1]), _p(bs[2]), n, din, d, _p(w), _p(bias),
+                        _stream())
+    return w, bias
+
+  @staticmethod
+  def _mha_operand(t, rows, d, what):
+    assert t.dim() == 2 and t.shape == (rows, d) and t.stride(1) == 1 and t.stride(0) >= d and \
+        t.dtype == torch.float32, '%s: [%d, %d] fp32 rows with unit inner stride expected' % (what, rows, d)
+    return t
+
+  def mha_fwd(self, q, k, v, to_mask, B, F, T, H, ds):
+    """q [B * F, H ds], k, v [B * T, H ds]: 2-D fp32 views with unit inner stride (column blocks of a packed buffer or
+    tensors of their own), to_mask int32 [B, T] or None -> ctx [B * F, H ds] = concat_h softmax(Q_h K_h^T / sqrt(ds)
+    + adder) V_h."""
+    d = H * ds
+    self._mha_operand(q, B * F, d, 'mha_fwd q')
+    self._mha_operand(k, B * T, d, 'mha_fwd k')
+    self._mha_operand(v, B * T, d, 'mha_fwd v')
+    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
+    ctx = torch.empty(B * F, d, dtype=torch.float32, device=q.device)
+    self.ck.er_mha_fwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), B, F, T, H, ds, _p(ctx),
+                       _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::mha_fwd_kernel', 4.0 * B * F * T * d))
+    return ctx
+
+  def mha_bwd(self, q, k, v, to_mask, dctx, B, F, T, H, ds, dq, dk, dv):
+    """dq [B * F, H ds], dk, dv [B * T, H ds] (views as above, written) from dctx [B * F, H ds] (contiguous)."""
+    d = H * ds
+    self._mha_operand(q, B * F, d, 'mha_bwd q')
+    self._mha_operand(k, B * T, d, 'mha_bwd k')
+    self._mha_operand(v, B * T, d, 'mha_bwd v')
+    self._mha_operand(dq, B * F, d, 'mha_bwd dq')
+    self._mha_operand(dk, B * T, d, 'mha_bwd dk')
+    self._mha_operand(dv, B * T, d, 'mha_bwd dv')
+    assert dctx.shape == (B * F, d)
+    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
+    self.ck.er_mha_bwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), _p(_f32c(dctx)), B, F,
+                       T, H, ds, _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv), dv.stride(0), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::mha_bwd_kernel', 12.0 * B * F * T * d))
+
+  def add_ln_grid(self, rows, W):
+    return int(self.lib.er_add_ln_grid(int(rows), int(W)))
+
+  def add_ln_fwd(self, x, res, gamma, beta, eps):
+    """x [rows, W], res [res_rows, W] (read at row % res_rows) or None -> (y, mean [rows], rstd [rows])."""
+    rows, W = x.shape
+    assert res is None or (res.dim() == 2 and res.shape[1] == W and rows % res.shape[0] == 0)
+    assert gamma.shape == (W,) and beta.shape == (W,)
+    y = torch.empty_like(x)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    self.ck.er_add_ln_fwd(_p(_f32c(x)), _p(None if res is None else _f32c(res)), rows,
+                          1 if res is None else res.shape[0], W, _p(_f32c(gamma)), _p(_f32c(beta)), float(eps), _p(y),
+                          _p(mean), _p(rstd), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::add_ln_fwd_kernel', 8.0 * rows * W))
+    return y, mean, rstd
+
+  def add_ln_bwd(self, dy, x, res, gamma, mean, rstd, grads, acc):
+    """-> dz [rows, W], the gradient with respect to x + res; dgamma and dbeta are added into (acc) or written to
+    `grads` (a ThetaGradTable of gamma's and beta's buffers) by the shared fixed-order reduce."""
+    rows, W = x.shape
+    assert dy.shape == x.shape and mean.numel() == rows and rstd.numel() == rows
+    dz = torch.empty_like(x)
+    grid = self.add_ln_grid(rows, W)
+    partials = torch.empty(grid * 2 * W, dtype=torch.float32, device=x.device)
+    self.ck.er_add_ln_bwd(_p(_f32c(dy)), _p(_f32c(x)), _p(None if res is None else _f32c(res)), rows,
+                          1 if res is None else res.shape[0], W, _p(_f32c(gamma)), _p(mean), _p(rstd), _p(dz),
+                          _p(partials), _stream())
+    self.theta_grad_reduce(partials, grid, grads, 8, acc)
+    if self.op_log is not None:
+      self.op_log.append(('er::add_ln_bwd_kernel', 12.0 * rows * W))
+    return dz
+
   # -- K8d FiBiNet's field blocks (layers/keras/fibinet.py)
   def bilinear_lds_bytes(self, F, D):
     return int(self.lib.er_bilinear_lds_bytes(int(F), int(D)))
@@ -4039,6 +4132,122 @@ class AutoIntAttnFn(torch.autograd.Function):
     qkvr, y = ctx.saved_tensors
     F, H, ds = ctx.shape
     return hip().autoint_attn_bwd(qkvr, y, dy.contiguous(), F, H, ds), None, None, None
+
+
+class MhaProjFn(torch.autograd.Function):
+  """The biased projections of one attention_layer that share an input (reference layers/multihead_cross_attention.py
+  :150-177): apply(x [rows, din], grads, n, w_0 .. w_{n-1}, b_0 .. b_{n-1}) -> x . [w_0 | ..] + [b_0 | ..] [rows, n d],
+  n = 3 (query | key | value of self-attention) or 2 (key | value of cross-attention): ONE contraction, bias in its
+  epilogue, on an operand packed by one launch.  Backward: dx is one NT contraction against the packed operand; each
+  weight gradient is x^T . its column slice of the incoming gradient and each bias gradient that slice's column sums,
+  ADDED into the variables' gradient buffers (`grads`: the 2 n buffers in the parameters' order, zeroed once per step by
+  VarStore.zero_grad), or returned to autograd when no buffers are given."""
+
+  @staticmethod
+  def forward(ctx, x, grads, n, *params):
+    be = hip()
+    assert len(params) == 2 * n
+    x = x if x.is_contiguous() else x.contiguous()
+    w, bias = be.mha_pack([p.detach() for p in params[:n]], [p.detach() for p in params[n:]])
+    out = be.gemm(GEMM_NN, x, w, bias=bias)
+    ctx.save_for_backward(x, w)
+    ctx.grads, ctx.n = grads, n
+    ctx.sink = be.wgrad_sink()
+    return out
+
+  @staticmethod
+  def backward(ctx, dg):
+    be = hip()
+    x, w = ctx.saved_tensors
+    n = ctx.n
+    dg = dg if dg.is_contiguous() else dg.contiguous()
+    d = w.shape[1] // n
+    dx = be.gemm(GEMM_NT, dg, w) if ctx.needs_input_grad[0] else None
+    out = [None] * (2 * n)
+    for k in range(n):
+      part = dg[:, k * d:(k + 1) * d]
+      # (given buffers always receive their gradient; the parameters themselves may be detached views)
+      if ctx.grads is not None:
+        _wgrad(be, x, part, ctx.grads[k], False, ctx.sink)
+        be.colsum(part, out=ctx.grads[n + k], accumulate=True)
+      else:
+        if ctx.needs_input_grad[3 + k]:
+          out[k] = _wgrad(be, x, part, None, False, ctx.sink)
+        if ctx.needs_input_grad[3 + n + k]:
+          out[n + k] = be.colsum(part)
+    return (dx, None, None) + tuple(out)
+
+
+class MhaAttnFn(torch.autograd.Function):
+  """reference layers/multihead_cross_attention.py:179-243 between the projections and the output dense:
+  apply(q_src, kv_src, to_mask, B, F, T, H, ds) -> concat_h softmax(Q_h K_h^T / sqrt(ds) + adder) V_h [B * F, H ds].
+  kv_src None: q_src is the packed [B * F, 3 H ds] buffer Q | K | V of self-attention (F == T); else q_src [B * F, H ds]
+  and kv_src [B * T, 2 H ds] = K | V.  to_mask: int32 [B, T] or None.  The backward (er_mha_bwd) recomputes the
+  probabilities and writes dQ | dK | dV into ONE buffer per source, so that the projections' backward is contractions."""
+
+  @staticmethod
+  def _split(q_src, kv_src, d):
+    if kv_src is None:
+      return q_src[:, :d], q_src[:, d:2 * d], q_src[:, 2 * d:3 * d]
+    return q_src, kv_src[:, :d], kv_src[:, d:2 * d]
+
+  @staticmethod
+  def forward(ctx, q_src, kv_src, to_mask, B, F, T, H, ds):
+    be = hip()
+    d = H * ds
+    q_src = q_src if q_src.is_contiguous() else q_src.contiguous()
+    if kv_src is not None:
+      kv_src = kv_src if kv_src.is_contiguous() else kv_src.contiguous()
+    assert q_src.shape == (B * F, d if kv_src is not None else 3 * d) and (kv_src is not None or F == T)
+    assert kv_src is None or kv_src.shape == (B * T, 2 * d)
+    q, k, v = MhaAttnFn._split(q_src, kv_src, d)
+    out = be.mha_fwd(q, k, v, to_mask, B, F, T, H, ds)
+    ctx.save_for_backward(q_src, kv_src, to_mask)
+    ctx.shape = (B, F, T, H, ds)
+    return out
+
+  @staticmethod
+  def backward(ctx, dctx):
+    be = hip()
+    q_src, kv_src, to_mask = ctx.saved_tensors
+    B, F, T, H, ds = ctx.shape
+    d = H * ds
+    dq_src = torch.empty_like(q_src)
+    dkv_src = None if kv_src is None else torch.empty_like(kv_src)
+    q, k, v = MhaAttnFn._split(q_src, kv_src, d)
+    dq, dk, dv = MhaAttnFn._split(dq_src, dkv_src, d)
+    be.mha_bwd(q, k, v, to_mask, dctx.contiguous(), B, F, T, H, ds, dq, dk, dv)
+    return dq_src, dkv_src, None, None, None, None, None, None
+
+
+class AddLayerNormFn(torch.autograd.Function):
+  """layer_norm(x + res) of the reference's encoder (layers/multihead_cross_attention.py:346, :365, :768;
+  compat/layers.py layer_norm): apply(x [rows, W], res, gamma, beta, eps, grads) -> (x + res - mean) * rstd * gamma +
+  beta.  res: None, [rows, W] (the residual) or [S, W] with rows % S == 0 (a per-position addend, read at row % S).
+  Backward (er_add_ln_bwd): one launch gives the gradient with respect to x + res, handed to both addends (summed over
+  the batch for the broadcast one); dgamma and dbeta are ADDED into `grads` = (gamma's, beta's gradient buffer) by the
+  shared fixed-order reduce, or returned to autograd when no buffers are given."""
+
+  @staticmethod
+  def forward(ctx, x, res, gamma, beta, eps, grads):
+    be = hip()
+    x = x if x.is_contiguous() else x.contiguous()
+    if res is not None:
+      res = res if res.is_contiguous() else res.contiguous()
+    y, mean, rstd = be.add_ln_fwd(x, None if res is None else res.detach(), gamma.detach(), beta.detach(), eps)
+    ctx.save_for_backward(x, res, gamma, beta, mean, rstd)
+    ctx.grads = grads
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    x, res, gamma, beta, mean, rstd = ctx.saved_tensors
+    table, acc, ret = _theta_grads(ctx, (gamma, beta))
+    dz = hip().add_ln_bwd(dy.contiguous(), x, res, gamma, mean, rstd, table, acc)
+    dres = None
+    if res is not None and ctx.needs_input_grad[1]:
+      dres = dz if res.shape[0] == x.shape[0] else dz.view(-1, res.shape[0], res.shape[1]).sum(dim=0)
+    return (dz, dres) + ret + (None, None)
 
 
 def _pack_theta(be, params, count, what):

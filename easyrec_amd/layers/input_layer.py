@@ -1069,18 +1069,25 @@ class InputLayer(object):
     eng = self._engine
     B = eng.batch_size
     assert all(isinstance(c, EmbeddingColumn) for c in seq_columns), 'sequence raw features: outside the hot-path scope'
-    lens = {features.seqs[c.raw_name]['ids'].shape[1] for c in seq_columns}
-    assert len(lens) == 1, 'the sequence features of group %s differ in max_seq_len' % group_name
-    L = lens.pop()
-    gkey = 'group:' + group_name + ':seq'
-    eng.declare_seq_output(gkey, B * L, sum(c.dimension for c in seq_columns), self._embedding_regularizer)
-    col, cols = 0, []
+    # columns of one static length share ONE output (all of them, when the group has one max_seq_len: the key without a
+    # suffix); a group whose sequences differ in max_seq_len (Uniter's `text`: title 16, genres 8) gets one per length
+    by_len = {}
     for c in seq_columns:
-      declare_lookup(eng, features, c, 'input_layer', gkey, col, B * L, seq=True,
-                     table_name='input_layer/%s/embedding_weights' % c.categorical_column.name)
-      cols.append((col, c.dimension, c.raw_name))
-      col += c.dimension
-    self._seq_plan[group_name] = {'gkey': gkey, 'cols': cols, 'L': L, 'width': col}
+      by_len.setdefault(features.seqs[c.raw_name]['ids'].shape[1], []).append(c)
+    outs, cols = [], []
+    for n, (L, cs) in enumerate(by_len.items()):
+      gkey = 'group:' + group_name + ':seq' + ('' if n == 0 else ':L%d' % L)
+      eng.declare_seq_output(gkey, B * L, sum(c.dimension for c in cs), self._embedding_regularizer)
+      col = 0
+      for c in cs:
+        declare_lookup(eng, features, c, 'input_layer', gkey, col, B * L, seq=True,
+                       table_name='input_layer/%s/embedding_weights' % c.categorical_column.name)
+        cols.append((len(outs), col, c.dimension, c.raw_name))
+        col += c.dimension
+      outs.append({'gkey': gkey, 'L': L, 'width': col})
+    order = {c.raw_name: i for i, c in enumerate(seq_columns)}
+    cols.sort(key=lambda t: order[t[3]])  # (the columns' own order, whatever their lengths)
+    self._seq_plan[group_name] = {'outs': outs, 'cols': cols}
 
   def _uncombined(self, features, group_name):
     """is_combine=False (layers/input_layer.py:268-278): ([(embedding [B, L, dim], length [B]) per sequence column],
@@ -1092,17 +1099,19 @@ class InputLayer(object):
     if group_name not in self._seq_plan:
       self._declare_sequences(features, group_name)  # (reference order: sequence features first, then the plain ones)
     sp = self._seq_plan[group_name]
-    B, L = eng.batch_size, sp['L']
-    if not eng.finalized:
-      seq_out = eng.groups[sp['gkey']]['out']
-    else:
-      eng.forward(features.version)
-      seq_out = eng.group_tensor(sp['gkey'], requires_grad=self._is_training)
-    seq3 = seq_out.view(B, L, sp['width'])
+    B = eng.batch_size
+    seq3 = []
+    for o in sp['outs']:
+      if not eng.finalized:
+        seq_out = eng.groups[o['gkey']]['out']
+      else:
+        eng.forward(features.version)
+        seq_out = eng.group_tensor(o['gkey'], requires_grad=self._is_training)
+      seq3.append(seq_out.view(B, o['L'], o['width']))
     seq_features = []
-    for c0, d, name in sp['cols']:
+    for oi, c0, d, name in sp['cols']:
       Lm = features.seq_pad_len(name)
-      seq_features.append((seq3[:, :Lm, c0:c0 + d], features.seqs[name]['len']))
+      seq_features.append((seq3[oi][:, :Lm, c0:c0 + d], features.seqs[name]['len']))
     if not columns:
       return seq_features, None, []
     plain, plain_list = self._combined(features, group_name, plain_only=True)
@@ -1110,7 +1119,7 @@ class InputLayer(object):
 
   def sequence_names(self, group_name):
     """The raw feature names of a group's sequence columns, in the order is_combine=False returns them (after that call)."""
-    return [name for _, _, name in self._seq_plan[group_name]['cols']]
+    return [name for _, _, _, name in self._seq_plan[group_name]['cols']]
 
   def __call__(self, features, group_name, is_combine=True, is_dict=False):
     assert group_name in self._feature_groups, 'invalid group_name[%s], list: %s' % (

@@ -670,6 +670,60 @@ int er_autoint_pack(const float* wq, const float* wk, const float* wv, const flo
                     float* w, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8f BERT-style encoder pieces: masked multi-head attention core and residual add + LayerNorm.
+ *     Replaces, of attention_layer layers/multihead_cross_attention.py:179-243, the Reshape / Transpose of
+ *     Q, K and V, BatchMatMul(transpose_b), Mul by 1 / sqrt(size_per_head), the mask's ExpandDims / Sub / Mul /
+ *     Add, Softmax, BatchMatMul and the Transpose / Reshape of the context; and the Add + layer_norm that
+ *     transformer_encoder (:346, :365), cross_attention_block (:460, :480) and embedding_postprocessor
+ *     (:732, :766-768) end with (compat/layers.py layer_norm, begin_norm_axis = -1, epsilon 1e-12).
+ * er_mha_fwd: q [B * F, .] at pitch ldq, k and v [B * T, .] at ldk / ldv (pitches in floats, >= H * ds):
+ *   head h is the column block h * ds .. (h + 1) * ds of each.  One launch serves a packed
+ *   [rows, 3 H ds] self-attention buffer (q, q + H ds, q + 2 H ds at pitch 3 H ds) and separate Q and K | V
+ *   buffers.  to_mask int32 [B, T] (1 attend, 0 masked) or NULL.  Per example and head:
+ *   S = Q_h K_h^T * (1 / sqrt(ds)) + adder, adder[j] = (1 - mask[b, j]) * -10000.f - max_j' of the same (a
+ *   row shift, which softmax ignores: with any open key it is the reference's adder; with none the row is
+ *   the softmax of the unmasked scores, not of scores rounded to the fp32 grid at -10000); P = softmax
+ *   over T; ctx [B * F, H ds] (contiguous): ctx[b, i, h ds ..] = P V_h.
+ * er_mha_bwd: recomputes P from q and k; from dctx [B * F, H ds] writes dq [B * F, .] at lddq, dk and dv
+ *   [B * T, .] at lddk / lddv: dV_h = P^T dctx_h, dP = dctx_h V_h^T, dS = P o (dP - rowsum(dP o P)),
+ *   dQ_h = dS K_h / sqrt(ds), dK_h = dS^T Q_h / sqrt(ds).  A workgroup owns whole (example, head) units: no
+ *   atomics, fixed summation order, nothing of size [B, H, F, T] in HBM.
+ * Envelope: 1 <= ds <= 128 and er_mha_lds_bytes(F, T, ds, 1) <= 81920 (two workgroups per CU), with
+ *   er_mha_lds_bytes(F, T, ds, bwd) = 4 * ((F + 2 T) * odd(ds) + F * odd(T) + T) forward,
+ *   4 * ((2 F + 2 T) * odd(ds) + 2 F * odd(T) + T) backward (odd(n) = n | 1); 0 for F, T or ds < 1.
+ *   (F, T, ds) = (33, 33, 128) takes 76956 bytes backward.  16-byte global loads where ds % 4 == 0, the
+ *   pitch % 4 == 0 and the base is 16-byte aligned; 4-byte loads otherwise.
+ * er_mha_pack: w [din, n d] = [w0 | w1 (| w2)], bias [n d] = [b0 | b1 (| b2)] for n = 2 (K | V) or 3
+ *   (Q | K | V): the operand and bias of the one projection contraction.
+ * er_add_ln_fwd: z = x + res[row % res_rows] (res NULL: z = x) over [rows, W]; mean = the row's mean, taken
+ *   about its first element; var = mean((z - mean)^2) (two passes, tf.nn.moments' form);
+ *   rstd = 1 / sqrt(var + eps); y = (z - mean) * rstd * gamma + beta.  mean, rstd [rows] are kept.
+ *   res_rows = rows: the encoder's residual; res_rows = S: the postprocessor's per-position addend.
+ * er_add_ln_bwd: re-reads x and res (16 W + 8 bytes per row in, 4 W out); dz [rows, W] = the gradient with
+ *   respect to x + res = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * gamma,
+ *   xhat = (z - mean) * rstd (no division by gamma); partials [er_add_ln_grid(rows, W), 2 W] = per
+ *   workgroup sum over its rows of dy * xhat | dy, which er_theta_grad_reduce (K8e) sums with
+ *   row_groups = 8 into gamma's and beta's buffers.  Workgroup g owns the rows
+ *   [g * ceil(rows / grid), ..): fixed order, no atomics.
+ * Envelope: 1 <= W <= 4096 (er_add_ln_grid returns 0 outside).
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_mha_lds_bytes(int32_t F, int32_t T, int32_t ds, int bwd);
+int er_mha_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+               const int32_t* to_mask, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds, float* ctx,
+               er_stream_t stream);
+int er_mha_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+               const int32_t* to_mask, const float* dctx, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds,
+               float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, er_stream_t stream);
+int er_mha_pack(const float* w0, const float* w1, const float* w2, const float* b0, const float* b1, const float* b2,
+                int32_t n, int32_t din, int32_t d, float* w, float* bias, er_stream_t stream);
+int32_t er_add_ln_grid(int64_t rows, int32_t W);
+int er_add_ln_fwd(const float* x, const float* res, int64_t rows, int64_t res_rows, int32_t W, const float* gamma,
+                  const float* beta, float eps, float* y, float* mean, float* rstd, er_stream_t stream);
+int er_add_ln_bwd(const float* dy, const float* x, const float* res, int64_t rows, int64_t res_rows, int32_t W,
+                  const float* gamma, const float* mean, const float* rstd, float* dz, float* partials,
+                  er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8d FiBiNet's field blocks.  x [B, F * D]: F fields of the same width D side by side, fp32.
  * Bilinear.  Replaces the per-field Dense (MatMul + BiasAdd), the per-pair expand_dims / MatMul / Squeeze
  *     (use_plus) or Mul, and the ConcatV2 of BiLinear.call layers/keras/fibinet.py:175-203 (types `all`

@@ -1,0 +1,200 @@
+"""Uniter and DBMTL.bottom_uniter on the CPU stand-in (easyrec_amd/layers/uniter.py, model/uniter.py, model/dbmtl.py):
+the class is registered, the variables carry the reference's names, token types and the mask follow the reference's
+numbering, what the reference asserts raises ValueError at build time, the sample's group combinations build and take
+two training steps, and the committed config is the sample's model section."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from easyrec_amd.utils import config_util, load_class
+from tests import _uniter_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _estimator(cfg, B=16, **kw):
+  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
+  return EasyRecEstimator(cfg, device='cpu', batch_size=B, seed=4, **kw).build()
+
+
+def test_model_class_is_registered():
+  load_class.import_all_models()
+  from easyrec_amd.model.easy_rec_model import _EASY_REC_MODEL_CLASS_MAP
+  assert 'Uniter' in _EASY_REC_MODEL_CLASS_MAP
+
+
+def test_committed_config_is_the_sample_model():
+  cfg = config_util.get_configs_from_pipeline_file(os.path.join(ROOT, 'configs', 'uniter_movielens.config'))
+  mc = cfg.model_config
+  assert mc.model_class == 'Uniter' and [g.group_name for g in mc.feature_groups] == ['image', 'general', 'text', 'other']
+  assert [len(g.feature_names) for g in mc.feature_groups] == [1, 7, 2, 2]
+  c = mc.uniter.config
+  assert (c.hidden_size, c.num_attention_heads, c.num_hidden_layers, c.intermediate_size) == (512, 4, 2, 512)
+  assert c.hidden_act == 'swish' and c.max_position_embeddings == 16 and abs(c.hidden_dropout_prob - 0.1) < 1e-7
+  assert c.attention_probs_dropout_prob == 0 and list(c.other_feature_dnn.hidden_units) == [256, 128]
+  assert list(mc.uniter.final_dnn.hidden_units) == [256, 64] and abs(mc.embedding_regularization - 1e-6) < 1e-12
+  assert cfg.data_config.batch_size == 1024
+  by_name = {f.input_names[0]: f for f in cfg.feature_config.features}
+  assert by_name['embedding'].raw_input_dim == 512 and by_name['title'].max_seq_len == 16 and by_name['genres'].max_seq_len == 8
+  # the sample's own model_config and feature_config (tests/golden/uniter_on_movielens_sections.config: settings only)
+  sample = config_util.get_configs_from_pipeline_file(os.path.join(ROOT, 'tests', 'golden', 'uniter_on_movielens_sections.config'))
+  assert sample.model_config == mc and sample.feature_config == cfg.feature_config
+
+
+UNITER_NAMES = {
+    'all': ['token_type/token_type_embeddings', 'position_embedding/img_position_embeddings', 'LayerNorm/beta',
+            'LayerNorm/gamma', 'txt_projection/kernel', 'txt_projection/bias', 'LayerNorm_1/beta', 'LayerNorm_1/gamma',
+            'txt_seq_projection_0/kernel', 'txt_seq_projection_0/bias', 'position_embedding/txt_position_embeddings_0',
+            'LayerNorm_2/beta', 'LayerNorm_2/gamma', 'txt_seq_projection_1/kernel', 'txt_seq_projection_1/bias',
+            'position_embedding/txt_position_embeddings_1', 'LayerNorm_3/beta', 'LayerNorm_3/gamma', 'cls_emb'],
+    'image': ['position_embedding/img_position_embeddings', 'LayerNorm/beta', 'LayerNorm/gamma', 'cls_emb'],
+    'text': ['txt_projection/kernel', 'txt_projection/bias', 'token_type/token_type_embeddings', 'LayerNorm/beta',
+             'LayerNorm/gamma', 'txt_seq_projection_0/kernel', 'txt_seq_projection_0/bias',
+             'position_embedding/txt_position_embeddings_0', 'LayerNorm_1/beta', 'LayerNorm_1/gamma',
+             'txt_seq_projection_1/kernel', 'txt_seq_projection_1/bias', 'position_embedding/txt_position_embeddings_1',
+             'LayerNorm_2/beta', 'LayerNorm_2/gamma', 'cls_emb'],
+}
+
+
+@pytest.mark.parametrize('kind,dbmtl', [('all', False), ('image', False), ('text', False), ('all', True)])
+def test_model_builds_names_its_variables_and_steps_on_the_stand_in(ref_backend, built_lib, kind, dbmtl):
+  """The three Uniter samples' group combinations and DBMTL over bottom_uniter at a small hidden size: the variables in
+  the order and under the names the reference's graph creates them (layers/uniter.py, multihead_cross_attention.py), only
+  final_dnn / other_dnn / the towers regularised, and two training steps with finite, changing losses."""
+  from easyrec_amd.input.synthetic import SyntheticBatches
+  cfg = ref.uniter_cfg(kind, batch_size=16, hidden=24, heads=3, layers=2, dbmtl=dbmtl)
+  est = _estimator(cfg)
+  names = [n for n in est.varstore.names()]
+  # (hidden 24 is not the image features' 512: `img_projection` comes first, as in image_embeddings, uniter.py:203-208)
+  head = (['img_projection/kernel', 'img_projection/bias'] if kind != 'text' else []) + UNITER_NAMES[kind]
+  assert names[:len(head)] == head
+  enc = ref.encoder_variable_names('uniter', 2)
+  assert names[len(head):len(head) + len(enc)] == enc
+  st = est.state_dict()
+  assert st['cls_emb'].shape == (1, 1, 24) and np.abs(st['cls_emb']).max() <= (6.0 / 25) ** 0.5
+  if kind != 'image':
+    assert st['token_type/token_type_embeddings'].shape == ({'all': 4, 'text': 3}[kind], 24)
+    assert st['position_embedding/txt_position_embeddings_0'].shape == (16, 24)
+  for n in names:
+    reg = n.endswith('/kernel') and n.split('/')[0] in ('final_dnn', 'other_dnn', 'classify', 'rating')
+    if not reg:
+      assert est.varstore.l2_of(n) == 0.0, n
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=16, seed=44)
+  losses = []
+  for _ in range(2):
+    est.train_step(gen.next_batch())
+    losses.append(est.loss_values())
+    assert all(np.isfinite(v) for v in losses[-1].values()), losses
+  assert losses[0]['total_loss'] != losses[1]['total_loss']
+  assert ('cross_entropy_loss_classify' in losses[0]) == dbmtl
+
+
+def test_token_types_and_the_mask_follow_the_reference(ref_backend, built_lib):
+  """uniter.py:66-72, :168, :235: image 0, general 1, the text features 2 and 3 (vocabulary 4); without an image group
+  general 0, text 1 and 2 (vocabulary 3); image alone uses no token types.  The to-mask is ones for [CLS], image and
+  general tokens, then position < length per text feature, in the group's feature order (title 16, genres 8)."""
+  from easyrec_amd.input.synthetic import SyntheticBatches
+  from easyrec_amd.layers import multihead_cross_attention as mca
+  est = _estimator(ref.uniter_cfg('all', hidden=24, heads=3))
+  layer = est.model._uniter_layer
+  assert layer.token_type_ids() == {'image': 0, 'general': 1, 'text': [2, 3]} and layer._token_type_vocab_size == 4
+  assert layer._use_token_type
+  text = _estimator(ref.uniter_cfg('text', hidden=24, heads=3)).model._uniter_layer
+  assert text.token_type_ids()['general'] == 0 and text.token_type_ids()['text'] == [1, 2]
+  assert text._token_type_vocab_size == 3 and text._use_token_type
+  image = _estimator(ref.uniter_cfg('image', hidden=24, heads=3)).model._uniter_layer
+  assert not image._use_token_type and image._token_type_vocab_size == 1
+  seen = {}
+  real = mca.transformer_encoder
+
+  def spy(x, attention_mask=None, **kw):
+    seen['mask'], seen['S'] = attention_mask, x.shape[1]
+    return real(x, attention_mask, **kw)
+
+  gen = SyntheticBatches(est.cfg.data_config if hasattr(est, 'cfg') else ref.uniter_cfg('all').data_config,
+                         est.feature_configs, batch_size=16, seed=3)
+  batch = gen.next_batch()
+  mca.transformer_encoder = spy
+  try:
+    est.predict(batch)
+  finally:
+    mca.transformer_encoder = real
+  assert seen['S'] == 33 and tuple(seen['mask'].shape) == (16, 33, 33) and not seen['mask'].is_floating_point()
+  row = seen['mask'][:, 0, :].cpu().numpy()
+  assert np.array_equal(row, seen['mask'][:, 7, :].cpu().numpy())
+  want = np.ones((16, 33), dtype=np.int64)
+  want[:, 9:25] = np.arange(16)[None, :] < batch['seq/title/len'][:, None]
+  want[:, 25:33] = np.arange(8)[None, :] < batch['seq/genres/len'][:, None]
+  assert np.array_equal(row, want)
+
+
+def test_rejected_combinations_raise_at_build_time(ref_backend, built_lib):
+  dup = ref.uniter_cfg('all', hidden=24, heads=3)
+  dup.model_config.feature_groups[1].feature_names.append('user_id')
+  with pytest.raises(ValueError, match='duplicate'):
+    _estimator(dup)
+  uneven = ref.uniter_cfg('all', hidden=24, heads=3)
+  uneven.feature_config.features[0].embedding_dim = 8
+  with pytest.raises(ValueError, match='consistent'):
+    _estimator(uneven)
+  short = ref.uniter_cfg('all', hidden=24, heads=3)
+  short.model_config.uniter.config.max_position_embeddings = 15
+  with pytest.raises(ValueError, match='max_position_embeddings'):
+    _estimator(short)
+  with pytest.raises(ValueError, match='bf16'):
+    _estimator(ref.uniter_cfg('all', hidden=24, heads=3), dense_dtype='bf16')
+  heads = ref.uniter_cfg('all', hidden=24, heads=5)
+  with pytest.raises(ValueError, match='multiple'):
+    _estimator(heads)
+  cmbf = ref.uniter_cfg('all', hidden=24, heads=3, dbmtl=True)
+  cmbf.model_config.dbmtl.ClearField('bottom_uniter')
+  cmbf.model_config.dbmtl.bottom_cmbf.SetInParent()
+  with pytest.raises(NotImplementedError, match='bottom_cmbf'):
+    _estimator(cmbf)
+
+
+def test_embedding_parallel_engine_is_refused():
+  from easyrec_amd.core import context
+  from easyrec_amd.layers import uniter
+  from easyrec_amd.layers.sharded_embedding import ShardedEmbeddingEngine
+  ctx = context.ModelContext(None, object.__new__(ShardedEmbeddingEngine))
+  with context.use(ctx), pytest.raises(ValueError, match='embedding-parallel'):
+    uniter.Uniter(ref.uniter_cfg('all').model_config, [], None, ref.uniter_cfg('all').model_config.uniter.config, None)
+
+
+def test_predict_is_deterministic_under_hidden_dropout(ref_backend, built_lib):
+  """hidden_dropout_prob 0.1: a training step gives finite losses, and two predictions of one batch in evaluation mode
+  are bit-equal: no dropout outside training.  The predictions are taken through `_predict_eval` (is_training False,
+  what evaluate() runs), not through two plain predict() calls: predict() on an estimator built for training keeps the
+  training flags, for every model of this project, so its dropout stays on."""
+  from easyrec_amd.input.synthetic import SyntheticBatches
+  cfg = ref.uniter_cfg('all', hidden=24, heads=3, hidden_dropout=0.1)
+  est = _estimator(cfg)
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=16, seed=5)
+  est.train_step(gen.next_batch())
+  assert all(np.isfinite(v) for v in est.loss_values().values())
+  b = gen.next_batch()
+  outs = [{k: v.detach().clone() for k, v in pred.items() if torch.is_tensor(v)} for _, pred in est._predict_eval([b, b])]
+  assert outs[0] and all(torch.equal(outs[0][k], outs[1][k]) for k in outs[0])
+
+
+@pytest.mark.parametrize('kind,dbmtl', [('all', False), ('image', False), ('text', False), ('all', True)])
+def test_first_steps_on_the_stand_in_match_the_fp64_oracle(ref_backend, built_lib, monkeypatch, kind, dbmtl):
+  """The product on the stand-in backend against tests/_uniter_oracle.py (the parent oracle's input layer, DNNs, losses
+  and optimizer around the fp64 restatement of the Uniter layer) at first_steps' bars: every loss, the logits and
+  every variable's gradient, the embedding tables' included.  initializer_range 0.3: see _uniter_ref.uniter_cfg."""
+  from tests import _oracle_steps
+  from tests._uniter_oracle import UniterOracle
+  monkeypatch.setattr(_oracle_steps, 'OracleTrainer', UniterOracle)
+  cfg = ref.uniter_cfg(kind, batch_size=16, hidden=24, heads=3, dbmtl=dbmtl, initializer_range=0.3)
+
+  def coverage(names, _):
+    assert 'cls_emb' in names and 'uniter_layer_1/attention/self/key/kernel' in names
+    assert any(n.startswith('final_dnn/') or n.startswith('classify/') for n in names)
+    if kind != 'image':
+      assert 'token_type/token_type_embeddings' in names and 'input_layer/title/embedding_weights' in names
+
+  _oracle_steps.first_steps(cfg, 16, 5, device='cpu', oracle_dtype=torch.float64, coverage=coverage,
+                            skip_bn_shadowed_bias=True)

@@ -305,6 +305,74 @@ def autoint_taobao(sequence=False, **kw):
   return cfg
 
 
+UNITER_MOVIELENS = """
+train_input_path: "data/test/movielens_1m/ml_train_data"
+eval_input_path: "data/test/movielens_1m/ml_test_data"
+model_dir: "experiments/uniter_movielens_ckpt"
+train_config {
+  optimizer_config { adam_optimizer { learning_rate { constant_learning_rate { learning_rate: 0.0001 } } beta1: 0.9 beta2: 0.999 }
+                     use_moving_average: false }
+  log_step_count_steps: 100 save_checkpoints_steps: 100 sync_replicas: true num_steps: 10
+}
+eval_config { metrics_set { auc {} } }
+data_config {
+  input_fields { input_name: 'rating' input_type: INT32 }
+  input_fields { input_name: 'label' input_type: INT32 }
+  input_fields { input_name: 'user_id' input_type: INT32 }
+  input_fields { input_name: 'movie_id' input_type: INT32 }
+  input_fields { input_name: 'gender' input_type: INT32 }
+  input_fields { input_name: 'age' input_type: INT32 }
+  input_fields { input_name: 'occupation' input_type: INT32 }
+  input_fields { input_name: 'zip_id' input_type: INT32 default_val: '0' }
+  input_fields { input_name: 'genres' input_type: STRING default_val: 'unknown' }
+  input_fields { input_name: 'title' input_type: STRING default_val: 'unknown' }
+  input_fields { input_name: 'movie_year_bin' input_type: INT32 }
+  input_fields { input_name: 'score_year_diff' input_type: INT32 default_val: '0' }
+  input_fields { input_name: 'score_time' input_type: DOUBLE }
+  input_fields { input_name: 'embedding' input_type: STRING default_val: '' }
+  label_fields: 'label'
+  batch_size: %(batch_size)d num_epochs: 10000 prefetch_size: 1 input_type: CSVInput
+}
+feature_config {
+  features { input_names: 'user_id' feature_type: IdFeature embedding_dim: 16 hash_bucket_size: 12000 }
+  features { input_names: 'movie_id' feature_type: IdFeature embedding_dim: 16 hash_bucket_size: 6000 }
+  features { input_names: 'gender' feature_type: IdFeature embedding_dim: 16 num_buckets: 2 }
+  features { input_names: 'zip_id' feature_type: IdFeature embedding_dim: 16 num_buckets: 3405 }
+  features { input_names: 'occupation' feature_type: IdFeature embedding_dim: 16 num_buckets: 21 }
+  features { input_names: 'age' feature_type: IdFeature embedding_dim: 16 num_buckets: 7 }
+  features { input_names: 'genres' feature_type: SequenceFeature separator: '|' embedding_dim: 16 max_seq_len: 8 hash_bucket_size: 100 }
+  features { input_names: 'title' feature_type: SequenceFeature separator: ' ' max_seq_len: 16 embedding_dim: 16 hash_bucket_size: 20000 }
+  features { input_names: 'movie_year_bin' feature_type: IdFeature embedding_dim: 16 num_buckets: 36 }
+  features { input_names: 'score_year_diff' feature_type: IdFeature embedding_dim: 16 num_buckets: 83 }
+  features { input_names: 'score_time' feature_type: RawFeature embedding_dim: 16 }
+  features { input_names: 'embedding' feature_type: RawFeature separator: '|' raw_input_dim: 512 }
+}
+model_config {
+  model_class: 'Uniter'
+  feature_groups { group_name: 'image' feature_names: 'embedding' wide_deep: DEEP }
+  feature_groups { group_name: 'general' feature_names: 'user_id' feature_names: 'movie_id' feature_names: 'gender'
+                   feature_names: 'age' feature_names: 'occupation' feature_names: 'zip_id' feature_names: 'movie_year_bin'
+                   wide_deep: DEEP }
+  feature_groups { group_name: 'text' feature_names: 'title' feature_names: 'genres' wide_deep: DEEP }
+  feature_groups { group_name: 'other' feature_names: 'score_year_diff' feature_names: 'score_time' wide_deep: DEEP }
+  uniter {
+    config { hidden_size: 512 num_attention_heads: 4 num_hidden_layers: 2 intermediate_size: 512 hidden_act: 'swish'
+             max_position_embeddings: 16 hidden_dropout_prob: 0.1 attention_probs_dropout_prob: 0
+             other_feature_dnn { hidden_units: 256 hidden_units: 128 } }
+    final_dnn { hidden_units: 256 hidden_units: 64 }
+  }
+  embedding_regularization: 1e-6
+}
+"""
+
+
+def uniter_movielens(batch_size=1024):
+  """Uniter: samples/model_config/uniter_on_movielens.config (its data, feature and model sections: 1 [CLS] + 1 image
+  + 7 general + 16 title + 8 genres = 33 tokens of hidden 512, 4 heads, 2 layers) on synthetic MovieLens-shaped
+  batches; batch size 1024 (the sample's 128 measures little but launch overhead); the metric set is auc alone."""
+  return text_format.Parse(UNITER_MOVIELENS % {'batch_size': batch_size}, pipeline_pb2.EasyRecConfig())
+
+
 def fibinet_taobao(bilinear_type='each', use_plus=True, **kw):
   """FiBiNet, the model section of samples/model_config/fibinet_on_taobao.config: RankModel over a backbone whose
   input-layer block batch-normalises the 17 fields of D = 16 and hands them on as a list, and a `FiBiNet` block (SENet
@@ -932,6 +1000,7 @@ if __name__ == '__main__':
   write(mmoe_taobao(), 'mmoe_taobao.config')
   write(bst_taobao(item_rows=10000000), 'bst_taobao_10m.config')
   write(autoint_taobao(item_rows=10000000), 'autoint_taobao_10m.config')
+  write(uniter_movielens(), 'uniter_movielens.config')
   write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
   write(dssm_taobao(item_rows=10000000), 'dssm_taobao_10m.config')
   write(dssm_taobao(in_batch=True, item_rows=10000000), 'dssm_inbatch_taobao_10m.config')
