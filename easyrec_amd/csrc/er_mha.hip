@@ -18,6 +18,11 @@
 // With an open key nothing changes (masked keys get exp(-10000 + ..) = 0 either way); with none the row is the softmax
 // of the unmasked scores, the value the reference's formula has in exact arithmetic.
 //
+// Grouped units (mha_group_*): for short sequences the 512 threads are G = 8, 4 or 2 groups, each owning a unit in its own
+// LDS region and running the same device functions with its own thread index and count; the results are the one-unit
+// kernels' bits.  Segment mean (segment_mean_*): CMBF's masked mean pooling over consecutive token segments (reference
+// layers/cmbf.py:292-326, :364), lanes along the width, one division per element.
+//
 // Add & LayerNorm.  One wave per row.  W % 4 == 0, W <= 1024 and 16-byte aligned operands: the row x + res lives in
 // registers (up to 4 float4 per lane) between the passes; otherwise the row is re-read (it sits in L1 / L2).  The mean
 // is taken about the row's first element and the variance as the mean of squared differences from that mean: a
@@ -37,7 +42,8 @@ constexpr int kMhaLdsBudget = 80 * 1024;  // bytes per workgroup: two workgroups
 constexpr int kMhaMaxGrid = 1024;         // persistent workgroups
 constexpr int kMhaMaxDs = 128;
 constexpr int kMhaThreads = 512;  // 8 waves: with two workgroups per CU, 4 waves per SIMD hide the LDS latency of mha_mm
-constexpr int kMhaWaves = kMhaThreads / kWave;
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 struct MhaGeom {
   int F, T, H, ds;
@@ -88,11 +94,11 @@ struct MhaArgs {
 };
 
 // rows x ds floats at `pitch` -> LDS rows at ld
-__device__ inline void mha_stage(const float* __restrict__ src, int64_t pitch, int rows, int ds, bool vec, int ld,
-                                 float* dst) {
+__device__ inline void mha_stage(int tid, int nthr, const float* __restrict__ src, int64_t pitch, int rows, int ds,
+                                 bool vec, int ld, float* dst) {
   if (vec) {
     const int q4 = ds >> 2, n = rows * q4;
-    for (int t = threadIdx.x; t < n; t += kMhaThreads) {
+    for (int t = tid; t < n; t += nthr) {
       const int r = t / q4, c = (t - r * q4) << 2;
       const float4 x = *reinterpret_cast<const float4*>(src + r * pitch + c);
       float* d = dst + r * ld + c;
@@ -103,7 +109,7 @@ __device__ inline void mha_stage(const float* __restrict__ src, int64_t pitch, i
     }
   } else {
     const int n = rows * ds;
-    for (int t = threadIdx.x; t < n; t += kMhaThreads) {
+    for (int t = tid; t < n; t += nthr) {
       const int r = t / ds, c = t - r * ds;
       dst[r * ld + c] = src[r * pitch + c];
     }
@@ -113,10 +119,10 @@ __device__ inline void mha_stage(const float* __restrict__ src, int64_t pitch, i
 // C[m, n] = sum_k A[m * sam + k * sak] * Bm[n * sbn + k * sbk] for m < M, n < N, from LDS: a thread owns rows
 // m0 .. m0 + 3 of one column n; lanes run along n (sbn is 1 or odd: conflict-free), A is a broadcast.
 template <class Out>
-__device__ __forceinline__ void mha_mm(int M, int N, int K, const float* A, int sam, int sak, const float* Bm, int sbn,
-                                       int sbk, Out out) {
+__device__ __forceinline__ void mha_mm(int tid, int nthr, int M, int N, int K, const float* A, int sam, int sak,
+                                       const float* Bm, int sbn, int sbk, Out out) {
   const int items = ((M + 3) >> 2) * N;
-  for (int t = threadIdx.x; t < items; t += kMhaThreads) {
+  for (int t = tid; t < items; t += nthr) {
     const int mb = t / N, n = t - mb * N, m0 = mb << 2;
     const float* a0 = A + m0 * sam;
     const float* a1 = A + min(m0 + 1, M - 1) * sam;  // (rows past M repeat the last one and are not written)
@@ -141,9 +147,9 @@ __device__ __forceinline__ void mha_mm(int M, int N, int K, const float* A, int 
 }
 
 // the keys' adders of example b, relative to the largest: 0 for an open key (or every key when none is open)
-__device__ inline void mha_stage_adder(const int32_t* mask, int64_t b, int T, float* madd) {
-  if (threadIdx.x < kWave) {  // one wave: T is small
-    const int lane = threadIdx.x;
+__device__ inline void mha_stage_adder(int tid, const int32_t* mask, int64_t b, int T, float* madd) {
+  if (tid < kWave) {  // one wave: T is small
+    const int lane = tid;
     float top = -INFINITY;
     if (mask != nullptr)
       for (int j = lane; j < T; j += kWave) top = fmaxf(top, (1.0f - static_cast<float>(mask[b * T + j])) * -10000.0f);
@@ -153,14 +159,18 @@ __device__ inline void mha_stage_adder(const int32_t* mask, int64_t b, int T, fl
   }
 }
 
-// S = Q K^T * scale -> P = softmax over the keys of S + adder, in S's place
-__device__ inline void mha_probs(const MhaGeom& g, const float* Qs, const float* Ks, const float* madd, float* S) {
+// S = Q K^T * scale
+__device__ inline void mha_scores(int tid, int nthr, const MhaGeom& g, const float* Qs, const float* Ks, float* S) {
   const float scale = g.scale;
   const int ldp = g.ldp;
-  mha_mm(g.F, g.T, g.ds, Qs, g.ld, 1, Ks, g.ld, 1, [=](int i, int j, float s) { S[i * ldp + j] = s * scale; });
-  __syncthreads();
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  for (int i = wave; i < g.F; i += kMhaWaves) {
+  mha_mm(tid, nthr, g.F, g.T, g.ds, Qs, g.ld, 1, Ks, g.ld, 1, [=](int i, int j, float s) { S[i * ldp + j] = s * scale; });
+}
+
+// P = softmax over the keys of S + adder, in S's place: one wave per row
+__device__ inline void mha_softmax(int tid, int nthr, const MhaGeom& g, const float* madd, float* S) {
+  const int ldp = g.ldp;
+  const int lane = tid & (kWave - 1), wave = tid / kWave, waves = nthr / kWave;
+  for (int i = wave; i < g.F; i += waves) {
     float* p = S + i * ldp;
     float m = -INFINITY;
     for (int j = lane; j < g.T; j += kWave) {
@@ -178,6 +188,27 @@ __device__ inline void mha_probs(const MhaGeom& g, const float* Qs, const float*
     sum = wave_sum(sum);
     for (int j = lane; j < g.T; j += kWave) p[j] = p[j] / sum;
   }
+}
+
+// dS = P o (dP - rowsum(dP o P)), times scale (both dQ and dK carry it), in dP's place: one wave per row
+__device__ inline void mha_ds(int tid, int nthr, const MhaGeom& g, const float* P, float* D) {
+  const int ldp = g.ldp;
+  const int lane = tid & (kWave - 1), wave = tid / kWave, waves = nthr / kWave;
+  for (int i = wave; i < g.F; i += waves) {
+    const float* p = P + i * ldp;
+    float* d = D + i * ldp;
+    float dot = 0.f;
+    for (int j = lane; j < g.T; j += kWave) dot += d[j] * p[j];
+    dot = wave_sum(dot);
+    for (int j = lane; j < g.T; j += kWave) d[j] = p[j] * (d[j] - dot) * g.scale;
+  }
+}
+
+// S = Q K^T * scale -> P = softmax over the keys of S + adder, in S's place
+__device__ inline void mha_probs(const MhaGeom& g, const float* Qs, const float* Ks, const float* madd, float* S) {
+  mha_scores(threadIdx.x, kMhaThreads, g, Qs, Ks, S);
+  __syncthreads();
+  mha_softmax(threadIdx.x, kMhaThreads, g, madd, S);
   __syncthreads();
 }
 
@@ -194,15 +225,15 @@ __global__ __launch_bounds__(kMhaThreads) void mha_fwd_kernel(MhaArgs a) {
   for (int64_t u = blockIdx.x; u < a.units; u += gridDim.x) {
     const int64_t b = u / g.H;
     const int h = static_cast<int>(u - b * g.H);
-    mha_stage(a.q + b * F * a.ldq + h * ds, a.ldq, F, ds, a.vec & 1, ld, Qs);
-    mha_stage(a.k + b * T * a.ldk + h * ds, a.ldk, T, ds, a.vec & 2, ld, Ks);
-    mha_stage(a.v + b * T * a.ldv + h * ds, a.ldv, T, ds, a.vec & 4, ld, Vs);
-    mha_stage_adder(a.mask, b, T, madd);
+    mha_stage(threadIdx.x, kMhaThreads, a.q + b * F * a.ldq + h * ds, a.ldq, F, ds, a.vec & 1, ld, Qs);
+    mha_stage(threadIdx.x, kMhaThreads, a.k + b * T * a.ldk + h * ds, a.ldk, T, ds, a.vec & 2, ld, Ks);
+    mha_stage(threadIdx.x, kMhaThreads, a.v + b * T * a.ldv + h * ds, a.ldv, T, ds, a.vec & 4, ld, Vs);
+    mha_stage_adder(threadIdx.x, a.mask, b, T, madd);
     __syncthreads();
     mha_probs(g, Qs, Ks, madd, S);
     // ctx_h = P V_h
     float* out = a.ctx + b * F * dctx + h * ds;
-    mha_mm(F, ds, T, S, g.ldp, 1, Vs, 1, ld, [=](int i, int c, float s) { out[i * dctx + c] = s; });
+    mha_mm(threadIdx.x, kMhaThreads, F, ds, T, S, g.ldp, 1, Vs, 1, ld, [=](int i, int c, float s) { out[i * dctx + c] = s; });
     __syncthreads();  // (the next unit restages)
   }
 }
@@ -219,40 +250,214 @@ __global__ __launch_bounds__(kMhaThreads) void mha_bwd_kernel(MhaArgs a) {
   float* D = P + F * ldp;    // dP, then dS * scale [F, ldp]
   float* madd = D + F * ldp;
   const int64_t dctx = static_cast<int64_t>(g.H) * ds;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   for (int64_t u = blockIdx.x; u < a.units; u += gridDim.x) {
     const int64_t b = u / g.H;
     const int h = static_cast<int>(u - b * g.H);
-    mha_stage(a.q + b * F * a.ldq + h * ds, a.ldq, F, ds, a.vec & 1, ld, Qs);
-    mha_stage(a.k + b * T * a.ldk + h * ds, a.ldk, T, ds, a.vec & 2, ld, Ks);
-    mha_stage(a.v + b * T * a.ldv + h * ds, a.ldv, T, ds, a.vec & 4, ld, Vs);
-    mha_stage(a.dctx + b * F * dctx + h * ds, dctx, F, ds, a.vec & 8, ld, Cs);
-    mha_stage_adder(a.mask, b, T, madd);
+    mha_stage(threadIdx.x, kMhaThreads, a.q + b * F * a.ldq + h * ds, a.ldq, F, ds, a.vec & 1, ld, Qs);
+    mha_stage(threadIdx.x, kMhaThreads, a.k + b * T * a.ldk + h * ds, a.ldk, T, ds, a.vec & 2, ld, Ks);
+    mha_stage(threadIdx.x, kMhaThreads, a.v + b * T * a.ldv + h * ds, a.ldv, T, ds, a.vec & 4, ld, Vs);
+    mha_stage(threadIdx.x, kMhaThreads, a.dctx + b * F * dctx + h * ds, dctx, F, ds, a.vec & 8, ld, Cs);
+    mha_stage_adder(threadIdx.x, a.mask, b, T, madd);
     __syncthreads();
     mha_probs(g, Qs, Ks, madd, P);
     // dP[i, j] = dctx_h[i] . V_h[j];  dV_h[j] = sum_i P[i, j] dctx_h[i]
-    mha_mm(F, T, ds, Cs, ld, 1, Vs, ld, 1, [=](int i, int j, float s) { D[i * ldp + j] = s; });
+    mha_mm(threadIdx.x, kMhaThreads, F, T, ds, Cs, ld, 1, Vs, ld, 1, [=](int i, int j, float s) { D[i * ldp + j] = s; });
     float* dv = a.dv + b * T * a.lddv + h * ds;
     const int64_t lddv = a.lddv;
-    mha_mm(T, ds, F, P, 1, ldp, Cs, 1, ld, [=](int j, int c, float s) { dv[j * lddv + c] = s; });
+    mha_mm(threadIdx.x, kMhaThreads, T, ds, F, P, 1, ldp, Cs, 1, ld, [=](int j, int c, float s) { dv[j * lddv + c] = s; });
     __syncthreads();
-    // dS = P o (dP - rowsum(dP o P)), times scale (both dQ and dK carry it)
-    for (int i = wave; i < F; i += kMhaWaves) {
-      const float* p = P + i * ldp;
-      float* d = D + i * ldp;
-      float dot = 0.f;
-      for (int j = lane; j < T; j += kWave) dot += d[j] * p[j];
-      dot = wave_sum(dot);
-      for (int j = lane; j < T; j += kWave) d[j] = p[j] * (d[j] - dot) * g.scale;
-    }
+    mha_ds(threadIdx.x, kMhaThreads, g, P, D);
     __syncthreads();
     // dQ_h[i] = sum_j dS[i, j] K_h[j];  dK_h[j] = sum_i dS[i, j] Q_h[i]
     float* dq = a.dq + b * F * a.lddq + h * ds;
     float* dk = a.dk + b * T * a.lddk + h * ds;
     const int64_t lddq = a.lddq, lddk = a.lddk;
-    mha_mm(F, ds, T, D, ldp, 1, Ks, 1, ld, [=](int i, int c, float s) { dq[i * lddq + c] = s; });
-    mha_mm(T, ds, F, D, 1, ldp, Qs, 1, ld, [=](int j, int c, float s) { dk[j * lddk + c] = s; });
+    mha_mm(threadIdx.x, kMhaThreads, F, ds, T, D, ldp, 1, Ks, 1, ld, [=](int i, int c, float s) { dq[i * lddq + c] = s; });
+    mha_mm(threadIdx.x, kMhaThreads, T, ds, F, D, 1, ldp, Qs, 1, ld, [=](int j, int c, float s) { dk[j * lddk + c] = s; });
     __syncthreads();  // (the next unit restages)
+  }
+}
+
+// ---------------------------------------------------------------------------------------- grouped units
+// The 512 threads split into G groups of 512 / G (a group is whole waves); group `grp` owns the unit
+// pass * G + grp in its own LDS region and runs the algorithm above with its loops striding by the group size.
+// Every barrier is the workgroup's: a group whose unit is past the end skips the work between them, never a barrier.
+// An output element is the same single-thread chain over k and a softmax row the same wave butterfly as in the one-unit
+// kernels, so the results are the same bits.
+__global__ __launch_bounds__(kMhaThreads) void mha_group_fwd_kernel(MhaArgs a, int G, int unit_floats) {
+  extern __shared__ float lds[];
+  const MhaGeom g = a.g;
+  const int F = g.F, T = g.T, ds = g.ds, ld = g.ld;
+  const int nthr = kMhaThreads / G, grp = threadIdx.x / nthr, tid = threadIdx.x - grp * nthr;
+  float* Qs = lds + grp * unit_floats;
+  float* Ks = Qs + F * ld;
+  float* Vs = Ks + T * ld;
+  float* S = Vs + T * ld;
+  float* madd = S + F * g.ldp;
+  const int64_t dctx = static_cast<int64_t>(g.H) * ds;
+  for (int64_t u0 = static_cast<int64_t>(blockIdx.x) * G; u0 < a.units; u0 += static_cast<int64_t>(gridDim.x) * G) {
+    const int64_t u = u0 + grp;
+    const bool on = u < a.units;
+    const int64_t b = on ? u / g.H : 0;
+    const int h = on ? static_cast<int>(u - b * g.H) : 0;
+    if (on) {
+      mha_stage(tid, nthr, a.q + b * F * a.ldq + h * ds, a.ldq, F, ds, a.vec & 1, ld, Qs);
+      mha_stage(tid, nthr, a.k + b * T * a.ldk + h * ds, a.ldk, T, ds, a.vec & 2, ld, Ks);
+      mha_stage(tid, nthr, a.v + b * T * a.ldv + h * ds, a.ldv, T, ds, a.vec & 4, ld, Vs);
+      mha_stage_adder(tid, a.mask, b, T, madd);
+    }
+    __syncthreads();
+    if (on) mha_scores(tid, nthr, g, Qs, Ks, S);
+    __syncthreads();
+    if (on) mha_softmax(tid, nthr, g, madd, S);
+    __syncthreads();
+    if (on) {
+      float* out = a.ctx + b * F * dctx + h * ds;
+      mha_mm(tid, nthr, F, ds, T, S, g.ldp, 1, Vs, 1, ld, [=](int i, int c, float s) { out[i * dctx + c] = s; });
+    }
+    __syncthreads();  // (the next pass restages)
+  }
+}
+
+__global__ __launch_bounds__(kMhaThreads, 4) void mha_group_bwd_kernel(MhaArgs a, int G, int unit_floats) {
+  extern __shared__ float lds[];
+  const MhaGeom g = a.g;
+  const int F = g.F, T = g.T, ds = g.ds, ld = g.ld, ldp = g.ldp;
+  const int nthr = kMhaThreads / G, grp = threadIdx.x / nthr, tid = threadIdx.x - grp * nthr;
+  float* Qs = lds + grp * unit_floats;
+  float* Ks = Qs + F * ld;
+  float* Vs = Ks + T * ld;
+  float* Cs = Vs + T * ld;
+  float* P = Cs + F * ld;
+  float* D = P + F * ldp;
+  float* madd = D + F * ldp;
+  const int64_t dctx = static_cast<int64_t>(g.H) * ds;
+  for (int64_t u0 = static_cast<int64_t>(blockIdx.x) * G; u0 < a.units; u0 += static_cast<int64_t>(gridDim.x) * G) {
+    const int64_t u = u0 + grp;
+    const bool on = u < a.units;
+    const int64_t b = on ? u / g.H : 0;
+    const int h = on ? static_cast<int>(u - b * g.H) : 0;
+    if (on) {
+      mha_stage(tid, nthr, a.q + b * F * a.ldq + h * ds, a.ldq, F, ds, a.vec & 1, ld, Qs);
+      mha_stage(tid, nthr, a.k + b * T * a.ldk + h * ds, a.ldk, T, ds, a.vec & 2, ld, Ks);
+      mha_stage(tid, nthr, a.v + b * T * a.ldv + h * ds, a.ldv, T, ds, a.vec & 4, ld, Vs);
+      mha_stage(tid, nthr, a.dctx + b * F * dctx + h * ds, dctx, F, ds, a.vec & 8, ld, Cs);
+      mha_stage_adder(tid, a.mask, b, T, madd);
+    }
+    __syncthreads();
+    if (on) mha_scores(tid, nthr, g, Qs, Ks, P);
+    __syncthreads();
+    if (on) mha_softmax(tid, nthr, g, madd, P);
+    __syncthreads();
+    if (on) {
+      mha_mm(tid, nthr, F, T, ds, Cs, ld, 1, Vs, ld, 1, [=](int i, int j, float s) { D[i * ldp + j] = s; });
+      float* dv = a.dv + b * T * a.lddv + h * ds;
+      const int64_t lddv = a.lddv;
+      mha_mm(tid, nthr, T, ds, F, P, 1, ldp, Cs, 1, ld, [=](int j, int c, float s) { dv[j * lddv + c] = s; });
+    }
+    __syncthreads();
+    if (on) mha_ds(tid, nthr, g, P, D);
+    __syncthreads();
+    if (on) {
+      float* dq = a.dq + b * F * a.lddq + h * ds;
+      float* dk = a.dk + b * T * a.lddk + h * ds;
+      const int64_t lddq = a.lddq, lddk = a.lddk;
+      mha_mm(tid, nthr, F, ds, T, D, ldp, 1, Ks, 1, ld, [=](int i, int c, float s) { dq[i * lddq + c] = s; });
+      mha_mm(tid, nthr, T, ds, F, D, 1, ldp, Qs, 1, ld, [=](int j, int c, float s) { dk[j * lddk + c] = s; });
+    }
+    __syncthreads();  // (the next pass restages)
+  }
+}
+
+// units per workgroup: the largest of 8, 4, 2 whose backward regions fit the budget; 1: only one; 0: outside
+inline int mha_group_units(int F, int T, int ds) {
+  if (!mha_shape_ok(F, T, 1, ds)) return 0;
+  const int64_t unit = 4 * mha_bwd_floats(F, T, ds);
+  for (int G : {8, 4, 2})
+    if (G * unit <= kMhaLdsBudget) return G;
+  return 1;
+}
+
+// ---------------------------------------------------------------------------------------- segment mean
+constexpr int kSegMaxSeg = 64;
+constexpr int kSegMaxW = 4096;
+constexpr int kSegMaxS = 4096;
+
+// rows [t0, t0 + len) of segment s of example b: the begins clamped into [0, S] and ascending, len into the width
+__device__ __forceinline__ void seg_range(const int32_t* __restrict__ seg_begin, const int32_t* __restrict__ lens,
+                                          int64_t b, int s, int n_seg, int S, int* t0, int* width, int* len) {
+  const int b0 = min(max(seg_begin[s], 0), S);
+  const int b1 = min(max(seg_begin[s + 1], b0), S);
+  *t0 = b0;
+  *width = b1 - b0;
+  *len = lens != nullptr ? min(max(lens[b * n_seg + s], 0), b1 - b0) : b1 - b0;
+}
+
+// a thread owns VEC columns of one (example, segment): the sum over t ascending, then one division
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void segment_mean_fwd_kernel(const float* __restrict__ x,
+                                                                 const int32_t* __restrict__ seg_begin,
+                                                                 const int32_t* __restrict__ lens, int64_t B, int S, int W,
+                                                                 int n_seg, float* __restrict__ out) {
+  const int wv = W / VEC;
+  const int64_t total = B * n_seg * wv;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; t < total;
+       t += static_cast<int64_t>(gridDim.x) * kBlock) {
+    const int c = static_cast<int>(t % wv) * VEC;
+    const int64_t bs = t / wv;
+    const int s = static_cast<int>(bs % n_seg);
+    const int64_t b = bs / n_seg;
+    int t0, width, len;
+    seg_range(seg_begin, lens, b, s, n_seg, S, &t0, &width, &len);
+    const float* src = x + (b * S + t0) * W + c;
+    const float n = static_cast<float>(len);
+    if (VEC == 4) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int r = 0; r < len; ++r) {
+        const float4 v = ld4(src + static_cast<int64_t>(r) * W);
+        acc.x += v.x;
+        acc.y += v.y;
+        acc.z += v.z;
+        acc.w += v.w;
+      }
+      *reinterpret_cast<float4*>(out + bs * W + c) = make_float4(acc.x / n, acc.y / n, acc.z / n, acc.w / n);
+    } else {
+      float acc = 0.f;
+      for (int r = 0; r < len; ++r) acc += src[static_cast<int64_t>(r) * W];
+      out[bs * W + c] = acc / n;
+    }
+  }
+}
+
+// the same ownership: dout / len to the segment's first len rows, 0 to the rest: every element of dx is written
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void segment_mean_bwd_kernel(const float* __restrict__ dout,
+                                                                 const int32_t* __restrict__ seg_begin,
+                                                                 const int32_t* __restrict__ lens, int64_t B, int S, int W,
+                                                                 int n_seg, float* __restrict__ dx) {
+  const int wv = W / VEC;
+  const int64_t total = B * n_seg * wv;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; t < total;
+       t += static_cast<int64_t>(gridDim.x) * kBlock) {
+    const int c = static_cast<int>(t % wv) * VEC;
+    const int64_t bs = t / wv;
+    const int s = static_cast<int>(bs % n_seg);
+    const int64_t b = bs / n_seg;
+    int t0, width, len;
+    seg_range(seg_begin, lens, b, s, n_seg, S, &t0, &width, &len);
+    float* dst = dx + (b * S + t0) * W + c;
+    const float n = static_cast<float>(len);
+    if (VEC == 4) {
+      const float4 d = ld4(dout + bs * W + c);
+      const float4 gq = len > 0 ? make_float4(d.x / n, d.y / n, d.z / n, d.w / n) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int r = 0; r < len; ++r) *reinterpret_cast<float4*>(dst + static_cast<int64_t>(r) * W) = gq;
+      for (int r = len; r < width; ++r) *reinterpret_cast<float4*>(dst + static_cast<int64_t>(r) * W) = zero;
+    } else {
+      const float gq = len > 0 ? dout[bs * W + c] / n : 0.f;
+      for (int r = 0; r < len; ++r) dst[static_cast<int64_t>(r) * W] = gq;
+      for (int r = len; r < width; ++r) dst[static_cast<int64_t>(r) * W] = 0.f;
+    }
   }
 }
 
@@ -293,8 +498,6 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 constexpr int kLnMaxW = 4096;
 constexpr int kLnMaxGrid = 1024;  // rows of `partials`
 constexpr int kLnRegW = 1024;     // widest row the register form keeps (4 float4 per lane)
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 template <int NV>
 __global__ __launch_bounds__(kBlock) void add_ln_fwd_vec_kernel(const float* __restrict__ x, const float* __restrict__ res,
@@ -637,6 +840,135 @@ int er_mha_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const f
   if (er::mha_set_lds(reinterpret_cast<const void*>(er::mha_bwd_kernel), bytes)) return 1;
   const unsigned grid = static_cast<unsigned>(a.units < er::kMhaMaxGrid ? a.units : er::kMhaMaxGrid);
   hipLaunchKernelGGL(er::mha_bwd_kernel, dim3(grid), dim3(er::kMhaThreads), bytes, er::as_stream(stream), a);
+  ER_LAUNCH_CHECK();
+  return 0;
+}
+
+int32_t er_mha_group_units(int32_t F, int32_t T, int32_t ds) { return er::mha_group_units(F, T, ds); }
+
+int er_mha_group_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                     const int32_t* to_mask, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds, float* ctx,
+                     er_stream_t stream) {
+  ER_REQUIRE(q && k && v && ctx && B > 0, "er_mha_group_fwd: bad arguments");
+  ER_REQUIRE(er::mha_shape_ok(F, T, H, ds), "er_mha_group_fwd: F = %d, T = %d, H = %d, ds = %d outside the envelope", F, T, H,
+             ds);
+  const int G = er::mha_group_units(F, T, ds);
+  ER_REQUIRE(G >= 2, "er_mha_group_fwd: F = %d, T = %d, ds = %d leaves room for one unit per workgroup", F, T, ds);
+  const int64_t d = static_cast<int64_t>(H) * ds;
+  ER_REQUIRE(ldq >= d && ldk >= d && ldv >= d, "er_mha_group_fwd: a row pitch is below H * ds = %lld",
+             static_cast<long long>(d));
+  er::MhaArgs a = {};
+  a.q = q;
+  a.k = k;
+  a.v = v;
+  a.mask = to_mask;
+  a.ctx = ctx;
+  a.ldq = ldq;
+  a.ldk = ldk;
+  a.ldv = ldv;
+  a.units = B * H;
+  a.g = er::mha_geom(F, T, H, ds);
+  if (ds % 4 == 0) {
+    if (ldq % 4 == 0 && er::aligned16(q)) a.vec |= 1;
+    if (ldk % 4 == 0 && er::aligned16(k)) a.vec |= 2;
+    if (ldv % 4 == 0 && er::aligned16(v)) a.vec |= 4;
+  }
+  const int unit_floats = static_cast<int>(er::mha_fwd_floats(F, T, ds));
+  const int bytes = 4 * unit_floats * G;
+  if (er::mha_set_lds(reinterpret_cast<const void*>(er::mha_group_fwd_kernel), bytes)) return 1;
+  const int64_t passes = er::ceil_div(a.units, static_cast<int64_t>(G));
+  const unsigned grid = static_cast<unsigned>(passes < er::kMhaMaxGrid ? passes : er::kMhaMaxGrid);
+  hipLaunchKernelGGL(er::mha_group_fwd_kernel, dim3(grid), dim3(er::kMhaThreads), bytes, er::as_stream(stream), a, G,
+                     unit_floats);
+  ER_LAUNCH_CHECK();
+  return 0;
+}
+
+int er_mha_group_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                     const int32_t* to_mask, const float* dctx, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds,
+                     float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, er_stream_t stream) {
+  ER_REQUIRE(q && k && v && dctx && dq && dk && dv && B > 0, "er_mha_group_bwd: bad arguments");
+  ER_REQUIRE(er::mha_shape_ok(F, T, H, ds), "er_mha_group_bwd: F = %d, T = %d, H = %d, ds = %d outside the envelope", F, T, H,
+             ds);
+  const int G = er::mha_group_units(F, T, ds);
+  ER_REQUIRE(G >= 2, "er_mha_group_bwd: F = %d, T = %d, ds = %d leaves room for one unit per workgroup", F, T, ds);
+  const int64_t d = static_cast<int64_t>(H) * ds;
+  ER_REQUIRE(ldq >= d && ldk >= d && ldv >= d && lddq >= d && lddk >= d && lddv >= d,
+             "er_mha_group_bwd: a row pitch is below H * ds = %lld", static_cast<long long>(d));
+  er::MhaArgs a = {};
+  a.q = q;
+  a.k = k;
+  a.v = v;
+  a.dctx = dctx;
+  a.mask = to_mask;
+  a.dq = dq;
+  a.dk = dk;
+  a.dv = dv;
+  a.ldq = ldq;
+  a.ldk = ldk;
+  a.ldv = ldv;
+  a.lddq = lddq;
+  a.lddk = lddk;
+  a.lddv = lddv;
+  a.units = B * H;
+  a.g = er::mha_geom(F, T, H, ds);
+  if (ds % 4 == 0) {
+    if (ldq % 4 == 0 && er::aligned16(q)) a.vec |= 1;
+    if (ldk % 4 == 0 && er::aligned16(k)) a.vec |= 2;
+    if (ldv % 4 == 0 && er::aligned16(v)) a.vec |= 4;
+    if (er::aligned16(dctx)) a.vec |= 8;  // (its pitch H * ds is a multiple of 4 with ds)
+  }
+  const int unit_floats = static_cast<int>(er::mha_bwd_floats(F, T, ds));
+  const int bytes = 4 * unit_floats * G;
+  if (er::mha_set_lds(reinterpret_cast<const void*>(er::mha_group_bwd_kernel), bytes)) return 1;
+  const int64_t passes = er::ceil_div(a.units, static_cast<int64_t>(G));
+  const unsigned grid = static_cast<unsigned>(passes < er::kMhaMaxGrid ? passes : er::kMhaMaxGrid);
+  hipLaunchKernelGGL(er::mha_group_bwd_kernel, dim3(grid), dim3(er::kMhaThreads), bytes, er::as_stream(stream), a, G,
+                     unit_floats);
+  ER_LAUNCH_CHECK();
+  return 0;
+}
+
+static int segment_mean_check(const char* what, const void* a, const void* seg_begin, const void* b, int64_t B, int32_t S,
+                              int32_t W, int32_t n_seg) {
+  ER_REQUIRE(a && seg_begin && b && B > 0, "%s: bad arguments", what);
+  ER_REQUIRE(S >= 1 && S <= er::kSegMaxS && W >= 1 && W <= er::kSegMaxW, "%s: S = %d, W = %d outside 1 .. %d", what, S, W,
+             er::kSegMaxW);
+  ER_REQUIRE(n_seg >= 1 && n_seg <= er::kSegMaxSeg && n_seg <= S, "%s: n_seg = %d outside 1 .. min(%d, S)", what, n_seg,
+             er::kSegMaxSeg);
+  return 0;
+}
+
+int er_segment_mean_fwd(const float* x, const int32_t* seg_begin, const int32_t* lens, int64_t B, int32_t S, int32_t W,
+                        int32_t n_seg, float* out, er_stream_t stream) {
+  if (segment_mean_check("er_segment_mean_fwd", x, seg_begin, out, B, S, W, n_seg)) return 1;
+  const bool vec = W % 4 == 0 && er::aligned16(x) && er::aligned16(out);
+  const int64_t total = B * n_seg * (vec ? W / 4 : W);
+  const int64_t blocks = er::ceil_div(total, static_cast<int64_t>(er::kBlock));
+  const dim3 grid(static_cast<unsigned>(blocks < 8192 ? blocks : 8192)), block(er::kBlock);
+  if (vec)
+    hipLaunchKernelGGL(er::segment_mean_fwd_kernel<4>, grid, block, 0, er::as_stream(stream), x, seg_begin, lens, B, S, W,
+                       n_seg, out);
+  else
+    hipLaunchKernelGGL(er::segment_mean_fwd_kernel<1>, grid, block, 0, er::as_stream(stream), x, seg_begin, lens, B, S, W,
+                       n_seg, out);
+  ER_LAUNCH_CHECK();
+  return 0;
+}
+
+int er_segment_mean_bwd(const float* dout, const int32_t* seg_begin, const int32_t* lens, int64_t B, int32_t S, int32_t W,
+                        int32_t n_seg, float* dx, er_stream_t stream) {
+  if (segment_mean_check("er_segment_mean_bwd", dout, seg_begin, dx, B, S, W, n_seg)) return 1;
+  const bool vec = W % 4 == 0 && er::aligned16(dout) && er::aligned16(dx);
+  const int64_t total = B * n_seg * (vec ? W / 4 : W);
+  const int64_t blocks = er::ceil_div(total, static_cast<int64_t>(er::kBlock));
+  const dim3 grid(static_cast<unsigned>(blocks < 8192 ? blocks : 8192)), block(er::kBlock);
+  if (vec)
+    hipLaunchKernelGGL(er::segment_mean_bwd_kernel<4>, grid, block, 0, er::as_stream(stream), dout, seg_begin, lens, B, S, W,
+                       n_seg, dx);
+  else
+    hipLaunchKernelGGL(er::segment_mean_bwd_kernel<1>, grid, block, 0, er::as_stream(stream), dout, seg_begin, lens, B, S, W,
+                       n_seg, dx);
   ER_LAUNCH_CHECK();
   return 0;
 }

@@ -1961,6 +1961,70 @@ class HipBackend(object):
     if self.op_log is not None:
       self.op_log.append(('er::mha_bwd_kernel', 12.0 * B * F * T * d))
 
+  def mha_group_units(self, F, T, ds):
+    """Units per workgroup of the grouped attention launches: 8, 4 or 2; 1: only one fits; 0: outside the envelope."""
+    return int(self.lib.er_mha_group_units(int(F), int(T), int(ds)))
+
+  def mha_group_fwd(self, q, k, v, to_mask, B, F, T, H, ds):
+    """mha_fwd's arguments and result bits, several (example, head) units per workgroup (mha_group_units >= 2)."""
+    d = H * ds
+    self._mha_operand(q, B * F, d, 'mha_group_fwd q')
+    self._mha_operand(k, B * T, d, 'mha_group_fwd k')
+    self._mha_operand(v, B * T, d, 'mha_group_fwd v')
+    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
+    ctx = torch.empty(B * F, d, dtype=torch.float32, device=q.device)
+    self.ck.er_mha_group_fwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), B, F, T, H, ds,
+                             _p(ctx), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::mha_group_fwd_kernel', 4.0 * B * F * T * d))
+    return ctx
+
+  def mha_group_bwd(self, q, k, v, to_mask, dctx, B, F, T, H, ds, dq, dk, dv):
+    """mha_bwd's arguments and result bits, several units per workgroup."""
+    d = H * ds
+    self._mha_operand(q, B * F, d, 'mha_group_bwd q')
+    self._mha_operand(k, B * T, d, 'mha_group_bwd k')
+    self._mha_operand(v, B * T, d, 'mha_group_bwd v')
+    self._mha_operand(dq, B * F, d, 'mha_group_bwd dq')
+    self._mha_operand(dk, B * T, d, 'mha_group_bwd dk')
+    self._mha_operand(dv, B * T, d, 'mha_group_bwd dv')
+    assert dctx.shape == (B * F, d)
+    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
+    self.ck.er_mha_group_bwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), _p(_f32c(dctx)), B,
+                             F, T, H, ds, _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv), dv.stride(0), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::mha_group_bwd_kernel', 12.0 * B * F * T * d))
+
+  SEGMENT_MEAN_MAX_W = 4096
+  SEGMENT_MEAN_MAX_S = 4096
+  SEGMENT_MEAN_MAX_SEG = 64
+
+  @staticmethod
+  def _segment_mean_operands(seg_begin, lens, B, n_seg):
+    assert seg_begin.dtype == torch.int32 and seg_begin.shape == (n_seg + 1,) and seg_begin.is_contiguous()
+    assert lens is None or (lens.dtype == torch.int32 and lens.shape == (B, n_seg) and lens.is_contiguous())
+
+  def segment_mean_fwd(self, x, seg_begin, lens, n_seg):
+    """x [B, S, W], seg_begin int32 [n_seg + 1] on the device (0 .. S ascending), lens int32 [B, n_seg] or None ->
+    out [B, n_seg, W]: per segment the mean of its first len rows (len == 0: NaN)."""
+    B, S, W = x.shape
+    self._segment_mean_operands(seg_begin, lens, B, n_seg)
+    out = torch.empty(B, n_seg, W, dtype=torch.float32, device=x.device)
+    self.ck.er_segment_mean_fwd(_p(_f32c(x)), _p(seg_begin), _p(lens), B, S, W, n_seg, _p(out), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::segment_mean_fwd_kernel', 1.0 * B * S * W))
+    return out
+
+  def segment_mean_bwd(self, dout, seg_begin, lens, S):
+    """dout [B, n_seg, W] -> dx [B, S, W] (every element written): dout / len on a segment's first len rows, else 0."""
+    B, n_seg, W = dout.shape
+    self._segment_mean_operands(seg_begin, lens, B, n_seg)
+    dx = torch.empty(B, S, W, dtype=torch.float32, device=dout.device)
+    self.ck.er_segment_mean_bwd(_p(_f32c(dout)), _p(seg_begin), _p(lens), B, S, W, n_seg, _p(dx), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::segment_mean_bwd_kernel', 1.0 * B * S * W))
+    return dx
+
   def add_ln_grid(self, rows, W):
     return int(self.lib.er_add_ln_grid(int(rows), int(W)))
 
@@ -4193,6 +4257,14 @@ class MhaAttnFn(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, q_src, kv_src, to_mask, B, F, T, H, ds):
+    return MhaAttnFn._forward(ctx, False, q_src, kv_src, to_mask, B, F, T, H, ds)
+
+  @staticmethod
+  def backward(ctx, dctx):
+    return MhaAttnFn._backward(ctx, False, dctx)
+
+  @staticmethod
+  def _forward(ctx, grouped, q_src, kv_src, to_mask, B, F, T, H, ds):
     be = hip()
     d = H * ds
     q_src = q_src if q_src.is_contiguous() else q_src.contiguous()
@@ -4201,13 +4273,13 @@ class MhaAttnFn(torch.autograd.Function):
     assert q_src.shape == (B * F, d if kv_src is not None else 3 * d) and (kv_src is not None or F == T)
     assert kv_src is None or kv_src.shape == (B * T, 2 * d)
     q, k, v = MhaAttnFn._split(q_src, kv_src, d)
-    out = be.mha_fwd(q, k, v, to_mask, B, F, T, H, ds)
+    out = (be.mha_group_fwd if grouped else be.mha_fwd)(q, k, v, to_mask, B, F, T, H, ds)
     ctx.save_for_backward(q_src, kv_src, to_mask)
     ctx.shape = (B, F, T, H, ds)
     return out
 
   @staticmethod
-  def backward(ctx, dctx):
+  def _backward(ctx, grouped, dctx):
     be = hip()
     q_src, kv_src, to_mask = ctx.saved_tensors
     B, F, T, H, ds = ctx.shape
@@ -4216,8 +4288,39 @@ class MhaAttnFn(torch.autograd.Function):
     dkv_src = None if kv_src is None else torch.empty_like(kv_src)
     q, k, v = MhaAttnFn._split(q_src, kv_src, d)
     dq, dk, dv = MhaAttnFn._split(dq_src, dkv_src, d)
-    be.mha_bwd(q, k, v, to_mask, dctx.contiguous(), B, F, T, H, ds, dq, dk, dv)
+    (be.mha_group_bwd if grouped else be.mha_bwd)(q, k, v, to_mask, dctx.contiguous(), B, F, T, H, ds, dq, dk, dv)
     return dq_src, dkv_src, None, None, None, None, None, None
+
+
+class MhaGroupAttnFn(MhaAttnFn):
+  """MhaAttnFn on the grouped-unit launches (er_mha_group_fwd / _bwd): several (example, head) units per workgroup for
+  short sequences (HipBackend.mha_group_units(F, T, ds) >= 2), the same result bits."""
+
+  @staticmethod
+  def forward(ctx, q_src, kv_src, to_mask, B, F, T, H, ds):
+    return MhaAttnFn._forward(ctx, True, q_src, kv_src, to_mask, B, F, T, H, ds)
+
+  @staticmethod
+  def backward(ctx, dctx):
+    return MhaAttnFn._backward(ctx, True, dctx)
+
+
+class SegmentMeanFn(torch.autograd.Function):
+  """CMBF's merge_text_embedding and image mean (reference layers/cmbf.py:292-326, :364) as one launch each way:
+  apply(x [B, S, W], seg_begin int32 [n_seg + 1] on the device, lens int32 [B, n_seg] or None, n_seg) -> [B, n_seg, W],
+  per segment the mean of its first len rows (every row without lens)."""
+
+  @staticmethod
+  def forward(ctx, x, seg_begin, lens, n_seg):
+    x = x if x.is_contiguous() else x.contiguous()
+    ctx.save_for_backward(seg_begin, lens)
+    ctx.S = x.shape[1]
+    return hip().segment_mean_fwd(x, seg_begin, lens, n_seg)
+
+  @staticmethod
+  def backward(ctx, dout):
+    seg_begin, lens = ctx.saved_tensors
+    return hip().segment_mean_bwd(dout.contiguous(), seg_begin, lens, ctx.S), None, None, None
 
 
 class AddLayerNormFn(torch.autograd.Function):

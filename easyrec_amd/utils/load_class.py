@@ -65,7 +65,7 @@ def load_keras_layer(name):
 
 MODEL_MODULES = ('deepfm', 'dcn', 'multi_tower_din', 'mmoe', 'rank_model', 'multi_task_model', 'wide_and_deep', 'fm',
                  'multi_tower', 'dlrm', 'simple_multi_task', 'ple', 'dbmtl', 'multi_tower_bst', 'autoint', 'match_model',
-                 'dssm', 'mind', 'uniter')
+                 'dssm', 'mind', 'uniter', 'cmbf')
 
 
 def import_all_models():

@@ -706,6 +706,23 @@ int er_autoint_pack(const float* wq, const float* wk, const float* wv, const flo
  *   row_groups = 8 into gamma's and beta's buffers.  Workgroup g owns the rows
  *   [g * ceil(rows / grid), ..): fixed order, no atomics.
  * Envelope: 1 <= W <= 4096 (er_add_ln_grid returns 0 outside).
+ * er_mha_group_fwd / er_mha_group_bwd: the arguments, semantics and RESULT BITS of er_mha_fwd / er_mha_bwd for
+ *   short sequences: the workgroup's 512 threads are G groups of 512 / G, each owning one (example, head) unit
+ *   at a time in an LDS region of its own; workgroups stay persistent (at most 1024) and walk units in steps of
+ *   G * grid; a group past the last unit stages and stores nothing but reaches every barrier.  An output
+ *   element is the same one-thread chain over k and a softmax row the same wave butterfly as in the one-unit
+ *   kernels.  G = er_mha_group_units(F, T, ds): the largest of 8, 4, 2 with
+ *   G * er_mha_lds_bytes(F, T, ds, 1) <= 81920; 1 when only one unit fits; 0 outside the envelope above.
+ *   Both return an error, launching nothing, when G < 2.
+ * er_segment_mean_fwd: x [B, S, W]; seg_begin int32 [n_seg + 1] in DEVICE memory, ascending, seg_begin[0] = 0,
+ *   seg_begin[n_seg] = S; lens int32 [B, n_seg] or NULL (every segment full), clamped to 0 .. the width:
+ *   out [B, n_seg, W]: out[b, s] = (sum over t < len, ascending, of x[b, seg_begin[s] + t]) / len, one IEEE
+ *   division; len == 0 gives 0 / 0 = NaN, the reference's emb_sum / count (layers/cmbf.py:311-316).
+ * er_segment_mean_bwd: dx [B, S, W]: dx[b, seg_begin[s] + t] = dout[b, s] / len for t < len, 0 for the rest of
+ *   the segment (the whole segment when len == 0): every element is written.  Replaces Slice, Mul by the
+ *   mask, both Sum, RealDiv and ConcatV2 of merge_text_embedding and the image Mean (layers/cmbf.py:292-326,
+ *   :364) and their gradients.  Lanes along W; 16-byte accesses where W % 4 == 0 and the bases are aligned.
+ * Envelope: 1 <= W <= 4096, 1 <= S <= 4096, 1 <= n_seg <= min(64, S).
  * -------------------------------------------------------------------------------------------- */
 int64_t er_mha_lds_bytes(int32_t F, int32_t T, int32_t ds, int bwd);
 int er_mha_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
@@ -716,6 +733,17 @@ int er_mha_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const f
                float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, er_stream_t stream);
 int er_mha_pack(const float* w0, const float* w1, const float* w2, const float* b0, const float* b1, const float* b2,
                 int32_t n, int32_t din, int32_t d, float* w, float* bias, er_stream_t stream);
+int32_t er_mha_group_units(int32_t F, int32_t T, int32_t ds);
+int er_mha_group_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                     const int32_t* to_mask, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds, float* ctx,
+                     er_stream_t stream);
+int er_mha_group_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                     const int32_t* to_mask, const float* dctx, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds,
+                     float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, er_stream_t stream);
+int er_segment_mean_fwd(const float* x, const int32_t* seg_begin, const int32_t* lens, int64_t B, int32_t S, int32_t W,
+                        int32_t n_seg, float* out, er_stream_t stream);
+int er_segment_mean_bwd(const float* dout, const int32_t* seg_begin, const int32_t* lens, int64_t B, int32_t S, int32_t W,
+                        int32_t n_seg, float* dx, er_stream_t stream);
 int32_t er_add_ln_grid(int64_t rows, int32_t W);
 int er_add_ln_fwd(const float* x, const float* res, int64_t rows, int64_t res_rows, int32_t W, const float* gamma,
                   const float* beta, float eps, float* y, float* mean, float* rstd, er_stream_t stream);

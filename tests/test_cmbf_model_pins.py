@@ -1,0 +1,172 @@
+"""CMBF on the CPU stand-in (easyrec_amd/layers/cmbf.py, model/cmbf.py): the class is registered, the committed config
+is the sample's model section, the variables carry the reference's names, what the reference asserts raises ValueError
+at build time as do bf16 dense and the embedding-parallel engine, the sample's group combinations build and take
+training steps that match the test-side fp64 oracle (tests/_cmbf_oracle.py) at first_steps' bars."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from easyrec_amd.utils import config_util, load_class
+from tests import _cmbf_ref as cref
+from tests import _uniter_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _estimator(cfg, B=16, **kw):
+  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
+  return EasyRecEstimator(cfg, device='cpu', batch_size=B, seed=4, **kw).build()
+
+
+def test_model_class_is_registered():
+  load_class.import_all_models()
+  from easyrec_amd.model.easy_rec_model import _EASY_REC_MODEL_CLASS_MAP
+  assert 'CMBF' in _EASY_REC_MODEL_CLASS_MAP
+
+
+def test_committed_config_is_the_sample_model():
+  cfg = config_util.get_configs_from_pipeline_file(os.path.join(ROOT, 'configs', 'cmbf_movielens.config'))
+  mc = cfg.model_config
+  assert mc.model_class == 'CMBF' and [g.group_name for g in mc.feature_groups] == ['image', 'general', 'text']
+  assert [len(g.feature_names) for g in mc.feature_groups] == [1, 9, 2]
+  c = mc.cmbf.config
+  assert (c.multi_head_num, c.text_multi_head_num, c.image_multi_head_num, c.image_head_size, c.text_head_size) == \
+      (2, 4, 3, 16, 8)
+  assert (c.image_feature_dim, c.image_self_attention_layer_num, c.text_self_attention_layer_num,
+          c.cross_modal_layer_num, c.image_cross_head_size, c.text_cross_head_size) == (64, 0, 2, 3, 16, 16)
+  assert c.max_position_embeddings == 16 and c.use_token_type and c.use_position_embeddings
+  assert abs(c.text_seq_emb_dropout_prob - 0.1) < 1e-7 and c.hidden_dropout_prob == 0 and c.attention_probs_dropout_prob == 0
+  assert list(mc.cmbf.final_dnn.hidden_units) == [256, 64] and abs(mc.embedding_regularization - 1e-6) < 1e-12
+  assert cfg.data_config.batch_size == 1024
+  # the sample's own model_config and feature_config (tests/golden/cmbf_on_movielens_sections.config: settings only)
+  sample = config_util.get_configs_from_pipeline_file(os.path.join(ROOT, 'tests', 'golden', 'cmbf_on_movielens_sections.config'))
+  assert sample.model_config == mc and sample.feature_config == cfg.feature_config
+
+
+HEAD = {
+    'all': ['img_projection/kernel', 'img_projection/bias', 'txt_projection/kernel', 'txt_projection/bias'],
+    'image': ['img_projection/kernel', 'img_projection/bias', 'img_map_matrix'],
+    'text': ['txt_projection/kernel', 'txt_projection/bias'],
+}
+TEXT = ['txt_seq_projection_0/kernel', 'txt_seq_projection_0/bias', 'token_type/token_type_embeddings',
+        'position_embedding/position_embeddings_0', 'LayerNorm/beta', 'LayerNorm/gamma', 'txt_seq_projection_1/kernel',
+        'txt_seq_projection_1/bias', 'position_embedding/position_embeddings_1', 'LayerNorm_1/beta', 'LayerNorm_1/gamma']
+
+
+@pytest.mark.parametrize('kind', ['all', 'image', 'text'])
+def test_model_builds_names_its_variables_and_steps_on_the_stand_in(ref_backend, built_lib, kind):
+  """The sample's group combinations: the variables in the order and under the names the reference's graph creates them
+  (layers/cmbf.py, multihead_cross_attention.py), only final_dnn regularised, and two training steps with finite,
+  changing losses."""
+  from easyrec_amd.input.synthetic import SyntheticBatches
+  cfg = cref.cmbf_cfg(kind, batch_size=16)
+  est = _estimator(cfg)
+  names = [n for n in est.varstore.names()]
+  want = list(HEAD[kind])
+  if kind == 'image':
+    want += ref.encoder_variable_names('image_self_attention', 2)
+  else:
+    want += TEXT + ref.encoder_variable_names('text_self_attention', 2)
+  if kind == 'all':
+    want += cref.cross_tower_variable_names(3)
+  assert names[:len(want)] == want
+  assert names[len(want)].startswith('final_dnn/')
+  st = est.state_dict()
+  if kind == 'image':  # (the only_image sample's form: 512 -> image_feature_dim 64 elements, each a token of 48)
+    assert st['img_projection/kernel'].shape == (512, 64) and st['img_map_matrix'].shape == (1, 64, 48)
+  if kind != 'image':
+    assert st['token_type/token_type_embeddings'].shape == (2, 32)
+    assert st['position_embedding/position_embeddings_0'].shape == (16, 32)
+    assert st['txt_projection/kernel'].shape == (16, 32)
+  if kind == 'all':
+    assert st['img_projection/kernel'].shape == (512, 32)
+    assert st['right_to_left_cross_layer_2/intermediate/dense/kernel'].shape == (32, 128)
+  for n in names:
+    if not (n.endswith('/kernel') and n.split('/')[0] == 'final_dnn'):
+      assert est.varstore.l2_of(n) == 0.0, n
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=16, seed=44)
+  losses = []
+  for _ in range(2):
+    est.train_step(gen.next_batch())
+    losses.append(est.loss_values())
+    assert all(np.isfinite(v) for v in losses[-1].values()), losses
+  assert losses[0]['total_loss'] != losses[1]['total_loss']
+
+
+def test_rejected_combinations_raise_at_build_time(ref_backend, built_lib):
+  dup = cref.cmbf_cfg('all')
+  dup.model_config.feature_groups[1].feature_names.append('user_id')
+  with pytest.raises(ValueError, match='duplicate'):
+    _estimator(dup)
+  uneven = cref.cmbf_cfg('all')
+  uneven.feature_config.features[0].embedding_dim = 8
+  with pytest.raises(ValueError, match='consistent'):
+    _estimator(uneven)
+  short = cref.cmbf_cfg('all')
+  short.model_config.cmbf.config.max_position_embeddings = 15
+  with pytest.raises(ValueError, match='max_position_embeddings'):
+    _estimator(short)
+  zero = cref.cmbf_cfg('all')
+  zero.model_config.cmbf.config.max_position_embeddings = 0
+  with pytest.raises(ValueError, match='greater than 0'):
+    _estimator(zero)
+  patches = cref.cmbf_cfg('image')
+  patches.model_config.cmbf.config.image_feature_patch_num = 3  # (512 is no multiple of 3)
+  with pytest.raises(ValueError, match='image feature dimension'):
+    _estimator(patches)
+  heads = cref.cmbf_cfg('all')
+  heads.model_config.cmbf.config.multi_head_num = 3  # (text hidden 32 is no multiple of 3)
+  with pytest.raises(ValueError, match='multiple'):
+    _estimator(heads)
+  with pytest.raises(ValueError, match='bf16'):
+    _estimator(cref.cmbf_cfg('all'), dense_dtype='bf16')
+
+
+def test_embedding_parallel_engine_is_refused():
+  from easyrec_amd.core import context
+  from easyrec_amd.layers import cmbf
+  from easyrec_amd.layers.sharded_embedding import ShardedEmbeddingEngine
+  ctx = context.ModelContext(None, object.__new__(ShardedEmbeddingEngine))
+  mc = cref.cmbf_cfg('all').model_config
+  with context.use(ctx), pytest.raises(ValueError, match='embedding-parallel'):
+    cmbf.CMBF(mc, [], None, mc.cmbf.config, None)
+
+
+def test_predict_is_deterministic_under_sequence_dropout(ref_backend, built_lib):
+  """text_seq_emb_dropout_prob 0.1 (the sample's): a training step gives finite losses, and two predictions of one batch
+  in evaluation mode (`_predict_eval`, what evaluate() runs) are bit-equal: no dropout outside training."""
+  from easyrec_amd.input.synthetic import SyntheticBatches
+  cfg = cref.cmbf_cfg('all', seq_dropout=0.1)
+  est = _estimator(cfg)
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=16, seed=5)
+  est.train_step(gen.next_batch())
+  assert all(np.isfinite(v) for v in est.loss_values().values())
+  b = gen.next_batch()
+  outs = [{k: v.detach().clone() for k, v in pred.items() if torch.is_tensor(v)} for _, pred in est._predict_eval([b, b])]
+  assert outs[0] and all(torch.equal(outs[0][k], outs[1][k]) for k in outs[0])
+
+
+@pytest.mark.parametrize('kind', ['all', 'image', 'text'])
+def test_first_steps_on_the_stand_in_match_the_fp64_oracle(ref_backend, built_lib, monkeypatch, kind):
+  """The product on the stand-in backend against tests/_cmbf_oracle.py (the parent oracle's input layer, DNNs, losses
+  and optimizer around the fp64 restatement of the CMBF layer) at first_steps' bars: every loss, the logits and every
+  variable's gradient, the embedding tables' included."""
+  from tests import _oracle_steps
+  from tests._cmbf_oracle import CMBFOracle
+  monkeypatch.setattr(_oracle_steps, 'OracleTrainer', CMBFOracle)
+  cfg = cref.cmbf_cfg(kind, batch_size=16)
+
+  def coverage(names, _):
+    assert any(n.startswith('final_dnn/') for n in names)
+    if kind == 'all':
+      assert 'right_to_left_cross_layer_2/attention/cross/value/kernel' in names and 'img_projection/kernel' in names
+    if kind == 'image':
+      assert 'img_map_matrix' in names and 'image_self_attention_layer_1/attention/self/key/kernel' in names
+    if kind != 'image':
+      assert 'token_type/token_type_embeddings' in names and 'input_layer/title/embedding_weights' in names
+      assert 'text_self_attention_layer_1/attention/self/key/kernel' in names
+
+  _oracle_steps.first_steps(cfg, 16, 5, device='cpu', oracle_dtype=torch.float64, coverage=coverage,
+                            skip_bn_shadowed_bias=True)

@@ -373,6 +373,35 @@ def uniter_movielens(batch_size=1024):
   return text_format.Parse(UNITER_MOVIELENS % {'batch_size': batch_size}, pipeline_pb2.EasyRecConfig())
 
 
+CMBF_MOVIELENS_MODEL = """
+model_config {
+  model_class: 'CMBF'
+  feature_groups { group_name: 'image' feature_names: 'embedding' wide_deep: DEEP }
+  feature_groups { group_name: 'general' feature_names: 'user_id' feature_names: 'movie_id' feature_names: 'gender'
+                   feature_names: 'age' feature_names: 'occupation' feature_names: 'zip_id' feature_names: 'movie_year_bin'
+                   feature_names: 'score_year_diff' feature_names: 'score_time' wide_deep: DEEP }
+  feature_groups { group_name: 'text' feature_names: 'title' feature_names: 'genres' wide_deep: DEEP }
+  cmbf {
+    config { multi_head_num: 2 text_multi_head_num: 4 image_multi_head_num: 3 image_head_size: 16 text_head_size: 8
+             image_feature_dim: 64 image_self_attention_layer_num: 0 text_self_attention_layer_num: 2
+             cross_modal_layer_num: 3 image_cross_head_size: 16 text_cross_head_size: 16 max_position_embeddings: 16
+             use_token_type: true }
+    final_dnn { hidden_units: 256 hidden_units: 64 }
+  }
+  embedding_regularization: 1e-6
+}
+"""
+
+
+def cmbf_movielens(batch_size=1024):
+  """CMBF: samples/model_config/cmbf_on_movielens.config (the data and feature sections are Uniter's sample's; the
+  model section: one image token through img_projection, 9 general + 16 title + 8 genres = 33 text tokens of hidden 32,
+  2 heads of 16, 2 text layers, 3 cross layers) on synthetic MovieLens-shaped batches; batch size 1024; the metric set
+  is auc alone."""
+  head = UNITER_MOVIELENS[:UNITER_MOVIELENS.index('model_config {')].replace('uniter_movielens_ckpt', 'cmbf_movielens_ckpt')
+  return text_format.Parse(head % {'batch_size': batch_size} + CMBF_MOVIELENS_MODEL, pipeline_pb2.EasyRecConfig())
+
+
 def fibinet_taobao(bilinear_type='each', use_plus=True, **kw):
   """FiBiNet, the model section of samples/model_config/fibinet_on_taobao.config: RankModel over a backbone whose
   input-layer block batch-normalises the 17 fields of D = 16 and hands them on as a list, and a `FiBiNet` block (SENet
@@ -1001,6 +1030,7 @@ if __name__ == '__main__':
   write(bst_taobao(item_rows=10000000), 'bst_taobao_10m.config')
   write(autoint_taobao(item_rows=10000000), 'autoint_taobao_10m.config')
   write(uniter_movielens(), 'uniter_movielens.config')
+  write(cmbf_movielens(), 'cmbf_movielens.config')
   write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
   write(dssm_taobao(item_rows=10000000), 'dssm_taobao_10m.config')
   write(dssm_taobao(in_batch=True, item_rows=10000000), 'dssm_inbatch_taobao_10m.config')
