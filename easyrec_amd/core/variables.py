@@ -89,6 +89,7 @@ class VarStore(object):
     self.l2coef = None
     self.slots = {}  # optimizer slots over the flat buffer
     self._offsets = {}
+    self._layer_uids = {}  # Keras' per-graph numbering of unnamed layers (next_layer_names)
 
   # -- TF-like name scopes
   def scope(self, name):
@@ -103,6 +104,13 @@ class VarStore(object):
         store._scope.pop()
 
     return _Scope()
+
+  def next_layer_names(self, base, n=1):
+    """The names Keras gives the next n unnamed layers of a class in a graph: `<base>`, `<base>_1`, ... counted over this
+    store.  Taken where Keras constructs the layer (a block's __init__, or its build())."""
+    first = self._layer_uids.get(base, 0)
+    self._layer_uids[base] = first + n
+    return [base if i == 0 else '%s_%d' % (base, i) for i in range(first, first + n)]
 
   def full_name(self, name):
     return '/'.join([s for s in self._scope if s] + [name])

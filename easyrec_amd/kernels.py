@@ -2134,6 +2134,113 @@ class HipBackend(object):
       self.op_log.append(('er::senet_bwd_kernel', 6.0 * B * R * (2 * F * G + F * D)))
     return dx
 
+  # -- K8h combining one sequence column over time (layers/keras/text_cnn.py, layers/input_layer.py)
+  @staticmethod
+  def _seq_view(x):
+    """x [B, L_buf, D], a column of the engine's [B * L_buf, width] sequence output read in place -> its row pitch."""
+    B, L, D = x.shape
+    assert x.dtype == torch.float32 and x.stride(2) == 1 and x.stride(1) >= D and x.stride(0) == L * x.stride(1), \
+        'a sequence column must be fp32 [B, L_buf, D] with unit column stride and every example at L_buf rows'
+    return x.stride(1)
+
+  @staticmethod
+  def _i32s(values):
+    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
+
+  def text_cnn_param_count(self, D, sizes, filters):
+    return int(self.lib.er_text_cnn_param_count(int(D), len(sizes), self._i32s(sizes), self._i32s(filters)))
+
+  def text_cnn_lds_bytes(self, P, D, sizes, filters):
+    return int(self.lib.er_text_cnn_lds_bytes(int(P), int(D), len(sizes), self._i32s(sizes), self._i32s(filters)))
+
+  def text_cnn_epb(self, P, D, sizes, filters):
+    """Examples per workgroup round; 0 outside the envelope (easyrec_hip.h K8h)."""
+    if not 1 <= len(sizes) <= 4 or len(sizes) != len(filters):
+      return 0
+    return int(self.lib.er_text_cnn_epb(int(P), int(D), len(sizes), self._i32s(sizes), self._i32s(filters)))
+
+  def text_cnn_grid(self, B, P, D, sizes, filters):
+    return int(self.lib.er_text_cnn_grid(int(B), int(P), int(D), len(sizes), self._i32s(sizes), self._i32s(filters)))
+
+  def text_cnn_fwd(self, x, theta, P, sizes, filters, relu, out=None, want_sel=False):
+    """x [B, L_buf, D] (a strided column view), theta: kernel_i [k_i, D, F_i], bias_i [F_i] per filter size packed ->
+    y [B, sum F_i]: the maxima over the window positions of act(conv); `out`: a [B, sum F_i] view of a wider buffer.
+    want_sel: also int64 [B, sum F_i], bit p set where window position p equals the maximum."""
+    B, L, D = x.shape
+    ld = self._seq_view(x)
+    SF = sum(int(f) for f in filters)
+    assert theta.numel() == self.text_cnn_param_count(D, sizes, filters)
+    y = torch.empty(B, SF, dtype=torch.float32, device=x.device) if out is None else out
+    assert y.shape == (B, SF) and y.stride(1) == 1 and y.stride(0) >= SF
+    sel = torch.empty(B, SF, dtype=torch.int64, device=x.device) if want_sel else None
+    self.ck.er_text_cnn_fwd(_p(x), ld, L, _p(_f32c(theta)), B, int(P), D, len(sizes), self._i32s(sizes),
+                            self._i32s(filters), bool(relu), _p(y), y.stride(0), _p(sel), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::text_cnn_fwd_kernel', 2.0 * B * self._text_cnn_macs(P, D, sizes, filters)))
+    return (y, sel) if want_sel else y
+
+  @staticmethod
+  def _text_cnn_macs(P, D, sizes, filters):
+    return sum((P - k + 1) * k * D * f for k, f in zip(sizes, filters))
+
+  def text_cnn_bwd(self, x, theta, dy, P, sizes, filters, relu, grads, acc=True, dx=None):
+    """-> dx [B, L_buf, D] (`dx`: a column view of a wider buffer, whose other columns are left alone); the parameter
+    gradients are added into (acc) or written to `grads` (a ThetaGradTable: kernel and bias per filter size)."""
+    B, L, D = x.shape
+    ld = self._seq_view(x)
+    SF = sum(int(f) for f in filters)
+    assert dy.shape == (B, SF) and dy.dtype == torch.float32 and dy.stride(1) == 1
+    if dx is None:
+      dx = torch.empty(B, L, D, dtype=torch.float32, device=x.device)
+    assert dx.shape == x.shape
+    lddx = self._seq_view(dx)
+    rows = self.text_cnn_grid(B, P, D, sizes, filters)
+    partials = torch.empty(rows * theta.numel(), dtype=torch.float32, device=x.device)
+    self.ck.er_text_cnn_bwd(_p(x), ld, L, _p(_f32c(theta)), _p(dy), dy.stride(0), B, int(P), D, len(sizes),
+                            self._i32s(sizes), self._i32s(filters), bool(relu), _p(dx), lddx, _p(partials), _stream())
+    self.theta_grad_reduce(partials, rows, grads, 8, acc)
+    if self.op_log is not None:
+      self.op_log.append(('er::text_cnn_bwd_kernel', 6.0 * B * self._text_cnn_macs(P, D, sizes, filters)))
+    return dx
+
+  def seq_attn_pool_lds_bytes(self, L_buf, D, bwd):
+    return int(self.lib.er_seq_attn_pool_lds_bytes(int(L_buf), int(D), bool(bwd)))
+
+  def seq_attn_pool_epb(self, L_buf, D):
+    """Examples per workgroup round; 0 outside the envelope (easyrec_hip.h K8h)."""
+    return int(self.lib.er_seq_attn_pool_epb(int(L_buf), int(D)))
+
+  def seq_attn_pool_grid(self, B, L_buf, D):
+    return int(self.lib.er_seq_attn_pool_grid(int(B), int(L_buf), int(D)))
+
+  def seq_attn_pool_fwd(self, x, seq_len, w):
+    """x [B, L_buf, D] (a strided column view), seq_len int32 [B], w [D] -> the softmax-weighted sum over time [B, D]."""
+    B, L, D = x.shape
+    ld = self._seq_view(x)
+    assert seq_len.dtype == torch.int32 and seq_len.numel() == B and seq_len.is_contiguous() and w.numel() == D
+    y = torch.empty(B, D, dtype=torch.float32, device=x.device)
+    self.ck.er_seq_attn_pool_fwd(_p(x), ld, _p(seq_len), _p(_f32c(w)), B, L, D, _p(y), D, _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::seq_attn_pool_fwd_kernel', 4.0 * B * L * D))
+    return y
+
+  def seq_attn_pool_bwd(self, x, seq_len, w, dy, grads, acc=True, dx=None):
+    """-> dx [B, L_buf, D] (`dx`: a column view of a wider buffer); dw is added into (acc) or written to `grads` (a
+    ThetaGradTable of w's buffer)."""
+    B, L, D = x.shape
+    if dx is None:
+      dx = torch.empty(B, L, D, dtype=torch.float32, device=x.device)
+    ld, lddx = self._seq_view(x), self._seq_view(dx)
+    assert dx.shape == x.shape and dy.shape == (B, D)
+    rows = self.seq_attn_pool_grid(B, L, D)
+    partials = torch.empty(rows * D, dtype=torch.float32, device=x.device)
+    self.ck.er_seq_attn_pool_bwd(_p(x), ld, _p(seq_len), _p(_f32c(w)), _p(_f32c(dy)), B, L, D, _p(dx), lddx, _p(partials),
+                                 _stream())
+    self.theta_grad_reduce(partials, rows, grads, 8, acc)
+    if self.op_log is not None:
+      self.op_log.append(('er::seq_attn_pool_bwd_kernel', 10.0 * B * L * D))
+    return dx
+
   # -- K8f the head of the two-tower retrieval models (model/match_model.py)
   MATCH_MAX_D = 128
 
@@ -4426,6 +4533,59 @@ class SENetFn(torch.autograd.Function):
     table, acc, ret = _theta_grads(ctx, ctx.saved_tensors[2:])
     dx = hip().senet_bwd(x, theta, dy.contiguous(), F, D, G, R, skip, ln, table, acc=acc)
     return (dx, None, None, None, None, None, None, None) + ret
+
+
+def _seq_column(x):
+  """x [B, L_buf, D] as the K8h kernels read it: in place when it is a column view of the engine's sequence output."""
+  ok = x.stride(2) == 1 and x.stride(1) >= x.shape[2] and x.stride(0) == x.shape[1] * x.stride(1)
+  return x if ok else x.contiguous()
+
+
+class TextCnnFn(torch.autograd.Function):
+  """reference layers/keras/blocks.py:243-257 up to the concatenation: apply(x [B, L_buf, D], P, sizes, filters, relu,
+  grads, kernel_0, bias_0[, kernel_1, bias_1, ..]) -> [B, sum filters], the maxima over the window positions of
+  act(Conv1D_i) of the sequence padded / truncated to P (er_text_cnn_*: one launch each way and a fixed-order reduce of
+  the parameter gradients; the backward recomputes the convolutions).  kernel_i [k_i, D, F_i]."""
+
+  @staticmethod
+  def forward(ctx, x, P, sizes, filters, relu, grads, *params):
+    be = hip()
+    x = _seq_column(x)
+    assert len(params) == 2 * len(sizes)
+    theta = _pack_theta(be, params, be.text_cnn_param_count(x.shape[2], sizes, filters), 'TextCnnFn')
+    y = be.text_cnn_fwd(x, theta, P, sizes, filters, relu)
+    ctx.save_for_backward(x, theta, *params)
+    ctx.cfg = (P, tuple(sizes), tuple(filters), relu)
+    ctx.grads = grads
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    x, theta = ctx.saved_tensors[:2]
+    P, sizes, filters, relu = ctx.cfg
+    table, acc, ret = _theta_grads(ctx, ctx.saved_tensors[2:])
+    dx = hip().text_cnn_bwd(x, theta, dy.contiguous(), P, sizes, filters, relu, table, acc=acc)
+    return (dx, None, None, None, None, None) + ret
+
+
+class SeqAttnPoolFn(torch.autograd.Function):
+  """reference layers/input_layer.py:323-338: apply(x [B, L_buf, D], seq_len int32 [B], grads, w [D, 1]) -> [B, D], the
+  sum over time weighted by softmax(<x_t, w> where t < len, -2^32 + 1 elsewhere) (er_seq_attn_pool_*)."""
+
+  @staticmethod
+  def forward(ctx, x, seq_len, grads, w):
+    x = _seq_column(x)
+    y = hip().seq_attn_pool_fwd(x, seq_len, w.detach().reshape(-1))
+    ctx.save_for_backward(x, seq_len, w)
+    ctx.grads = grads
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    x, seq_len, w = ctx.saved_tensors
+    table, acc, ret = _theta_grads(ctx, (w,))
+    dx = hip().seq_attn_pool_bwd(x, seq_len, w.detach().reshape(-1), dy.contiguous(), table, acc=acc)
+    return (dx, None, None) + ret
 
 
 class MatchNormalizeFn(torch.autograd.Function):

@@ -1031,10 +1031,7 @@ class InputLayer(object):
     fg = self._feature_groups[group_name]
     columns, seq_columns = fg.select_columns(self._fc_parser)
     if seq_columns and not plain_only:
-      raise NotImplementedError(
-          'combining sequence columns over time inside a feature group (sequence_combiner attention / text_cnn) is '
-          'outside the hot-path scope; use sequence_features / seq_att_groups (DIN), an input_layer block with '
-          'output_seq_and_normal_feature, or TagFeature')
+      self._check_sequence_combiners(features, group_name, fg, seq_columns)
     scope = self._next_scope()
     eng = self._engine
     B = eng.batch_size
@@ -1061,8 +1058,49 @@ class InputLayer(object):
       col += c.dimension
     self._group_plan[(group_name, plain_only)] = {'gkey': gkey, 'columns': columns, 'cols': cols, 'dims': dims,
                                                   'numeric': numeric, 'rows': rows}
+    if seq_columns and not plain_only:
+      # the group's sequence columns, combined over time after the plain ones (layers/input_layer.py:309-347): kept over
+      # time in one output per static length, tables `<scope>/<column scope>/embedding_weights`
+      self._declare_sequences(features, group_name, table_scope=scope, plan_key=(group_name, 'combined'))
+      plan = self._seq_plan[(group_name, 'combined')]
+      by_name = {c.raw_name: c for c in seq_columns}
+      combiners = []
+      for oi, c0, d, name in sorted(plan['cols'], key=lambda t: by_name[t[3]].name):
+        c = by_name[name]
+        kind = c.sequence_combiner.WhichOneof('combiner')
+        var_scope = '%s/%s' % (scope, c.var_scope_name)
+        layer = None
+        if kind == 'text_cnn':
+          from easyrec_amd.layers.keras.text_cnn import TextCNN
+          from easyrec_amd.layers.utils import Parameter
+          layer = TextCNN(Parameter.make_from_pb(c.sequence_combiner.text_cnn),
+                          name='%s/%s_text_cnn' % (var_scope, c.name))
+        combiners.append({'out': oi, 'col': c0, 'dim': d, 'name': name, 'kind': kind, 'scope': var_scope,
+                          'layer': layer, 'column': c})
+      plan['combiners'] = combiners
 
-  def _declare_sequences(self, features, group_name):
+  def _check_sequence_combiners(self, features, group_name, fg, seq_columns):
+    """What a group that combines sequence columns over time cannot be, at build time."""
+    from easyrec_amd.core import context
+    from easyrec_amd.layers.sharded_embedding import ShardedEmbeddingEngine
+    for c in sorted(seq_columns, key=lambda x: x.name):
+      if c.sequence_combiner is None:
+        raise ValueError('sequence_combiner is none, please set sequence_combiner or use TagFeature')
+      kind = c.sequence_combiner.WhichOneof('combiner')
+      if kind not in ('attention', 'text_cnn'):
+        raise NotImplementedError('sequence_combiner %s of feature %s (the reference raises NotImplementedError too)' % (
+            kind, c.raw_name))
+    what = 'feature group %s combines sequence columns over time (sequence_combiner)' % group_name
+    ctx = context.current()
+    if getattr(ctx, 'dense_dtype', 'f32') == 'bf16':
+      raise ValueError('%s: dense_dtype bf16 is not supported (the sequence combiners are fp32)' % what)
+    if isinstance(self._engine, ShardedEmbeddingEngine):
+      raise ValueError('%s: embedding-parallel training is not supported' % what)
+    if (fg.config.HasField('negative_sampler') and fg.config.negative_sampler) or \
+        any(c.raw_name in getattr(features, 'extended', {}) for c in fg.select_columns(self._fc_parser)[0]):
+      raise ValueError('%s: a negative sampler on the group is not supported' % what)
+
+  def _declare_sequences(self, features, group_name, table_scope=None, plan_key=None):
     """The sequence columns of a group kept over time (`get_sequence_feature`, layers/input_layer.py:164-200): one
     lookup per column into ONE [B * L, sum(dim)] output; tables `input_layer/<categorical column>/embedding_weights`."""
     fg = self._feature_groups[group_name]
@@ -1077,18 +1115,19 @@ class InputLayer(object):
       by_len.setdefault(features.seqs[c.raw_name]['ids'].shape[1], []).append(c)
     outs, cols = [], []
     for n, (L, cs) in enumerate(by_len.items()):
-      gkey = 'group:' + group_name + ':seq' + ('' if n == 0 else ':L%d' % L)
+      gkey = 'group:' + group_name + (':seq' if table_scope is None else ':cseq') + ('' if n == 0 else ':L%d' % L)
       eng.declare_seq_output(gkey, B * L, sum(c.dimension for c in cs), self._embedding_regularizer)
       col = 0
       for c in cs:
-        declare_lookup(eng, features, c, 'input_layer', gkey, col, B * L, seq=True,
-                       table_name='input_layer/%s/embedding_weights' % c.categorical_column.name)
+        declare_lookup(eng, features, c, 'input_layer' if table_scope is None else table_scope, gkey, col, B * L,
+                       seq=True, table_name='input_layer/%s/embedding_weights' % c.categorical_column.name
+                       if table_scope is None else None)
         cols.append((len(outs), col, c.dimension, c.raw_name))
         col += c.dimension
       outs.append({'gkey': gkey, 'L': L, 'width': col})
     order = {c.raw_name: i for i, c in enumerate(seq_columns)}
     cols.sort(key=lambda t: order[t[3]])  # (the columns' own order, whatever their lengths)
-    self._seq_plan[group_name] = {'outs': outs, 'cols': cols}
+    self._seq_plan[group_name if plan_key is None else plan_key] = {'outs': outs, 'cols': cols}
 
   def _uncombined(self, features, group_name):
     """is_combine=False (layers/input_layer.py:268-278): ([(embedding [B, L, dim], length [B]) per sequence column],
@@ -1163,9 +1202,47 @@ class InputLayer(object):
       out = out[:eng.batch_size]  # (a step that does not sample: the batch's own rows, as the reference's PREDICT mode)
     views = [out[:, c0:c0 + d] for c0, d in zip(plan['cols'], plan['dims'])]
     flist = FeatureList(views, base=out, col0=0, dims=plan['dims'])
+    name_to_out = {c.raw_name: v for c, v in zip(plan['columns'], views)}
+    if (group_name, 'combined') in self._seq_plan and not plain_only:
+      out, flist, name_to_out = self._append_combined_sequences(features, group_name, out, views, name_to_out)
     if is_dict:
-      return out, flist, {c.raw_name: v for c, v in zip(plan['columns'], views)}
+      return out, flist, name_to_out
     return out, flist
+
+  def _append_combined_sequences(self, features, group_name, plain, views, name_to_out):
+    """The group's sequence columns, sorted by name, each through its sequence_combiner, after the plain columns
+    (layers/input_layer.py:309-347, :364-366)."""
+    from easyrec_amd.layers.keras.text_cnn import seq_attention_pool
+    eng = self._engine
+    sp = self._seq_plan[(group_name, 'combined')]
+    B = eng.batch_size
+    seq3 = []
+    for o in sp['outs']:
+      if not eng.finalized:
+        seq_out = eng.groups[o['gkey']]['out']
+      else:
+        eng.forward(features.version)
+        seq_out = eng.group_tensor(o['gkey'], requires_grad=self._is_training)
+      seq3.append(seq_out.view(B, o['L'], o['width']))
+    combined = []
+    for cb in sp['combiners']:
+      # `full`: the column where the engine left it, every static position (zero embeddings from the length on): what the
+      # kernels read in place; the composition sees the loaded batch's longest sequence, as the reference does
+      full = seq3[cb['out']][:, :, cb['col']:cb['col'] + cb['dim']]
+      seq_emb = full[:, :features.seq_pad_len(cb['name'])]
+      seq_len = features.seqs[cb['name']]['len']
+      if cb['kind'] == 'attention':
+        fea = seq_attention_pool(seq_emb, seq_len, cb['scope'], self._kernel_regularizer, full_seq=full)
+      else:
+        fea = cb['layer']((seq_emb, seq_len), training=self._is_training, full_seq=full)
+      combined.append(fea)
+      name_to_out[cb['name']] = fea
+    has_plain = plain is not None and plain.shape[1] > 0
+    out = kernels.concat_cols(([plain] if has_plain else []) + combined) if (has_plain or len(combined) > 1) \
+        else combined[0]
+    # the feature list keeps the group's own order of the sequence columns (:366-367); only the concat is sorted
+    in_group_order = [name_to_out[name] for _, _, _, name in sp['cols']]
+    return out, FeatureList((list(views) if has_plain else []) + in_group_order), name_to_out
 
 
 def declare_lookup(eng, features, column, scope, gkey, col, n_out_rows, seq=False, table_name=None):

@@ -1,15 +1,23 @@
-"""Keras-style `MLP` block (reference easy_rec/python/layers/keras/blocks.py:22-128).
+"""Keras-style `MLP` block (reference easy_rec/python/layers/keras/blocks.py:22-128) and `Highway` (:131-177).
 
 Differs from the legacy `DNN` (layers/dnn.py): no bias by default, `he_uniform` kernels, BatchNorm +
 activation also on the LAST layer unless `use_final_bn` / `final_activation` say otherwise
 (SURVEY.md App. B.10).  Variables: `<name>/layer_<i>/dense/kernel[, bias]`, `<name>/layer_<i>/bn/*`.
 Per layer: one MFMA GEMM (er_gemm) + one fused bias/BatchNorm/ReLU kernel pair (er_bn_act).
+
+`Highway`: value = gate * act(transform(value)) + (1 - gate) * value per layer, composed of the dense layers below and
+torch elementwise ops (no kernel of its own).  Variables: `<name>/input_projection/*` when emb_size differs from the
+input width, `<name>/gate_<i>/*` (bias initialised to init_gate_bias) and the unnamed transform layers, which Keras
+numbers per graph in creation order (`<name>/dense`, `<name>/dense_1`, ...; here VarStore.next_layer_names, taken at
+the first call, where Keras' build() constructs them).
 """
 import logging
 
+import numpy as np
 import torch
 
 from easyrec_amd import kernels
+from easyrec_amd.core import context
 from easyrec_amd.layers import dnn
 from easyrec_amd.utils.activation import get_activation, is_relu
 
@@ -81,3 +89,46 @@ class Add(object):
     for t in inputs[1:]:
       out = out + t
     return out
+
+
+class Highway(object):
+
+  def __init__(self, params, name='highway', reuse=None, **kwargs):
+    self.name = name
+    self.emb_size = params.get_or_default('emb_size', None)
+    self.num_layers = int(params.get_or_default('num_layers', 1))
+    self.activation = params.get_or_default('activation', 'relu')
+    self.dropout_rate = float(params.get_or_default('dropout_rate', 0.0))
+    self.init_gate_bias = float(params.get_or_default('init_gate_bias', -3.0))
+    self._transform_names = None
+
+  def _act(self, x, training):
+    act = None if self.activation is None else str(self.activation).lower()
+    if act in (None, '', 'linear'):
+      return x
+    if is_relu(act):
+      return torch.relu(x)
+    fn = get_activation(act, training=training) if act == 'dice' else get_activation(act)
+    return x if fn is None else fn(x)
+
+  def __call__(self, inputs, training=None, **kwargs):
+    vs = context.varstore()
+    value = inputs
+    dim = int(inputs.shape[-1])
+    if self.emb_size is not None and dim != int(self.emb_size):
+      dim = int(self.emb_size)
+      value = dnn.dense(inputs, dim, self.name + '/input_projection')
+    if self._transform_names is None:  # (Keras constructs the unnamed transform layers in build(): the first call)
+      self._transform_names = vs.next_layer_names('dense', self.num_layers)
+    gate_bias = self.init_gate_bias
+    for i in range(self.num_layers):
+      gname = '%s/gate_%d' % (self.name, i)
+      # (created here so that the bias starts at init_gate_bias; dnn.dense below fetches it)
+      vs.get_variable(gname + '/kernel', (dim, dim), 'glorot_uniform')
+      vs.get_variable(gname + '/bias', (dim,), lambda shape, rng: np.full(shape, gate_bias, dtype=np.float32))
+      gate = torch.sigmoid(dnn.dense(value, dim, gname))
+      transformed = self._act(dnn.dense(value, dim, '%s/%s' % (self.name, self._transform_names[i])), training)
+      if self.dropout_rate > 0.0 and training:
+        transformed = torch.nn.functional.dropout(transformed, p=self.dropout_rate, training=True)
+      value = gate * transformed + (1.0 - gate) * value
+    return value

@@ -1001,6 +1001,74 @@ int er_knn_hits(const int64_t* out_ids, const int32_t* user_emb_num, const int64
                 int64_t U, int32_t I, int32_t K, int32_t* hits, int32_t* gt_count, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8h Combining one sequence column over time inside a feature group (sequence_combiner).  fp32, no
+ *     atomics; two runs and a graph replay give the same bits.  Both blocks read the column where the
+ *     embedding engine left it: x points at the column's first float, consecutive positions lie ld
+ *     floats apart (ld >= D), an example owns L_buf positions: x[b, t, d] = x[(b * L_buf + t) * ld + d].
+ * TextCNN.  Replaces pad_or_truncate_sequence, the Conv1D (+ BiasAdd, activation) and GlobalMaxPool1D
+ *     per filter size and the Concatenate of TextCNN.call layers/keras/blocks.py:243-257, and their
+ *     gradients (the `mlp` after it stays a contraction).
+ * sizes, filters: HOST arrays of n_sizes entries, k_i and F_i.  theta packs per filter size i, in order,
+ *   kernel_i [k_i, D, F_i] (Keras Conv1D: the window at position p is the contiguous k_i * D floats of
+ *   the example's row-major [P, D] block) then bias_i [F_i] (er_text_cnn_param_count).
+ * er_text_cnn_fwd: x_t = the input for t < min(P, L_buf), 0 for t in [L_buf, P) (the reference's pad and
+ *   truncate); z_i[p, f] = act(bias_i[f] + sum_{j, d} x[p + j, d] kernel_i[j, d, f]), p = 0 .. P - k_i, one
+ *   fmaf chain over (j, d) ascending starting from the bias; y[b * ldy + off_i + f] = max_p z_i[p, f],
+ *   off_i = F_0 + .. + F_{i-1}; ldy >= sum F_i.  act: 0 = linear, 1 = relu.  Lengths do not mask: windows
+ *   in the padding take part in the max with act(bias), as in the reference.  sel [B, sum F_i] when not null:
+ *   bit p set where z_i[p, f] equals the maximum (the positions the backward will share the gradient among).
+ * er_text_cnn_bwd: recomputes z; dy [B, sum F_i] at pitch lddy.  The gradient of the max follows
+ *   TensorFlow's reduce_max (the rule of K8d's SENet): dy / count of ties to each position that equals
+ *   the maximum, nothing to the others; relu passes it where the output is > 0.  dx [B, L_buf, D at pitch lddx]:
+ *   every position t < L_buf of the column's D floats is written, zeros where nothing arrives
+ *   (t >= P included); the floats between D and lddx are not touched.  Per-workgroup partial sums of the
+ *   packed parameter gradient go to partials [er_text_cnn_grid, param_count], which er_theta_grad_reduce
+ *   (K8e) sums with row_groups = 8 into the 2 n_sizes variables.
+ * Envelope: 1 <= P, D <= 64, 1 <= n_sizes <= 4, 1 <= k_i <= min(P, 8), F_i >= 1, sum F_i <= 64.  With
+ *   per = round4(P * odd(D) + sum_i (P - k_i + 1) F_i) floats per example (x at an odd row pitch, z) and
+ *   T = round4(sum_i (k_i D odd(F_i) + F_i)) floats of theta with the kernels' rows at an odd pitch
+ *   (odd(n) = n | 1, round4 = up to a multiple of 4): when T + per <= 16384 theta is staged in LDS once
+ *   per workgroup, else T = 0 and the kernels read theta in place.  er_text_cnn_epb =
+ *   min(8, (16384 - T) / per) examples that fit a workgroup round (>= 1 over the whole envelope), 0 outside
+ *   the envelope; er_text_cnn_lds_bytes = 4 * (T + epb * per) <= 65536, what a launch requests at most.  A
+ *   launch over B examples takes min(epb, max(1, ceil(B / 512))) examples per round - as few as fill the
+ *   grid - and er_text_cnn_grid = min(ceil(B / that), 512) persistent workgroups of 256 threads.
+ * Attention pooling.  Replaces the Dense(1) `attention`, Squeeze, sequence_mask, Select, Softmax, Mul
+ *     and Sum of single_call_input_layer layers/input_layer.py:323-338 and their gradients.
+ * er_seq_attn_pool_fwd: len int32 [B]; logit_t = <x_t, w>, w [D], for t < len[b] and -2^32 + 1 for the
+ *   other t < L_buf; p = softmax over t < L_buf with max subtraction; y[b * ldy + d] = sum_t p_t x[b, t, d].
+ *   A row of length 0 has the uniform softmax (over the zero embeddings the engine leaves there: 0).
+ * er_seq_attn_pool_bwd: dy [B, D] contiguous; dx_t = p_t dy + dlogit_t w with
+ *   dlogit_t = p_t (<dy, x_t> - sum_s p_s <dy, x_s>) for t < len[b] and 0 for the masked positions (their
+ *   logit is the constant); dx [B, L_buf, D at pitch lddx], every position t < L_buf written.  partials
+ *   [er_seq_attn_pool_grid, D] = per-workgroup sums of dlogit_t x_t, which er_theta_grad_reduce (K8e) sums
+ *   with row_groups = 8 into w's buffer.
+ * One wave per example: a lane per position for the logits, then 64 / pow2(D) lane groups over the
+ *   positions with a lane per column.  Envelope: 1 <= L_buf <= 1024, 1 <= D <= 128 (the grid and epb
+ *   functions return 0 outside).  er_seq_attn_pool_epb = 4 examples per workgroup round;
+ *   er_seq_attn_pool_lds_bytes = 16 * round4(L_buf) forward, 16 * (2 * round4(L_buf) + 128) backward;
+ *   er_seq_attn_pool_grid = min(ceil(B / 4), 512).
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_text_cnn_param_count(int32_t D, int32_t n_sizes, const int32_t* sizes, const int32_t* filters);
+int64_t er_text_cnn_lds_bytes(int32_t P, int32_t D, int32_t n_sizes, const int32_t* sizes, const int32_t* filters);
+int32_t er_text_cnn_epb(int32_t P, int32_t D, int32_t n_sizes, const int32_t* sizes, const int32_t* filters);
+int32_t er_text_cnn_grid(int64_t B, int32_t P, int32_t D, int32_t n_sizes, const int32_t* sizes,
+                         const int32_t* filters);  /* rows of `partials` */
+int er_text_cnn_fwd(const float* x, int64_t ld, int32_t L_buf, const float* theta, int64_t B, int32_t P, int32_t D,
+                    int32_t n_sizes, const int32_t* sizes, const int32_t* filters, int act, float* y, int64_t ldy,
+                    uint64_t* sel, er_stream_t stream);
+int er_text_cnn_bwd(const float* x, int64_t ld, int32_t L_buf, const float* theta, const float* dy, int64_t lddy,
+                    int64_t B, int32_t P, int32_t D, int32_t n_sizes, const int32_t* sizes, const int32_t* filters,
+                    int act, float* dx, int64_t lddx, float* partials, er_stream_t stream);
+int64_t er_seq_attn_pool_lds_bytes(int32_t L_buf, int32_t D, int bwd);
+int32_t er_seq_attn_pool_epb(int32_t L_buf, int32_t D);
+int32_t er_seq_attn_pool_grid(int64_t B, int32_t L_buf, int32_t D);  /* rows of `partials` */
+int er_seq_attn_pool_fwd(const float* x, int64_t ld, const int32_t* len, const float* w, int64_t B, int32_t L_buf,
+                         int32_t D, float* y, int64_t ldy, er_stream_t stream);
+int er_seq_attn_pool_bwd(const float* x, int64_t ld, const int32_t* len, const float* w, const float* dy, int64_t B,
+                         int32_t L_buf, int32_t D, float* dx, int64_t lddx, float* partials, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed

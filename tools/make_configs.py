@@ -402,6 +402,64 @@ def cmbf_movielens(batch_size=1024):
   return text_format.Parse(head % {'batch_size': batch_size} + CMBF_MOVIELENS_MODEL, pipeline_pb2.EasyRecConfig())
 
 
+DEEPFM_TEXTCNN_MOVIELENS = """
+train_input_path: "examples/data/movielens_1m/movies_train_data"
+eval_input_path: "examples/data/movielens_1m/movies_test_data"
+model_dir: "experiments/deepfm_textcnn_movielens_ckpt"
+train_config {
+  optimizer_config { adam_optimizer { learning_rate { exponential_decay_learning_rate { initial_learning_rate: 0.001
+                     decay_steps: 1000 decay_factor: 0.5 min_learning_rate: 0.00001 } } } use_moving_average: false }
+  log_step_count_steps: 100 save_checkpoints_steps: 100 sync_replicas: true num_steps: 2500
+}
+eval_config { metrics_set { auc {} } }
+data_config {
+  input_fields { input_name: 'label' input_type: INT32 }
+  input_fields { input_name: 'user_id' input_type: INT32 }
+  input_fields { input_name: 'movie_id' input_type: INT32 }
+  input_fields { input_name: 'rating' input_type: INT32 }
+  input_fields { input_name: 'gender' input_type: INT32 }
+  input_fields { input_name: 'age' input_type: INT32 }
+  input_fields { input_name: 'job_id' input_type: INT32 }
+  input_fields { input_name: 'zip_id' input_type: STRING }
+  input_fields { input_name: 'title' input_type: STRING }
+  input_fields { input_name: 'genres' input_type: STRING }
+  input_fields { input_name: 'year' input_type: INT32 }
+  label_fields: 'label'
+  batch_size: %(batch_size)d num_epochs: 10000 prefetch_size: 1 input_type: CSVInput separator: '\\t'
+}
+feature_config {
+  features { input_names: 'user_id' feature_type: IdFeature embedding_dim: 16 hash_bucket_size: 12000 }
+  features { input_names: 'movie_id' feature_type: IdFeature embedding_dim: 16 hash_bucket_size: 6000 }
+  features { input_names: 'gender' feature_type: IdFeature embedding_dim: 16 num_buckets: 2 }
+  features { input_names: 'job_id' feature_type: IdFeature embedding_dim: 16 num_buckets: 21 }
+  features { input_names: 'age' feature_type: IdFeature embedding_dim: 16 num_buckets: 7 }
+  features { input_names: 'genres' feature_type: TagFeature separator: '|' embedding_dim: 16 hash_bucket_size: 100 }
+  features { input_names: 'title' feature_type: SequenceFeature separator: ' ' embedding_dim: 16 hash_bucket_size: 10000
+             sequence_combiner { text_cnn { filter_sizes: [2, 3, 4] num_filters: [8, 4, 4] pad_sequence_length: 14 } } }
+  features { input_names: 'year' feature_type: IdFeature embedding_dim: 16 num_buckets: 36 }
+}
+model_config {
+  model_class: 'DeepFM'
+  feature_groups { group_name: 'wide' feature_names: 'user_id' feature_names: 'movie_id' feature_names: 'job_id'
+                   feature_names: 'age' feature_names: 'gender' feature_names: 'year' feature_names: 'genres'
+                   wide_deep: WIDE }
+  feature_groups { group_name: 'deep' feature_names: 'user_id' feature_names: 'movie_id' feature_names: 'job_id'
+                   feature_names: 'age' feature_names: 'gender' feature_names: 'year' feature_names: 'genres'
+                   feature_names: 'title' wide_deep: DEEP }
+  deepfm { dnn { hidden_units: [256, 128, 64] } l2_regularization: 1e-4 }
+  embedding_regularization: 1e-4
+}
+"""
+
+
+def deepfm_textcnn_movielens(batch_size=1024):
+  """DeepFM with a TextCNN sequence_combiner: examples/configs/deepfm_on_movielens.config (its data, feature and model
+  sections: seven plain columns of D = 16 and the `title` SequenceFeature combined over time by TextCNN, filters
+  [2, 3, 4] x [8, 4, 4] over 14 padded positions, in the `deep` group) on synthetic MovieLens-shaped batches; batch size
+  1024; the metric set is auc alone."""
+  return text_format.Parse(DEEPFM_TEXTCNN_MOVIELENS % {'batch_size': batch_size}, pipeline_pb2.EasyRecConfig())
+
+
 def fibinet_taobao(bilinear_type='each', use_plus=True, **kw):
   """FiBiNet, the model section of samples/model_config/fibinet_on_taobao.config: RankModel over a backbone whose
   input-layer block batch-normalises the 17 fields of D = 16 and hands them on as a list, and a `FiBiNet` block (SENet
@@ -1031,6 +1089,7 @@ if __name__ == '__main__':
   write(autoint_taobao(item_rows=10000000), 'autoint_taobao_10m.config')
   write(uniter_movielens(), 'uniter_movielens.config')
   write(cmbf_movielens(), 'cmbf_movielens.config')
+  write(deepfm_textcnn_movielens(), 'deepfm_textcnn_movielens.config')
   write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
   write(dssm_taobao(item_rows=10000000), 'dssm_taobao_10m.config')
   write(dssm_taobao(in_batch=True, item_rows=10000000), 'dssm_inbatch_taobao_10m.config')
