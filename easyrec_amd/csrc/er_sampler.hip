@@ -13,6 +13,8 @@
 //      (eight at a time) before it stores any: the table is far larger than the caches, every load is a miss.
 // Nothing here is ordered by timing: two runs and a graph replay give the same bits.  The step is read from the device
 // counter, so a replayed graph draws fresh rows.
+// K1c, negative_sampler's weighted draw with replacement (er_neg_sample_weighted), follows it below and shares the set,
+// the column records and samp_copy_row.
 #include "er_common.h"
 
 namespace er {
@@ -203,6 +205,160 @@ __global__ void __launch_bounds__(kSampThreads) neg_sample_kernel(
 
 static int g_samp_lds = 0;  // (per process: one device per process, one launching thread - see er_capsule.hip)
 
+// ---- K1c: negative_sampler, the weighted draw with replacement (include/easyrec_hip.h next to er_neg_sample_weighted).
+// Every draw is independent, so there is no order to keep: one lane per draw, ceil(N / 256) drawing workgroups, each
+// with its own copy of the batch-id set in LDS (the set of the kernel above), and a lane gathers the columns of the row
+// it drew itself.  The chain of one draw is alias record -> table id -> column rows, each a miss at a table far larger
+// than the caches, so what can be issued early is: the first attempt's alias record is in flight while the set is
+// cleared, its id and its first eight columns (read before the id is judged: a first attempt is rejected with
+// probability q, the batch's weight mass) while the set is filled.  A rejected lane goes on alone; the attempts and the
+// walk behind them are bounded.
+constexpr int kWsampThreads = 256;
+constexpr int kWsampAttempts = 32;
+constexpr int kWsampIdsPerLane = kSampMaxB / kWsampThreads;
+
+inline int64_t wsamp_lds_bytes(int B) {
+  if (B < 1 || B > kSampMaxB) return 0;
+  return 8 * static_cast<int64_t>(samp_capacity(B)) + 16;
+}
+
+__device__ __forceinline__ bool samp_is_member(const unsigned long long* set, unsigned long long slot_mask,
+                                               bool empty_is_member, unsigned long long id) {
+  if (id == kSampEmpty) return empty_is_member;
+  unsigned long long slot = mix64(id) & slot_mask;
+  for (unsigned long long probe = 0; probe <= slot_mask; ++probe) {
+    const unsigned long long cur = set[slot];
+    if (cur == id) return true;
+    if (cur == kSampEmpty) return false;
+    slot = (slot + 1) & slot_mask;
+  }
+  return false;
+}
+
+// the two halves of samp_copy_row for columns [c0, c0 + kSampColGroup) of the table
+__device__ __forceinline__ void samp_load_group(const SampCols& cols, int c0, int64_t r, uint64_t (&v)[kSampColGroup]) {
+#pragma unroll
+  for (int u = 0; u < kSampColGroup; ++u) {
+    const int c = c0 + u;
+    if (c < cols.ncols)
+      v[u] = ((cols.wide >> c) & 1u) ? static_cast<const uint64_t*>(cols.table[c])[r]
+                                     : static_cast<const uint32_t*>(cols.table[c])[r];
+  }
+}
+__device__ __forceinline__ void samp_store_group(const SampCols& cols, int c0, int64_t j, const uint64_t (&v)[kSampColGroup]) {
+#pragma unroll
+  for (int u = 0; u < kSampColGroup; ++u) {
+    const int c = c0 + u;
+    if (c < cols.ncols) {
+      if ((cols.wide >> c) & 1u) static_cast<uint64_t*>(cols.out[c])[j] = v[u];
+      else static_cast<uint32_t*>(cols.out[c])[j] = static_cast<uint32_t>(v[u]);
+    }
+  }
+}
+
+// candidate row of (draw j, attempt a) from its alias record: (k, the record) in two steps so that the record's load
+// can be issued apart from its use
+__device__ __forceinline__ void wsamp_random(uint64_t base, int j, int a, uint64_t n, uint32_t* k, float* f) {
+  const uint64_t r0 = mix64(base ^ mix64((static_cast<uint64_t>(j) << 32) | static_cast<uint64_t>(a)));
+  const uint64_t r1 = mix64(r0 + 0xD1B54A32D192ED03ull);
+  *k = static_cast<uint32_t>(__umul64hi(r0, n));
+  *f = static_cast<float>(static_cast<uint32_t>(r1 >> 40)) * 0x1p-24f;
+}
+__device__ __forceinline__ uint32_t wsamp_row(uint64_t rec, uint32_t k, float f, uint64_t n) {
+  const uint32_t alias = static_cast<uint32_t>(rec >> 32);
+  if (f < __uint_as_float(static_cast<uint32_t>(rec))) return k;
+  return alias < n ? alias : k;
+}
+
+// grid = D + C, D = ceil(N / 256) drawing workgroups, C = ceil(B / 256) that copy the batch's own values into [0, B)
+__global__ void __launch_bounds__(kWsampThreads) neg_sample_weighted_kernel(
+    const uint64_t* __restrict__ alias_tab, const int64_t* __restrict__ table_ids, int64_t n_rows,
+    const int64_t* __restrict__ batch_ids, int B, int N, int draw_groups, const int64_t* __restrict__ step,
+    int64_t step_offset, uint64_t seed, int cap, SampCols cols, int32_t* __restrict__ sel) {
+  const int tid = threadIdx.x;
+  if (static_cast<int>(blockIdx.x) >= draw_groups) {
+    const int j = (blockIdx.x - draw_groups) * kWsampThreads + tid;
+    if (j < B) samp_copy_row(cols, false, j, j);
+    return;
+  }
+  extern __shared__ __align__(16) unsigned char samp_lds[];
+  unsigned long long* set = reinterpret_cast<unsigned long long*>(samp_lds);
+  int* has_empty = reinterpret_cast<int*>(set + cap);
+  const unsigned long long slot_mask = static_cast<unsigned long long>(cap - 1);
+  const uint64_t n = static_cast<uint64_t>(n_rows);
+  const int j = blockIdx.x * kWsampThreads + tid;
+  const bool draws = j < N;
+
+  // attempt 0: its alias record is in flight while the set is cleared
+  const uint64_t base = mix64(seed ^ mix64(static_cast<uint64_t>(*step + step_offset)));
+  uint32_t k = 0;
+  float f = 0.f;
+  uint64_t rec = 0;
+  if (draws) {
+    wsamp_random(base, j, 0, n, &k, &f);
+    rec = alias_tab[k];
+  }
+  unsigned long long mine[kWsampIdsPerLane];
+#pragma unroll
+  for (int u = 0; u < kWsampIdsPerLane; ++u) {
+    const int i = tid + u * kWsampThreads;
+    mine[u] = i < B ? static_cast<unsigned long long>(batch_ids[i]) : 0ull;
+  }
+  for (int i = tid; i < cap; i += kWsampThreads) set[i] = kSampEmpty;
+  if (tid == 0) *has_empty = 0;
+  // its id and first column group are in flight while the set is filled
+  uint32_t row = 0;
+  unsigned long long id = 0;
+  uint64_t v[kSampColGroup];
+  if (draws) {
+    row = wsamp_row(rec, k, f, n);
+    id = static_cast<unsigned long long>(table_ids[row]);
+    samp_load_group(cols, 0, row, v);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < kWsampIdsPerLane; ++u) {
+    if (tid + u * kWsampThreads >= B) continue;
+    const unsigned long long bid = mine[u];
+    if (bid == kSampEmpty) {
+      *has_empty = 1;
+      continue;
+    }
+    unsigned long long slot = mix64(bid) & slot_mask;
+    for (int probe = 0; probe < cap; ++probe) {  // (at most B < cap slots are ever taken: an empty one is found)
+      const unsigned long long prev = atomicCAS(&set[slot], kSampEmpty, bid);
+      if (prev == kSampEmpty || prev == bid) break;
+      slot = (slot + 1) & slot_mask;
+    }
+  }
+  __syncthreads();
+  if (!draws) return;  // (no barrier follows)
+  const bool empty_is_member = *has_empty != 0;
+
+  bool member = samp_is_member(set, slot_mask, empty_is_member, id);
+  if (member) {
+    for (int a = 1; a < kWsampAttempts && member; ++a) {
+      wsamp_random(base, j, a, n, &k, &f);
+      row = wsamp_row(alias_tab[k], k, f, n);
+      member = samp_is_member(set, slot_mask, empty_is_member, static_cast<unsigned long long>(table_ids[row]));
+    }
+    for (int w = 0; w <= B && member; ++w) {  // the weights are left behind: the next eligible row
+      row = row + 1 < n ? row + 1 : 0;
+      member = samp_is_member(set, slot_mask, empty_is_member, static_cast<unsigned long long>(table_ids[row]));
+    }
+    samp_load_group(cols, 0, row, v);
+  }
+  sel[j] = static_cast<int32_t>(row);
+  const int64_t out = static_cast<int64_t>(B) + j;
+  samp_store_group(cols, 0, out, v);
+  for (int c0 = kSampColGroup; c0 < cols.ncols; c0 += kSampColGroup) {
+    samp_load_group(cols, c0, row, v);
+    samp_store_group(cols, c0, out, v);
+  }
+}
+
+static int g_wsamp_lds = 0;
+
 }  // namespace er
 
 extern "C" {
@@ -242,6 +398,50 @@ int er_neg_sample(const int64_t* table_ids, int64_t n, const int64_t* batch_ids,
   hipLaunchKernelGGL(er::neg_sample_kernel, dim3(grid), dim3(er::kSampThreads), static_cast<size_t>(bytes),
                      er::as_stream(stream), table_ids, n, batch_ids, B, N, step, step_offset, seed, er::samp_capacity(B),
                      cols, sel);
+  ER_LAUNCH_CHECK();
+  return 0;
+}
+
+int64_t er_neg_sample_weighted_lds_bytes(int32_t B) { return er::wsamp_lds_bytes(B); }
+
+int er_neg_sample_weighted(const uint64_t* alias_tab, const int64_t* table_ids, int64_t n, const int64_t* batch_ids,
+                           int32_t B, int32_t N, const int64_t* step, int64_t step_offset, uint64_t seed,
+                           const void* const* table_cols_host, const void* const* batch_cols_host,
+                           void* const* out_cols_host, const int32_t* elem_bytes_host, int32_t ncols, int32_t* sel,
+                           er_stream_t stream) {
+  const int64_t bytes = er::wsamp_lds_bytes(B);
+  ER_REQUIRE(bytes > 0, "er_neg_sample_weighted: B %d outside the envelope 1 .. %d", B, er::kSampMaxB);
+  ER_REQUIRE(alias_tab && table_ids && batch_ids && step && sel, "er_neg_sample_weighted: null argument");
+  ER_REQUIRE(N >= 1 && static_cast<int64_t>(B) + N <= n && n <= 0x7fffffffll,
+             "er_neg_sample_weighted: need 1 <= N and B + N <= n < 2^31 (B %d, N %d, n %lld)", B, N,
+             static_cast<long long>(n));
+  ER_REQUIRE(ncols >= 0 && ncols <= er::kSampMaxCols, "er_neg_sample_weighted: %d columns, at most %d", ncols,
+             er::kSampMaxCols);
+  ER_REQUIRE(ncols == 0 || (table_cols_host && batch_cols_host && out_cols_host && elem_bytes_host),
+             "er_neg_sample_weighted: null column list");
+  er::SampCols cols;
+  memset(&cols, 0, sizeof(cols));
+  cols.ncols = ncols;
+  for (int c = 0; c < ncols; ++c) {
+    ER_REQUIRE(table_cols_host[c] && batch_cols_host[c] && out_cols_host[c],
+               "er_neg_sample_weighted: column %d: null buffer", c);
+    ER_REQUIRE(elem_bytes_host[c] == 4 || elem_bytes_host[c] == 8, "er_neg_sample_weighted: column %d: %d-byte elements",
+               c, elem_bytes_host[c]);
+    cols.table[c] = table_cols_host[c];
+    cols.batch[c] = batch_cols_host[c];
+    cols.out[c] = out_cols_host[c];
+    if (elem_bytes_host[c] == 8) cols.wide |= 1u << c;
+  }
+  const void* fn = reinterpret_cast<const void*>(er::neg_sample_weighted_kernel);
+  if (bytes > 65536 && bytes > er::g_wsamp_lds) {  // (no stream work: safe inside a capture)
+    ER_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+    er::g_wsamp_lds = static_cast<int>(bytes);
+  }
+  const int draw_groups = static_cast<int>(er::ceil_div(N, er::kWsampThreads));
+  const int grid = draw_groups + static_cast<int>(er::ceil_div(B, er::kWsampThreads));
+  hipLaunchKernelGGL(er::neg_sample_weighted_kernel, dim3(grid), dim3(er::kWsampThreads), static_cast<size_t>(bytes),
+                     er::as_stream(stream), alias_tab, table_ids, n, batch_ids, B, N, draw_groups, step, step_offset, seed,
+                     er::samp_capacity(B), cols, sel);
   ER_LAUNCH_CHECK();
   return 0;
 }

@@ -2342,6 +2342,34 @@ class HipBackend(object):
         _p(table_ids), n, _p(batch_ids), B, int(N), _p(step), int(step_offset), int(seed) & 0xFFFFFFFFFFFFFFFF, ptrs(*tabs),
         ptrs(*bats), ptrs(*outs), (ctypes.c_int32 * max(nc, 1))(*sizes), nc, _p(sel), _stream())
 
+  # -- K1c negative_sampler: the weighted draw with replacement (input/neg_sampler.py)
+  def neg_sample_weighted_lds_bytes(self, B):
+    return int(self.lib.er_neg_sample_weighted_lds_bytes(int(B)))
+
+  def neg_sample_weighted(self, alias_tab, table_ids, batch_ids, N, step, step_offset, seed, columns, sel):
+    """The draw of easyrec_hip.h K1c at step *step + step_offset.  alias_tab: int64 [n] holding the uint64 records
+    (neg_sampler.alias_table); the other arguments as neg_sample."""
+    n, B = table_ids.numel(), batch_ids.numel()
+    assert alias_tab.dtype == torch.int64 and alias_tab.numel() == n and alias_tab.is_contiguous()
+    assert table_ids.dtype == torch.int64 and batch_ids.dtype == torch.int64 and step.dtype == torch.int64
+    assert table_ids.is_contiguous() and batch_ids.is_contiguous()
+    assert sel.dtype == torch.int32 and sel.numel() == N and sel.is_contiguous()
+    nc = len(columns)
+    tabs, bats, outs, sizes = [], [], [], []
+    for tab, bat, out in columns:
+      assert tab.dtype == bat.dtype == out.dtype and tab.dtype in (torch.int64, torch.float32), tab.dtype
+      assert tab.numel() == n and bat.numel() == B and out.numel() == B + N
+      assert tab.is_contiguous() and bat.is_contiguous() and out.is_contiguous()
+      tabs.append(tab.data_ptr())
+      bats.append(bat.data_ptr())
+      outs.append(out.data_ptr())
+      sizes.append(tab.element_size())
+    ptrs = ctypes.c_void_p * max(nc, 1)
+    self.ck.er_neg_sample_weighted(
+        _p(alias_tab), _p(table_ids), n, _p(batch_ids), B, int(N), _p(step), int(step_offset),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, ptrs(*tabs), ptrs(*bats), ptrs(*outs), (ctypes.c_int32 * max(nc, 1))(*sizes), nc,
+        _p(sel), _stream())
+
   # -- K9k full-corpus top-K search and hit count (core/knn.py, core/hit_rate.py)
   def knn_lds_bytes(self, D, K):
     return int(self.lib.er_knn_lds_bytes(int(D), int(K)))

@@ -1172,6 +1172,10 @@ class InputLayer(object):
       seq_cfgs = self._group_name_to_seq_features[group_name]
       assert not self._feature_groups[group_name].config.HasField('negative_sampler') or \
           not self._feature_groups[group_name].config.negative_sampler, 'negative sampler: outside the hot-path scope'
+      sampled = [k for cfg in seq_cfgs for m in cfg.seq_att_map for k in m.key if k in getattr(features, 'extended', {})]
+      if sampled:
+        raise NotImplementedError('feature group %s: the sequence_features keys %s are attribute fields of the negative '
+                                  'sampler (target attention over sampled rows is not built)' % (group_name, ', '.join(sampled)))
       _, all_seq_fea = self._sequence_feature_layer(features, out, seq_cfgs, dict(name_to_out), scope_name=group_name)
       views = list(flist) + list(all_seq_fea)
       for cfg, fea in zip(seq_cfgs, all_seq_fea):

@@ -102,15 +102,21 @@ class EasyRecEstimator(object):
       model_cls = EasyRecModel.create_class(cfg.model_config.model_class)
       if hasattr(model_cls, 'check_data_config'):
         model_cls.check_data_config(cfg.data_config)  # (what the input pipeline would have to deliver: model/match_model.py)
-      # negative_sampler_in_memory: the item table goes to the device and the attribute features get their extended
-      # buffers before the model declares its groups (item_table: an input/neg_sampler.py ItemTable instead of input_path)
+      # negative_sampler_in_memory / negative_sampler: the item table goes to the device and the attribute features get
+      # their extended buffers before the model declares its groups (item_table: an input/neg_sampler.py ItemTable
+      # instead of input_path)
       self.sampler = None
-      if cfg.data_config.WhichOneof('sampler') == 'negative_sampler_in_memory':
+      sampler_kind = cfg.data_config.WhichOneof('sampler')
+      if sampler_kind in ('negative_sampler_in_memory', 'negative_sampler'):
         if not getattr(model_cls, 'supports_sampled_negatives', False):
-          raise NotImplementedError('data_config.negative_sampler_in_memory: %s takes no sampled negatives' %
-                                    cfg.model_config.model_class)
+          raise NotImplementedError('data_config.%s: %s takes no sampled negatives' %
+                                    (sampler_kind, cfg.model_config.model_class))
+        if sampler_kind == 'negative_sampler' and item_table is None and not cfg.data_config.negative_sampler.input_path:
+          raise NotImplementedError('data_config.negative_sampler: no input_path names a local item table (and no '
+                                    'item_table= was given); the graphlearn service paths are not built')
         from easyrec_amd.input.neg_sampler import NegativeSampler
-        self.sampler = NegativeSampler(cfg.data_config, self.feature_configs, self.features, seed, item_table)
+        self.sampler = NegativeSampler(cfg.data_config, self.feature_configs, self.features, seed, item_table,
+                                       is_training=is_training)
       self.model = model_cls(cfg.model_config, self.feature_configs, self.features, labels,
                              is_training=is_training)
 
@@ -400,7 +406,7 @@ class EasyRecEstimator(object):
         self.features.version += 1  # (the extended columns change: the lookups run again)
       self.sampler.run(self.step_counter, 0, sample=bool(sample_negatives))
     else:
-      assert not sample_negatives, 'predict(sample_negatives=True) needs data_config.negative_sampler_in_memory'
+      assert not sample_negatives, 'predict(sample_negatives=True) needs a negative sampler in data_config'
     # no row update follows these lookups: bring the tables current once, then look up without the catch-up
     # (running it here would re-apply the pending Adam decay on every call)
     self.engine.begin_inference()
@@ -527,8 +533,9 @@ class EasyRecEstimator(object):
     if id_field is None:
       from easyrec_amd.input.features import feature_name_of
       by_name = {feature_name_of(fc): fc.input_names[0] for fc in self.feature_configs if len(fc.input_names) == 1}
+      dc = self.pipeline_config.data_config
       id_field = by_name.get(self.model._item_id_name) or \
-          self.pipeline_config.data_config.negative_sampler_in_memory.item_id_field
+          getattr(getattr(dc, dc.WhichOneof('sampler') or 'negative_sampler_in_memory'), 'item_id_field', '')
     if not id_field:
       raise ValueError('hit_rate: the model config names no item_id and there is no negative sampler: pass id_field')
     ids, emb = self.item_embeddings(item_batches, id_field)

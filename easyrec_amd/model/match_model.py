@@ -11,9 +11,9 @@ form (:145-205).
 While training, the list-wise head never builds its [B, B] logits: build_predict_graph stops at the tower embeddings and
 build_loss_graph hands them to layers/match_head.py (one fused forward, the backward recomputing the logits).  Outside
 training `logits` and `probs` are composed of torch ops.  Item rows beyond the batch come from
-`negative_sampler_in_memory` alone (input/neg_sampler.py: N rows drawn on the device inside the step, the item group then
-has B + N rows and every head function here takes M = B + N columns); the graphlearn samplers and hard negatives are
-refused at build time.  predict() does not sample (the reference's PREDICT mode): the item tower sees the batch's B rows.
+`negative_sampler_in_memory` and `negative_sampler` (input/neg_sampler.py: N rows drawn on the device inside the step -
+uniform without replacement, or weighted with replacement - the item group then has B + N rows and every head function
+here takes M = B + N columns); the per-user and hard-negative graphlearn samplers are refused at build time.  predict() does not sample (the reference's PREDICT mode): the item tower sees the batch's B rows.
 """
 import logging
 
@@ -27,7 +27,7 @@ from easyrec_amd.model.easy_rec_model import EasyRecModel
 from easyrec_amd.protos.loss_pb2 import LossType
 from easyrec_amd.protos.simi_pb2 import Similarity
 
-_REFUSED_SAMPLERS = ('negative_sampler', 'negative_sampler_v2', 'hard_negative_sampler', 'hard_negative_sampler_v2')
+_REFUSED_SAMPLERS = ('negative_sampler_v2', 'hard_negative_sampler', 'hard_negative_sampler_v2')
 
 
 class MatchModel(EasyRecModel):
@@ -70,8 +70,9 @@ class MatchModel(EasyRecModel):
 
   @staticmethod
   def check_data_config(data_config):
-    """The estimator's build-time hook: negative_sampler_in_memory is built (input/neg_sampler.py); the other four
-    delegate their draw to graphlearn (weighted, per-user, hard negatives), which nothing here restates."""
+    """The estimator's build-time hook: negative_sampler_in_memory and negative_sampler are built
+    (input/neg_sampler.py); the other three draw per user or hard negatives along graphlearn edges, which nothing
+    here restates."""
     sampler = data_config.WhichOneof('sampler')
     if sampler in _REFUSED_SAMPLERS:
       raise NotImplementedError('data_config.%s: negative sampling is not supported (the item tower sees the '

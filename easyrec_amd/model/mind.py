@@ -10,10 +10,11 @@ COSINE both are L2-normalised (no temperature).  The label-aware attention weigh
 the positive item (simi_pow; >= 100: the most similar one only) into `user_tower_emb`; from there on the head, the
 losses and the recall metrics are MatchModel's.  `reg_interest_simi` joins the losses when max_interests_simi < 1.
 
-With `negative_sampler_in_memory` (input/neg_sampler.py) the `item` group has B + N rows: item_dnn's BatchNorm covers them
-all, the label-aware attention reads the batch's own B, the head and the recall metrics take all B + N columns.
+With `negative_sampler_in_memory` or `negative_sampler` (input/neg_sampler.py) the `item` group has B + N rows: item_dnn's
+BatchNorm covers them all, the label-aware attention reads the batch's own B, the head and the recall metrics take all
+B + N columns.
 
-Not built: the graphlearn samplers and hard negatives (refused at build time by MatchModel, `hard_neg_acc` with them),
+Not built: the per-user and hard-negative samplers (refused at build time by MatchModel, `hard_neg_acc` with them),
 bf16 dense and the embedding-parallel engine (MatchModel.check_supported)."""
 import logging
 

@@ -943,6 +943,50 @@ int er_neg_sample(const int64_t* table_ids, int64_t n, const int64_t* batch_ids,
                   int32_t ncols, int32_t* sel, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K1c negative_sampler on the device: N rows of the item table drawn in proportion to a per-item
+ *     weight, WITH replacement, none of them an item of the batch.  Replaces the graphlearn call of
+ *     NegativeSampler core/sampler.py:261-318 (g.negative_sampler('item', expand_factor,
+ *     strategy='node_weight'), ids padded to batch_size, the result flattened and cut to num_sample)
+ *     and the tf.concat of input/input.py:823-845.  graphlearn's source is not part of the
+ *     reference: the semantics are its documentation's (docs/source/models/dssm_neg_sampler.md:
+ *     weighted random, the mini-batch's item ids excluded) and the draw below is this project's.
+ *     The two agree in distribution only, as for K1b.
+ * The item table, batch_ids, the columns, sel, s = *step + step_offset: as in K1b.
+ * alias_tab [n] uint64, built on the host from the weights (Vose's alias method): one 8-byte record
+ *   per row, low 32 bits = the fp32 bits of prob[k] in [0, 1], high 32 bits = alias[k] in [0, n) (an
+ *   alias outside [0, n) is read as k: a malformed table never indexes outside the table).  It
+ *   implies p_i = (prob_i + sum over k with alias_k = i of (1 - prob_k)) / n.
+ * Draw j of N (j = 0 .. N - 1), attempt a = 0, 1, .., 31, with mix64 as in K1b and
+ *   GOLDEN = 0xD1B54A32D192ED03:
+ *     base = mix64(seed ^ mix64(s));
+ *     r0 = mix64(base ^ mix64((uint64(j) << 32) | a));  r1 = mix64(r0 + GOLDEN) mod 2^64;
+ *     k = floor(r0 * n / 2^64) (the high 64 bits of the 128-bit product);
+ *     f = float(r1 >> 40) * 2^-24 (24 bits: exact in fp32, in [0, 1));
+ *     row = f < prob[k] ? k : alias[k].
+ *   The row is accepted if table_ids[row] is none of the B batch ids; otherwise the next attempt.
+ *   After 32 rejected attempts: from the last candidate, row = (row + 1) mod n, at most B + 1 times,
+ *   until table_ids[row] is no batch id.  Table ids are unique and n >= B + N, so that walk ends on
+ *   an eligible row (a table that breaks the rule keeps the row the walk stops at).  The walk IGNORES
+ *   the weights; a draw takes it with probability q^32, q = the weight mass of the batch's items.
+ *   No loop in the kernel is unbounded.
+ *   sel [N] int32: sel[j] = the accepted row; the same row may be drawn for several j.  The result is
+ *   a pure function of (seed, s, alias_tab, table_ids, the SET of batch ids): not of the launch
+ *   shape, the thread order or how membership is tested; two runs and a graph replay give the same bits.
+ * Columns: out_c [B + N]: [0, B) = batch_c, out_c[B + j] = table_c[sel[j]], ncols <= 32, as in K1b.
+ * Envelope: 1 <= B <= 4096, 1 <= N, B + N <= n < 2^31.  One launch: ceil(N / 256) workgroups draw,
+ *   one lane per draw, each with its own copy of the batch-id set in LDS, a lane gathering the
+ *   columns of the row it drew; ceil(B / 256) more copy the batch's own values meanwhile.
+ *   er_neg_sample_weighted_lds_bytes(B) = 8 * cap + 16 with cap as in K1b; 0 outside the envelope,
+ *   where (and on a CPU backend) easyrec_amd/input/neg_sampler.py composes the same draw.
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_neg_sample_weighted_lds_bytes(int32_t B);
+int er_neg_sample_weighted(const uint64_t* alias_tab, const int64_t* table_ids, int64_t n, const int64_t* batch_ids,
+                           int32_t B, int32_t N, const int64_t* step, int64_t step_offset, uint64_t seed,
+                           const void* const* table_cols_host, const void* const* batch_cols_host,
+                           void* const* out_cols_host, const int32_t* elem_bytes_host, int32_t ncols, int32_t* sel,
+                           er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K9k Full-corpus hit rate: exact top-K item search and the hit count.  Replaces g.search (graphlearn's
  *     KNN index, a faiss flat index) and batch_hitrate of utils/hit_rate_utils.py:37-94, :148-220 as
  *     tools/hit_rate_ds.py drives them.  ("K9" alone is the MLP section below.)  fp32.

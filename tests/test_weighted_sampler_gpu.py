@@ -1,0 +1,286 @@
+"""negative_sampler on the GPU: er_neg_sample_weighted (csrc/er_sampler.hip) against the restatement
+(tests/_weighted_sampler_ref.py, written from include/easyrec_hip.h K1c) bit for bit - sel and every extended column -
+at the shapes of tests/test_weighted_sampler_pins.py; column counts around the group of eight, the refused 33rd column,
+the id that doubles as the LDS set's empty mark, duplicate batch ids; two runs and a captured launch replayed over two
+steps; the distribution of 500 device steps; DSSM's and MIND's first steps with weighted negatives against the fp64
+oracle fed the restatement's rows; the recall metrics and the hit rate's id field."""
+import numpy as np
+import pytest
+import torch
+
+import _oracle_steps
+import _weighted_sampler_ref as ref
+import test_match_pins
+import test_mind_pins
+import test_neg_sampler_pins as pins
+import test_weighted_sampler_pins as wpins
+from oracle import match_ref as mref
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+SEED = wpins.SEED
+
+
+# ---------------------------------------------------------------------------------------- the kernel through the sampler
+@pytest.mark.parametrize('B,N,n', wpins.CASES)
+def test_kernel_equals_the_restatement(built_lib, B, N, n):
+  sampler, features, cols = wpins.sampler_on(DEV, B, N, n)
+  assert sampler.weighted and sampler.uses_kernel()
+  batch = pins.load_batch(features, wpins.case_inputs(B, N, n)[2].copy())
+  counter = torch.zeros(1, dtype=torch.int64, device=DEV)
+  for step in wpins.STEPS:
+    counter.fill_(step + 1)
+    sampler.run(counter, -1)
+    torch.cuda.synchronize()
+    wpins.assert_draw_is_the_restatement(sampler, features, cols, batch, wpins.expected(B, N, n, step))
+
+
+def test_switch_selects_the_composition(built_lib, monkeypatch):
+  from easyrec_amd.input import neg_sampler
+  B, N, n = 67, 130, 300
+  sampler, features, cols = wpins.sampler_on(DEV, B, N, n)
+  monkeypatch.setattr(neg_sampler, 'device_sampler', False)
+  assert not sampler.uses_kernel()
+  batch = pins.load_batch(features, wpins.case_inputs(B, N, n)[2].copy())
+  sampler.run(torch.ones(1, dtype=torch.int64, device=DEV), -1)
+  wpins.assert_draw_is_the_restatement(sampler, features, cols, batch, wpins.expected(B, N, n, 0))
+
+
+# ---------------------------------------------------------------------------------------- the kernel, called directly
+def launch(tab, table_ids, batch_ids, N, step, columns=(), seed=SEED, counter=None):
+  """er_neg_sample_weighted on host arrays -> (sel, [extended column per (table column, batch column)]) as numpy"""
+  from easyrec_amd import kernels
+  dev = lambda a: torch.from_numpy(np.array(a)).to(DEV)  # (a copy: the shared inputs are read-only)
+  B = len(batch_ids)
+  triples = [(dev(t), dev(b), torch.zeros(B + N, dtype=dev(t).dtype, device=DEV)) for t, b in columns]
+  sel = torch.full((N,), -1, dtype=torch.int32, device=DEV)
+  counter = torch.full((1,), step, dtype=torch.int64, device=DEV) if counter is None else counter
+  kernels.hip().neg_sample_weighted(dev(np.asarray(tab).view(np.int64)), dev(table_ids), dev(batch_ids), N, counter, 0, seed,
+                                    triples, sel)
+  torch.cuda.synchronize()
+  return sel.cpu().numpy(), [out.cpu().numpy() for _, _, out in triples]
+
+
+def mixed_columns(n, B, count):
+  """`count` (table column, batch column) pairs, int64 and fp32 alternating"""
+  rng = np.random.default_rng(count)
+  cols = []
+  for c in range(count):
+    if c % 2 == 0:
+      cols.append((rng.integers(-2 ** 62, 2 ** 62, size=n), rng.integers(-2 ** 62, 2 ** 62, size=B)))
+    else:
+      cols.append((rng.random(n).astype(np.float32), rng.random(B).astype(np.float32)))
+  return cols
+
+
+@pytest.mark.parametrize('ncols', [0, 9, 32])
+def test_column_counts(built_lib, ncols):
+  """no column at all; nine mixed int64 / fp32 columns (a second group of eight, partly filled); the most there can be"""
+  B, N, n = 67, 130, 300
+  w, ids, batch = wpins.case_inputs(B, N, n)
+  cols = mixed_columns(n, B, ncols)
+  sel, outs = launch(wpins.alias_of(B, N, n), ids, batch, N, 1, cols)
+  want = wpins.expected(B, N, n, 1)
+  assert np.array_equal(sel, want.astype(np.int32)) and len(outs) == ncols
+  for (tab, bat), out in zip(cols, outs):
+    assert out.dtype == tab.dtype and np.array_equal(out.view(np.uint8), ref.extended(bat, tab, want).view(np.uint8))
+
+
+def test_a_33rd_column_is_refused(built_lib):
+  B, N, n = 67, 130, 300
+  w, ids, batch = wpins.case_inputs(B, N, n)
+  with pytest.raises(RuntimeError, match='er_neg_sample_weighted failed .*33 columns'):
+    launch(wpins.alias_of(B, N, n), ids, batch, N, 1, mixed_columns(n, B, 33))
+
+
+def test_an_id_that_equals_the_empty_mark(built_lib):
+  """INT64_MIN marks an empty slot of the LDS set: the table row with that id - here the heaviest - is excluded exactly
+  when the batch holds it"""
+  from easyrec_amd.input import neg_sampler
+  B, N, n = 67, 130, 300
+  w, ids, batch = (a.copy() for a in wpins.case_inputs(B, N, n))
+  lowest = np.iinfo(np.int64).min
+  heavy = int(np.argmax(w))
+  ids[heavy] = lowest
+  tab = wpins.alias_of(B, N, n)
+  drawn = []
+  for member in (True, False):
+    batch[0] = lowest if member else 10 ** 6 + 5  # (batch[0] held the heavy row's former id)
+    batch[-1] = batch[0]
+    sel, _ = launch(tab, ids, batch, N, 2)
+    assert np.array_equal(sel, ref.draw(SEED, 2, tab, ids, batch, N).astype(np.int32))
+    assert np.array_equal(sel, neg_sampler.draw_weighted(SEED, 2, tab, ids, batch, N).astype(np.int32))
+    drawn.append(heavy in sel.tolist())
+  assert drawn == [False, True]
+
+
+def test_duplicate_batch_ids(built_lib):
+  """a batch that repeats three ids: the set holds three members, whatever the order and the count of each"""
+  B, N, n = 67, 130, 300
+  w, ids, _ = wpins.case_inputs(B, N, n)
+  heavy = np.argsort(w)[-3:]
+  batch = np.resize(ids[heavy], B)
+  tab = wpins.alias_of(B, N, n)
+  sel, _ = launch(tab, ids, batch, N, 3)
+  assert np.array_equal(sel, ref.draw(SEED, 3, tab, ids, batch, N).astype(np.int32))
+  assert not set(sel.tolist()) & set(heavy.tolist())
+  again, _ = launch(tab, ids, np.random.default_rng(1).permutation(batch), N, 3)
+  assert np.array_equal(again, sel)
+
+
+# ---------------------------------------------------------------------------------------- determinism and capture
+def test_two_runs_are_bit_identical(built_lib):
+  B, N, n = 4096, 64, 4200
+  sampler, features, cols = wpins.sampler_on(DEV, B, N, n)
+  pins.load_batch(features, wpins.case_inputs(B, N, n)[2].copy())
+  counter = torch.full((1,), 8, dtype=torch.int64, device=DEV)
+  outs = []
+  for _ in range(2):
+    sampler.run(counter, -1)
+    outs.append([sampler.sel.clone()] + [buf.clone() for _, _, _, buf in sampler.columns])
+    sampler.sel.fill_(-1)
+    for _, _, _, buf in sampler.columns:
+      buf.zero_()
+  torch.cuda.synchronize()
+  assert all(torch.equal(a, b) for a, b in zip(*outs)) and int(outs[0][0].min()) >= 0
+
+
+def test_a_replayed_graph_draws_the_next_step(built_lib):
+  """The step is read on the device: one captured launch replayed at steps s and s + 1 gives the restatement's draws of
+  both (a step number baked in at capture would give the same rows twice)."""
+  B, N, n = 1024, 1030, 5000
+  sampler, features, cols = wpins.sampler_on(DEV, B, N, n)
+  batch = pins.load_batch(features, wpins.case_inputs(B, N, n)[2].copy())
+  counter = torch.full((1,), -1, dtype=torch.int64, device=DEV)
+
+  def step_fn():
+    counter.add_(1)  # (the prologue's part)
+    sampler.run(counter, 0)
+  s = torch.cuda.Stream()
+  s.wait_stream(torch.cuda.current_stream())
+  with torch.cuda.stream(s):
+    step_fn()  # step 0, eager: the kernel's first launch is not a captured one
+  torch.cuda.current_stream().wait_stream(s)
+  torch.cuda.synchronize()
+  wpins.assert_draw_is_the_restatement(sampler, features, cols, batch, wpins.expected(B, N, n, 0))
+  counter.fill_(-1)
+  graph = torch.cuda.CUDAGraph()
+  with torch.cuda.graph(graph):
+    step_fn()
+  for step in (0, 1):
+    graph.replay()
+    torch.cuda.synchronize()
+    assert int(counter.item()) == step
+    wpins.assert_draw_is_the_restatement(sampler, features, cols, batch, wpins.expected(B, N, n, step))
+  assert not np.array_equal(wpins.expected(B, N, n, 0), wpins.expected(B, N, n, 1))
+
+
+def test_the_device_s_counts_are_the_restatement_s(built_lib):
+  """the chi-square inputs of tests/test_weighted_sampler_pins.py over steps 0..499 on the device: the same row counts as
+  the restatement, exactly - so the same chi-square, under the same bar, and no draw on a zero-weight or batch row"""
+  from easyrec_amd import kernels
+  from easyrec_amd.input import neg_sampler
+  steps, N = 500, 40
+  w, ids, batch, rows = wpins.chi_inputs()
+  tab = neg_sampler.alias_table(w)
+  dev = lambda a: torch.from_numpy(np.array(a)).to(DEV)  # (a copy: the shared inputs are read-only)
+  d_tab, d_ids, d_batch = dev(tab.view(np.int64)), dev(ids), dev(batch)
+  sels = torch.zeros(steps, N, dtype=torch.int32, device=DEV)
+  counter = torch.zeros(1, dtype=torch.int64, device=DEV)
+  for step in range(steps):
+    kernels.hip().neg_sample_weighted(d_tab, d_ids, d_batch, N, counter, 0, 12345, [], sels[step])
+    counter.add_(1)
+  torch.cuda.synchronize()
+  got = np.bincount(sels.cpu().numpy().reshape(-1), minlength=w.size).astype(np.float64)
+  chi, df, outside, want = wpins.chi_square(ref.draw, steps, N)
+  assert np.array_equal(got, want)
+  print('device: chi-square %.1f (df %d, bar %.1f)' % (chi, df, wpins.CHI_BAR))
+  assert df == 54 and outside == 0 and chi <= wpins.CHI_BAR and got[rows].sum() == 0 and got[5] == 0
+
+
+# ---------------------------------------------------------------------------------------- the models
+B, N, ROWS = 67, 40, 300
+
+
+def _first_steps(model, coverage, monkeypatch, after_step=None):
+  """first_steps of a config with the weighted sampler (seed 5) against the fp64 oracle fed the restatement's rows; after
+  each of the product's steps: the item group had B + N rows and the extended id columns are the restatement's"""
+  from easyrec_amd.input import neg_sampler
+  cfg = wpins.wnegsam_cfg(B, N, ROWS, model=model)
+  table = wpins.weighted_item_table_for(cfg, ROWS)
+  tab = neg_sampler.alias_table(table.weights)
+  wpins.use_weighted_oracle(monkeypatch)
+
+  def check(est, orc, step, batch):
+    assert est.sampler.weighted and est.sampler.uses_kernel()
+    pd = est.model._prediction_dict
+    assert pd['item_tower_emb'].shape[0] == B + N and pd['user_tower_emb'].shape[0] == B
+    _check_the_draw(cfg, table, tab, est, batch, step)
+    if after_step is not None:
+      after_step(est, orc, step, batch)
+  est = _oracle_steps.first_steps(cfg, B, seed=5, oracle_dtype=torch.float64, coverage=coverage,
+                                  est_kw=dict(item_table=table), oracle_kw=dict(item_table=table, sampler_seed=5),
+                                  after_step=check)
+  return cfg, table, tab, est
+
+
+def _check_the_draw(cfg, table, tab, est, batch, step):
+  sch = est.schema
+  batch_ids = batch['hash_ids'][sch.hash_single['adgroup_id']['col']]
+  sel = ref.draw(5, step, tab, table.ids, batch_ids, N)
+  assert np.array_equal(est.sampler.sel.cpu().numpy(), sel.astype(np.int32))
+  assert (table.weights[sel] > 0).all() and not set(table.ids[sel].tolist()) & set(np.asarray(batch_ids).tolist())
+  for name in cfg.data_config.negative_sampler.attr_fields:
+    own = batch['hash_ids'][sch.hash_single[name]['col']] if name in sch.hash_single else \
+        batch['int_ids'][sch.int_single[name]['col']]
+    assert np.array_equal(est.features.ids_of(name).cpu().numpy(), ref.extended(own, table.columns[name]['ids'], sel)), name
+
+
+def test_dssm_first_steps_with_weighted_negatives(built_lib, monkeypatch):
+  """tests/test_match_gpu.py test_model_first_steps with the weighted sampler: B = 67, N = 40, a 300-row table, two steps;
+  then the evaluation mode's metrics over the B + N columns."""
+  from easyrec_amd.input.synthetic import SyntheticBatches
+  cfg, table, tab, est = _first_steps('dssm', test_match_pins.dssm_coverage, monkeypatch)
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
+  est.model._is_training = est.ctx.is_training = False
+  pred = est.predict(gen.next_batch(), sample_negatives=True)
+  assert pred['item_tower_emb'].shape == (B + N, 32) and pred['logits'].shape == (B, B + N)
+  metrics = est.model.build_metric_graph(cfg.eval_config)
+  u, i = pred['user_tower_emb'].double().cpu(), pred['item_tower_emb'].double().cpu()
+  st = est.state_dict()
+  z = mref.logits(u, i, 1.0, torch.from_numpy(st['sim_w']).double(), torch.from_numpy(st['sim_b']).double(),
+                  est.features.ids_of('adgroup_id').cpu())
+  assert set(metrics) == {'recall@10', 'recall_neg_sam@10', 'recall_in_batch@10'}
+  assert metrics == pytest.approx(mref.recall_at_k(z.numpy(), 10), abs=1e-12)
+
+
+def test_mind_first_steps_with_weighted_negatives(built_lib, monkeypatch):
+  """tests/test_mind_gpu.py test_model_first_steps (list-wise) with the weighted sampler, then the step as a hipGraph: each
+  replay draws the next step's negatives."""
+  from easyrec_amd.input.synthetic import SyntheticBatches
+  from easyrec_amd.layers import capsule_layer
+  monkeypatch.setattr(capsule_layer, 'fused_capsule', True)
+  cfg, table, tab, est = _first_steps('mind', test_mind_pins.mind_coverage, monkeypatch,
+                                      test_mind_pins.hand_over_routing_logits())
+  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
+  est.capture()  # (warms up over three steps: 2, 3, 4; the replays are steps 5 and 6)
+  for step in (5, 6):
+    batch = gen.next_batch()
+    est.train_step(batch)
+    torch.cuda.synchronize()
+    assert est.graph is not None and est.global_step == step + 1
+    _check_the_draw(cfg, table, tab, est, batch, step)
+
+
+def test_hit_rate_finds_the_id_field_in_the_sampler_s_message(built_lib):
+  """a model config without item_id: hit_rate's item ids are those of negative_sampler.item_id_field"""
+  import test_hit_rate_gpu as hr
+  from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator
+  cfg = wpins.wnegsam_cfg(hr.B, 8, ROWS)
+  cfg.model_config.dssm.ClearField('item_id')
+  est = EasyRecEstimator(cfg, device=DEV, batch_size=hr.B, seed=4, item_table=wpins.weighted_item_table_for(cfg, ROWS)).build()
+  assert est.model._item_id_name is None
+  items, users, col = hr._batches(est, 45)
+  gt = [[[int(v)] for v in np.asarray(items[k]['hash_ids'])[col]] for k in range(hr.USER_BATCHES)]
+  got = est.hit_rate(items, users, gt, hr.TOP_K)
+  assert got == est.hit_rate(items, users, gt, hr.TOP_K, id_field='adgroup_id') and got['gt_count'] == hr.B * hr.USER_BATCHES

@@ -33,6 +33,13 @@ def main():
           fc.hash_bucket_size = 2000
         if fc.num_buckets > 2000:
           fc.num_buckets = 2000
+      # a sampler's item table that is not on this disk: a small generated one stands in (as many rows as the shrunk
+      # tables have buckets; the configs' num_sample is 1024)
+      kind = cfg.data_config.WhichOneof('sampler')
+      if kind in ('negative_sampler', 'negative_sampler_in_memory'):
+        sc = getattr(cfg.data_config, kind)
+        if sc.input_path and not os.path.exists(sc.input_path):
+          sc.input_path = 'synthetic://2000'
       est = EasyRecEstimator(cfg, device='cpu', batch_size=8, seed=1).build()
       gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=8, seed=2)
       est.train_step(gen.next_batch())

@@ -548,11 +548,11 @@ def mind_taobao(list_wise=False, **kw):
          'loss_type: SOFTMAX_CROSS_ENTROPY' if list_wise else ''))
 
 
-def with_negative_sampler(cfg, rows, num_sample=1024, input_path=None):
+def with_negative_sampler(cfg, rows, num_sample=1024, input_path=None, weighted=False):
   """`cfg` (a list-wise two-tower config over the Taobao item fields) plus negative_sampler_in_memory: num_sample rows of
   an item table of `rows` items per step, excluded by adgroup_id; the table is generated (synthetic://<rows>) unless a
-  file is named."""
-  ns = cfg.data_config.negative_sampler_in_memory
+  file is named.  weighted: negative_sampler instead, the draw in proportion to the table's weights, with replacement."""
+  ns = cfg.data_config.negative_sampler if weighted else cfg.data_config.negative_sampler_in_memory
   ns.input_path = input_path or 'synthetic://%d' % rows
   ns.num_sample = num_sample
   ns.attr_fields.extend(TAOBAO_ITEM)
@@ -1098,6 +1098,9 @@ if __name__ == '__main__':
   for make, name in ((dssm_taobao(in_batch=True, item_rows=10000000), 'dssm'), (mind_taobao(list_wise=True, item_rows=10000000), 'mind')):
     make.model_dir = 'experiments/%s_negsam_taobao_ckpt' % name
     write(with_negative_sampler(make, 10000000), '%s_negsam_taobao_10m.config' % name)
+  for make, name in ((dssm_taobao(in_batch=True, item_rows=10000000), 'dssm'), (mind_taobao(list_wise=True, item_rows=10000000), 'mind')):
+    make.model_dir = 'experiments/%s_wnegsam_taobao_ckpt' % name
+    write(with_negative_sampler(make, 10000000, weighted=True), '%s_wnegsam_taobao_10m.config' % name)
   write(mmoe_taobao(n_tasks=4, embedding_dim=64, batch_size=8192), 'mmoe_taobao_4task_d64.config')
   # BASELINE config 5 at full size (200 M embedding rows of 64 floats: 51 GB + Adam slots, row-sharded over 8 GPUs) and
   # the share one GPU owns of it (25 M rows) for single-GPU runs
