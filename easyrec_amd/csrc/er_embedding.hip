@@ -3535,6 +3535,8 @@ int er_emb_group_destroy(er_emb_group* g) {
 
 int64_t er_emb_group_num_entries(const er_emb_group* g) { return g ? g->n_entries : -1; }
 
+int32_t er_emb_group_tile_entries(const er_emb_group* g) { return g ? g->tile_entries : -1; }
+
 static int fill_u32(uint32_t* p, uint32_t value, int64_t n, hipStream_t s) {
   if (n <= 0) return 0;
   int64_t blocks = er::ceil_div(n, er::kBlock);

@@ -683,6 +683,10 @@ class HipBackend(object):
     if ld != group['dim'] or ls_ld != 1:
       self.ck.er_emb_group_set_row_pitch(group['handle'], ld, ls_ld)
 
+  def emb_group_tile_entries(self, group):
+    """Entries of the key-sorted list per workgroup of the backward (runs that cross a multiple of it take the fix launch)."""
+    return int(self.lib.er_emb_group_tile_entries(group['handle']))
+
   def emb_group_destroy(self, group):
     self.lib.er_emb_group_destroy(group['handle'])
 

@@ -222,6 +222,9 @@ int er_emb_group_update(er_emb_group* group, const er_lookup_desc* descs_host, i
 int er_emb_group_destroy(er_emb_group* group);
 /* total entries (sort length) of the group */
 int64_t er_emb_group_num_entries(const er_emb_group* group);
+/* entries of the key-sorted list one workgroup of the backward reduces (a tile): read-only, fixed by the group's dim;
+ * runs of equal keys that cross a multiple of it are combined by a second launch.  -1 for a null group. */
+int32_t er_emb_group_tile_entries(const er_emb_group* group);
 /* backward + update.  opt_kind: ER_OPT_*; hyper: device pointer. */
 int er_emb_bwd_update(er_emb_group* group, int opt_kind, const er_opt_hyper* hyper,
                       er_stream_t stream);
