@@ -22,8 +22,14 @@ to /root/reference/easy_rec/python) and TF's documented op semantics (SURVEY.md 
   MIND           model/mind.py:50-299, layers/capsule_layer.py:60-176 (oracle/mind_ref.py); the `hist` sequences
                  layers/input_layer.py:164-200, :268-278.  The initial routing logits are an INPUT
                  (OracleTrainer.routing_logits): capsule_layer.py:83-85 draws them from TensorFlow's generator
+  Uniter         model/uniter.py:38-46, layers/uniter.py (oracle/uniter_ref.py); under DBMTL as bottom_uniter, model/dbmtl.py:35-53
+  CMBF           model/cmbf.py:39-47, layers/cmbf.py (oracle/cmbf_ref.py)
+  sequence_combiner  layers/input_layer.py:309-347: a group's SequenceFeature columns combined over time after the plain
+                 ones, by `attention` or `text_cnn`; the backbone's TextCNN block (oracle/seq_combiner_ref.py)
   negative_sampler_in_memory  the draw of include/easyrec_hip.h K1b (oracle/neg_sampler_ref.py; the reference's
                  core/sampler.py:321-473 draws with np.random.choice (:431): parity in distribution only)
+  negative_sampler  the weighted draw of include/easyrec_hip.h K1c (oracle/weighted_sampler_ref.py) over an alias table
+                 the caller hands in (OracleTrainer(alias_tab=): oracle/ has no builder of its own)
   loss           model/rank_model.py:105-111,213-332, builders/loss_builder.py:35-39
   regularisation model/easy_rec_estimator.py:166-184, compat/regularizers.py:76-108
   optimizer      builders/optimizer_builder.py:61-66 (tf.train.AdamOptimizer, dense-decay sparse
@@ -57,7 +63,8 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from oracle import autoint_ref, bst_ref, fibinet_ref, hashing, match_ref, mind_ref, neg_sampler_ref
+from oracle import (autoint_ref, bst_ref, cmbf_ref, fibinet_ref, hashing, match_ref, mind_ref, neg_sampler_ref,
+                    seq_combiner_ref, uniter_ref, weighted_sampler_ref)
 
 F32 = np.float32
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
@@ -147,9 +154,12 @@ class _ByName(object):
 
 class OracleTrainer(object):
 
-  def __init__(self, cfg, state, batch_size, dtype=torch.float32, compact_ids=None, item_table=None, sampler_seed=None):
-    """item_table, sampler_seed: what data_config.negative_sampler_in_memory draws from - anything with `.ids` and
-    `.columns[name]['ids' | 'raw']` as numpy arrays, and the seed of the draw (oracle/neg_sampler_ref.py).
+  def __init__(self, cfg, state, batch_size, dtype=torch.float32, compact_ids=None, item_table=None, sampler_seed=None,
+               alias_tab=None):
+    """item_table, sampler_seed: what data_config.negative_sampler_in_memory / negative_sampler draw from - anything with
+    `.ids` and `.columns[name]['ids' | 'raw']` as numpy arrays, and the seed of the draw (oracle/neg_sampler_ref.py).
+    alias_tab: negative_sampler's alias table of the item table's weights, uint64 records as include/easyrec_hip.h K1c
+    lays them out (oracle/weighted_sampler_ref.py reads it; the caller builds it).
     compact_ids: {embedding table name: ascending int64 ids}: `state[name]` (and the slots handed to resume()) hold
     ONLY those rows - every id the batches of this trainer's life will look up must be among them.  Rows that no lookup
     reads cannot influence a loss, and TF-Adam's every-row decay acts on each row independently, so the losses and the
@@ -199,7 +209,7 @@ class OracleTrainer(object):
         if oc[0].HasField('embedding_learning_rate_multiplier') else 1.0
     self.model_class = cfg.model_config.model_class
     self.last_bst = []  # MultiTowerBST: the BST towers' block outputs of the last forward pass
-    self.item_table, self.sampler_seed = item_table, sampler_seed
+    self.item_table, self.sampler_seed, self.alias_tab = item_table, sampler_seed, alias_tab
     # MIND: the initial routing logits [B, max_seq_len, max_k] of the NEXT training step.  The reference draws them from
     # TensorFlow's generator and the product from the device's (parity in distribution only, layers/capsule_layer.py), so
     # the caller sets what the product drew; forward() consumes them
@@ -471,6 +481,13 @@ class OracleTrainer(object):
       names.extend(['%s%d' % (m.group(1), t) for t in range(int(m.group(2)), int(m.group(3)) + 1)] if m else [n])
     if only is not None:
       names = [n for n in names if n in only]
+    # SequenceFeature columns with a sequence_combiner are combined after the plain ones (below), in the order of their
+    # column names `<name>_embedding`: the names'
+    seq_names = sorted(n for n in names if only is None and self.fc_by_name[n].feature_type == self.fc_by_name[n].SequenceFeature
+                       and self.fc_by_name[n].sequence_combiner.WhichOneof('combiner') in ('attention', 'text_cnn'))
+    names = [n for n in names if n not in seq_names]
+    if seq_names and len(group.sequence_features) > 0:
+      raise NotImplementedError('oracle: sequence_combiner columns beside sequence_features in group %s' % group_name)
     hashed, raws, ints = self._cache
     outs = []
     lam = self.cfg.model_config.embedding_regularization
@@ -523,6 +540,19 @@ class OracleTrainer(object):
         if is_emb:
           self._reg = self._reg + lam * 0.5 * (e * e).sum()  # scale * tf.nn.l2_loss(out_f)
     feats = [e for e, _ in outs]
+    for n in seq_names:
+      # layers/input_layer.py:309-347: the embedding regulariser on the raw [B, L, D] embedding, then `attention` (its
+      # kernel under the model's kernel regulariser) or TextCNN
+      fc = self.fc_by_name[n]
+      var_scope = '%s/%s_embedding' % (scope, n)
+      e, lens = self._seq_lookup(V, var_scope + '/embedding_weights', batch, n)
+      if lam > 0:
+        self._reg = self._reg + lam * 0.5 * (e * e).sum()
+      if fc.sequence_combiner.WhichOneof('combiner') == 'attention':
+        w = V.get(var_scope + '/attention/kernel', l2=self._l2_of(self.cfg.model_config))
+        feats.append(seq_combiner_ref.seq_attn_pool_ref(e, torch.as_tensor(lens), w))
+      else:
+        feats.append(self._text_cnn(V, e, fc.sequence_combiner.text_cnn, '%s/%s_embedding_text_cnn' % (var_scope, n), None))
     concat = torch.cat(feats, dim=1)
     if only is None and len(group.sequence_features) > 0:
       # target attention over the group's sequence_features (layers/input_layer.py:96-111, sequence_feature_layer.py:
@@ -883,6 +913,66 @@ class OracleTrainer(object):
     out = self.dense(V, x.reshape(B, -1), mc.num_class, 'output', 0.0)
     return {'logits': out.squeeze(1)}
 
+  def _modal_layer(self, V, batch, c, l2, encode):
+    """What layers/uniter.py and layers/cmbf.py share: the groups read in the constructor's order (image, general, text
+    with is_combine=False, other; each combined call takes the next `input_layer[_n]` scope, the sequence tables are
+    `input_layer/<feature>/embedding_weights` with the embedding regulariser), encode(params by name, img [B, n_img *
+    dim] or None, n_img, general [B, n_general, dim] or None, [(text embedding [B, L, dim], lengths)]) -> [B, .], and
+    `other_dnn` (or the raw `other` features) beside it.  Only other_dnn carries the kernel regulariser."""
+    mc = self.cfg.model_config
+    groups = {g.group_name: g for g in mc.feature_groups}
+    if any(getattr(c, f, 0) > 0 for f in ('hidden_dropout_prob', 'attention_probs_dropout_prob', 'text_seq_emb_dropout_prob')):
+      raise NotImplementedError('oracle: the oracle has no random dropout (a dropout probability above 0 in %s)' %
+                                type(c).__name__)
+    scopes = iter(['input_layer'] + ['input_layer_%d' % i for i in range(1, 4)])
+    img = general = None
+    n_img = 0
+    if 'image' in groups:
+      img, _ = self.input_layer(V, batch, 'image', next(scopes))
+      n_img = len(groups['image'].feature_names)
+    if 'general' in groups:
+      fea, _ = self.input_layer(V, batch, 'general', next(scopes))
+      general = fea.reshape(fea.shape[0], len(groups['general'].feature_names), -1)
+    seqs = []
+    if 'text' in groups:
+      lam = mc.embedding_regularization
+      for n in groups['text'].feature_names:
+        e, lens = self._seq_lookup(V, 'input_layer/%s/embedding_weights' % n, batch, n)
+        if lam > 0:
+          self._reg = self._reg + lam * 0.5 * (e * e).sum()
+        seqs.append((e, lens))
+    parts = []
+    if img is not None or general is not None or seqs:
+      parts.append(encode(_ByName(V), img, n_img, general, seqs))
+    if 'other' in groups:
+      other, _ = self.input_layer(V, batch, 'other', next(scopes))
+      if c.HasField('other_feature_dnn'):
+        other = self.dnn(V, other, c.other_feature_dnn, 'other_dnn', l2)
+      parts.append(other)
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+
+  def _uniter_layer(self, V, batch, c, l2):
+    """layers/uniter.py: the [CLS] feature of the encoder (oracle/uniter_ref.py) over the image tokens [B, n, dim]"""
+    return self._modal_layer(V, batch, c, l2, lambda params, img, n_img, general, seqs: uniter_ref.uniter_cls(
+        params, c, None if img is None else img.reshape(img.shape[0], n_img, -1), general, seqs))
+
+  def _uniter(self, V, batch):
+    """model/uniter.py:38-46: the layer -> final_dnn -> dense `output` without a regulariser"""
+    mc = self.cfg.model_config
+    l2 = self._l2_of(mc)
+    x = self.dnn(V, self._uniter_layer(V, batch, mc.uniter.config, l2), mc.uniter.final_dnn, 'final_dnn', l2)
+    return {'logits': self.dense(V, x, mc.num_class, 'output', 0.0).squeeze(1)}
+
+  def _cmbf(self, V, batch):
+    """model/cmbf.py:39-47: both towers, the cross-attention tower and the poolings (oracle/cmbf_ref.py) -> final_dnn ->
+    dense `output` without a regulariser"""
+    mc = self.cfg.model_config
+    c, l2 = mc.cmbf.config, self._l2_of(mc)
+    hidden = self._modal_layer(V, batch, c, l2, lambda params, img, n_img, general, seqs: cmbf_ref.cmbf_towers(
+        params, c, img, n_img, general, seqs)['fused'])
+    x = self.dnn(V, hidden, mc.cmbf.final_dnn, 'final_dnn', l2)
+    return {'logits': self.dense(V, x, mc.num_class, 'output', 0.0).squeeze(1)}
+
   # ------------------------------------------------------------------ two-tower models (MatchModel)
   def _match_inputs(self, batch, head):
     """What the head of model/match_model.py:161-279 reads beside the tower outputs -> (the label, the item ids of
@@ -946,18 +1036,26 @@ class OracleTrainer(object):
                                  dnn=dnn, batch_norm=lambda x, var, name, training=True: self.batch_norm(V, x, name))
 
   def _sampled_negatives(self, batch):
-    """data_config.negative_sampler_in_memory (oracle/neg_sampler_ref.py): at step s the draw of N table rows that hold
-    none of the batch's item ids; every attribute feature's column - ids and raw values alike - becomes the batch's B
-    values followed by the drawn rows'.  The groups of those features then have B + N rows."""
-    ns = self.cfg.data_config.negative_sampler_in_memory
-    if self.item_table is None or self.sampler_seed is None:
-      raise NotImplementedError('oracle: data_config.negative_sampler_in_memory needs the item table and the seed of the '
-                                'draw (OracleTrainer(item_table=, sampler_seed=))')
+    """data_config.negative_sampler_in_memory (oracle/neg_sampler_ref.py) / negative_sampler (the weighted draw with
+    replacement, oracle/weighted_sampler_ref.py): at step s the draw of N table rows that hold none of the batch's item
+    ids; every attribute feature's column - ids and raw values alike - becomes the batch's B values followed by the drawn
+    rows'.  The groups of those features then have B + N rows."""
+    kind = self.cfg.data_config.WhichOneof('sampler')
+    ns = getattr(self.cfg.data_config, kind)
+    weighted = kind == 'negative_sampler'
+    if self.item_table is None or self.sampler_seed is None or (weighted and self.alias_tab is None):
+      raise NotImplementedError('oracle: data_config.%s needs the item table and the seed of the draw, negative_sampler '
+                                'the alias table of the weights too (OracleTrainer(item_table=, sampler_seed=, alias_tab=))'
+                                % kind)
     hashed, raws, ints = self._cache
     feats = {field: [n for n, f in self.fc_by_name.items() if list(f.input_names) == [field]]
              for field in list(ns.attr_fields) + [ns.item_id_field]}
     batch_ids = self._categorical_ids(batch, None, feats[ns.item_id_field][0])
-    sel = neg_sampler_ref.draw(self.sampler_seed, self.global_step, self.item_table.ids, batch_ids, ns.num_sample)
+    if weighted:
+      sel = weighted_sampler_ref.draw(self.sampler_seed, self.global_step, self.alias_tab, self.item_table.ids, batch_ids,
+                                      ns.num_sample)
+    else:
+      sel = neg_sampler_ref.draw(self.sampler_seed, self.global_step, self.item_table.ids, batch_ids, ns.num_sample)
     for name in [n for field in ns.attr_fields for n in feats[field]]:
       for cols, kind in ((hashed, 'ids'), (ints, 'ids'), (raws, 'raw')):
         if name in cols:
@@ -1041,14 +1139,18 @@ class OracleTrainer(object):
     return pred
 
   def _dbmtl(self, V, batch):
-    """model/dbmtl.py:46-116: bottom (dnn) -> optional MMoE block -> tower dnn -> relation dnn over
-    [own features, earlier towers' relation features] -> output."""
+    """model/dbmtl.py:35-116: bottom (the Uniter layer in place of the `all` group, :35-53, or the group through an
+    optional dnn) -> optional MMoE block -> tower dnn -> relation dnn over [own features, earlier towers' relation
+    features] -> output."""
     mc = self.cfg.model_config
     c = mc.dbmtl
     l2 = self._l2_of(mc)
-    x, _ = self.input_layer(V, batch, 'all', 'input_layer')
-    if c.HasField('bottom_dnn'):
-      x = self.dnn(V, x, c.bottom_dnn, 'bottom_dnn', l2)
+    if c.HasField('bottom_uniter'):
+      x = self._uniter_layer(V, batch, c.bottom_uniter, l2)
+    else:
+      x, _ = self.input_layer(V, batch, 'all', 'input_layer')
+      if c.HasField('bottom_dnn'):
+        x = self.dnn(V, x, c.bottom_dnn, 'bottom_dnn', l2)
     if c.HasField('expert_dnn'):
       task_in = self._mmoe_layer(V, x, [c.expert_dnn] * c.num_expert, len(c.task_towers), l2)
     else:
@@ -1196,6 +1298,20 @@ class OracleTrainer(object):
       out.append((stacked * gate[:, :, None]).sum(dim=1))
     return out
 
+  def _text_cnn(self, V, seq, pb, name, l2):
+    """layers/keras/text_cnn.py: a Conv1D per filter size - TF's `conv1d[_n]`, numbered over the graph in call order -
+    max over the windows (oracle/seq_combiner_ref.py), then the optional mlp"""
+    ks, bs = [], []
+    for _ in pb.filter_sizes:
+      cname = 'conv1d' if self._conv_uid == 0 else 'conv1d_%d' % self._conv_uid
+      self._conv_uid += 1
+      ks.append(V.get('%s/%s/kernel' % (name, cname)))
+      bs.append(V.get('%s/%s/bias' % (name, cname)))
+    net = seq_combiner_ref.text_cnn_ref(seq, int(pb.pad_sequence_length), ks, bs, pb.activation)
+    if pb.HasField('mlp'):
+      net = self._keras_mlp(V, net, pb.mlp, name + '/mlp', l2)
+    return net
+
   def _standard_keras(self, V, x, kl, name):
     """tensorflow.keras.layers.Dense / Activation / Dropout named directly in a backbone (st_params = constructor
     keyword arguments, backbone.py:381-397)"""
@@ -1311,6 +1427,8 @@ class OracleTrainer(object):
         if node.WhichOneof('name') == 'feature_group_name' and node.feature_group_name in groups:
           group_out(node.feature_group_name)
     for blk in bb.blocks:
+      if len(blk.layers) > 0:
+        raise NotImplementedError('oracle: a backbone block with a `layers` list (%s)' % blk.name)
       if blk.WhichOneof('layer') == 'input_layer':
         gname = blk.inputs[0].feature_group_name
         if blk.input_layer.output_seq_and_normal_feature:
@@ -1377,6 +1495,9 @@ class OracleTrainer(object):
           x = self._keras_mmoe(V, x, kl.mmoe, blk.name, l2)
         elif kl.class_name in ('Dense', 'Activation', 'Dropout'):
           x = self._standard_keras(V, x, kl, blk.name)
+        elif kl.class_name == 'TextCNN':  # (over a sequence kept over time: the first output of _seq_block)
+          seq = x[0]
+          x = self._text_cnn(V, seq[0] if isinstance(seq, (list, tuple)) else seq, kl.text_cnn, blk.name, l2)
         elif kl.class_name == 'SENet':
           x = self._keras_senet(V, x, kl.senet, blk.name)
         elif kl.class_name == 'FiBiNet':
@@ -1436,8 +1557,9 @@ class OracleTrainer(object):
     self._reg = torch.zeros((), dtype=self.dtype)
     self._moving = {}
     self._touched = {}
+    self._conv_uid = 0  # (TextCNN's `conv1d[_n]` numbering: per graph)
     self._cache = (self._hashed_ids(batch), self._raw_values(batch), self._int_ids(batch))
-    if self.cfg.data_config.WhichOneof('sampler') == 'negative_sampler_in_memory':
+    if self.cfg.data_config.WhichOneof('sampler') in ('negative_sampler_in_memory', 'negative_sampler'):
       self._sampled_negatives(batch)
     labels_np = np.asarray(batch['labels'], dtype=np.float32)
     def ce_of(z, y):
@@ -1495,6 +1617,9 @@ class OracleTrainer(object):
         y = torch.as_tensor(labels_np[label_fields.index(lname)], dtype=self.dtype)
         z = pred['logits_%s' % tower.tower_name]
         pred['probs_%s' % tower.tower_name] = torch.sigmoid(z)
+        if tower.loss_type in (LossType.L2_LOSS, LossType.SIGMOID_L2_LOSS):
+          # a regression tower's output is `y_<tower>` (rank_model.py:123-128, for every multi-task class)
+          pred['y_%s' % tower.tower_name] = pred.pop('logits_%s' % tower.tower_name)
         suffix = '_%s' % tower.tower_name
         if len(tower.losses) == 0:
           # tf.losses.sigmoid_cross_entropy (SUM_BY_NONZERO_WEIGHTS) x task weight (multi_task_model.py:229-240)
@@ -1518,28 +1643,13 @@ class OracleTrainer(object):
       losses.update(task)
       ce = sum(task.values())
     else:
-      if self.model_class == 'DeepFM':
-        pred = self._deepfm(V, batch)
-      elif self.model_class == 'DCN':
-        pred = self._dcn(V, batch)
-      elif self.model_class == 'MultiTowerDIN':
-        pred = self._multi_tower_din(V, batch)
-      elif self.model_class == 'MultiTowerBST':
-        pred = self._multi_tower_bst(V, batch)
-      elif self.model_class == 'AutoInt':
-        pred = self._autoint(V, batch)
-      elif self.model_class == 'RankModel':
-        pred = self._rank_backbone(V, batch)
-      elif self.model_class == 'WideAndDeep':
-        pred = self._wide_and_deep(V, batch)
-      elif self.model_class == 'FM':
-        pred = self._fm(V, batch)
-      elif self.model_class == 'MultiTower':
-        pred = self._multi_tower(V, batch)
-      elif self.model_class == 'DLRM':
-        pred = self._dlrm(V, batch)
-      else:
+      fn = {'DeepFM': self._deepfm, 'DCN': self._dcn, 'MultiTowerDIN': self._multi_tower_din,
+            'MultiTowerBST': self._multi_tower_bst, 'AutoInt': self._autoint, 'Uniter': self._uniter, 'CMBF': self._cmbf,
+            'RankModel': self._rank_backbone, 'WideAndDeep': self._wide_and_deep, 'FM': self._fm,
+            'MultiTower': self._multi_tower, 'DLRM': self._dlrm}.get(self.model_class)
+      if fn is None:
         raise NotImplementedError('oracle: model_class %s' % self.model_class)
+      pred = fn(V, batch)
       labels = torch.as_tensor(labels_np[0], dtype=self.dtype)
       z = pred['logits']
       mc = self.cfg.model_config

@@ -1,8 +1,10 @@
 """Test infrastructure shared by the model tests (-m gpu: tests/test_models_gpu.py, test_bst_gpu.py,
-test_autoint_gpu.py, test_fibinet_gpu.py, test_match_gpu.py, test_mind_gpu.py, test_neg_sampler_gpu.py; on the CPU
-stand-in: test_match_pins.py, test_mind_pins.py, test_neg_sampler_pins.py): a model's first training steps against the
-CPU oracle, the two-runs-and-a-hipGraph-replay bit identity check of a kernel sequence, and the
-max-error-over-max-value comparison."""
+test_autoint_gpu.py, test_fibinet_gpu.py, test_match_gpu.py, test_mind_gpu.py, test_neg_sampler_gpu.py,
+test_uniter_model_gpu.py, test_cmbf_model_gpu.py, test_seq_combiner_gpu.py, test_weighted_sampler_gpu.py; on the CPU
+stand-in: test_match_pins.py, test_mind_pins.py, test_neg_sampler_pins.py, test_uniter_model_pins.py,
+test_cmbf_model_pins.py, test_seq_combiner_pins.py, test_weighted_sampler_pins.py): a model's first training steps
+against the CPU oracle - as figures in units of their bars (step_figures) and held to them (first_steps) - the
+two-runs-and-a-hipGraph-replay bit identity check of a kernel sequence, and the max-error-over-max-value comparison."""
 import numpy as np
 import torch
 
@@ -23,21 +25,24 @@ def close(got, want, tol, what, scale=None):
   assert err <= tol * scale, (what, err, scale)
 
 
-def first_steps(cfg, B, seed, steps=2, step0_tol=1e-5, device='cuda:0', grad_views=True, skip_bn_shadowed_bias=True,
-                coverage=None, oracle_dtype=torch.float32, est_kw=None, oracle_kw=None, after_step=None):
-  """`steps` training steps of the product and of the oracle from the same state on the same synthetic batches: every
-  loss within step0_tol (first step) / 1e-4 (later steps) relative; after the first step the logits (1e-4) and the
-  gradient of every variable, read back as Adam's first moment, within 2e-4 of the tensor's gradient scale.
+def step_figures(cfg, B, seed, steps=2, step0_tol=1e-5, device='cuda:0', grad_views=True, skip_bn_shadowed_bias=True,
+                 oracle_dtype=torch.float32, est_kw=None, oracle_kw=None, after_step=None):
+  """`steps` training steps of the product and of the oracle from the same state on the same synthetic batches
+  -> (the estimator, {comparison: its error in units of its bar - <= 1 holds it}, the names of the compared variables).
+  The comparisons: ('loss', step, name): every loss, the bar step0_tol (first step) / 1e-4 (later steps) of
+  max(1e-3, |expected|); after the first step ('logits', key): the logits, the bar atol 1e-5 + rtol 1e-4 elementwise
+  (np.allclose's inequality divided through), and ('grad', variable): the gradient of every variable, read back as
+  Adam's first moment, the bar 2e-4 of the tensor's gradient scale + 2e-6 of the largest one.
   grad_views: autograd accumulated in place into the flat gradient buffer; skip_bn_shadowed_bias: a dense bias under
-  BatchNorm has a zero gradient (rounding noise) and is not compared; coverage(names, cfg): the caller's own assertions
-  on the list of compared variables.  oracle_dtype: the oracle's forward and backward pass; est_kw / oracle_kw: further
-  constructor arguments (an item table, the sampler's seed); after_step(est, orc, step, batch): called between the
-  product's step and the oracle's (MIND: hands the routing logits the product drew to the oracle).  A list-wise
-  two-tower model never builds its logits while training: the two tower embeddings they are the product of are
-  compared instead."""
+  BatchNorm has a zero gradient (rounding noise) and is not compared.  oracle_dtype: the oracle's forward and backward
+  pass; est_kw / oracle_kw: further constructor arguments (an item table, the sampler's seed); after_step(est, orc,
+  step, batch): called between the product's step and the oracle's (MIND: hands the routing logits the product drew to
+  the oracle).  A list-wise two-tower model never builds its logits while training: the two tower embeddings they are
+  the product of are compared instead.  A regression tower's output is `y_<tower>`."""
   est = EasyRecEstimator(cfg, device=device, batch_size=B, seed=seed, **(est_kw or {})).build()
   orc = OracleTrainer(cfg, est.state_dict(), batch_size=B, dtype=oracle_dtype, **(oracle_kw or {}))
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 100)
+  fig, compared = {}, []
   for step in range(steps):
     b = gen.next_batch()
     est.train_step(b)
@@ -46,22 +51,21 @@ def first_steps(cfg, B, seed, steps=2, step0_tol=1e-5, device='cuda:0', grad_vie
     got, exp = est.loss_values(), orc.train_step(b)
     assert sorted(got) == sorted(exp)
     for k in exp:
-      assert abs(got[k] - exp[k]) <= (step0_tol if step == 0 else 1e-4) * max(1e-3, abs(exp[k])), (step, k, got[k], exp[k])
+      fig['loss', step, k] = abs(got[k] - exp[k]) / ((step0_tol if step == 0 else 1e-4) * max(1e-3, abs(exp[k])))
     if step > 0:
       continue
     got_pred = est.model._prediction_dict
-    keys = [k for k in orc.last_pred if k.startswith('logits')]
+    keys = [k for k in orc.last_pred if k.startswith('logits') or k.startswith('y_')]
     if keys == ['logits'] and 'logits' not in got_pred:  # (a list-wise two-tower model while training)
       keys = ['user_tower_emb', 'item_tower_emb']
     for k in keys:
       got_l, ref = got_pred[k].detach().cpu().numpy(), orc.last_pred[k]
-      assert np.allclose(got_l, ref, rtol=1e-4, atol=1e-5), k
+      fig['logits', k] = float(np.max(np.abs(got_l - ref) / (1e-5 + 1e-4 * np.abs(ref))))
     if grad_views:
       est.varstore.check_grad_views()
     st = est.state_dict(slots=True)
     names = set(orc.state)
     gmax = max(float(np.max(np.abs(v))) for kk, v in orc.slots.items() if kk.endswith('/m'))
-    compared = []
     for k in orc.state:
       key = k + '/m'
       if key not in orc.slots or key not in st:
@@ -69,12 +73,29 @@ def first_steps(cfg, B, seed, steps=2, step0_tol=1e-5, device='cuda:0', grad_vie
       if skip_bn_shadowed_bias and k.endswith('/bias') and (k[:-len('/bias')] + '/bn/gamma') in names:
         continue  # d(loss)/d(bias) == 0 under BatchNorm: rounding noise
       ref = orc.slots[key]
-      d, scale = float(np.max(np.abs(st[key] - ref))), float(np.max(np.abs(ref)))
-      assert d <= 2e-4 * scale + 2e-6 * gmax, (key, d, scale)
+      fig['grad', k] = float(np.max(np.abs(st[key] - ref))) / (2e-4 * float(np.max(np.abs(ref))) + 2e-6 * gmax)
       compared.append(k)
-    assert len(compared) > 5
-    if coverage is not None:
-      coverage(compared, cfg)
+  return est, fig, compared
+
+
+def worst(fig):
+  """step_figures' figures by kind -> {'loss<step>', 'logits', 'grads': the largest}"""
+  out = {}
+  for k, v in fig.items():
+    name = {'loss': 'loss%s' % k[1], 'grad': 'grads'}.get(k[0], k[0])
+    out[name] = v if np.isnan(v) else max(out.get(name, 0.0), v)
+  return out
+
+
+def first_steps(cfg, B, seed, coverage=None, **kw):
+  """step_figures with every figure held to its bar; coverage(names, cfg): the caller's own assertions on the list of
+  compared variables.  -> the estimator"""
+  est, fig, compared = step_figures(cfg, B, seed, **kw)
+  for k, v in fig.items():
+    assert v <= 1.0, (k, v)
+  assert len(compared) > 5
+  if coverage is not None:
+    coverage(compared, cfg)
   return est
 
 

@@ -1,6 +1,6 @@
 """CMBF on the GPU: the cases of the reference's own run (tests/golden/cmbf_vectors.npz) with their gradients, training
-steps at the sample's model section (hidden 32, 33 text tokens, 3 cross layers) against the test-side fp64 oracle
-(tests/_cmbf_oracle.py) at first_steps' bars, steps on the grouped attention launches against steps on the one-unit
+steps at the sample's model section (hidden 32, 33 text tokens, 3 cross layers) against the fp64 oracle
+(oracle/model_oracle.py) at first_steps' bars, steps on the grouped attention launches against steps on the one-unit
 launches bit for bit, the launches a step runs, a step with the sample's sequence dropout, and evaluate()."""
 import logging
 
@@ -13,11 +13,12 @@ pytestmark = pytest.mark.gpu
 from easyrec_amd import kernels  # noqa: E402
 from easyrec_amd.input.synthetic import SyntheticBatches  # noqa: E402
 from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator  # noqa: E402
-from tests import _cmbf_ref as cref  # noqa: E402
+from oracle import cmbf_ref as cref  # noqa: E402
+from tests import _cmbf_cases as ccases  # noqa: E402
 
 logging.disable(logging.WARNING)
 DEV = 'cuda:0'
-GOLD = cref.fixture()
+GOLD = ccases.fixture()
 
 
 @pytest.mark.parametrize('tag', sorted({k.split(':')[0] for k in GOLD.files}))
@@ -25,12 +26,12 @@ def test_fixture_cases_on_the_gpu(tag, monkeypatch):
   """Every case of tests/golden/cmbf_vectors.npz (the reference's own run) through the product on the GPU, on the
   grouped launches: towers, cross outputs, the layer output and the logits against the npz at 1e-5, and (the
   training-mode cases) the gradient of every variable the layer output depends on against the fp64 restatement's at
-  1e-4, with tests/test_cmbf_pins.py's floors (_cmbf_ref.grad_floor; a bias under BatchNorm is skipped)."""
+  1e-4, with tests/test_cmbf_pins.py's floors (cmbf_ref.grad_floor; a bias under BatchNorm is skipped)."""
   from easyrec_amd.core import context
   from tests._oracle_steps import close
   monkeypatch.setenv('EASYREC_AMD_MHA_GROUP_UNITS', '1')
-  cfg, groups, training, inputs, var = cref.fixture_case(GOLD, tag)
-  vs, ctx, run = cref.product_fixture_forward(DEV, cfg, training, inputs, var)
+  cfg, groups, training, inputs, var = ccases.fixture_case(GOLD, tag)
+  vs, ctx, run = ccases.product_fixture_forward(DEV, cfg, training, inputs, var)
   W = GOLD['%s:hidden' % tag].shape[1]
   dy64 = torch.randn(6, W, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
   vs.zero_grad()
@@ -69,45 +70,14 @@ def test_fixture_cases_on_the_gpu(tag, monkeypatch):
 
 # ------------------------------------------------------------------------------------------------ against the fp64 oracle
 def _figures(cfg, B, seed, fused, monkeypatch):
-  """One training step of the product and of the fp64 oracle (tests/_cmbf_oracle.py) from the same state on the same
-  batch, then a second: every comparison of first_steps as a figure in units of ITS bar (<= 1 holds it): the losses
-  (1e-5 first step, 1e-4 second), the logits (rtol 1e-4, atol 1e-5), each variable's first moment (2e-4 of its scale +
-  2e-6 of the largest)."""
-  from tests._cmbf_oracle import CMBFOracle
+  """tests/_oracle_steps.step_figures against the fp64 oracle: every comparison of first_steps in units of ITS bar
+  (<= 1 holds it), the largest of each kind."""
+  from tests._oracle_steps import step_figures, worst
   monkeypatch.setenv('EASYREC_AMD_FUSED_MHA', '1' if fused else '0')
   monkeypatch.setenv('EASYREC_AMD_MHA_GROUP_UNITS', '1')
-  est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=seed).build()
-  orc = CMBFOracle(cfg, est.state_dict(), batch_size=B, dtype=torch.float64)
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 100)
-  fig = {}
-  for step in range(2):
-    b = gen.next_batch()
-    est.train_step(b)
-    got, exp = est.loss_values(), orc.train_step(b)
-    assert sorted(got) == sorted(exp)
-    tol = 1e-5 if step == 0 else 1e-4
-    fig['loss%d' % step] = max(abs(got[k] - exp[k]) / (tol * max(1e-3, abs(exp[k]))) for k in exp)
-    if step > 0:
-      continue
-    keys = [k for k in orc.last_pred if k.startswith('logits')]
-    fig['logits'] = max(float(np.max(np.abs(est.model._prediction_dict[k].detach().cpu().numpy().ravel() - orc.last_pred[k]) /
-                                     (1e-5 + 1e-4 * np.abs(orc.last_pred[k])))) for k in keys)
-    est.varstore.check_grad_views()
-    st = est.state_dict(slots=True)
-    gmax = max(float(np.max(np.abs(v))) for kk, v in orc.slots.items() if kk.endswith('/m'))
-    worst, n = 0.0, 0
-    for k in orc.state:
-      key = k + '/m'
-      if key not in orc.slots or key not in st:
-        continue
-      if k.endswith('/bias') and (k[:-len('/bias')] + '/bn/gamma') in orc.state:
-        continue  # d(loss)/d(bias) == 0 under BatchNorm: rounding noise
-      ref_m = orc.slots[key]
-      worst = max(worst, float(np.max(np.abs(st[key] - ref_m))) / (2e-4 * float(np.max(np.abs(ref_m))) + 2e-6 * gmax))
-      n += 1
-    assert n > 40
-    fig['grads'] = worst
-  return fig
+  _, fig, compared = step_figures(cfg, B, seed, device=DEV, oracle_dtype=torch.float64)
+  assert len(compared) > 40
+  return worst(fig)
 
 
 @pytest.mark.parametrize('kind', ['all', 'image', 'text'])
@@ -123,7 +93,7 @@ def test_first_steps_against_the_fp64_oracle(kind, monkeypatch):
   (Image only: 64 tokens of hidden 48 at initializer_range 0.02 pool to rows that are nearly equal across the batch, and
   final_dnn's BatchNorm divides by their spread; kernels and composition sit at the same distance from fp64.)"""
   B = 64
-  cfg = cref.cmbf_cfg(kind, batch_size=B)
+  cfg = ccases.cmbf_cfg(kind, batch_size=B)
   fused = _figures(cfg, B, 21, True, monkeypatch)
   comp = _figures(cfg, B, 21, False, monkeypatch)
   print('cmbf first steps vs fp64 oracle, in units of the first_steps bar:', kind, 'kernels', fused, 'composition', comp)
@@ -155,7 +125,7 @@ def test_steps_on_the_grouped_launches_equal_steps_on_the_one_unit_launches_bit_
   """EASYREC_AMD_MHA_GROUP_UNITS=1 against =0: the grouped kernels give the one-unit kernels' bits, so two training
   steps give the same losses, logits and first moments of every variable, bit for bit."""
   B = 64
-  cfg = cref.cmbf_cfg(kind, batch_size=B)
+  cfg = ccases.cmbf_cfg(kind, batch_size=B)
   got, got_logits, got_m = _run(cfg, B, 21, True, monkeypatch)
   exp, exp_logits, exp_m = _run(cfg, B, 21, False, monkeypatch)
   assert got == exp, (got, exp)
@@ -177,7 +147,7 @@ def test_the_step_runs_the_new_launches(grouped, monkeypatch):
   reshape)."""
   monkeypatch.setenv('EASYREC_AMD_FUSED_MHA', '1')
   monkeypatch.setenv('EASYREC_AMD_MHA_GROUP_UNITS', '1' if grouped else '0')
-  cfg = cref.cmbf_cfg('all', batch_size=32, seq_dropout=0.1)
+  cfg = ccases.cmbf_cfg('all', batch_size=32, seq_dropout=0.1)
   est = EasyRecEstimator(cfg, device=DEV, batch_size=32, seed=3).build()
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=32, seed=9)
   be = kernels.hip()
@@ -198,7 +168,7 @@ def test_a_step_with_sequence_dropout_and_evaluation_without():
   """text_seq_emb_dropout_prob 0.1 (the sample's): finite losses over three steps; two evaluation-mode predictions of
   one batch (`_predict_eval`, what evaluate() runs) are bit-equal; evaluate() returns an AUC."""
   B = 64
-  cfg = cref.cmbf_cfg('all', batch_size=B, seq_dropout=0.1)
+  cfg = ccases.cmbf_cfg('all', batch_size=B, seq_dropout=0.1)
   est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=5).build()
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
   for _ in range(3):

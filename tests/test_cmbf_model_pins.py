@@ -1,7 +1,7 @@
 """CMBF on the CPU stand-in (easyrec_amd/layers/cmbf.py, model/cmbf.py): the class is registered, the committed config
 is the sample's model section, the variables carry the reference's names, what the reference asserts raises ValueError
 at build time as do bf16 dense and the embedding-parallel engine, the sample's group combinations build and take
-training steps that match the test-side fp64 oracle (tests/_cmbf_oracle.py) at first_steps' bars."""
+training steps that match the fp64 oracle (oracle/model_oracle.py) at first_steps' bars."""
 import os
 
 import numpy as np
@@ -9,8 +9,9 @@ import pytest
 import torch
 
 from easyrec_amd.utils import config_util, load_class
-from tests import _cmbf_ref as cref
-from tests import _uniter_ref as ref
+from oracle import cmbf_ref as cref
+from oracle import uniter_ref as ref
+from tests import _cmbf_cases as ccases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -61,7 +62,7 @@ def test_model_builds_names_its_variables_and_steps_on_the_stand_in(ref_backend,
   (layers/cmbf.py, multihead_cross_attention.py), only final_dnn regularised, and two training steps with finite,
   changing losses."""
   from easyrec_amd.input.synthetic import SyntheticBatches
-  cfg = cref.cmbf_cfg(kind, batch_size=16)
+  cfg = ccases.cmbf_cfg(kind, batch_size=16)
   est = _estimator(cfg)
   names = [n for n in est.varstore.names()]
   want = list(HEAD[kind])
@@ -96,32 +97,32 @@ def test_model_builds_names_its_variables_and_steps_on_the_stand_in(ref_backend,
 
 
 def test_rejected_combinations_raise_at_build_time(ref_backend, built_lib):
-  dup = cref.cmbf_cfg('all')
+  dup = ccases.cmbf_cfg('all')
   dup.model_config.feature_groups[1].feature_names.append('user_id')
   with pytest.raises(ValueError, match='duplicate'):
     _estimator(dup)
-  uneven = cref.cmbf_cfg('all')
+  uneven = ccases.cmbf_cfg('all')
   uneven.feature_config.features[0].embedding_dim = 8
   with pytest.raises(ValueError, match='consistent'):
     _estimator(uneven)
-  short = cref.cmbf_cfg('all')
+  short = ccases.cmbf_cfg('all')
   short.model_config.cmbf.config.max_position_embeddings = 15
   with pytest.raises(ValueError, match='max_position_embeddings'):
     _estimator(short)
-  zero = cref.cmbf_cfg('all')
+  zero = ccases.cmbf_cfg('all')
   zero.model_config.cmbf.config.max_position_embeddings = 0
   with pytest.raises(ValueError, match='greater than 0'):
     _estimator(zero)
-  patches = cref.cmbf_cfg('image')
+  patches = ccases.cmbf_cfg('image')
   patches.model_config.cmbf.config.image_feature_patch_num = 3  # (512 is no multiple of 3)
   with pytest.raises(ValueError, match='image feature dimension'):
     _estimator(patches)
-  heads = cref.cmbf_cfg('all')
+  heads = ccases.cmbf_cfg('all')
   heads.model_config.cmbf.config.multi_head_num = 3  # (text hidden 32 is no multiple of 3)
   with pytest.raises(ValueError, match='multiple'):
     _estimator(heads)
   with pytest.raises(ValueError, match='bf16'):
-    _estimator(cref.cmbf_cfg('all'), dense_dtype='bf16')
+    _estimator(ccases.cmbf_cfg('all'), dense_dtype='bf16')
 
 
 def test_embedding_parallel_engine_is_refused():
@@ -129,7 +130,7 @@ def test_embedding_parallel_engine_is_refused():
   from easyrec_amd.layers import cmbf
   from easyrec_amd.layers.sharded_embedding import ShardedEmbeddingEngine
   ctx = context.ModelContext(None, object.__new__(ShardedEmbeddingEngine))
-  mc = cref.cmbf_cfg('all').model_config
+  mc = ccases.cmbf_cfg('all').model_config
   with context.use(ctx), pytest.raises(ValueError, match='embedding-parallel'):
     cmbf.CMBF(mc, [], None, mc.cmbf.config, None)
 
@@ -138,7 +139,7 @@ def test_predict_is_deterministic_under_sequence_dropout(ref_backend, built_lib)
   """text_seq_emb_dropout_prob 0.1 (the sample's): a training step gives finite losses, and two predictions of one batch
   in evaluation mode (`_predict_eval`, what evaluate() runs) are bit-equal: no dropout outside training."""
   from easyrec_amd.input.synthetic import SyntheticBatches
-  cfg = cref.cmbf_cfg('all', seq_dropout=0.1)
+  cfg = ccases.cmbf_cfg('all', seq_dropout=0.1)
   est = _estimator(cfg)
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=16, seed=5)
   est.train_step(gen.next_batch())
@@ -149,14 +150,12 @@ def test_predict_is_deterministic_under_sequence_dropout(ref_backend, built_lib)
 
 
 @pytest.mark.parametrize('kind', ['all', 'image', 'text'])
-def test_first_steps_on_the_stand_in_match_the_fp64_oracle(ref_backend, built_lib, monkeypatch, kind):
-  """The product on the stand-in backend against tests/_cmbf_oracle.py (the parent oracle's input layer, DNNs, losses
-  and optimizer around the fp64 restatement of the CMBF layer) at first_steps' bars: every loss, the logits and every
+def test_first_steps_on_the_stand_in_match_the_fp64_oracle(ref_backend, built_lib, kind):
+  """The product on the stand-in backend against the model oracle (its input layer, DNNs, losses and optimizer around
+  oracle/cmbf_ref.py's fp64 restatement of the CMBF layer) at first_steps' bars: every loss, the logits and every
   variable's gradient, the embedding tables' included."""
   from tests import _oracle_steps
-  from tests._cmbf_oracle import CMBFOracle
-  monkeypatch.setattr(_oracle_steps, 'OracleTrainer', CMBFOracle)
-  cfg = cref.cmbf_cfg(kind, batch_size=16)
+  cfg = ccases.cmbf_cfg(kind, batch_size=16)
 
   def coverage(names, _):
     assert any(n.startswith('final_dnn/') for n in names)

@@ -1,5 +1,5 @@
 """The cross-attention blocks, the CMBF layer and segment mean pooling on the CPU: the fp64 restatement
-(tests/_cmbf_ref.py) against the REFERENCE'S OWN run (tests/golden/cmbf_vectors.npz, made by
+(oracle/cmbf_ref.py) against the REFERENCE'S OWN run (tests/golden/cmbf_vectors.npz, made by
 tests/golden/make_cmbf_vectors.py from the reference's layers/cmbf.py, layers/multihead_cross_attention.py and
 model/cmbf.py over the numpy stand-in) at 1e-9; the product on the stand-in backend with the reference's variable names
 and order, its layer output and logits at 1e-5 and every gradient against the restatement at 1e-4; the Python mirror of
@@ -10,11 +10,13 @@ import torch
 
 from easyrec_amd.core import context
 from easyrec_amd.layers import multihead_cross_attention as mca
-from tests import _cmbf_ref as cref
-from tests import _uniter_ref as ref
+from oracle import cmbf_ref as cref
+from oracle import uniter_ref as ref
+from tests import _cmbf_cases as ccases
+from tests import _uniter_cases as cases
 from tests._oracle_steps import close
 
-GOLD = cref.fixture()
+GOLD = ccases.fixture()
 CASES = sorted({k.split(':')[0] for k in GOLD.files})
 TAPS = ('image_tower', 'text_tower', 'image_cross', 'text_cross')
 
@@ -22,7 +24,7 @@ TAPS = ('image_tower', 'text_tower', 'image_cross', 'text_cross')
 def test_fixture_covers_the_cases():
   assert CASES == sorted(['all', 'img0', 'patches', 'multi_image', 'image_only', 'text_only', 'general_only',
                           'no_token_type_no_pos', 'other_plain', 'eval'])
-  cfg, groups, training, inputs, var = cref.fixture_case(GOLD, 'all')
+  cfg, groups, training, inputs, var = ccases.fixture_case(GOLD, 'all')
   c = cfg.model_config.cmbf.config
   assert (c.multi_head_num, c.text_head_size, c.image_head_size, c.image_cross_head_size, c.text_cross_head_size) == \
       (2, 4, 3, 3, 4)
@@ -31,24 +33,24 @@ def test_fixture_covers_the_cases():
   assert any(n.startswith('other_dnn/') for n in var)
   lens = [n.tolist() for _, n in inputs['text']]
   assert all(n.count(1) >= 2 and 0 not in n for n in lens) and 5 in lens[0] and 3 in lens[1] and len(lens[0]) == 6
-  c0 = cref.fixture_case(GOLD, 'img0')
+  c0 = ccases.fixture_case(GOLD, 'img0')
   assert c0[0].model_config.cmbf.config.image_self_attention_layer_num == 0 and GOLD['img0:image_tower'].shape == (6, 1, 6)
   assert 'img_projection/kernel' in c0[4] and 'img_map_matrix' not in c0[4]
-  assert cref.fixture_case(GOLD, 'patches')[0].model_config.cmbf.config.image_feature_patch_num == 3
+  assert ccases.fixture_case(GOLD, 'patches')[0].model_config.cmbf.config.image_feature_patch_num == 3
   assert GOLD['patches:image_tower'].shape == (6, 3, 6) and GOLD['multi_image:image_tower'].shape == (6, 2, 6)
-  assert cref.fixture_case(GOLD, 'image_only')[1] == ['image'] and cref.fixture_case(GOLD, 'text_only')[1] == ['general', 'text']
-  assert cref.fixture_case(GOLD, 'general_only')[1] == ['image', 'general'] and GOLD['general_only:hidden'].shape == (6, 6 + 3 * 8)
-  nt = cref.fixture_case(GOLD, 'no_token_type_no_pos')
+  assert ccases.fixture_case(GOLD, 'image_only')[1] == ['image'] and ccases.fixture_case(GOLD, 'text_only')[1] == ['general', 'text']
+  assert ccases.fixture_case(GOLD, 'general_only')[1] == ['image', 'general'] and GOLD['general_only:hidden'].shape == (6, 6 + 3 * 8)
+  nt = ccases.fixture_case(GOLD, 'no_token_type_no_pos')
   assert not any(n.startswith('token_type/') or n.startswith('position_embedding/') for n in nt[4])
   assert 'token_type/token_type_embeddings' in var and 'position_embedding/position_embeddings_1' in var
-  assert not any(n.startswith('other_dnn/') for n in cref.fixture_case(GOLD, 'other_plain')[4])
-  assert not cref.fixture_case(GOLD, 'eval')[2]
+  assert not any(n.startswith('other_dnn/') for n in ccases.fixture_case(GOLD, 'other_plain')[4])
+  assert not ccases.fixture_case(GOLD, 'eval')[2]
 
 
 @pytest.mark.parametrize('tag', CASES)
 def test_restatement_matches_the_reference(tag):
   """Every tensor of the fixture - both towers, both cross outputs, the layer output, logits and probs - at 1e-9."""
-  cfg, groups, training, inputs, var = cref.fixture_case(GOLD, tag)
+  cfg, groups, training, inputs, var = ccases.fixture_case(GOLD, tag)
   towers, hidden, logits = cref.cmbf_model(var, cfg, inputs, training)
   seen = 0
   for k in TAPS:
@@ -66,11 +68,11 @@ def test_product_names_forward_and_gradients_match_the_reference(ref_backend, ta
   """The variables the product creates are the reference's (BatchNorm's moving statistics aside: the stand-in creates
   them only where it reads them, in eval mode), in the reference's creation order; towers, cross outputs, layer output
   and logits match the reference's at 1e-5 (fp32 against fp64); in the training cases the gradient of every variable
-  the layer output depends on matches the fp64 restatement's at 1e-4 (_cmbf_ref.grad_floor: a key bias as for Uniter,
+  the layer output depends on matches the fp64 restatement's at 1e-4 (cmbf_ref.grad_floor: a key bias as for Uniter,
   and a cross block's query / key projections at their value kernel's scale - the block collapses a side's tokens and
   those gradients are zero up to rounding)."""
-  cfg, groups, training, inputs, var = cref.fixture_case(GOLD, tag)
-  vs, ctx, run = cref.product_fixture_forward('cpu', cfg, training, inputs, var)
+  cfg, groups, training, inputs, var = ccases.fixture_case(GOLD, tag)
+  vs, ctx, run = ccases.product_fixture_forward('cpu', cfg, training, inputs, var)
   got = [n for n in vs.names() if '/moving_' not in n]
   assert got == [n for n in var if '/moving_' not in n]
   assert all(tuple(vs.state_dict()[n].shape) == tuple(var[n].shape) for n in var)
@@ -110,7 +112,7 @@ def test_cross_tower_names_order_and_the_refused_left_mask(ref_backend):
     return mca.cross_attention_tower(left, right, num_hidden_layers=2, num_attention_heads=2, left_size_per_head=3,
                                      right_size_per_head=4, **kw)
 
-  vs, ctx = ref.product_store('cpu', lambda: tower(right_input_mask=torch.ones(3, 5, dtype=torch.int32)))
+  vs, ctx = cases.product_store('cpu', lambda: tower(right_input_mask=torch.ones(3, 5, dtype=torch.int32)))
   assert vs.names() == cref.cross_tower_variable_names(2)
   st = vs.state_dict()
   # a block's projections read the OTHER side's width for key / value; intermediate <= 0 means H * size_per_head
@@ -139,9 +141,9 @@ def test_cross_tower_on_the_stand_in_matches_the_restatement(ref_backend):
                                      right_size_per_head=rds, left_intermediate_size=7, right_intermediate_size=0,
                                      right_input_mask=mask, initializer_range=0.5)
 
-  vs, ctx = ref.product_store('cpu', lambda: tower(l64.float(), r64.float()))
+  vs, ctx = cases.product_store('cpu', lambda: tower(l64.float(), r64.float()))
   params = {n: torch.randn(v.shape, generator=g, dtype=torch.float64) * 0.4 for n, v in vs.state_dict().items()}
-  vs, ctx = ref.product_store('cpu', lambda: tower(l64.float(), r64.float()), params)
+  vs, ctx = cases.product_store('cpu', lambda: tower(l64.float(), r64.float()), params)
   a, b = l64.float().requires_grad_(True), r64.float().requires_grad_(True)
   da, db = torch.randn(B, L, H * lds, generator=g, dtype=torch.float64), torch.randn(B, R, H * rds, generator=g, dtype=torch.float64)
   with context.use(ctx):

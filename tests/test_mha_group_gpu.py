@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 
 from easyrec_amd import kernels  # noqa: E402
 from easyrec_amd.layers import multihead_cross_attention as mca  # noqa: E402
-from tests import _cmbf_ref as cref  # noqa: E402
-from tests import _uniter_ref as ref  # noqa: E402
+from oracle import cmbf_ref as cref  # noqa: E402
+from oracle import uniter_ref as ref  # noqa: E402
 from tests._oracle_steps import close as _close  # noqa: E402
 
 logging.disable(logging.WARNING)

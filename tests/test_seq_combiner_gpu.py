@@ -1,5 +1,5 @@
 """The sequence-combiner HIP kernels (csrc/er_seq_combine.hip) on the GPU: forward and every gradient against the fp64
-torch restatement (tests/_seq_combiner_oracle.py) with the column read at a pitch from inside a wider buffer, the max's
+torch restatement (oracle/seq_combiner_ref.py) with the column read at a pitch from inside a wider buffer, the max's
 tie rule, the composed path (outside the envelope, switch off, another activation, no padding), path selection,
 bit-identity (two runs, eager vs hipGraph replay), the models against the test-side oracle, and evaluate()."""
 import logging
@@ -15,7 +15,7 @@ from easyrec_amd.input.synthetic import SyntheticBatches  # noqa: E402
 from easyrec_amd.layers.keras import text_cnn as tc  # noqa: E402
 from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator  # noqa: E402
 from easyrec_amd.utils import config_util  # noqa: E402
-from tests import _seq_combiner_oracle as sref  # noqa: E402
+from oracle import seq_combiner_ref as sref  # noqa: E402
 from tests._oracle_steps import assert_runs_and_replay_bit_identical  # noqa: E402
 from tests._oracle_steps import close as _close  # noqa: E402
 from tests.test_seq_combiner_pins import (GOLD, GOLD_CNN, NEAR_TIE_CAP, PATTERN_TOL, POOL_CASES,  # noqa: E402
@@ -262,7 +262,7 @@ def test_model_matches_the_oracle(kind, monkeypatch):
   for fn in (kernels.TextCnnFn, kernels.SeqAttnPoolFn):
     real = fn.apply
     monkeypatch.setattr(fn, 'apply', (lambda real: lambda *a: calls.append(1) or real(*a))(real))
-  steps_against_the_oracle(kind, 128, 4, DEV, monkeypatch)
+  steps_against_the_oracle(kind, 128, 4, DEV)
   assert calls, 'the model did not run the sequence-combiner kernels'
 
 

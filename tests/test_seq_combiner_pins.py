@@ -1,5 +1,5 @@
 """sequence_combiner (TextCNN, attention pooling) off the GPU: the torch compositions against the fp64 restatement
-(tests/_seq_combiner_oracle.py), the combined group's column order, feature list and variable names, the embedding
+(oracle/seq_combiner_ref.py), the combined group's column order, feature list and variable names, the embedding
 regulariser on the raw sequence embedding, every configuration that must raise, the model sections that did not build
 before (on the stand-in backend, against the fp64 oracle), the max's tie rule, the Python envelope functions against the
 header's formulas, the share of near-tie outputs in the GPU tests' inputs, and the Highway block."""
@@ -13,7 +13,7 @@ import torch
 from _oracle_steps import close as _close
 from easyrec_amd.layers.keras import text_cnn as tc
 from easyrec_amd.utils import config_util
-import _seq_combiner_oracle as sref
+from oracle import seq_combiner_ref as sref
 
 logging.disable(logging.WARNING)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -165,8 +165,8 @@ def coverage(kind):
   return check
 
 
-def steps_against_the_oracle(kind, B, seed, device, monkeypatch):
-  """Two steps of tests/_oracle_steps.first_steps (its own bars) with the test-side oracle in the parent oracle's place.
+def steps_against_the_oracle(kind, B, seed, device):
+  """Two steps of tests/_oracle_steps.first_steps (its own bars).
   backbone_textcnn_bn: its Conv1D biases sit under the mlp's bias-free Dense + BatchNorm, so their gradient is zero up
   to rounding (compared all the same in the first step, against the floor first_steps gives such a tensor), and Adam
   turns that rounding noise into steps of the learning rate in directions no two arithmetics share.  Those bias
@@ -174,7 +174,6 @@ def steps_against_the_oracle(kind, B, seed, device, monkeypatch):
   values the product's first step left in them; every other variable is the oracle's own.  backbone_textcnn is the same
   section without that BatchNorm, where the biases have a gradient to check."""
   import _oracle_steps
-  monkeypatch.setattr(_oracle_steps, 'OracleTrainer', sref.SeqCombinerOracle)
   after_step = None
   if kind.endswith('_bn'):
     kept = {}
@@ -395,11 +394,11 @@ def test_combined_group_order_feature_list_and_names(ref_backend, built_lib):
 
 @pytest.mark.parametrize('kind', ['deepfm_textcnn', 'deepfm_attention', 'deepfm_no_pad', 'backbone_mlp',
                                   'backbone_textcnn', 'backbone_textcnn_bn'])
-def test_model_sections_build_and_step_against_the_oracle(kind, ref_backend, built_lib, monkeypatch):
+def test_model_sections_build_and_step_against_the_oracle(kind, ref_backend, built_lib):
   """Each section builds and takes two training steps on the stand-in backend (the compositions), at first_steps' bars
   against the fp64 oracle: every loss key - the regularisation loss holds the embedding regulariser on the RAW [B, L, D]
   sequence embedding and the kernel regulariser on `attention` - the logits and every variable's first moment."""
-  steps_against_the_oracle(kind, 8, 4, 'cpu', monkeypatch)
+  steps_against_the_oracle(kind, 8, 4, 'cpu')
 
 
 def test_what_must_raise_raises(ref_backend, built_lib):

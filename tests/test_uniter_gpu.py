@@ -1,5 +1,5 @@
 """The K8f kernels (csrc/er_mha.hip) on the GPU: the masked attention core and the residual add + LayerNorm, forward
-and every gradient against the fp64 restatement (tests/_uniter_ref.py), both calling forms of the attention launch, a
+and every gradient against the fp64 restatement (oracle/uniter_ref.py), both calling forms of the attention launch, a
 constant LayerNorm row, bit-identity (two runs, eager vs hipGraph replay) of one encoder layer with gradients into the
 variables' buffers, and the encoder layer on the fused path against the restatement and against the composition."""
 import logging
@@ -12,13 +12,14 @@ pytestmark = pytest.mark.gpu
 from easyrec_amd import kernels  # noqa: E402
 from easyrec_amd.core import context  # noqa: E402
 from easyrec_amd.layers import multihead_cross_attention as mca  # noqa: E402
-from tests import _uniter_ref as ref  # noqa: E402
+from oracle import uniter_ref as ref  # noqa: E402
+from tests import _uniter_cases as cases  # noqa: E402
 from tests._oracle_steps import assert_runs_and_replay_bit_identical  # noqa: E402
 from tests._oracle_steps import close as _close  # noqa: E402
 
 logging.disable(logging.WARNING)
 DEV = 'cuda:0'
-_encoder, _mask = ref.product_encoder, ref.mixed_mask
+_encoder, _mask = cases.product_encoder, ref.mixed_mask
 
 # (B, F, T, H, ds): the sample; more units than persistent workgroups; odd widths (4-byte staging); one query row and
 # F != T; a cross shape; degenerate widths
@@ -197,7 +198,7 @@ def _encoder_case(B, S, hidden, H, layers, inter, seed):
   mask = _mask(B, S, seed + 2)
   x = x64.to(DEV, torch.float32)
   mask_d = mask.to(DEV)
-  vs, ctx = ref.product_store(DEV, lambda: _encoder(x, mask_d, H, layers, inter), params)
+  vs, ctx = cases.product_store(DEV, lambda: _encoder(x, mask_d, H, layers, inter), params)
   return params, x64, mask, x, mask_d, vs, ctx
 
 
@@ -273,9 +274,9 @@ def test_postprocessor_on_the_kernels_matches_the_restatement():
                                          position_embedding_name='txt_position_embeddings_0', max_position_embeddings=20)
 
   x = x64.to(DEV, torch.float32)
-  vs, ctx = ref.product_store(DEV, lambda: forward(x, 3))
+  vs, ctx = cases.product_store(DEV, lambda: forward(x, 3))
   params = {n: torch.randn(v.shape, generator=g, dtype=torch.float64) for n, v in vs.state_dict().items()}
-  vs, ctx = ref.product_store(DEV, lambda: forward(x, 3), params)
+  vs, ctx = cases.product_store(DEV, lambda: forward(x, 3), params)
   dy64 = torch.randn(B, S, W, generator=g, dtype=torch.float64)
   for ids, ids64 in ((3, torch.full((S,), 3)), (ids_b, ids_b)):
     vs.zero_grad()

@@ -1,5 +1,5 @@
 """Uniter and DBMTL.bottom_uniter on the GPU: training steps at the sample's model section (hidden 512, 33 tokens)
-against the test-side fp64 oracle (tests/_uniter_oracle.py) at first_steps' bars, the cases of the reference's own run
+against the fp64 oracle (oracle/model_oracle.py) at first_steps' bars, the cases of the reference's own run
 (tests/golden/uniter_vectors.npz) with their gradients, the kernels against the torch composition
 (EASYREC_AMD_FUSED_MHA=0) at the same bars, the launches a step runs, a step with hidden dropout, and evaluate()."""
 import logging
@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 from easyrec_amd import kernels  # noqa: E402
 from easyrec_amd.input.synthetic import SyntheticBatches  # noqa: E402
 from easyrec_amd.model.easy_rec_estimator import EasyRecEstimator  # noqa: E402
-from tests import _uniter_ref as ref  # noqa: E402
+from oracle import uniter_ref as ref  # noqa: E402
+from tests import _uniter_cases as cases  # noqa: E402
 
 logging.disable(logging.WARNING)
 DEV = 'cuda:0'
@@ -41,7 +42,7 @@ def test_steps_on_the_kernels_match_the_composition(kind, dbmtl, monkeypatch):
   """first_steps' bars between the two paths: losses 1e-5 (first step) / 1e-4 (second), logits rtol 1e-4 / atol 1e-5,
   every variable's gradient (Adam's first moment) within 2e-4 of its scale + 2e-6 of the largest."""
   B = 128
-  cfg = ref.uniter_cfg(kind, batch_size=B, hidden=512, heads=4, layers=2, hidden_dropout=0.0, dbmtl=dbmtl)
+  cfg = cases.uniter_cfg(kind, batch_size=B, hidden=512, heads=4, layers=2, hidden_dropout=0.0, dbmtl=dbmtl)
   got, got_logits, got_m = _run(cfg, B, 21, True, monkeypatch)
   exp, exp_logits, exp_m = _run(cfg, B, 21, False, monkeypatch)
   for step in range(2):
@@ -63,7 +64,7 @@ def test_steps_on_the_kernels_match_the_composition(kind, dbmtl, monkeypatch):
 
 
 def test_the_step_runs_the_new_launches():
-  cfg = ref.uniter_cfg('all', batch_size=32, hidden=64, heads=4, layers=2)
+  cfg = cases.uniter_cfg('all', batch_size=32, hidden=64, heads=4, layers=2)
   est = EasyRecEstimator(cfg, device=DEV, batch_size=32, seed=3).build()
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=32, seed=9)
   be = kernels.hip()
@@ -84,7 +85,7 @@ def test_a_step_with_hidden_dropout_and_evaluation_without():
   (is_training False, what evaluate() runs) and not through two plain predict() calls: predict() on an estimator built
   for training keeps the training flags, for every model of this project."""
   B = 128
-  cfg = ref.uniter_cfg('all', batch_size=B, hidden=512, heads=4, layers=2, hidden_dropout=0.1)
+  cfg = cases.uniter_cfg('all', batch_size=B, hidden=512, heads=4, layers=2, hidden_dropout=0.1)
   est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=5).build()
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
   for _ in range(3):
@@ -99,44 +100,13 @@ def test_a_step_with_hidden_dropout_and_evaluation_without():
 
 # ------------------------------------------------------------------------------------------------ against the fp64 oracle
 def _figures(cfg, B, seed, fused, monkeypatch):
-  """One training step of the product and of the fp64 oracle (tests/_uniter_oracle.py) from the same state on the same
-  batch, then a second: every comparison of first_steps as a figure in units of ITS bar (<= 1 holds it): the losses
-  (1e-5 first step, 1e-4 second), the logits (rtol 1e-4, atol 1e-5), each variable's first moment (2e-4 of its scale +
-  2e-6 of the largest)."""
-  from tests._uniter_oracle import UniterOracle
+  """tests/_oracle_steps.step_figures against the fp64 oracle: every comparison of first_steps in units of ITS bar
+  (<= 1 holds it), the largest of each kind."""
+  from tests._oracle_steps import step_figures, worst
   monkeypatch.setenv('EASYREC_AMD_FUSED_MHA', '1' if fused else '0')
-  est = EasyRecEstimator(cfg, device=DEV, batch_size=B, seed=seed).build()
-  orc = UniterOracle(cfg, est.state_dict(), batch_size=B, dtype=torch.float64)
-  gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=seed + 100)
-  fig = {}
-  for step in range(2):
-    b = gen.next_batch()
-    est.train_step(b)
-    got, exp = est.loss_values(), orc.train_step(b)
-    assert sorted(got) == sorted(exp)
-    tol = 1e-5 if step == 0 else 1e-4
-    fig['loss%d' % step] = max(abs(got[k] - exp[k]) / (tol * max(1e-3, abs(exp[k]))) for k in exp)
-    if step > 0:
-      continue
-    keys = [k for k in orc.last_pred if k.startswith('logits') or k.startswith('y_')]
-    fig['logits'] = max(float(np.max(np.abs(est.model._prediction_dict[k].detach().cpu().numpy().ravel() - orc.last_pred[k]) /
-                                     (1e-5 + 1e-4 * np.abs(orc.last_pred[k])))) for k in keys)
-    est.varstore.check_grad_views()
-    st = est.state_dict(slots=True)
-    gmax = max(float(np.max(np.abs(v))) for kk, v in orc.slots.items() if kk.endswith('/m'))
-    worst, n = 0.0, 0
-    for k in orc.state:
-      key = k + '/m'
-      if key not in orc.slots or key not in st:
-        continue
-      if k.endswith('/bias') and (k[:-len('/bias')] + '/bn/gamma') in orc.state:
-        continue  # d(loss)/d(bias) == 0 under BatchNorm: rounding noise
-      ref_m = orc.slots[key]
-      worst = max(worst, float(np.max(np.abs(st[key] - ref_m))) / (2e-4 * float(np.max(np.abs(ref_m))) + 2e-6 * gmax))
-      n += 1
-    assert n > 40
-    fig['grads'] = worst
-  return fig
+  _, fig, compared = step_figures(cfg, B, seed, device=DEV, oracle_dtype=torch.float64)
+  assert len(compared) > 40
+  return worst(fig)
 
 
 @pytest.mark.parametrize('kind,dbmtl', [('all', False), ('text', False), ('all', True)], ids=['all', 'text', 'dbmtl'])
@@ -149,7 +119,7 @@ def test_first_steps_against_the_fp64_oracle(kind, dbmtl, monkeypatch):
     text only   loss 0.025 / 0.036, logits 0.49 / 0.69, gradients 0.047 / 0.036, second step's loss 0.010 / 0.003
     DBMTL       loss 0.099 / 0.176, logits 0.79 / 0.74, gradients 0.054 / 0.049, second step's loss 0.007 / 0.027"""
   B = 128
-  cfg = ref.uniter_cfg(kind, batch_size=B, hidden=512, heads=4, layers=2, hidden_dropout=0.0, dbmtl=dbmtl)
+  cfg = cases.uniter_cfg(kind, batch_size=B, hidden=512, heads=4, layers=2, hidden_dropout=0.0, dbmtl=dbmtl)
   fused = _figures(cfg, B, 21, True, monkeypatch)
   comp = _figures(cfg, B, 21, False, monkeypatch)
   print('uniter first steps vs fp64 oracle, in units of the first_steps bar:', kind, dbmtl, 'kernels', fused,
@@ -159,7 +129,7 @@ def test_first_steps_against_the_fp64_oracle(kind, dbmtl, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ the reference's fixture
-GOLD = ref.fixture()
+GOLD = cases.fixture()
 
 
 @pytest.mark.parametrize('tag', sorted({k.split(':')[0] for k in GOLD.files}))
@@ -170,8 +140,8 @@ def test_fixture_cases_on_the_gpu(tag):
   autograd and there is no gradient to compare)."""
   from easyrec_amd.core import context
   from tests._oracle_steps import close
-  cfg, groups, training, inputs, var = ref.fixture_case(GOLD, tag)
-  vs, ctx, run = ref.product_fixture_forward(DEV, cfg, training, inputs, var)
+  cfg, groups, training, inputs, var = cases.fixture_case(GOLD, tag)
+  vs, ctx, run = cases.product_fixture_forward(DEV, cfg, training, inputs, var)
   H = cfg.model_config.uniter.config.hidden_size
   dy64 = torch.randn(6, H, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
   vs.zero_grad()

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from easyrec_amd.utils import config_util, load_class
-from tests import _uniter_ref as ref
+from oracle import uniter_ref as ref
+from tests import _uniter_cases as cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -64,7 +65,7 @@ def test_model_builds_names_its_variables_and_steps_on_the_stand_in(ref_backend,
   the order and under the names the reference's graph creates them (layers/uniter.py, multihead_cross_attention.py), only
   final_dnn / other_dnn / the towers regularised, and two training steps with finite, changing losses."""
   from easyrec_amd.input.synthetic import SyntheticBatches
-  cfg = ref.uniter_cfg(kind, batch_size=16, hidden=24, heads=3, layers=2, dbmtl=dbmtl)
+  cfg = cases.uniter_cfg(kind, batch_size=16, hidden=24, heads=3, layers=2, dbmtl=dbmtl)
   est = _estimator(cfg)
   names = [n for n in est.varstore.names()]
   # (hidden 24 is not the image features' 512: `img_projection` comes first, as in image_embeddings, uniter.py:203-208)
@@ -97,14 +98,14 @@ def test_token_types_and_the_mask_follow_the_reference(ref_backend, built_lib):
   general tokens, then position < length per text feature, in the group's feature order (title 16, genres 8)."""
   from easyrec_amd.input.synthetic import SyntheticBatches
   from easyrec_amd.layers import multihead_cross_attention as mca
-  est = _estimator(ref.uniter_cfg('all', hidden=24, heads=3))
+  est = _estimator(cases.uniter_cfg('all', hidden=24, heads=3))
   layer = est.model._uniter_layer
   assert layer.token_type_ids() == {'image': 0, 'general': 1, 'text': [2, 3]} and layer._token_type_vocab_size == 4
   assert layer._use_token_type
-  text = _estimator(ref.uniter_cfg('text', hidden=24, heads=3)).model._uniter_layer
+  text = _estimator(cases.uniter_cfg('text', hidden=24, heads=3)).model._uniter_layer
   assert text.token_type_ids()['general'] == 0 and text.token_type_ids()['text'] == [1, 2]
   assert text._token_type_vocab_size == 3 and text._use_token_type
-  image = _estimator(ref.uniter_cfg('image', hidden=24, heads=3)).model._uniter_layer
+  image = _estimator(cases.uniter_cfg('image', hidden=24, heads=3)).model._uniter_layer
   assert not image._use_token_type and image._token_type_vocab_size == 1
   seen = {}
   real = mca.transformer_encoder
@@ -113,7 +114,7 @@ def test_token_types_and_the_mask_follow_the_reference(ref_backend, built_lib):
     seen['mask'], seen['S'] = attention_mask, x.shape[1]
     return real(x, attention_mask, **kw)
 
-  gen = SyntheticBatches(est.cfg.data_config if hasattr(est, 'cfg') else ref.uniter_cfg('all').data_config,
+  gen = SyntheticBatches(est.cfg.data_config if hasattr(est, 'cfg') else cases.uniter_cfg('all').data_config,
                          est.feature_configs, batch_size=16, seed=3)
   batch = gen.next_batch()
   mca.transformer_encoder = spy
@@ -131,24 +132,24 @@ def test_token_types_and_the_mask_follow_the_reference(ref_backend, built_lib):
 
 
 def test_rejected_combinations_raise_at_build_time(ref_backend, built_lib):
-  dup = ref.uniter_cfg('all', hidden=24, heads=3)
+  dup = cases.uniter_cfg('all', hidden=24, heads=3)
   dup.model_config.feature_groups[1].feature_names.append('user_id')
   with pytest.raises(ValueError, match='duplicate'):
     _estimator(dup)
-  uneven = ref.uniter_cfg('all', hidden=24, heads=3)
+  uneven = cases.uniter_cfg('all', hidden=24, heads=3)
   uneven.feature_config.features[0].embedding_dim = 8
   with pytest.raises(ValueError, match='consistent'):
     _estimator(uneven)
-  short = ref.uniter_cfg('all', hidden=24, heads=3)
+  short = cases.uniter_cfg('all', hidden=24, heads=3)
   short.model_config.uniter.config.max_position_embeddings = 15
   with pytest.raises(ValueError, match='max_position_embeddings'):
     _estimator(short)
   with pytest.raises(ValueError, match='bf16'):
-    _estimator(ref.uniter_cfg('all', hidden=24, heads=3), dense_dtype='bf16')
-  heads = ref.uniter_cfg('all', hidden=24, heads=5)
+    _estimator(cases.uniter_cfg('all', hidden=24, heads=3), dense_dtype='bf16')
+  heads = cases.uniter_cfg('all', hidden=24, heads=5)
   with pytest.raises(ValueError, match='multiple'):
     _estimator(heads)
-  cmbf = ref.uniter_cfg('all', hidden=24, heads=3, dbmtl=True)
+  cmbf = cases.uniter_cfg('all', hidden=24, heads=3, dbmtl=True)
   cmbf.model_config.dbmtl.ClearField('bottom_uniter')
   cmbf.model_config.dbmtl.bottom_cmbf.SetInParent()
   with pytest.raises(NotImplementedError, match='bottom_cmbf'):
@@ -161,7 +162,7 @@ def test_embedding_parallel_engine_is_refused():
   from easyrec_amd.layers.sharded_embedding import ShardedEmbeddingEngine
   ctx = context.ModelContext(None, object.__new__(ShardedEmbeddingEngine))
   with context.use(ctx), pytest.raises(ValueError, match='embedding-parallel'):
-    uniter.Uniter(ref.uniter_cfg('all').model_config, [], None, ref.uniter_cfg('all').model_config.uniter.config, None)
+    uniter.Uniter(cases.uniter_cfg('all').model_config, [], None, cases.uniter_cfg('all').model_config.uniter.config, None)
 
 
 def test_predict_is_deterministic_under_hidden_dropout(ref_backend, built_lib):
@@ -170,7 +171,7 @@ def test_predict_is_deterministic_under_hidden_dropout(ref_backend, built_lib):
   what evaluate() runs), not through two plain predict() calls: predict() on an estimator built for training keeps the
   training flags, for every model of this project, so its dropout stays on."""
   from easyrec_amd.input.synthetic import SyntheticBatches
-  cfg = ref.uniter_cfg('all', hidden=24, heads=3, hidden_dropout=0.1)
+  cfg = cases.uniter_cfg('all', hidden=24, heads=3, hidden_dropout=0.1)
   est = _estimator(cfg)
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=16, seed=5)
   est.train_step(gen.next_batch())
@@ -181,14 +182,12 @@ def test_predict_is_deterministic_under_hidden_dropout(ref_backend, built_lib):
 
 
 @pytest.mark.parametrize('kind,dbmtl', [('all', False), ('image', False), ('text', False), ('all', True)])
-def test_first_steps_on_the_stand_in_match_the_fp64_oracle(ref_backend, built_lib, monkeypatch, kind, dbmtl):
-  """The product on the stand-in backend against tests/_uniter_oracle.py (the parent oracle's input layer, DNNs, losses
-  and optimizer around the fp64 restatement of the Uniter layer) at first_steps' bars: every loss, the logits and
-  every variable's gradient, the embedding tables' included.  initializer_range 0.3: see _uniter_ref.uniter_cfg."""
+def test_first_steps_on_the_stand_in_match_the_fp64_oracle(ref_backend, built_lib, kind, dbmtl):
+  """The product on the stand-in backend against the model oracle (its input layer, DNNs, losses and optimizer around
+  oracle/uniter_ref.py's fp64 restatement of the Uniter layer) at first_steps' bars: every loss, the logits and
+  every variable's gradient, the embedding tables' included.  initializer_range 0.3: see tests/_uniter_cases.py uniter_cfg."""
   from tests import _oracle_steps
-  from tests._uniter_oracle import UniterOracle
-  monkeypatch.setattr(_oracle_steps, 'OracleTrainer', UniterOracle)
-  cfg = ref.uniter_cfg(kind, batch_size=16, hidden=24, heads=3, dbmtl=dbmtl, initializer_range=0.3)
+  cfg = cases.uniter_cfg(kind, batch_size=16, hidden=24, heads=3, dbmtl=dbmtl, initializer_range=0.3)
 
   def coverage(names, _):
     assert 'cls_emb' in names and 'uniter_layer_1/attention/self/key/kernel' in names

@@ -1,5 +1,5 @@
 """The BERT-style encoder layer (easyrec_amd/layers/multihead_cross_attention.py) on the CPU: the torch composition on
-the stand-in backend against the fp64 restatement (tests/_uniter_ref.py), the reference's variable names, the mask and
+the stand-in backend against the fp64 restatement (oracle/uniter_ref.py), the reference's variable names, the mask and
 the 1 / sqrt(ds) scaling, and the Python mirror of the K8f kernels' envelope against the library."""
 import math
 
@@ -9,12 +9,13 @@ import torch
 
 from easyrec_amd.core import context
 from easyrec_amd.layers import multihead_cross_attention as mca
-from tests import _uniter_ref as ref
+from oracle import uniter_ref as ref
+from tests import _uniter_cases as cases
 from tests._oracle_steps import close
 
 
 _mask = ref.mixed_mask
-_encoder = ref.product_encoder
+_encoder = cases.product_encoder
 
 
 def test_envelope_formula_is_the_library_s(built_lib):
@@ -90,7 +91,7 @@ def test_encoder_on_the_stand_in_matches_the_restatement(ref_backend, act):
   x64 = torch.randn(B, S, hidden, generator=torch.Generator().manual_seed(1), dtype=torch.float64)
   mask = _mask(B, S, 3)
   x = x64.float().requires_grad_(True)
-  vs, ctx = ref.product_store('cpu', lambda: _encoder(x.detach(), mask, H, layers, inter, act), params)
+  vs, ctx = cases.product_store('cpu', lambda: _encoder(x.detach(), mask, H, layers, inter, act), params)
   assert vs.names() == ref.encoder_variable_names('uniter', layers)
   assert all(vs.l2_of(n) == 0.0 for n in vs.names())  # (the encoder's dense layers carry no regulariser)
   dy = torch.randn(B, S, hidden, generator=torch.Generator().manual_seed(2), dtype=torch.float64)
@@ -111,7 +112,7 @@ def test_encoder_on_the_stand_in_matches_the_restatement(ref_backend, act):
 def test_initializers_are_the_reference_s(ref_backend):
   """Kernels: truncated normal with stddev initializer_range (nothing beyond 2 sigma); biases and beta zeros, gamma ones."""
   x = torch.randn(2, 5, 64)
-  vs, _ = ref.product_store('cpu', lambda: mca.transformer_encoder(
+  vs, _ = cases.product_store('cpu', lambda: mca.transformer_encoder(
       x, None, hidden_size=64, num_hidden_layers=1, num_attention_heads=4, intermediate_size=256, initializer_range=0.03))
   st = vs.state_dict()
   for n, v in st.items():
@@ -141,12 +142,12 @@ def test_postprocessor_names_numbering_and_values(ref_backend):
                                        max_position_embeddings=7)
     return ya, yb
 
-  vs, ctx = ref.product_store('cpu', lambda: forward(xa.float(), xb.float()))
+  vs, ctx = cases.product_store('cpu', lambda: forward(xa.float(), xb.float()))
   assert vs.names() == ['token_type/token_type_embeddings', 'LayerNorm/beta', 'LayerNorm/gamma',
                         'position_embedding/txt_position_embeddings_0', 'LayerNorm_1/beta', 'LayerNorm_1/gamma']
   assert vs.state_dict()['position_embedding/txt_position_embeddings_0'].shape == (7, W)
   params = {n: torch.randn(v.shape, generator=g, dtype=torch.float64) for n, v in vs.state_dict().items()}
-  vs, ctx = ref.product_store('cpu', lambda: forward(xa.float(), xb.float()), params)
+  vs, ctx = cases.product_store('cpu', lambda: forward(xa.float(), xb.float()), params)
   a, b = xa.float().requires_grad_(True), xb.float().requires_grad_(True)
   with context.use(ctx):
     ya, yb = forward(a, b)
@@ -177,7 +178,7 @@ def test_dropout_runs_only_while_training(ref_backend):
                                    intermediate_size=8, hidden_dropout_prob=hidden_p,
                                    attention_probs_dropout_prob=att_p, initializer_range=0.5)
 
-  vs, ctx = ref.product_store('cpu', lambda: enc(0.0, 0.0))
+  vs, ctx = cases.product_store('cpu', lambda: enc(0.0, 0.0))
   with context.use(ctx), torch.no_grad():
     plain = enc(0.0, 0.0)
     torch.manual_seed(1)

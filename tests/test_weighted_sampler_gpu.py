@@ -1,5 +1,5 @@
 """negative_sampler on the GPU: er_neg_sample_weighted (csrc/er_sampler.hip) against the restatement
-(tests/_weighted_sampler_ref.py, written from include/easyrec_hip.h K1c) bit for bit - sel and every extended column -
+(oracle/weighted_sampler_ref.py, written from include/easyrec_hip.h K1c) bit for bit - sel and every extended column -
 at the shapes of tests/test_weighted_sampler_pins.py; column counts around the group of eight, the refused 33rd column,
 the id that doubles as the LDS set's empty mark, duplicate batch ids; two runs and a captured launch replayed over two
 steps; the distribution of 500 device steps; DSSM's and MIND's first steps with weighted negatives against the fp64
@@ -9,12 +9,12 @@ import pytest
 import torch
 
 import _oracle_steps
-import _weighted_sampler_ref as ref
 import test_match_pins
 import test_mind_pins
 import test_neg_sampler_pins as pins
 import test_weighted_sampler_pins as wpins
 from oracle import match_ref as mref
+from oracle import weighted_sampler_ref as ref
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -202,14 +202,13 @@ def test_the_device_s_counts_are_the_restatement_s(built_lib):
 B, N, ROWS = 67, 40, 300
 
 
-def _first_steps(model, coverage, monkeypatch, after_step=None):
+def _first_steps(model, coverage, after_step=None):
   """first_steps of a config with the weighted sampler (seed 5) against the fp64 oracle fed the restatement's rows; after
   each of the product's steps: the item group had B + N rows and the extended id columns are the restatement's"""
   from easyrec_amd.input import neg_sampler
   cfg = wpins.wnegsam_cfg(B, N, ROWS, model=model)
   table = wpins.weighted_item_table_for(cfg, ROWS)
   tab = neg_sampler.alias_table(table.weights)
-  wpins.use_weighted_oracle(monkeypatch)
 
   def check(est, orc, step, batch):
     assert est.sampler.weighted and est.sampler.uses_kernel()
@@ -219,8 +218,8 @@ def _first_steps(model, coverage, monkeypatch, after_step=None):
     if after_step is not None:
       after_step(est, orc, step, batch)
   est = _oracle_steps.first_steps(cfg, B, seed=5, oracle_dtype=torch.float64, coverage=coverage,
-                                  est_kw=dict(item_table=table), oracle_kw=dict(item_table=table, sampler_seed=5),
-                                  after_step=check)
+                                  est_kw=dict(item_table=table),
+                                  oracle_kw=dict(item_table=table, sampler_seed=5, alias_tab=tab), after_step=check)
   return cfg, table, tab, est
 
 
@@ -236,11 +235,11 @@ def _check_the_draw(cfg, table, tab, est, batch, step):
     assert np.array_equal(est.features.ids_of(name).cpu().numpy(), ref.extended(own, table.columns[name]['ids'], sel)), name
 
 
-def test_dssm_first_steps_with_weighted_negatives(built_lib, monkeypatch):
+def test_dssm_first_steps_with_weighted_negatives(built_lib):
   """tests/test_match_gpu.py test_model_first_steps with the weighted sampler: B = 67, N = 40, a 300-row table, two steps;
   then the evaluation mode's metrics over the B + N columns."""
   from easyrec_amd.input.synthetic import SyntheticBatches
-  cfg, table, tab, est = _first_steps('dssm', test_match_pins.dssm_coverage, monkeypatch)
+  cfg, table, tab, est = _first_steps('dssm', test_match_pins.dssm_coverage)
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
   est.model._is_training = est.ctx.is_training = False
   pred = est.predict(gen.next_batch(), sample_negatives=True)
@@ -260,7 +259,7 @@ def test_mind_first_steps_with_weighted_negatives(built_lib, monkeypatch):
   from easyrec_amd.input.synthetic import SyntheticBatches
   from easyrec_amd.layers import capsule_layer
   monkeypatch.setattr(capsule_layer, 'fused_capsule', True)
-  cfg, table, tab, est = _first_steps('mind', test_mind_pins.mind_coverage, monkeypatch,
+  cfg, table, tab, est = _first_steps('mind', test_mind_pins.mind_coverage,
                                       test_mind_pins.hand_over_routing_logits())
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=105)
   est.capture()  # (warms up over three steps: 2, 3, 4; the replays are steps 5 and 6)

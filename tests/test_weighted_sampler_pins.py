@@ -1,6 +1,6 @@
 """negative_sampler (the weighted draw with replacement) on the CPU: the host alias builder implies the weights, the
 product's composed draw (easyrec_amd/input/neg_sampler.py draw_weighted) equals the restatement
-(tests/_weighted_sampler_ref.py, written from include/easyrec_hip.h K1c) bit for bit, the draw's distribution, the
+(oracle/weighted_sampler_ref.py, written from include/easyrec_hip.h K1c) bit for bit, the draw's distribution, the
 table file's weight column, the build-time refusals and the num_eval_sample rule, the reference's own composition
 around the graphlearn call (tests/golden/weighted_sampler_vectors.npz), and a DSSM config with the sampler training on
 the stand-in backend against the fp64 oracle fed the restatement's rows."""
@@ -12,10 +12,10 @@ import pytest
 import torch
 
 import _oracle_steps
-import _weighted_sampler_ref as ref
 import test_match_pins
 import test_neg_sampler_pins as pins
 from oracle import match_ref as mref
+from oracle import weighted_sampler_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 1234
@@ -467,33 +467,7 @@ def test_extended_columns_are_the_reference_s_composition(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------- the model
-def use_weighted_oracle(monkeypatch):
-  """tests/_oracle_steps.first_steps builds the fp64 model oracle from the product's config; the oracle knows the
-  in-memory sampler only.  This wraps its sampler input: the config it sees names negative_sampler_in_memory with the
-  same fields, and the rows it appends are the restatement's weighted draw from the alias table of the item table's
-  weights."""
-  from easyrec_amd.input import neg_sampler
-  from oracle import model_oracle
-  import types
-
-  class WeightedOracle(model_oracle.OracleTrainer):
-
-    def __init__(self, cfg, *args, **kw):
-      seen = type(cfg)()
-      seen.CopyFrom(cfg)
-      seen.data_config.negative_sampler_in_memory.ParseFromString(cfg.data_config.negative_sampler.SerializeToString())
-      super(WeightedOracle, self).__init__(seen, *args, **kw)
-      self.alias_tab = neg_sampler.alias_table(self.item_table.weights)
-
-    def _sampled_negatives(self, batch):
-      draw = lambda seed, step, ids, batch_ids, N: ref.draw(seed, step, self.alias_tab, ids, batch_ids, N)
-      with monkeypatch.context() as m:
-        m.setattr(model_oracle, 'neg_sampler_ref', types.SimpleNamespace(draw=draw, extended=ref.extended))
-        super(WeightedOracle, self)._sampled_negatives(batch)
-  monkeypatch.setattr(_oracle_steps, 'OracleTrainer', WeightedOracle)
-
-
-def test_dssm_with_the_sampler_steps_on_the_stand_in(ref_backend, built_lib, monkeypatch):
+def test_dssm_with_the_sampler_steps_on_the_stand_in(ref_backend, built_lib):
   """tests/test_neg_sampler_pins.py's step test with the weighted sampler: two steps against the fp64 model oracle fed the
   restatement's rows, the item group's rows being B + N; then predict() without and with negatives."""
   from easyrec_amd.input import neg_sampler
@@ -502,7 +476,6 @@ def test_dssm_with_the_sampler_steps_on_the_stand_in(ref_backend, built_lib, mon
   cfg = wnegsam_cfg(B, N, rows)
   table = weighted_item_table_for(cfg, rows)
   tab = neg_sampler.alias_table(table.weights)
-  use_weighted_oracle(monkeypatch)
 
   def check(est, orc, step, batch):
     assert est.model._prediction_dict['item_tower_emb'].shape == (B + N, 32)
@@ -513,7 +486,7 @@ def test_dssm_with_the_sampler_steps_on_the_stand_in(ref_backend, built_lib, mon
     assert (table.weights[sel] > 0).all()
   est = _oracle_steps.first_steps(cfg, B, seed=4, device='cpu', oracle_dtype=torch.float64,
                                   coverage=test_match_pins.dssm_coverage, est_kw=dict(item_table=table),
-                                  oracle_kw=dict(item_table=table, sampler_seed=4), after_step=check)
+                                  oracle_kw=dict(item_table=table, sampler_seed=4, alias_tab=tab), after_step=check)
   gen = SyntheticBatches(cfg.data_config, est.feature_configs, batch_size=B, seed=44)
   est.model._is_training = est.ctx.is_training = False
   pred = est.predict(gen.next_batch())

@@ -1,6 +1,9 @@
 """For every config the reference ships that builds here: two training steps of the product (host code on the oracle's
-stand-in kernels) against the model oracle, on the same synthetic batches - loss by loss.  Run where /root/reference
-exists.  usage: python tools/check_reference_configs_vs_oracle.py [/root/reference]"""
+stand-in kernels) against the model oracle, on the same synthetic batches - loss by loss.  Tables are capped at 2000
+rows, and the dropout probabilities of the Uniter and CMBF layers are set to 0: dropout is random on both sides, the
+oracle refuses it.  negative_sampler_in_memory gets its item table; no reference config with the weighted
+negative_sampler builds here (their item tables are files the reference does not ship), so that branch has nothing to
+pass.  Run where /root/reference exists.  usage: python tools/check_reference_configs_vs_oracle.py [/root/reference] [-v]"""
 import collections
 import glob
 import logging
@@ -31,8 +34,14 @@ def main():
         fc.hash_bucket_size = min(fc.hash_bucket_size, 2000) if fc.HasField('hash_bucket_size') else fc.hash_bucket_size
         if fc.num_buckets > 2000:
           fc.num_buckets = 2000
-        for dr in fc.ListFields():
-          pass
+      model = cfg.model_config.WhichOneof('model')
+      mc = cfg.model_config
+      towers = {'uniter': [mc.uniter.config], 'cmbf': [mc.cmbf.config],
+                'dbmtl': [mc.dbmtl.bottom_uniter] if mc.dbmtl.HasField('bottom_uniter') else []}.get(model, [])
+      for tower in towers:
+        for field in ('hidden_dropout_prob', 'attention_probs_dropout_prob', 'text_seq_emb_dropout_prob'):
+          if hasattr(tower, field):
+            setattr(tower, field, 0.0)
       table = None
       if cfg.data_config.WhichOneof('sampler') == 'negative_sampler_in_memory':
         from easyrec_amd.input.neg_sampler import ItemTable
