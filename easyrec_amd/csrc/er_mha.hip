@@ -19,9 +19,11 @@
 // of the unmasked scores, the value the reference's formula has in exact arithmetic.
 //
 // Grouped units (mha_group_*): for short sequences the 512 threads are G = 8, 4 or 2 groups, each owning a unit in its own
-// LDS region and running the same device functions with its own thread index and count; the results are the one-unit
-// kernels' bits.  Segment mean (segment_mean_*): CMBF's masked mean pooling over consecutive token segments (reference
-// layers/cmbf.py:292-326, :364), lanes along the width, one division per element.
+// LDS region with its own thread index and count.  The forward of both forms is ONE body (mha_fwd_units, a template on
+// the grouped flag); the backward kernels are the same statements written out twice (see there for why); the results
+// are the one-unit kernels' bits.  Segment mean (segment_mean_*):
+// CMBF's masked mean pooling over consecutive token segments (reference layers/cmbf.py:292-326, :364), lanes along the
+// width, one division per element.
 //
 // Add & LayerNorm.  One wave per row.  W % 4 == 0, W <= 1024 and 16-byte aligned operands: the row x + res lives in
 // registers (up to 4 float4 per lane) between the passes; otherwise the row is re-read (it sits in L1 / L2).  The mean
@@ -204,40 +206,65 @@ __device__ inline void mha_ds(int tid, int nthr, const MhaGeom& g, const float* 
   }
 }
 
-// S = Q K^T * scale -> P = softmax over the keys of S + adder, in S's place
-__device__ inline void mha_probs(const MhaGeom& g, const float* Qs, const float* Ks, const float* madd, float* S) {
-  mha_scores(threadIdx.x, kMhaThreads, g, Qs, Ks, S);
-  __syncthreads();
-  mha_softmax(threadIdx.x, kMhaThreads, g, madd, S);
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(kMhaThreads) void mha_fwd_kernel(MhaArgs a) {
+// ------------------------------------------------------------------------------- the unit loops, one-unit and grouped
+// Grouped: the 512 threads split into G groups of 512 / G (a group is whole waves); group `grp` owns the unit
+// pass * G + grp in its own LDS region (unit_floats apart) and its loops stride by the group size.  Every barrier is the
+// workgroup's: a group whose unit is past the end skips the work between them, never a barrier.  An output element is
+// the same single-thread chain over k and a softmax row the same wave butterfly in either form, so the results are the
+// same bits.
+//
+// The forward is ONE body for both forms: one-unit is the grouped loop with the compile-time constants nthr = 512,
+// grp = 0, on = true.  (MhaArgs BY VALUE: through a reference the compiler copies the kernel argument and allocates
+// the one-unit kernel's registers differently - 1 % slower at CMBF's shapes; by value the ISA is the hand-written
+// kernels' but for a handful of scalar instructions.)
+template <bool kGroup>
+__device__ __forceinline__ void mha_fwd_units(const MhaArgs a, int G, int unit_floats) {
   extern __shared__ float lds[];
   const MhaGeom g = a.g;
   const int F = g.F, T = g.T, ds = g.ds, ld = g.ld;
-  float* Qs = lds;
+  const int nthr = kGroup ? kMhaThreads / G : kMhaThreads, grp = kGroup ? threadIdx.x / nthr : 0;
+  const int tid = threadIdx.x - grp * nthr;
+  float* Qs = lds + grp * unit_floats;
   float* Ks = Qs + F * ld;
   float* Vs = Ks + T * ld;
   float* S = Vs + T * ld;
   float* madd = S + F * g.ldp;
   const int64_t dctx = static_cast<int64_t>(g.H) * ds;
-  for (int64_t u = blockIdx.x; u < a.units; u += gridDim.x) {
-    const int64_t b = u / g.H;
-    const int h = static_cast<int>(u - b * g.H);
-    mha_stage(threadIdx.x, kMhaThreads, a.q + b * F * a.ldq + h * ds, a.ldq, F, ds, a.vec & 1, ld, Qs);
-    mha_stage(threadIdx.x, kMhaThreads, a.k + b * T * a.ldk + h * ds, a.ldk, T, ds, a.vec & 2, ld, Ks);
-    mha_stage(threadIdx.x, kMhaThreads, a.v + b * T * a.ldv + h * ds, a.ldv, T, ds, a.vec & 4, ld, Vs);
-    mha_stage_adder(threadIdx.x, a.mask, b, T, madd);
+  const int64_t per = kGroup ? G : 1;  // units a workgroup takes per pass
+  for (int64_t u0 = blockIdx.x * per; u0 < a.units; u0 += gridDim.x * per) {
+    const int64_t u = u0 + grp;
+    const bool on = !kGroup || u < a.units;
+    const int64_t b = on ? u / g.H : 0;
+    const int h = on ? static_cast<int>(u - b * g.H) : 0;
+    if (on) {
+      mha_stage(tid, nthr, a.q + b * F * a.ldq + h * ds, a.ldq, F, ds, a.vec & 1, ld, Qs);
+      mha_stage(tid, nthr, a.k + b * T * a.ldk + h * ds, a.ldk, T, ds, a.vec & 2, ld, Ks);
+      mha_stage(tid, nthr, a.v + b * T * a.ldv + h * ds, a.ldv, T, ds, a.vec & 4, ld, Vs);
+      mha_stage_adder(tid, a.mask, b, T, madd);
+    }
     __syncthreads();
-    mha_probs(g, Qs, Ks, madd, S);
-    // ctx_h = P V_h
-    float* out = a.ctx + b * F * dctx + h * ds;
-    mha_mm(threadIdx.x, kMhaThreads, F, ds, T, S, g.ldp, 1, Vs, 1, ld, [=](int i, int c, float s) { out[i * dctx + c] = s; });
-    __syncthreads();  // (the next unit restages)
+    if (on) mha_scores(tid, nthr, g, Qs, Ks, S);
+    __syncthreads();
+    if (on) mha_softmax(tid, nthr, g, madd, S);
+    __syncthreads();
+    if (on) {
+      // ctx_h = P V_h
+      float* out = a.ctx + b * F * dctx + h * ds;
+      mha_mm(tid, nthr, F, ds, T, S, g.ldp, 1, Vs, 1, ld, [=](int i, int c, float s) { out[i * dctx + c] = s; });
+    }
+    __syncthreads();  // (the next pass restages)
   }
 }
 
+__global__ __launch_bounds__(kMhaThreads) void mha_fwd_kernel(MhaArgs a) { mha_fwd_units<false>(a, 1, 0); }
+__global__ __launch_bounds__(kMhaThreads) void mha_group_fwd_kernel(MhaArgs a, int G, int unit_floats) {
+  mha_fwd_units<true>(a, G, unit_floats);
+}
+
+// The backward is written out per form.  Through a shared body as above the one-unit kernel keeps its register and
+// instruction counts, but the compiler allocates its registers otherwise and it runs 0.2 - 0.9 % slower at every shape
+// (CMBF's and Uniter's, alternating windows in one process); by reference, by value and with the loop restated it stays
+// so.  A change to the order of calls and barriers is made in BOTH kernels below.
 __global__ __launch_bounds__(kMhaThreads) void mha_bwd_kernel(MhaArgs a) {
   extern __shared__ float lds[];
   const MhaGeom g = a.g;
@@ -259,7 +286,10 @@ __global__ __launch_bounds__(kMhaThreads) void mha_bwd_kernel(MhaArgs a) {
     mha_stage(threadIdx.x, kMhaThreads, a.dctx + b * F * dctx + h * ds, dctx, F, ds, a.vec & 8, ld, Cs);
     mha_stage_adder(threadIdx.x, a.mask, b, T, madd);
     __syncthreads();
-    mha_probs(g, Qs, Ks, madd, P);
+    mha_scores(threadIdx.x, kMhaThreads, g, Qs, Ks, P);
+    __syncthreads();
+    mha_softmax(threadIdx.x, kMhaThreads, g, madd, P);
+    __syncthreads();
     // dP[i, j] = dctx_h[i] . V_h[j];  dV_h[j] = sum_i P[i, j] dctx_h[i]
     mha_mm(threadIdx.x, kMhaThreads, F, T, ds, Cs, ld, 1, Vs, ld, 1, [=](int i, int j, float s) { D[i * ldp + j] = s; });
     float* dv = a.dv + b * T * a.lddv + h * ds;
@@ -275,47 +305,6 @@ __global__ __launch_bounds__(kMhaThreads) void mha_bwd_kernel(MhaArgs a) {
     mha_mm(threadIdx.x, kMhaThreads, F, ds, T, D, ldp, 1, Ks, 1, ld, [=](int i, int c, float s) { dq[i * lddq + c] = s; });
     mha_mm(threadIdx.x, kMhaThreads, T, ds, F, D, 1, ldp, Qs, 1, ld, [=](int j, int c, float s) { dk[j * lddk + c] = s; });
     __syncthreads();  // (the next unit restages)
-  }
-}
-
-// ---------------------------------------------------------------------------------------- grouped units
-// The 512 threads split into G groups of 512 / G (a group is whole waves); group `grp` owns the unit
-// pass * G + grp in its own LDS region and runs the algorithm above with its loops striding by the group size.
-// Every barrier is the workgroup's: a group whose unit is past the end skips the work between them, never a barrier.
-// An output element is the same single-thread chain over k and a softmax row the same wave butterfly as in the one-unit
-// kernels, so the results are the same bits.
-__global__ __launch_bounds__(kMhaThreads) void mha_group_fwd_kernel(MhaArgs a, int G, int unit_floats) {
-  extern __shared__ float lds[];
-  const MhaGeom g = a.g;
-  const int F = g.F, T = g.T, ds = g.ds, ld = g.ld;
-  const int nthr = kMhaThreads / G, grp = threadIdx.x / nthr, tid = threadIdx.x - grp * nthr;
-  float* Qs = lds + grp * unit_floats;
-  float* Ks = Qs + F * ld;
-  float* Vs = Ks + T * ld;
-  float* S = Vs + T * ld;
-  float* madd = S + F * g.ldp;
-  const int64_t dctx = static_cast<int64_t>(g.H) * ds;
-  for (int64_t u0 = static_cast<int64_t>(blockIdx.x) * G; u0 < a.units; u0 += static_cast<int64_t>(gridDim.x) * G) {
-    const int64_t u = u0 + grp;
-    const bool on = u < a.units;
-    const int64_t b = on ? u / g.H : 0;
-    const int h = on ? static_cast<int>(u - b * g.H) : 0;
-    if (on) {
-      mha_stage(tid, nthr, a.q + b * F * a.ldq + h * ds, a.ldq, F, ds, a.vec & 1, ld, Qs);
-      mha_stage(tid, nthr, a.k + b * T * a.ldk + h * ds, a.ldk, T, ds, a.vec & 2, ld, Ks);
-      mha_stage(tid, nthr, a.v + b * T * a.ldv + h * ds, a.ldv, T, ds, a.vec & 4, ld, Vs);
-      mha_stage_adder(tid, a.mask, b, T, madd);
-    }
-    __syncthreads();
-    if (on) mha_scores(tid, nthr, g, Qs, Ks, S);
-    __syncthreads();
-    if (on) mha_softmax(tid, nthr, g, madd, S);
-    __syncthreads();
-    if (on) {
-      float* out = a.ctx + b * F * dctx + h * ds;
-      mha_mm(tid, nthr, F, ds, T, S, g.ldp, 1, Vs, 1, ld, [=](int i, int c, float s) { out[i * dctx + c] = s; });
-    }
-    __syncthreads();  // (the next pass restages)
   }
 }
 
@@ -774,51 +763,26 @@ int64_t er_mha_lds_bytes(int32_t F, int32_t T, int32_t ds, int bwd) {
   return 4 * (bwd ? er::mha_bwd_floats(F, T, ds) : er::mha_fwd_floats(F, T, ds));
 }
 
-int er_mha_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
-               const int32_t* to_mask, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds, float* ctx,
-               er_stream_t stream) {
-  ER_REQUIRE(q && k && v && ctx && B > 0, "er_mha_fwd: bad arguments");
-  ER_REQUIRE(er::mha_shape_ok(F, T, H, ds), "er_mha_fwd: F = %d, T = %d, H = %d, ds = %d outside the envelope", F, T, H, ds);
+// the four attention entries: `what` names the caller in the error texts; the forward passes ctx and no dctx / dq / dk /
+// dv, the backward the reverse; group: G = mha_group_units(F, T, ds) units per workgroup, refused below 2
+static int mha_launch(const char* what, bool bwd, bool group, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                      const float* v, int64_t ldv, const int32_t* to_mask, const float* dctx, int64_t B, int32_t F,
+                      int32_t T, int32_t H, int32_t ds, float* ctx, float* dq, int64_t lddq, float* dk, int64_t lddk,
+                      float* dv, int64_t lddv, er_stream_t stream) {
+  ER_REQUIRE(q && k && v && (bwd ? dctx && dq && dk && dv : ctx != nullptr) && B > 0, "%s: bad arguments", what);
+  ER_REQUIRE(er::mha_shape_ok(F, T, H, ds), "%s: F = %d, T = %d, H = %d, ds = %d outside the envelope", what, F, T, H, ds);
+  const int G = group ? er::mha_group_units(F, T, ds) : 1;
+  ER_REQUIRE(!group || G >= 2, "%s: F = %d, T = %d, ds = %d leaves room for one unit per workgroup", what, F, T, ds);
   const int64_t d = static_cast<int64_t>(H) * ds;
-  ER_REQUIRE(ldq >= d && ldk >= d && ldv >= d, "er_mha_fwd: a row pitch is below H * ds = %lld", static_cast<long long>(d));
-  er::MhaArgs a = {};
-  a.q = q;
-  a.k = k;
-  a.v = v;
-  a.mask = to_mask;
-  a.ctx = ctx;
-  a.ldq = ldq;
-  a.ldk = ldk;
-  a.ldv = ldv;
-  a.units = B * H;
-  a.g = er::mha_geom(F, T, H, ds);
-  if (ds % 4 == 0) {
-    if (ldq % 4 == 0 && er::aligned16(q)) a.vec |= 1;
-    if (ldk % 4 == 0 && er::aligned16(k)) a.vec |= 2;
-    if (ldv % 4 == 0 && er::aligned16(v)) a.vec |= 4;
-  }
-  const int bytes = static_cast<int>(4 * er::mha_fwd_floats(F, T, ds));
-  if (er::mha_set_lds(reinterpret_cast<const void*>(er::mha_fwd_kernel), bytes)) return 1;
-  const unsigned grid = static_cast<unsigned>(a.units < er::kMhaMaxGrid ? a.units : er::kMhaMaxGrid);
-  hipLaunchKernelGGL(er::mha_fwd_kernel, dim3(grid), dim3(er::kMhaThreads), bytes, er::as_stream(stream), a);
-  ER_LAUNCH_CHECK();
-  return 0;
-}
-
-int er_mha_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
-               const int32_t* to_mask, const float* dctx, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds,
-               float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, er_stream_t stream) {
-  ER_REQUIRE(q && k && v && dctx && dq && dk && dv && B > 0, "er_mha_bwd: bad arguments");
-  ER_REQUIRE(er::mha_shape_ok(F, T, H, ds), "er_mha_bwd: F = %d, T = %d, H = %d, ds = %d outside the envelope", F, T, H, ds);
-  const int64_t d = static_cast<int64_t>(H) * ds;
-  ER_REQUIRE(ldq >= d && ldk >= d && ldv >= d && lddq >= d && lddk >= d && lddv >= d,
-             "er_mha_bwd: a row pitch is below H * ds = %lld", static_cast<long long>(d));
+  ER_REQUIRE(ldq >= d && ldk >= d && ldv >= d && (!bwd || (lddq >= d && lddk >= d && lddv >= d)),
+             "%s: a row pitch is below H * ds = %lld", what, static_cast<long long>(d));
   er::MhaArgs a = {};
   a.q = q;
   a.k = k;
   a.v = v;
   a.dctx = dctx;
   a.mask = to_mask;
+  a.ctx = ctx;
   a.dq = dq;
   a.dk = dk;
   a.dv = dv;
@@ -834,14 +798,38 @@ int er_mha_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const f
     if (ldq % 4 == 0 && er::aligned16(q)) a.vec |= 1;
     if (ldk % 4 == 0 && er::aligned16(k)) a.vec |= 2;
     if (ldv % 4 == 0 && er::aligned16(v)) a.vec |= 4;
-    if (er::aligned16(dctx)) a.vec |= 8;  // (its pitch H * ds is a multiple of 4 with ds)
+    if (bwd && er::aligned16(dctx)) a.vec |= 8;  // (its pitch H * ds is a multiple of 4 with ds)
   }
-  const int bytes = static_cast<int>(4 * er::mha_bwd_floats(F, T, ds));
-  if (er::mha_set_lds(reinterpret_cast<const void*>(er::mha_bwd_kernel), bytes)) return 1;
-  const unsigned grid = static_cast<unsigned>(a.units < er::kMhaMaxGrid ? a.units : er::kMhaMaxGrid);
-  hipLaunchKernelGGL(er::mha_bwd_kernel, dim3(grid), dim3(er::kMhaThreads), bytes, er::as_stream(stream), a);
+  const int unit_floats = static_cast<int>(bwd ? er::mha_bwd_floats(F, T, ds) : er::mha_fwd_floats(F, T, ds));
+  const int bytes = 4 * unit_floats * G;
+  const int64_t passes = er::ceil_div(a.units, static_cast<int64_t>(G));
+  const dim3 grid(static_cast<unsigned>(passes < er::kMhaMaxGrid ? passes : er::kMhaMaxGrid)), block(er::kMhaThreads);
+  const hipStream_t s = er::as_stream(stream);
+  if (group) {
+    const auto fn = bwd ? er::mha_group_bwd_kernel : er::mha_group_fwd_kernel;
+    if (er::mha_set_lds(reinterpret_cast<const void*>(fn), bytes)) return 1;
+    hipLaunchKernelGGL(fn, grid, block, bytes, s, a, G, unit_floats);
+  } else {
+    const auto fn = bwd ? er::mha_bwd_kernel : er::mha_fwd_kernel;
+    if (er::mha_set_lds(reinterpret_cast<const void*>(fn), bytes)) return 1;
+    hipLaunchKernelGGL(fn, grid, block, bytes, s, a);
+  }
   ER_LAUNCH_CHECK();
   return 0;
+}
+
+int er_mha_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+               const int32_t* to_mask, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds, float* ctx,
+               er_stream_t stream) {
+  return mha_launch("er_mha_fwd", false, false, q, ldq, k, ldk, v, ldv, to_mask, nullptr, B, F, T, H, ds, ctx, nullptr, 0,
+                    nullptr, 0, nullptr, 0, stream);
+}
+
+int er_mha_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+               const int32_t* to_mask, const float* dctx, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds,
+               float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, er_stream_t stream) {
+  return mha_launch("er_mha_bwd", true, false, q, ldq, k, ldk, v, ldv, to_mask, dctx, B, F, T, H, ds, nullptr, dq, lddq, dk,
+                    lddk, dv, lddv, stream);
 }
 
 int32_t er_mha_group_units(int32_t F, int32_t T, int32_t ds) { return er::mha_group_units(F, T, ds); }
@@ -849,84 +837,15 @@ int32_t er_mha_group_units(int32_t F, int32_t T, int32_t ds) { return er::mha_gr
 int er_mha_group_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
                      const int32_t* to_mask, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds, float* ctx,
                      er_stream_t stream) {
-  ER_REQUIRE(q && k && v && ctx && B > 0, "er_mha_group_fwd: bad arguments");
-  ER_REQUIRE(er::mha_shape_ok(F, T, H, ds), "er_mha_group_fwd: F = %d, T = %d, H = %d, ds = %d outside the envelope", F, T, H,
-             ds);
-  const int G = er::mha_group_units(F, T, ds);
-  ER_REQUIRE(G >= 2, "er_mha_group_fwd: F = %d, T = %d, ds = %d leaves room for one unit per workgroup", F, T, ds);
-  const int64_t d = static_cast<int64_t>(H) * ds;
-  ER_REQUIRE(ldq >= d && ldk >= d && ldv >= d, "er_mha_group_fwd: a row pitch is below H * ds = %lld",
-             static_cast<long long>(d));
-  er::MhaArgs a = {};
-  a.q = q;
-  a.k = k;
-  a.v = v;
-  a.mask = to_mask;
-  a.ctx = ctx;
-  a.ldq = ldq;
-  a.ldk = ldk;
-  a.ldv = ldv;
-  a.units = B * H;
-  a.g = er::mha_geom(F, T, H, ds);
-  if (ds % 4 == 0) {
-    if (ldq % 4 == 0 && er::aligned16(q)) a.vec |= 1;
-    if (ldk % 4 == 0 && er::aligned16(k)) a.vec |= 2;
-    if (ldv % 4 == 0 && er::aligned16(v)) a.vec |= 4;
-  }
-  const int unit_floats = static_cast<int>(er::mha_fwd_floats(F, T, ds));
-  const int bytes = 4 * unit_floats * G;
-  if (er::mha_set_lds(reinterpret_cast<const void*>(er::mha_group_fwd_kernel), bytes)) return 1;
-  const int64_t passes = er::ceil_div(a.units, static_cast<int64_t>(G));
-  const unsigned grid = static_cast<unsigned>(passes < er::kMhaMaxGrid ? passes : er::kMhaMaxGrid);
-  hipLaunchKernelGGL(er::mha_group_fwd_kernel, dim3(grid), dim3(er::kMhaThreads), bytes, er::as_stream(stream), a, G,
-                     unit_floats);
-  ER_LAUNCH_CHECK();
-  return 0;
+  return mha_launch("er_mha_group_fwd", false, true, q, ldq, k, ldk, v, ldv, to_mask, nullptr, B, F, T, H, ds, ctx, nullptr,
+                    0, nullptr, 0, nullptr, 0, stream);
 }
 
 int er_mha_group_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
                      const int32_t* to_mask, const float* dctx, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds,
                      float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv, int64_t lddv, er_stream_t stream) {
-  ER_REQUIRE(q && k && v && dctx && dq && dk && dv && B > 0, "er_mha_group_bwd: bad arguments");
-  ER_REQUIRE(er::mha_shape_ok(F, T, H, ds), "er_mha_group_bwd: F = %d, T = %d, H = %d, ds = %d outside the envelope", F, T, H,
-             ds);
-  const int G = er::mha_group_units(F, T, ds);
-  ER_REQUIRE(G >= 2, "er_mha_group_bwd: F = %d, T = %d, ds = %d leaves room for one unit per workgroup", F, T, ds);
-  const int64_t d = static_cast<int64_t>(H) * ds;
-  ER_REQUIRE(ldq >= d && ldk >= d && ldv >= d && lddq >= d && lddk >= d && lddv >= d,
-             "er_mha_group_bwd: a row pitch is below H * ds = %lld", static_cast<long long>(d));
-  er::MhaArgs a = {};
-  a.q = q;
-  a.k = k;
-  a.v = v;
-  a.dctx = dctx;
-  a.mask = to_mask;
-  a.dq = dq;
-  a.dk = dk;
-  a.dv = dv;
-  a.ldq = ldq;
-  a.ldk = ldk;
-  a.ldv = ldv;
-  a.lddq = lddq;
-  a.lddk = lddk;
-  a.lddv = lddv;
-  a.units = B * H;
-  a.g = er::mha_geom(F, T, H, ds);
-  if (ds % 4 == 0) {
-    if (ldq % 4 == 0 && er::aligned16(q)) a.vec |= 1;
-    if (ldk % 4 == 0 && er::aligned16(k)) a.vec |= 2;
-    if (ldv % 4 == 0 && er::aligned16(v)) a.vec |= 4;
-    if (er::aligned16(dctx)) a.vec |= 8;  // (its pitch H * ds is a multiple of 4 with ds)
-  }
-  const int unit_floats = static_cast<int>(er::mha_bwd_floats(F, T, ds));
-  const int bytes = 4 * unit_floats * G;
-  if (er::mha_set_lds(reinterpret_cast<const void*>(er::mha_group_bwd_kernel), bytes)) return 1;
-  const int64_t passes = er::ceil_div(a.units, static_cast<int64_t>(G));
-  const unsigned grid = static_cast<unsigned>(passes < er::kMhaMaxGrid ? passes : er::kMhaMaxGrid);
-  hipLaunchKernelGGL(er::mha_group_bwd_kernel, dim3(grid), dim3(er::kMhaThreads), bytes, er::as_stream(stream), a, G,
-                     unit_floats);
-  ER_LAUNCH_CHECK();
-  return 0;
+  return mha_launch("er_mha_group_bwd", true, true, q, ldq, k, ldk, v, ldv, to_mask, dctx, B, F, T, H, ds, nullptr, dq, lddq,
+                    dk, lddk, dv, lddv, stream);
 }
 
 static int segment_mean_check(const char* what, const void* a, const void* seg_begin, const void* b, int64_t B, int32_t S,

@@ -1933,37 +1933,46 @@ class HipBackend(object):
         t.dtype == torch.float32, '%s: [%d, %d] fp32 rows with unit inner stride expected' % (what, rows, d)
     return t
 
+  def _mha_fwd(self, group, q, k, v, to_mask, B, F, T, H, ds):
+    """mha_fwd (group False) | mha_group_fwd (True): the checks, the launch and the op-log line of both."""
+    name, entry = ('mha_group_fwd', self.ck.er_mha_group_fwd) if group else ('mha_fwd', self.ck.er_mha_fwd)
+    d = H * ds
+    self._mha_operand(q, B * F, d, name + ' q')
+    self._mha_operand(k, B * T, d, name + ' k')
+    self._mha_operand(v, B * T, d, name + ' v')
+    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
+    ctx = torch.empty(B * F, d, dtype=torch.float32, device=q.device)
+    entry(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), B, F, T, H, ds, _p(ctx), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::%s_kernel' % name, 4.0 * B * F * T * d))
+    return ctx
+
+  def _mha_bwd(self, group, q, k, v, to_mask, dctx, B, F, T, H, ds, dq, dk, dv):
+    """mha_bwd (group False) | mha_group_bwd (True)."""
+    name, entry = ('mha_group_bwd', self.ck.er_mha_group_bwd) if group else ('mha_bwd', self.ck.er_mha_bwd)
+    d = H * ds
+    self._mha_operand(q, B * F, d, name + ' q')
+    self._mha_operand(k, B * T, d, name + ' k')
+    self._mha_operand(v, B * T, d, name + ' v')
+    self._mha_operand(dq, B * F, d, name + ' dq')
+    self._mha_operand(dk, B * T, d, name + ' dk')
+    self._mha_operand(dv, B * T, d, name + ' dv')
+    assert dctx.shape == (B * F, d)
+    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
+    entry(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), _p(_f32c(dctx)), B, F, T, H, ds,
+          _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv), dv.stride(0), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::%s_kernel' % name, 12.0 * B * F * T * d))
+
   def mha_fwd(self, q, k, v, to_mask, B, F, T, H, ds):
     """q [B * F, H ds], k, v [B * T, H ds]: 2-D fp32 views with unit inner stride (column blocks of a packed buffer or
     tensors of their own), to_mask int32 [B, T] or None -> ctx [B * F, H ds] = concat_h softmax(Q_h K_h^T / sqrt(ds)
     + adder) V_h."""
-    d = H * ds
-    self._mha_operand(q, B * F, d, 'mha_fwd q')
-    self._mha_operand(k, B * T, d, 'mha_fwd k')
-    self._mha_operand(v, B * T, d, 'mha_fwd v')
-    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
-    ctx = torch.empty(B * F, d, dtype=torch.float32, device=q.device)
-    self.ck.er_mha_fwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), B, F, T, H, ds, _p(ctx),
-                       _stream())
-    if self.op_log is not None:
-      self.op_log.append(('er::mha_fwd_kernel', 4.0 * B * F * T * d))
-    return ctx
+    return self._mha_fwd(False, q, k, v, to_mask, B, F, T, H, ds)
 
   def mha_bwd(self, q, k, v, to_mask, dctx, B, F, T, H, ds, dq, dk, dv):
     """dq [B * F, H ds], dk, dv [B * T, H ds] (views as above, written) from dctx [B * F, H ds] (contiguous)."""
-    d = H * ds
-    self._mha_operand(q, B * F, d, 'mha_bwd q')
-    self._mha_operand(k, B * T, d, 'mha_bwd k')
-    self._mha_operand(v, B * T, d, 'mha_bwd v')
-    self._mha_operand(dq, B * F, d, 'mha_bwd dq')
-    self._mha_operand(dk, B * T, d, 'mha_bwd dk')
-    self._mha_operand(dv, B * T, d, 'mha_bwd dv')
-    assert dctx.shape == (B * F, d)
-    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
-    self.ck.er_mha_bwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), _p(_f32c(dctx)), B, F,
-                       T, H, ds, _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv), dv.stride(0), _stream())
-    if self.op_log is not None:
-      self.op_log.append(('er::mha_bwd_kernel', 12.0 * B * F * T * d))
+    self._mha_bwd(False, q, k, v, to_mask, dctx, B, F, T, H, ds, dq, dk, dv)
 
   def mha_group_units(self, F, T, ds):
     """Units per workgroup of the grouped attention launches: 8, 4 or 2; 1: only one fits; 0: outside the envelope."""
@@ -1971,33 +1980,11 @@ class HipBackend(object):
 
   def mha_group_fwd(self, q, k, v, to_mask, B, F, T, H, ds):
     """mha_fwd's arguments and result bits, several (example, head) units per workgroup (mha_group_units >= 2)."""
-    d = H * ds
-    self._mha_operand(q, B * F, d, 'mha_group_fwd q')
-    self._mha_operand(k, B * T, d, 'mha_group_fwd k')
-    self._mha_operand(v, B * T, d, 'mha_group_fwd v')
-    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
-    ctx = torch.empty(B * F, d, dtype=torch.float32, device=q.device)
-    self.ck.er_mha_group_fwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), B, F, T, H, ds,
-                             _p(ctx), _stream())
-    if self.op_log is not None:
-      self.op_log.append(('er::mha_group_fwd_kernel', 4.0 * B * F * T * d))
-    return ctx
+    return self._mha_fwd(True, q, k, v, to_mask, B, F, T, H, ds)
 
   def mha_group_bwd(self, q, k, v, to_mask, dctx, B, F, T, H, ds, dq, dk, dv):
     """mha_bwd's arguments and result bits, several units per workgroup."""
-    d = H * ds
-    self._mha_operand(q, B * F, d, 'mha_group_bwd q')
-    self._mha_operand(k, B * T, d, 'mha_group_bwd k')
-    self._mha_operand(v, B * T, d, 'mha_group_bwd v')
-    self._mha_operand(dq, B * F, d, 'mha_group_bwd dq')
-    self._mha_operand(dk, B * T, d, 'mha_group_bwd dk')
-    self._mha_operand(dv, B * T, d, 'mha_group_bwd dv')
-    assert dctx.shape == (B * F, d)
-    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
-    self.ck.er_mha_group_bwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), _p(_f32c(dctx)), B,
-                             F, T, H, ds, _p(dq), dq.stride(0), _p(dk), dk.stride(0), _p(dv), dv.stride(0), _stream())
-    if self.op_log is not None:
-      self.op_log.append(('er::mha_group_bwd_kernel', 12.0 * B * F * T * d))
+    self._mha_bwd(True, q, k, v, to_mask, dctx, B, F, T, H, ds, dq, dk, dv)
 
   SEGMENT_MEAN_MAX_W = 4096
   SEGMENT_MEAN_MAX_S = 4096
