@@ -1558,7 +1558,8 @@ emb_bwd_own_wgrad_kernel(OwnMulti ma, GroupedArgs ga, int n_gemm, int n_own, Los
   if (bid < n_gemm) {
     const GroupedCoords c = grouped_coords(ga, bid);
     if (c.split < 0) return;
-    gemm_f32_block<false, false>(ga.p[c.p], c.tile, c.split, smem, c.plain);
+    // (PINNED: the k loop's pinned issue order, er_gemm_core.h - this launch's contraction 50.1 -> 47.8 us)
+    gemm_f32_block<false, false, false, 0, 0, true>(ga.p[c.p], c.tile, c.split, smem, c.plain);
     return;
   }
   if (bid - n_gemm < n_own) own_block(bid - n_gemm, ma, smem);

@@ -39,6 +39,26 @@ gemm_f32_bn_bwd_kernel(GemmArgs g) {
   gemm_f32_block<A_KC, B_KC, true>(g, blockIdx.x, 0, lds);
 }
 
+// The same two with the k loop's issue order pinned (er_gemm_core.h, kPinnedMaxWorkgroups: launch_gemm takes them for
+// launches of at most one workgroup per compute unit).  Overloads, told apart by a tag argument and not by a name of their
+// own: the benchmark attributes a launch's FLOPs to a profiled kernel whose name CONTAINS the logged
+// `er::gemm_f32_kernel<..>`, which a renamed kernel or one more template argument would no longer do; a profiler shows them
+// as `gemm_f32_kernel<..>(er::GemmArgs, er::PinnedOrder)`.
+struct PinnedOrder {};
+template <bool A_KC, bool B_KC>
+__global__ void __launch_bounds__(kBlock)
+gemm_f32_kernel(GemmArgs g, PinnedOrder) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * 2 * kOpTile];
+  gemm_f32_block<A_KC, B_KC, false, 0, 0, true>(g, blockIdx.x, blockIdx.z, lds);
+}
+
+template <bool A_KC, bool B_KC>
+__global__ void __launch_bounds__(kBlock, 4)  // (four workgroups per CU, as the LDS allows: at most 128 registers)
+gemm_f32_bn_bwd_kernel(GemmArgs g, PinnedOrder) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * 2 * kOpTile];
+  gemm_f32_block<A_KC, B_KC, true, 0, 0, true>(g, blockIdx.x, 0, lds);
+}
+
 // ... with the DCN-v2 cross layer's elementwise part in the epilogue (er_gemm_f32_cross)
 template <bool A_KC, bool B_KC, int XEPI>
 __global__ void __launch_bounds__(kBlock)
@@ -487,13 +507,22 @@ int launch_gemm(int layout, er::GemmArgs& a, hipStream_t s) {
     case ER_GEMM_TN: hipLaunchKernelGGL((KERNEL<false, false>), grid, block, 0, s, a); break; \
     default: er::set_error("er_gemm: unknown layout %d", layout); return 2;     \
   }
+#define ER_LAUNCH_GEMM_PINNED(KERNEL)                                              \
+  switch (layout) {                                                              \
+    case ER_GEMM_NN: hipLaunchKernelGGL((KERNEL<true, false>), grid, block, 0, s, a, er::PinnedOrder()); break;  \
+    case ER_GEMM_NT: hipLaunchKernelGGL((KERNEL<true, true>), grid, block, 0, s, a, er::PinnedOrder()); break;   \
+    case ER_GEMM_TN: hipLaunchKernelGGL((KERNEL<false, false>), grid, block, 0, s, a, er::PinnedOrder()); break; \
+    default: er::set_error("er_gemm: unknown layout %d", layout); return 2;     \
+  }
+  const bool pinned = n_tiles * a.splits <= er::kPinnedMaxWorkgroups;  // (the same arithmetic, the same bits either way)
   if (BF16) {
     ER_LAUNCH_GEMM(er::gemm_bf16_kernel)
   } else if (a.bn.partial) {
-    ER_LAUNCH_GEMM(er::gemm_f32_bn_bwd_kernel)
+    if (pinned) { ER_LAUNCH_GEMM_PINNED(er::gemm_f32_bn_bwd_kernel) } else { ER_LAUNCH_GEMM(er::gemm_f32_bn_bwd_kernel) }
   } else {
-    ER_LAUNCH_GEMM(er::gemm_f32_kernel)
+    if (pinned) { ER_LAUNCH_GEMM_PINNED(er::gemm_f32_kernel) } else { ER_LAUNCH_GEMM(er::gemm_f32_kernel) }
   }
+#undef ER_LAUNCH_GEMM_PINNED
 #undef ER_LAUNCH_GEMM
   ER_LAUNCH_CHECK();
   return 0;

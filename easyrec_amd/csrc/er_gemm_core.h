@@ -2,6 +2,8 @@
 // with the launches that carry a GEMM next to other work in ONE grid (er_embedding.hip: the weight gradients of a step
 // beside the embedding row update).  Design notes: er_gemm.hip.
 #pragma once
+#include <type_traits>
+
 #include "er_common.h"
 
 namespace er {
@@ -260,6 +262,12 @@ __device__ __forceinline__ void tile_bn_bwd_partial(const f32x16& acc, const BnB
 // k-tiles to hide in.  Interior tiles take branch-free loads; edge tiles (uniform test) masked scalar loads.
 // ------------------------------------------------------------------------------------------------
 constexpr int SK = BK32 + 4;      // floats per LDS row
+// The k loop of gemm_f32_block exists with the compiler's issue order and with a pinned one (PINNED).  The pinned one is for
+// workgroups that have a SIMD to themselves: the plain and BatchNorm-backward single-problem launches of at most this many
+// workgroups - one per compute unit - and the single-GPU step's tail take it, where it measured faster; every other
+// instantiation and size keeps the compiler's, because where several waves share a SIMD they fill each other's waits and
+// the pinned order measured 1 - 6 % slower.
+constexpr int kPinnedMaxWorkgroups = 256;
 constexpr int kOpTile = BM * SK;  // floats per operand tile (BM == BN)
 
 // A thread's unit i (0 / 1) of an operand tile: 4 elements that are consecutive in HBM.
@@ -281,81 +289,85 @@ __device__ __forceinline__ void unit_pos(int tid, int i, int& row, int& k) {
 // Branch-free 16-byte loads of a thread's 2 units: indices outside the operand are clamped to a valid address and
 // the values zeroed later, in stage_tile (NOT here: a use of the loaded value would wait for the load).  Needs
 // ld % 4 == 0 and a 16-byte aligned base; the extent along the contiguous dimension rounded up to 4 is <= ld.
+// (per unit i: the pinned k loop issues a tile's loads one at a time, each behind an MFMA of its own)
 template <bool KC>
-__device__ __forceinline__ void fetch_tile(const float* __restrict__ P, int ld, int mn0, int MN, int k0, int kend,
-                                           int K, int tid, f32x4v (&r)[2]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int row, k;
-    unit_pos<KC>(tid, i, row, k);
-    int mn = mn0 + row;
-    k += k0;
-    if (KC) {
-      const int kpad = (K + 3) & ~3;
-      mn = mn < MN ? mn : MN - 1;
-      k = k < kpad - 4 ? k : kpad - 4;
-      r[i] = *reinterpret_cast<const f32x4v*>(P + static_cast<int64_t>(mn) * ld + k);
-    } else {
-      const int mnpad = (MN + 3) & ~3;
-      mn = mn < mnpad - 4 ? mn : mnpad - 4;
-      k = k < kend ? k : kend - 1;
-      r[i] = *reinterpret_cast<const f32x4v*>(P + static_cast<int64_t>(k) * ld + mn);
-    }
+__device__ __forceinline__ void fetch_unit(const float* __restrict__ P, int ld, int mn0, int MN, int k0, int kend,
+                                           int K, int tid, int i, f32x4v& r) {
+  int row, k;
+  unit_pos<KC>(tid, i, row, k);
+  int mn = mn0 + row;
+  k += k0;
+  if (KC) {
+    const int kpad = (K + 3) & ~3;
+    mn = mn < MN ? mn : MN - 1;
+    k = k < kpad - 4 ? k : kpad - 4;
+    r = *reinterpret_cast<const f32x4v*>(P + static_cast<int64_t>(mn) * ld + k);
+  } else {
+    const int mnpad = (MN + 3) & ~3;
+    mn = mn < mnpad - 4 ? mn : mnpad - 4;
+    k = k < kend ? k : kend - 1;
+    r = *reinterpret_cast<const f32x4v*>(P + static_cast<int64_t>(k) * ld + mn);
   }
 }
 
 // Generic loads (any alignment): masked scalar loads, used by the non-pipelined loop only.
 template <bool KC>
+__device__ __forceinline__ void fetch_unit_generic(const float* __restrict__ P, int ld, int mn0, int MN, int k0,
+                                                   int kend, int tid, int i, f32x4v& r) {
+  int row, k;
+  unit_pos<KC>(tid, i, row, k);
+  const int mn = mn0 + row;
+  k += k0;
+  // branch-free: an element outside the operand is loaded from a clamped (valid) address and zeroed by a select - a load
+  // inside `if (inside)` is waited for inside its branch (s_waitcnt vmcnt(0) behind every global_load_dword in the ISA):
+  // 16 dependent round trips per thread and k-tile on e.g. DeepFM's [B, 81] -> 256 layer (lda = 81)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    bool ok;
+    int64_t at;
+    if (KC) {
+      ok = mn < MN && k + j < kend;
+      at = static_cast<int64_t>(mn < MN ? mn : MN - 1) * ld + (k + j < kend ? k + j : kend - 1);
+    } else {
+      ok = mn + j < MN && k < kend;
+      at = static_cast<int64_t>(k < kend ? k : kend - 1) * ld + (mn + j < MN ? mn + j : MN - 1);
+    }
+    const float v = P[at];
+    r[j] = ok ? v : 0.f;
+  }
+}
+template <bool KC>
 __device__ __forceinline__ void fetch_tile_generic(const float* __restrict__ P, int ld, int mn0, int MN, int k0,
                                                    int kend, int tid, f32x4v (&r)[2]) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int row, k;
-    unit_pos<KC>(tid, i, row, k);
-    const int mn = mn0 + row;
-    k += k0;
-    // branch-free: an element outside the operand is loaded from a clamped (valid) address and zeroed by a select - a load
-    // inside `if (inside)` is waited for inside its branch (s_waitcnt vmcnt(0) behind every global_load_dword in the ISA):
-    // 16 dependent round trips per thread and k-tile on e.g. DeepFM's [B, 81] -> 256 layer (lda = 81)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      bool ok;
-      int64_t at;
-      if (KC) {
-        ok = mn < MN && k + j < kend;
-        at = static_cast<int64_t>(mn < MN ? mn : MN - 1) * ld + (k + j < kend ? k + j : kend - 1);
-      } else {
-        ok = mn + j < MN && k < kend;
-        at = static_cast<int64_t>(k < kend ? k : kend - 1) * ld + (mn + j < MN ? mn + j : MN - 1);
-      }
-      const float v = P[at];
-      r[i][j] = ok ? v : 0.f;
-    }
-  }
+  for (int i = 0; i < 2; ++i) fetch_unit_generic<KC>(P, ld, mn0, MN, k0, kend, tid, i, r[i]);
 }
 
+template <bool KC>
+__device__ __forceinline__ void stage_unit(float* __restrict__ S, int tid, int i, const f32x4v& r, bool interior, int mn0,
+                                           int MN, int k0, int kend) {
+  int row, k;
+  unit_pos<KC>(tid, i, row, k);
+  f32x4v v = r;
+  if (!interior) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool ok = KC ? (mn0 + row < MN && k0 + k + j < kend) : (mn0 + row + j < MN && k0 + k < kend);
+      if (!ok) v[j] = 0.f;
+    }
+  }
+  if (KC) {
+    *reinterpret_cast<f32x4v*>(&S[row * SK + k]) = v;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) S[(row + j) * SK + k] = v[j];
+  }
+}
 template <bool KC>
 __device__ __forceinline__ void stage_tile(float* __restrict__ S, int tid, const f32x4v (&r)[2], bool interior, int mn0,
                                            int MN, int k0, int kend) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int row, k;
-    unit_pos<KC>(tid, i, row, k);
-    f32x4v v = r[i];
-    if (!interior) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool ok = KC ? (mn0 + row < MN && k0 + k + j < kend) : (mn0 + row + j < MN && k0 + k < kend);
-        if (!ok) v[j] = 0.f;
-      }
-    }
-    if (KC) {
-      *reinterpret_cast<f32x4v*>(&S[row * SK + k]) = v;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) S[(row + j) * SK + k] = v[j];
-    }
-  }
+  for (int i = 0; i < 2; ++i) stage_unit<KC>(S, tid, i, r[i], interior, mn0, MN, k0, kend);
 }
 
 // DIN's attention input [q, h, q - h, q * h] ([B * L, 4E], reference model/multi_tower_din.py:62-80) as a GENERATED operand:
@@ -432,24 +444,21 @@ __device__ __forceinline__ void din_prepare(const DinGen& d, int mn0, int MN, in
 }
 // loads of a thread's 2 units of the GENERATED A tile (clamped like fetch_tile; the values are combined at staging)
 template <bool KC>
-__device__ __forceinline__ void fetch_din(const DinGen& d, const DinPre& p, int k0, int kend, int K, f32x4v (&rh)[2],
-                                          f32x4v (&rq)[2]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    if (KC) {
-      int c = k0 + p.off[i];
-      c = c < K - 4 ? c : K - 4;
-      const int seg = static_cast<int>((static_cast<uint64_t>(static_cast<uint32_t>(c)) * d.inv_E) >> 32);
-      const int j = c - seg * d.E;
-      rq[i] = *reinterpret_cast<const f32x4v*>(p.qp[i] + j);
-      rh[i] = *reinterpret_cast<const f32x4v*>(p.hp[i] + j);
-    } else {
-      int r = k0 + p.off[i];
-      r = r < kend ? r : kend - 1;
-      const int b = din_div_L(d, r);
-      rq[i] = *reinterpret_cast<const f32x4v*>(p.qp[i] + static_cast<int64_t>(b) * d.ldq);
-      rh[i] = *reinterpret_cast<const f32x4v*>(p.hp[i] + static_cast<int64_t>(r) * d.ldh);
-    }
+__device__ __forceinline__ void fetch_din_unit(const DinGen& d, const DinPre& p, int k0, int kend, int K, int i,
+                                               f32x4v (&rh)[2], f32x4v (&rq)[2]) {
+  if (KC) {
+    int c = k0 + p.off[i];
+    c = c < K - 4 ? c : K - 4;
+    const int seg = static_cast<int>((static_cast<uint64_t>(static_cast<uint32_t>(c)) * d.inv_E) >> 32);
+    const int j = c - seg * d.E;
+    rq[i] = *reinterpret_cast<const f32x4v*>(p.qp[i] + j);
+    rh[i] = *reinterpret_cast<const f32x4v*>(p.hp[i] + j);
+  } else {
+    int r = k0 + p.off[i];
+    r = r < kend ? r : kend - 1;
+    const int b = din_div_L(d, r);
+    rq[i] = *reinterpret_cast<const f32x4v*>(p.qp[i] + static_cast<int64_t>(b) * d.ldq);
+    rh[i] = *reinterpret_cast<const f32x4v*>(p.hp[i] + static_cast<int64_t>(r) * d.ldh);
   }
 }
 template <bool KC>
@@ -468,18 +477,15 @@ __device__ __forceinline__ void combine_din(const DinGen& d, const DinPre& p, in
 }
 // B rows of the input-gradient contraction in the permuted order: tile column c' of column tile tx is concat column
 // (c' / 16) * E + tx * 16 + c' % 16 (all four segments of 16 embedding positions in one 64-column tile)
-__device__ __forceinline__ void fetch_tile_din_perm(const float* __restrict__ P, int ld, int tx, int E, int k0, int kend, int K,
-                                                    int tid, f32x4v (&r)[2]) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int row, k;
-    unit_pos<true>(tid, i, row, k);
-    const int n = (row >> 4) * E + tx * 16 + (row & 15);
-    k += k0;
-    const int kpad = (K + 3) & ~3;
-    k = k < kpad - 4 ? k : kpad - 4;
-    r[i] = *reinterpret_cast<const f32x4v*>(P + static_cast<int64_t>(n) * ld + k);
-  }
+__device__ __forceinline__ void fetch_unit_din_perm(const float* __restrict__ P, int ld, int tx, int E, int k0, int kend, int K,
+                                                    int tid, int i, f32x4v& r) {
+  int row, k;
+  unit_pos<true>(tid, i, row, k);
+  const int n = (row >> 4) * E + tx * 16 + (row & 15);
+  k += k0;
+  const int kpad = (K + 3) & ~3;
+  k = k < kpad - 4 ? k : kpad - 4;
+  r = *reinterpret_cast<const f32x4v*>(P + static_cast<int64_t>(n) * ld + k);
 }
 
 // The A operand as the PRODUCING layer's pre-normalisation values z with that layer's BatchNorm + activation applied while
@@ -539,7 +545,8 @@ __device__ __forceinline__ void bna_apply(const BnA& b, const float* __restrict_
 // DIN: 1 = the A operand is DinGen's generated block (forward NN, weight gradient TN); 2 = the input-gradient contraction
 // (NT) with permuted B rows and the epilogue that reduces dcat to dh / dq partials (nothing is stored to C); 3 = the A
 // operand is a BatchNorm'd layer's z, normalised while staging (BnA *ba, its coefficient table `coef` in LDS; NN, K % 4 == 0).
-template <bool A_KC, bool B_KC, bool BN_EPI = false, int XEPI = 0, int DIN = 0>
+// PINNED: the k loop's issue order - pinned by scheduling fences, or (false) left to the compiler; kPinnedMaxWorkgroups, above.
+template <bool A_KC, bool B_KC, bool BN_EPI = false, int XEPI = 0, int DIN = 0, bool PINNED = false>
 __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz, float* __restrict__ lds,
                                                bool plain_tiles = false, const er_gemm_epilogue* xe = nullptr,
                                                const DinGen* dg = nullptr, const BnA* ba = nullptr,
@@ -631,21 +638,38 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
     if (DIN == 1) din_prepare<A_KC>(*dg, m0, g.M, tid, dpre);
     // k-tile indices past the end are clamped to the last tile: the loop body has the same loads every
     // iteration (the compiler can then wait for exactly the older register set), the duplicate tile is never used
-    auto fetch = [&](f32x4v (&ra)[2], f32x4v (&rb)[2], f32x4v (&rq)[2], int t) {
+    // (in pieces - A's unit 0 / 1, B's unit 0 / 1 - because the pinned step issues them one at a time)
+    auto fetch_part = [&](f32x4v (&ra)[2], f32x4v (&rb)[2], f32x4v (&rq)[2], int t, int part) {
       const int k0 = kbeg + (t < T ? t : T - 1) * BK32;
-      if (DIN == 1) fetch_din<A_KC>(*dg, dpre, k0, kend, g.K, ra, rq);
-      else fetch_tile<A_KC>(g.A, g.lda, m0, g.M, k0, kend, g.K, tid, ra);
-      if (DIN == 2) fetch_tile_din_perm(g.B, g.ldb, tx, dg->E, k0, kend, g.K, tid, rb);
-      else if (DIN == 3 && !b_vec) fetch_tile_generic<B_KC>(g.B, g.ldb, n0, g.N, k0, kend, tid, rb);  // (e.g. a [K, 1] weight)
-      else fetch_tile<B_KC>(g.B, g.ldb, n0, g.N, k0, kend, g.K, tid, rb);
+      const int i = part & 1;
+      if (part < 2) {
+        if (DIN == 1) fetch_din_unit<A_KC>(*dg, dpre, k0, kend, g.K, i, ra, rq);
+        else fetch_unit<A_KC>(g.A, g.lda, m0, g.M, k0, kend, g.K, tid, i, ra[i]);
+      } else {
+        if (DIN == 2) fetch_unit_din_perm(g.B, g.ldb, tx, dg->E, k0, kend, g.K, tid, i, rb[i]);
+        else if (DIN == 3 && !b_vec) fetch_unit_generic<B_KC>(g.B, g.ldb, n0, g.N, k0, kend, tid, i, rb[i]);
+        else fetch_unit<B_KC>(g.B, g.ldb, n0, g.N, k0, kend, g.K, tid, i, rb[i]);
+      }
+    };
+    auto stage_part = [&](int buf, f32x4v (&ra)[2], const f32x4v (&rb)[2], const f32x4v (&rq)[2], int t, int part,
+                          bool interior) {
+      const int k0 = kbeg + t * BK32;  // unclamped: a tile past the end is masked to zero
+      const int i = part & 1;
+      if (part == 0) {
+        if (DIN == 1) combine_din<A_KC>(*dg, dpre, kbeg + (t < T ? t : T - 1) * BK32, g.K, ra, rq);
+        if (DIN == 3) bna_apply(*ba, coef, tid, m0, g.M, kbeg + (t < T ? t : T - 1) * BK32, g.K, tx == 0 && t < T && ba->y != nullptr, ra);
+      }
+      if (part < 2) stage_unit<A_KC>(lds + buf * 2 * kOpTile, tid, i, ra[i], interior, m0, g.M, k0, kend);
+      else stage_unit<B_KC>(lds + buf * 2 * kOpTile + kOpTile, tid, i, rb[i], interior, n0, g.N, k0, kend);
+    };
+    auto fetch = [&](f32x4v (&ra)[2], f32x4v (&rb)[2], f32x4v (&rq)[2], int t) {
+#pragma unroll
+      for (int part = 0; part < 4; ++part) fetch_part(ra, rb, rq, t, part);
     };
     auto stage = [&](int buf, f32x4v (&ra)[2], const f32x4v (&rb)[2], const f32x4v (&rq)[2], int t) {
-      const int k0 = kbeg + t * BK32;  // unclamped: a tile past the end is masked to zero
-      const bool interior = rows_full && (k0 + BK32 <= kend);
-      if (DIN == 1) combine_din<A_KC>(*dg, dpre, kbeg + (t < T ? t : T - 1) * BK32, g.K, ra, rq);
-      if (DIN == 3) bna_apply(*ba, coef, tid, m0, g.M, kbeg + (t < T ? t : T - 1) * BK32, g.K, tx == 0 && t < T && ba->y != nullptr, ra);
-      stage_tile<A_KC>(lds + buf * 2 * kOpTile, tid, ra, interior, m0, g.M, k0, kend);
-      stage_tile<B_KC>(lds + buf * 2 * kOpTile + kOpTile, tid, rb, interior, n0, g.N, k0, kend);
+      const bool interior = rows_full && (kbeg + t * BK32 + BK32 <= kend);  // (unclamped: a tile past the end is masked to zero)
+#pragma unroll
+      for (int part = 0; part < 4; ++part) stage_part(buf, ra, rb, rq, t, part, interior);
     };
     // One step = one k-tile: read its fragments from LDS stage `buf`, issue the global loads of k-tile t + 2 into
     // the register set that was written to LDS at the end of the previous step, contract, and - after three
@@ -667,11 +691,65 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
     // the input-gradient launches 7.7 -> 9.6 / 8.4 -> 9.6: DeepFM 0.3015 -> 0.3072 ms.  These launches are ~5 us of
     // prologue + epilogue + drain and 0.73 us per k-tile; halving the k-tiles per wave buys less than the second barrier
     // population and the LDS add cost.  profiles/r06_s13_gemm_ksplit_pair_rejected_*.txt)
-    // Fragments are read a quarter of the k-tile at a time, right before their four MFMAs, and the compiler places the
-    // instructions (no scheduling fences): against "every fragment first, fences around the MFMA groups" the bare core
-    // (tools/micro/gemm_core.hip, variants 9 -> 1) gains 10 % on 8192 x 1152 x 256, 7 % on 8192 x 256 x 1152.
-    auto step = [&](int buf, f32x4v (&fa_)[2], f32x4v (&fb_)[2], f32x4v (&fq_)[2], f32x4v (&sa)[2], f32x4v (&sb)[2],
-                    f32x4v (&sq)[2], int t) {
+    // Issue order.  A wave issues in order and every MFMA of a k-tile accumulates into the same registers, so the wave sits
+    // at each MFMA until the one before it has left the pipe (64 cycles): whatever stands BETWEEN two MFMAs in the stream
+    // is issued - and runs - under the first of them, and whatever stands behind a group of four gets the cover of one.
+    // Left to itself the compiler emits the MFMAs in groups of four with the next quarter's fragment reads behind the
+    // group (an LDS round trip under one MFMA, four times per k-tile), and the staging writes, the last quarter's reads,
+    // a wait for all of them and the barrier in one place (tools/mfma_cover.py, profiles/r10_kloop_cover_parent.txt).
+    // The step therefore PINS the order with scheduling fences, one small piece of other work behind each MFMA:
+    //   quarter 0:  m | reads of quarter 1, load 1 of tile t + 2 | m | load 2 | m | m
+    //   quarter 1:  m | reads of quarter 2, load 3               | m | load 4 | m | m
+    //   quarter 2:  m | reads of quarter 3, staging of A's units | m | B's unit 0 | m | B's unit 1 | m
+    //   quarter 3:  m | m | m | wait for the writes, barrier | m
+    // - fragment reads have three MFMAs of cover before their wait (a counted one in front of quarter 3: the LDS returns in
+    // order and the staging writes were issued behind the reads), the staging writes four before the barrier's wait, and
+    // the first reads of the next k-tile, behind the barrier, the last MFMA of this one.  The arithmetic is untouched: the
+    // same MFMAs on the same operands in the same order.  The uniform test "is the staged tile interior" would split the
+    // loop body into basic blocks - a fence orders within one - so the step exists in two forms, the bodies
+    // of two loops: masked = false while both tiles an iteration stages are interior, then masked = true (every element
+    // under its predicate, which an interior tile passes) for the rest.
+#define ER_PIN() __builtin_amdgcn_sched_barrier(0)
+    auto step = [&](auto masked, int buf, f32x4v (&fa_)[2], f32x4v (&fb_)[2], f32x4v (&fq_)[2], f32x4v (&sa)[2],
+                    f32x4v (&sb)[2], f32x4v (&sq)[2], int t) {
+      constexpr bool kInterior = !decltype(masked)::value;
+      const float* base = lds + buf * 2 * kOpTile;
+      f32x4v a[2], b[2];
+      a[0] = *reinterpret_cast<const f32x4v*>(base + fa);
+      b[0] = *reinterpret_cast<const f32x4v*>(base + fb);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4v aq = a[q & 1], bq = b[q & 1];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (q == 3 && i == 3) {  // the staged tile is complete once every wave's writes have landed
+            ER_PIN();
+            __syncthreads();
+            ER_PIN();
+          }
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[i], bq[i], acc, 0, 0, 0);
+          if (q == 3) continue;
+          ER_PIN();
+          if (i == 0) {
+            a[(q + 1) & 1] = *reinterpret_cast<const f32x4v*>(base + fa + 4 * (q + 1));
+            b[(q + 1) & 1] = *reinterpret_cast<const f32x4v*>(base + fb + 4 * (q + 1));
+          }
+          if (q < 2 && i < 2) fetch_part(fa_, fb_, fq_, t + 2, 2 * q + i);
+          if (q == 2 && i == 0) {
+            ER_PIN();  // (the reads stay in front of the writes: their wait is then a counted one)
+            stage_part(buf ^ 1, sa, sb, sq, t + 1, 0, kInterior);
+            stage_part(buf ^ 1, sa, sb, sq, t + 1, 1, kInterior);
+          }
+          if (q == 2 && (i == 1 || i == 2)) stage_part(buf ^ 1, sa, sb, sq, t + 1, i + 1, kInterior);
+          ER_PIN();
+        }
+      }
+    };
+#undef ER_PIN
+    // The same k-tile with the order left to the compiler (PINNED = false, the default): fragments a quarter at a time in
+    // front of their four MFMAs, the staging in front of the last quarter.
+    auto step_free = [&](int buf, f32x4v (&fa_)[2], f32x4v (&fb_)[2], f32x4v (&fq_)[2], f32x4v (&sa)[2], f32x4v (&sb)[2],
+                         f32x4v (&sq)[2], int t) {
       const float* base = lds + buf * 2 * kOpTile;
       fetch(fa_, fb_, fq_, t + 2);
 #pragma unroll
@@ -694,9 +772,24 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
     fetch(ra1, rb1, rq1, 1);
     stage(0, ra0, rb0, rq0, 0);
     __syncthreads();
-    for (int t = 0; t < T; t += 2) {
-      step(0, ra0, rb0, rq0, ra1, rb1, rq1, t);
-      step(1, ra1, rb1, rq1, ra0, rb0, rq0, t + 1);
+    // (two loops, not one loop with two arms: the accumulator then stays in its registers from the first MFMA to the last)
+    int t = 0;
+    if (!PINNED) {
+      for (; t < T; t += 2) {
+        step_free(0, ra0, rb0, rq0, ra1, rb1, rq1, t);
+        step_free(1, ra1, rb1, rq1, ra0, rb0, rq0, t + 1);
+      }
+    } else {
+      if (rows_full) {
+        for (; kbeg + (t + 3) * BK32 <= kend; t += 2) {  // k-tiles t + 1 and t + 2, staged here, are interior
+          step(std::false_type(), 0, ra0, rb0, rq0, ra1, rb1, rq1, t);
+          step(std::false_type(), 1, ra1, rb1, rq1, ra0, rb0, rq0, t + 1);
+        }
+      }
+      for (; t < T; t += 2) {
+        step(std::true_type(), 0, ra0, rb0, rq0, ra1, rb1, rq1, t);
+        step(std::true_type(), 1, ra1, rb1, rq1, ra0, rb0, rq0, t + 1);
+      }
     }
   } else {
     // unaligned operands (e.g. lda = 81): masked scalar loads, one k-tile at a time
