@@ -540,6 +540,16 @@ cast_bf16_kernel(CastMulti cm) {
       const int64_t r = static_cast<int64_t>(tr) * 32 + tx;      // dst col
       if (c < d.cols && r < d.ld_dst) d.dst[static_cast<int64_t>(c) * d.ld_dst + r] = r < d.rows ? f32_to_bf16(tile[tx][k]) : 0;
     }
+    // the padding columns past the last tile, [ceil32(rows), ld_dst), of the same dst rows: zeroed by the blocks of the
+    // last tile row, 32 lanes along a dst row
+    const int tiles_r = (d.rows + 31) / 32;
+    if (tr == tiles_r - 1) {
+      for (int k = ty; k < 32; k += 8) {
+        const int c = tc * 32 + k;
+        if (c >= d.cols) break;
+        for (int r = tiles_r * 32 + tx; r < d.ld_dst; r += 32) d.dst[static_cast<int64_t>(c) * d.ld_dst + r] = 0;
+      }
+    }
   }
 }
 
