@@ -172,22 +172,34 @@ __device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, flo
   n = tot;
 }
 
+// rows_all (uniform): the workgroup's 64 rows all exist - the lane's sums then run over its 16 registers without row
+// predicates and the count is the constant 16 (what sixteen `n += 1.f` give): the same operations on the same values in
+// the same order, so the same bits as the predicated form, which the last row tile takes.
 __device__ __forceinline__ void tile_col_stats(const float (&out)[16] /* acc + bias */, int row_base, int M, int col, int N, int wm,
                                                int wn, int lane, float* lds /* >= 2*32*3 floats */,
-                                               float* __restrict__ out_tile /* [N][3] of this row tile */) {
+                                               float* __restrict__ out_tile /* [N][3] of this row tile */,
+                                               bool rows_all = false) {
   const int khalf = lane >> 5;
-  float n = 0.f, s = 0.f;
+  float n = 0.f, s = 0.f, mean, m2 = 0.f;
+  if (rows_all) {
+    n = 16.f;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-    if (row < M) { n += 1.f; s += out[r]; }
-  }
-  float mean = n > 0.f ? s / n : 0.f;
-  float m2 = 0.f;
+    for (int r = 0; r < 16; ++r) s += out[r];
+    mean = s / n;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-    if (row < M) { const float d = out[r] - mean; m2 += d * d; }
+    for (int r = 0; r < 16; ++r) { const float d = out[r] - mean; m2 += d * d; }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+      if (row < M) { n += 1.f; s += out[r]; }
+    }
+    mean = n > 0.f ? s / n : 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+      if (row < M) { const float d = out[r] - mean; m2 += d * d; }
+    }
   }
   // the other 16 rows of this column live in lane ^ 32: lower half first so both lanes compute the same bits
   const float on = __shfl_xor(n, 32, 64), om = __shfl_xor(mean, 32, 64), o2 = __shfl_xor(m2, 32, 64);
@@ -208,7 +220,7 @@ __device__ __forceinline__ void tile_col_stats(const float (&out)[16] /* acc + b
 // register order, then the lane pair (l, l ^ 32), then the two waves that share the columns.
 __device__ __forceinline__ void tile_bn_bwd_partial(const f32x16& acc, const BnBwdEpi& e, const float (&py)[16],
                                                     const float (&pz)[16], int row_base, int M, int col, int N, int wm,
-                                                    int wn, int lane, float* lds, int ty) {
+                                                    int wn, int lane, float* lds, int ty, bool rows_all = false) {
   const int khalf = lane >> 5;
   float sg = 0.f, sgx = 0.f;
   const bool col_ok = col >= 0 && col < N;  // (col, N: the SOURCE column and width - BnBwdEpi.col0)
@@ -217,14 +229,24 @@ __device__ __forceinline__ void tile_bn_bwd_partial(const f32x16& acc, const BnB
     float mu = e.use_bn ? e.mean[col] : 0.f;
     float is = e.use_bn ? e.invstd[col] : 0.f;
     pin(bv); pin(mu); pin(is);  // (waited for once, here, not inside each row's branch)
+    if (rows_all) {  // (uniform) every row exists: the same sums over the same registers, no row predicates
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-      if (row < M) {
+      for (int r = 0; r < 16; ++r) {
         float g = acc[r];
         if (e.act == ER_ACT_RELU && !(py[r] > 0.f)) g = 0.f;
         sg = sg + g;
         if (e.use_bn) sgx = sgx + g * ((pz[r] + bv - mu) * is);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = row_base + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+        if (row < M) {
+          float g = acc[r];
+          if (e.act == ER_ACT_RELU && !(py[r] > 0.f)) g = 0.f;
+          sg = sg + g;
+          if (e.use_bn) sgx = sgx + g * ((pz[r] + bv - mu) * is);
+        }
       }
     }
   }
@@ -561,46 +583,59 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
   int kend = kbeg + g.k_per_split;
   if (kend > g.K) kend = g.K;
   const int T = (kend - kbeg + BK32 - 1) / BK32;
+  // What the epilogues read at the lane's 16 output positions is requested by request_epilogue_operands(), which the k loop's
+  // prologue calls BEHIND the loads of the first two k-tiles: the vector memory returns in order, so in front of them these
+  // (strided rows, cold after the previous launch) stood between the launch's start and its first staging write; behind
+  // them that write waits with a counted vmcnt that leaves them in flight, and they still have the whole loop to arrive.
   float py[16], pz[16];
-  if (BN_EPI && g.bn.partial != nullptr) {  // (a grouped launch may mix problems with and without the epilogue)
-    int c = n0 + wn * 32 + (lane & 31) - g.bn.col0;  // (source column, clamped: a lane outside the block loads what it ignores)
-    c = c < 0 ? 0 : (c < g.bn.n_src ? c : g.bn.n_src - 1);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      row = row < g.M ? row : g.M - 1;
-      const int64_t i = static_cast<int64_t>(row) * g.bn.ld + c;
-      py[r] = g.bn.y[i];
-      pz[r] = g.bn.z[i];
-    }
-  }
   // cross epilogues: x0 / x_l (forward), dout / du_in and the lower layer's x0 / u / x_l / dx0 (backward) of the 16 positions
   float qa[XEPI ? 16 : 1], qb[XEPI ? 16 : 1], qc[XEPI == ER_EPI_CROSS_BWD ? 16 : 1], qd[XEPI == ER_EPI_CROSS_BWD ? 16 : 1],
       qe[XEPI == ER_EPI_CROSS_BWD ? 16 : 1], qf[XEPI == ER_EPI_CROSS_BWD ? 16 : 1];
-  if (XEPI && XEPI != kEpiFrozenBn && XEPI != kEpiFrozenDz) {
-    int c = n0 + wn * 32 + (lane & 31);
-    c = c < g.N ? c : g.N - 1;
-    const bool with_diag = xe->diag != 0.f;
+  auto request_epilogue_operands = [&]() {
+    if (BN_EPI) {
+      // Branch-free: a grouped launch may mix problems with and without the epilogue, and loads inside `if (partial)` leave
+      // the compiler, where the branches join, a wait sized for the arm WITHOUT them - in front of the first staging write
+      // it then waits for all but a few of these.  A problem without the epilogue loads A's first element 32 times instead
+      // and ignores it.
+      const bool on = g.bn.partial != nullptr;
+      const float* ysrc = on ? g.bn.y : g.A;
+      const float* zsrc = on ? g.bn.z : g.A;
+      int c = n0 + wn * 32 + (lane & 31) - g.bn.col0;  // (source column, clamped: a lane outside the block loads what it ignores)
+      c = c < 0 ? 0 : (c < g.bn.n_src ? c : g.bn.n_src - 1);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      row = row < g.M ? row : g.M - 1;
-      const int64_t rr = row;
-      if (XEPI == ER_EPI_CROSS_FWD) {
-        qa[r] = xe->x0[rr * xe->ld_x0 + c];
-        qb[r] = xe->xl[rr * xe->ld_xl + c];
-      } else {
-        qa[r] = xe->dout[rr * xe->ld_dout + c];
-        qb[r] = with_diag ? xe->du_in[rr * xe->ld_du_in + c] : 0.f;
-        if (xe->prev_u) {
-          qc[r] = xe->x0[rr * xe->ld_x0 + c];
-          qd[r] = xe->prev_u[rr * xe->ld_prev_u + c];
-          qe[r] = with_diag ? xe->xl[rr * xe->ld_xl + c] : 0.f;
-          qf[r] = xe->accumulate_dx0 ? xe->dx0[rr * xe->ld_dx0 + c] : 0.f;
+      for (int r = 0; r < 16; ++r) {
+        int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        row = row < g.M ? row : g.M - 1;
+        const int64_t i = on ? static_cast<int64_t>(row) * g.bn.ld + c : 0;
+        py[r] = ysrc[i];
+        pz[r] = zsrc[i];
+      }
+    }
+    if (XEPI && XEPI != kEpiFrozenBn && XEPI != kEpiFrozenDz) {
+      int c = n0 + wn * 32 + (lane & 31);
+      c = c < g.N ? c : g.N - 1;
+      const bool with_diag = xe->diag != 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        row = row < g.M ? row : g.M - 1;
+        const int64_t rr = row;
+        if (XEPI == ER_EPI_CROSS_FWD) {
+          qa[r] = xe->x0[rr * xe->ld_x0 + c];
+          qb[r] = xe->xl[rr * xe->ld_xl + c];
+        } else {
+          qa[r] = xe->dout[rr * xe->ld_dout + c];
+          qb[r] = with_diag ? xe->du_in[rr * xe->ld_du_in + c] : 0.f;
+          if (xe->prev_u) {
+            qc[r] = xe->x0[rr * xe->ld_x0 + c];
+            qd[r] = xe->prev_u[rr * xe->ld_prev_u + c];
+            qe[r] = with_diag ? xe->xl[rr * xe->ld_xl + c] : 0.f;
+            qf[r] = xe->accumulate_dx0 ? xe->dx0[rr * xe->ld_dx0 + c] : 0.f;
+          }
         }
       }
     }
-  }
+  };
   const bool a_vec = (g.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.A) & 15) == 0);
   const bool b_vec = (g.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.B) & 15) == 0);
   const bool rows_full = (m0 + BM <= g.M) && (n0 + BN <= g.N);
@@ -770,6 +805,7 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
     };
     fetch(ra0, rb0, rq0, 0);
     fetch(ra1, rb1, rq1, 1);
+    request_epilogue_operands();
     stage(0, ra0, rb0, rq0, 0);
     __syncthreads();
     // (two loops, not one loop with two arms: the accumulator then stays in its registers from the first MFMA to the last)
@@ -794,6 +830,7 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
   } else {
     // unaligned operands (e.g. lda = 81): masked scalar loads, one k-tile at a time
     f32x4v ra[2], rb[2];
+    request_epilogue_operands();
     for (int t = 0; t < T; ++t) {
       const int k0 = kbeg + t * BK32;
       fetch_tile_generic<A_KC>(g.A, g.lda, m0, g.M, k0, kend, tid, ra);
@@ -809,6 +846,8 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
   }
   // epilogue.  C/D map of the 32x32 tile: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
   // Every path below forms the lane's 16 values, pins them and then stores them (store16, above): no wait between stores.
+  // (the column statistics and the BatchNorm-backward sums stay IN FRONT of the plain stores: storing first - out, acc, y and
+  //  z all live across the stores - was built and measured, bit-identical and no faster: DESIGN.md 3.7)
   const int row0 = m0 + wm * 32 + 4 * khalf;  // the lane's first row: register r holds row0 + acc_row(r)
   pin(bv);
   float out[16];  // acc + bias
@@ -816,9 +855,10 @@ __device__ __forceinline__ void gemm_f32_block(const GemmArgs& g, int bx, int bz
   for (int r = 0; r < 16; ++r) out[r] = acc[r] + bv;
   if (g.col_stats)  // (host guarantees splits == 1) every thread takes part: it synchronises the workgroup
     tile_col_stats(out, m0 + wm * 32, g.M, col, g.N, wm, wn, lane, lds,
-                   g.col_stats + static_cast<int64_t>(ty) * g.N * 3);
+                   g.col_stats + static_cast<int64_t>(ty) * g.N * 3, rows_all);
   if (BN_EPI && g.bn.partial != nullptr) {
-    tile_bn_bwd_partial(acc, g.bn, py, pz, m0 + wm * 32, g.M, col < g.N ? col - g.bn.col0 : -1, g.bn.n_src, wm, wn, lane, lds, ty);
+    tile_bn_bwd_partial(acc, g.bn, py, pz, m0 + wm * 32, g.M, col < g.N ? col - g.bn.col0 : -1, g.bn.n_src, wm, wn, lane, lds, ty,
+                        rows_all);
     if (XEPI == kEpiFrozenDz && g.bn.dz_out) {  // (uniform per problem; host: col0 == 0, n_src == N, one k-split, no accumulate)
       if (col >= g.N) return;
       const float ga = g.bn.gamma ? g.bn.gamma[col] : 1.f;
