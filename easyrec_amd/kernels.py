@@ -2050,6 +2050,89 @@ class HipBackend(object):
       self.op_log.append(('er::add_ln_bwd_kernel', 12.0 * rows * W))
     return dz
 
+  # -- K8i MaskNet's mask multiply and LayerNorm + ReLU (layers/keras/mask_net.py)
+  @staticmethod
+  def _rows_table(ts, what):
+    """HOST arrays of the addresses and row pitches of 2-D fp32 tensors whose rows are contiguous (column slices of a
+    wider tensor included)."""
+    for t in ts:
+      assert t.dim() == 2 and t.dtype == torch.float32 and (t.shape[1] == 1 or t.stride(1) == 1), what
+    return ((ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts]),
+            (ctypes.c_int64 * len(ts))(*[t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in ts]))
+
+  @staticmethod
+  def _row_major(t):
+    return t if (t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1) and (t.shape[0] == 1 or t.stride(0) >= t.shape[1])) \
+        else t.contiguous()
+
+  def mask_mul_fwd(self, x, vs):
+    """x [B, W], vs: n tensors [B, W] (row pitches of their own) -> n fresh tensors x * v_i, one launch."""
+    B, W = x.shape
+    x, vs = self._row_major(x), [self._row_major(v) for v in vs]
+    assert all(v.shape == (B, W) for v in vs)
+    outs = [torch.empty(B, W, dtype=torch.float32, device=x.device) for _ in vs]
+    (xp, ldx), (vp, ldv), (op, ldo) = self._rows_table([x], 'x'), self._rows_table(vs, 'v'), self._rows_table(outs, 'out')
+    self.ck.er_mask_mul_fwd(xp[0], ldx[0], vp, ldv, len(vs), B, W, op, ldo, _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::mask_mul_fwd_kernel', 1.0 * len(vs) * B * W))
+    return outs
+
+  def mask_mul_bwd(self, x, vs, douts, want_dx=True):
+    """-> ([dv_i = dout_i * x], dx = sum_i dout_i * v_i or None), one launch."""
+    B, W = x.shape
+    x, vs = self._row_major(x), [self._row_major(v) for v in vs]
+    douts = [self._row_major(d) for d in douts]
+    assert len(douts) == len(vs) and all(t.shape == (B, W) for t in vs + douts)
+    dvs = [torch.empty(B, W, dtype=torch.float32, device=x.device) for _ in vs]
+    dx = torch.empty(B, W, dtype=torch.float32, device=x.device) if want_dx else None
+    (xp, ldx), (vp, ldv) = self._rows_table([x], 'x'), self._rows_table(vs, 'v')
+    (dp, ldd), (op, ldo) = self._rows_table(douts, 'dout'), self._rows_table(dvs, 'dv')
+    self.ck.er_mask_mul_bwd(xp[0], ldx[0], vp, ldv, dp, ldd, len(vs), B, W, op, ldo, _p(dx), W, _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::mask_mul_bwd_kernel', (3.0 if want_dx else 1.0) * len(vs) * B * W))
+    return dvs, dx
+
+  def ln_relu_grid(self, B, O, n):
+    return int(self.lib.er_ln_relu_grid(int(B), int(O), int(n)))
+
+  def ln_relu_fwd(self, hs, gammas, betas, eps, y=None):
+    """hs: n tensors [B, O]; gammas, betas: n tensors [O] -> (y [B, n * O], mean [n, B], rstd [n, B]); y: the [B, n * O]
+    column block of a wider row-major buffer to write into (fresh when None)."""
+    n, (B, O) = len(hs), hs[0].shape
+    hs = [self._row_major(h) for h in hs]
+    assert all(h.shape == (B, O) for h in hs) and all(t.shape == (O,) and t.is_contiguous() for t in gammas + betas)
+    if y is None:
+      y = torch.empty(B, n * O, dtype=torch.float32, device=hs[0].device)
+    assert y.shape == (B, n * O) and y.dtype == torch.float32
+    mean = torch.empty(n, B, dtype=torch.float32, device=y.device)
+    rstd = torch.empty(n, B, dtype=torch.float32, device=y.device)
+    (hp, ldh), (yp, ldy) = self._rows_table(hs, 'h'), self._rows_table([y], 'y')
+    gp = (ctypes.c_void_p * n)(*[_p(_f32c(g)) for g in gammas])
+    bp = (ctypes.c_void_p * n)(*[_p(_f32c(b)) for b in betas])
+    self.ck.er_ln_relu_fwd(hp, ldh, gp, bp, n, B, O, float(eps), yp[0], ldy[0], _p(mean), _p(rstd), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::ln_relu_fwd_kernel', 9.0 * n * B * O))
+    return y, mean, rstd
+
+  def ln_relu_bwd(self, dy, y, hs, gammas, mean, rstd, grads, acc):
+    """dy, y [B, n * O] (row pitches of their own) -> [dh_i [B, O]]; dgamma_i and dbeta_i are added into (acc) or written
+    to `grads` (a ThetaGradTable in the order gamma_0, beta_0, gamma_1, ..) by the shared fixed-order reduce."""
+    n, (B, O) = len(hs), hs[0].shape
+    hs, dy, y = [self._row_major(h) for h in hs], self._row_major(dy), self._row_major(y)
+    assert dy.shape == (B, n * O) and y.shape == (B, n * O) and len(grads.grads) == 2 * n
+    dhs = [torch.empty(B, O, dtype=torch.float32, device=dy.device) for _ in hs]
+    grid = self.ln_relu_grid(B, O, n)
+    partials = torch.empty(grid * 2 * n * O, dtype=torch.float32, device=dy.device)
+    (hp, ldh), (dp, ldd) = self._rows_table(hs, 'h'), self._rows_table(dhs, 'dh')
+    (dyp, lddy), (yp, ldy) = self._rows_table([dy], 'dy'), self._rows_table([y], 'y')
+    gp = (ctypes.c_void_p * n)(*[_p(_f32c(g)) for g in gammas])
+    self.ck.er_ln_relu_bwd(dyp[0], lddy[0], yp[0], ldy[0], hp, ldh, gp, _p(mean), _p(rstd), n, B, O, dp, ldd,
+                           _p(partials), _stream())
+    self.theta_grad_reduce(partials, grid, grads, 8, acc)
+    if self.op_log is not None:
+      self.op_log.append(('er::ln_relu_bwd_kernel', 13.0 * n * B * O))
+    return dhs
+
   # -- K8d FiBiNet's field blocks (layers/keras/fibinet.py)
   def bilinear_lds_bytes(self, F, D):
     return int(self.lib.er_bilinear_lds_bytes(int(F), int(D)))
@@ -4552,6 +4635,79 @@ class SENetFn(torch.autograd.Function):
     table, acc, ret = _theta_grads(ctx, ctx.saved_tensors[2:])
     dx = hip().senet_bwd(x, theta, dy.contiguous(), F, D, G, R, skip, ln, table, acc=acc)
     return (dx, None, None, None, None, None, None, None) + ret
+
+
+class MaskMulFn(torch.autograd.Function):
+  """reference layers/keras/mask_net.py:100 for the n mask blocks that share one input: apply(x [B, W], v_0, .., v_{n-1})
+  -> (x * v_0, .., x * v_{n-1}), one launch each way (er_mask_mul_*).  The v_i are read where their Dense layers wrote
+  them (column slices of a wider tensor included).  A caller that does not need the gradient with respect to x (x does
+  not require one) gets none, and the launch skips it."""
+
+  @staticmethod
+  def forward(ctx, x, *vs):
+    outs = hip().mask_mul_fwd(x.detach(), [v.detach() for v in vs])
+    ctx.save_for_backward(x, *vs)
+    return tuple(outs)
+
+  @staticmethod
+  def backward(ctx, *douts):
+    x, vs = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
+    douts = [d if d is not None else torch.zeros_like(x) for d in douts]
+    dvs, dx = hip().mask_mul_bwd(x, vs, douts, want_dx=ctx.needs_input_grad[0])
+    return (dx,) + tuple(dvs)
+
+
+class LnReluFn(torch.autograd.Function):
+  """reference layers/keras/mask_net.py:106-107 for n mask blocks of one output width: apply(eps, grads, out, col0,
+  h_0, .., h_{n-1}, gamma_0, beta_0, .., gamma_{n-1}, beta_{n-1}) -> relu(LayerNormalization_i(h_i)) side by side.
+  out None: a fresh [B, n * O], the parallel form's concatenation.  out a row-major [B, >= col0 + n * O] buffer: written
+  IN PLACE at columns [col0, col0 + n * O) and returned whole (blocks of unequal widths fill one concatenation launch by
+  launch; the other columns pass their gradient through).  Backward (er_ln_relu_bwd): the ReLU pattern is the saved
+  output's (y > 0); dgamma_i and dbeta_i are ADDED into `grads` = (gamma_0's, beta_0's, gamma_1's, .. gradient buffers)
+  by the shared fixed-order reduce, or returned to autograd when no buffers are given."""
+
+  @staticmethod
+  def forward(ctx, eps, grads, out, col0, *tensors):
+    n = len(tensors) // 3
+    assert len(tensors) == 3 * n and n >= 1
+    hs, gb = [h.detach() for h in tensors[:n]], [t.detach() for t in tensors[n:]]
+    B, O = hs[0].shape
+    if out is None:
+      y, mean, rstd = hip().ln_relu_fwd(hs, gb[0::2], gb[1::2], eps)
+      ret = y
+    else:
+      assert not out.requires_grad or not out.is_leaf
+      y = out.detach()[:, col0:col0 + n * O]
+      _, mean, rstd = hip().ln_relu_fwd(hs, gb[0::2], gb[1::2], eps, y=y)
+      ctx.mark_dirty(out)
+      ret = out
+    ctx.save_for_backward(mean, rstd, *tensors)
+    # (the saved output is the storage autograd already holds; a later block's in-place write into OTHER columns of the
+    # same buffer must not invalidate it, so it is kept as a view and not through save_for_backward - a DETACHED one: the
+    # returned tensor itself would own this node and the node it, a cycle that keeps the graph alive until a collection)
+    ctx.y = y.detach()
+    ctx.grads, ctx.n, ctx.cols = grads, n, (None if out is None else (col0, col0 + n * O))
+    return ret
+
+  @staticmethod
+  def backward(ctx, dy):
+    mean, rstd = ctx.saved_tensors[:2]
+    n = ctx.n
+    hs, gb = list(ctx.saved_tensors[2:2 + n]), list(ctx.saved_tensors[2 + n:])
+    table, acc, ret = _theta_grads(ctx, gb)
+    dout = None
+    if ctx.cols is not None:
+      c0, c1 = ctx.cols
+      if dy.stride(-1) != 1:
+        dy = dy.contiguous()
+      dmine = dy[:, c0:c1]
+      if ctx.needs_input_grad[2]:  # (what was in these columns before is overwritten: no gradient reaches it)
+        dout = dy.clone()
+        dout[:, c0:c1] = 0
+    else:
+      dmine = dy
+    dhs = hip().ln_relu_bwd(dmine, ctx.y, hs, gb[0::2], mean, rstd, table, acc)
+    return (None, None, dout, None) + tuple(dhs) + ret
 
 
 def _seq_column(x):

@@ -1116,6 +1116,57 @@ int er_seq_attn_pool_bwd(const float* x, int64_t ld, const int32_t* len, const f
                          int32_t L_buf, int32_t D, float* dx, int64_t lddx, float* partials, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8i MaskNet's instance-guided mask and the LayerNormalization + ReLU that ends a mask block (reference
+ *     layers/keras/mask_net.py:100, :106-107).  fp32, no atomics, no MFMA, fixed summation orders: two runs
+ *     and a graph replay give the same bits.  n blocks share one launch: every `*_host` argument is a HOST
+ *     array of n entries (device addresses, pitches in floats), copied by value into the kernel's
+ *     arguments, so nothing is built on the device and a first call inside a stream capture works.  The
+ *     operands are read where the Dense layers wrote them; no concat copy is made.
+ * Mask multiply.  Replaces the n Mul of the parallel form (and their gradients: 2 n Mul and the n - 1
+ *     AddN terms of the shared input).  x [B, W] at pitch ldx; v_i [B, W] at pitch ldv_i (the `weights`
+ *     layers' outputs).
+ * er_mask_mul_fwd: out_i[b, c] = x[b, c] * v_i[b, c], out_i [B, W] at pitch ldout_i.
+ * er_mask_mul_bwd: dv_i[b, c] = dout_i[b, c] * x[b, c]; dx[b, c] = ((dout_0 v_0 + dout_1 v_1) + ..)[b, c]:
+ *   i ascending, one fmaf chain per element, the first term a plain product.  Every element of every
+ *   output is written.  dx may be NULL (a caller that does not need the gradient with respect to x).
+ * Envelope: 1 <= W <= 4096, 1 <= n <= 8, B >= 1, every pitch >= W; outside it both return an error and
+ *   launch nothing.  16-byte accesses where W % 4 == 0 and every base and pitch is a multiple of 16 bytes;
+ *   4-byte accesses otherwise.
+ * LayerNorm + ReLU.  Replaces moments, the normalisation's Sub / Mul / Rsqrt / Add and Relu per block, the
+ *     ConcatV2 of the parallel form, and their gradients.  h_i [B, O] at pitch ldh_i (the `output` layers'
+ *     results); gamma_i, beta_i [O] (the variables themselves); y [B, .] at pitch ldy >= n O, block i at
+ *     columns [i O, (i + 1) O): with ldy = n O the concatenation that feeds the MLP.
+ * er_ln_relu_fwd: one wave per (row, block).  mean = the row's mean, taken about its first element;
+ *   var = mean((h - mean)^2) (two passes, biased, tf.nn.moments' form); rstd = 1 / sqrt(var + eps);
+ *   y = max(0, (h - mean) * rstd * gamma + beta).  mean, rstd [n, B] are kept.  The arithmetic of
+ *   er_add_ln_fwd (K8f) with res = NULL, then the max.
+ * er_ln_relu_bwd: re-reads h; the ReLU pattern is the saved output's, d = y > 0 ? dy : 0 (dy [B, .] at
+ *   pitch lddy, the columns of y); g = d * gamma; dh_i [B, O] at pitch lddh_i =
+ *   rstd * (g - mean(g) - xhat * mean(g * xhat)), xhat = (h - mean) * rstd.  partials
+ *   [er_ln_relu_grid(B, O, n), 2 n O]: per workgroup row, for block i at columns [2 i O, 2 (i + 1) O), the
+ *   sum over the workgroup's rows of d * xhat [O] | d [O], which er_theta_grad_reduce (K8e) sums with
+ *   row_groups = 8 into gamma_0's, beta_0's, gamma_1's, .. buffers.  Workgroup g owns the rows
+ *   [g * ceil(B / grid), ..): fixed order, no atomics.
+ * Envelope: 1 <= O <= 4096, 1 <= n <= 8, B >= 1 and 2 n O < 65536 (K8e's limit on a partials row; it
+ *   excludes only n = 8 at O = 4096); er_ln_relu_grid returns 0 outside, and the launches an error.
+ *   O % 4 == 0, O <= 1024 and 16-byte aligned operands and pitches: the row lives in registers between the
+ *   passes; otherwise it is re-read.  er_ln_relu_grid = min(ceil(B / 4), 1024).
+ * -------------------------------------------------------------------------------------------- */
+int er_mask_mul_fwd(const float* x, int64_t ldx, const float* const* v_host, const int64_t* ldv_host, int32_t n, int64_t B,
+                    int32_t W, float* const* out_host, const int64_t* ldout_host, er_stream_t stream);
+int er_mask_mul_bwd(const float* x, int64_t ldx, const float* const* v_host, const int64_t* ldv_host,
+                    const float* const* dout_host, const int64_t* lddout_host, int32_t n, int64_t B, int32_t W,
+                    float* const* dv_host, const int64_t* lddv_host, float* dx, int64_t lddx, er_stream_t stream);
+int32_t er_ln_relu_grid(int64_t B, int32_t O, int32_t n);  /* rows of `partials` */
+int er_ln_relu_fwd(const float* const* h_host, const int64_t* ldh_host, const float* const* gamma_host,
+                   const float* const* beta_host, int32_t n, int64_t B, int32_t O, float eps, float* y, int64_t ldy,
+                   float* mean, float* rstd, er_stream_t stream);
+int er_ln_relu_bwd(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* const* h_host,
+                   const int64_t* ldh_host, const float* const* gamma_host, const float* mean, const float* rstd, int32_t n,
+                   int64_t B, int32_t O, float* const* dh_host, const int64_t* lddh_host, float* partials,
+                   er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed

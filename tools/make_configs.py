@@ -487,6 +487,30 @@ def fibinet_taobao(bilinear_type='each', use_plus=True, **kw):
   ''' % (names, bilinear_type, 'true' if use_plus else 'false'))
 
 
+def masknet_taobao(**kw):
+  """MaskNet, the model section of samples/model_config/masknet_on_taobao.config: RankModel over a backbone whose one
+  block is `MaskNet` on the 17 fields of D = 16 (group `all`): parallel, model-level input layer norm, 3 mask blocks of
+  aggregation 512 -> output 256, MLP [512, 256]; l2 1e-6, embedding l2 1e-4."""
+  cfg = taobao_base('tag', **kw)
+  cfg.model_dir = 'experiments/masknet_taobao_ckpt'
+  cfg.data_config.label_fields.append('clk')
+  feats = TAOBAO_USER + TAOBAO_ITEM + ['tag_category_list', 'tag_brand_list']
+  names = ' '.join("feature_names: '%s'" % n for n in feats)
+  block = 'mask_blocks { aggregation_size: 512 output_size: 256 } '
+  return _model_text(cfg, '''
+    model_class: 'RankModel'
+    feature_groups { group_name: 'all' %s wide_deep: DEEP }
+    backbone {
+      blocks { name: 'mask_net' inputs { feature_group_name: 'all' }
+               keras_layer { class_name: 'MaskNet'
+                             masknet { %s mlp { hidden_units: [512, 256] } } } }
+      concat_blocks: 'mask_net'
+    }
+    model_params { l2_regularization: 1e-6 }
+    embedding_regularization: 1e-4
+  ''' % (names, block * 3))
+
+
 def dssm_taobao(in_batch=False, **kw):
   """DSSM, the model section of samples/model_config/dssm_on_taobao.config: the user tower over the 8 user fields and
   the two tag lists, the item tower over the 7 item fields, [256, 128, 64, 32] each, cosine similarity with scale_simi,
@@ -1091,6 +1115,7 @@ if __name__ == '__main__':
   write(cmbf_movielens(), 'cmbf_movielens.config')
   write(deepfm_textcnn_movielens(), 'deepfm_textcnn_movielens.config')
   write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
+  write(masknet_taobao(item_rows=10000000), 'masknet_taobao_10m.config')
   write(dssm_taobao(item_rows=10000000), 'dssm_taobao_10m.config')
   write(dssm_taobao(in_batch=True, item_rows=10000000), 'dssm_inbatch_taobao_10m.config')
   write(mind_taobao(item_rows=10000000), 'mind_taobao_10m.config')
