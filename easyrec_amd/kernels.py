@@ -1292,21 +1292,28 @@ class HipBackend(object):
                              _stream())
     return tuple(float(x) for x in out.cpu().tolist())
 
-  def dot_interaction_fwd(self, x, F, D, self_interaction):
-    """x [B, F*D] -> [B, P] pairwise dot products in the order of model/dlrm.py:51-57."""
+  def dot_interaction_fwd(self, x, F, D, self_interaction, out=None):
+    """x [B, >=F*D] (stride(0) = row stride) -> [B, P] pairwise dot products in the order of model/dlrm.py:51-57;
+    `out`: a caller's [B, P] destination, rows out.stride(0) apart."""
     B = x.shape[0]
     P = F * (F - 1) // 2 + (F if self_interaction else 0)
-    out = torch.empty(B, P, dtype=torch.float32, device=x.device)
+    if out is None:
+      out = torch.empty(B, P, dtype=torch.float32, device=x.device)
+    assert x.dtype == torch.float32 and x.stride(1) == 1
+    assert out.dtype == torch.float32 and out.shape == (B, P) and out.stride(1) == 1
     self.ck.er_dot_interaction_fwd(_p(x), B, F, D, x.stride(0), self_interaction, _p(out),
                                    out.stride(0), _stream())
     return out
 
-  def dot_interaction_bwd(self, x, g, F, D, self_interaction):
+  def dot_interaction_bwd(self, x, g, F, D, self_interaction, into=None, accumulate=False):
+    """dx [B, F*D] of the pairwise dot products; x and g rows x.stride(0) / g.stride(0) apart; `into`: a caller's
+    destination (rows into.stride(0) apart), written, or added to when `accumulate`."""
     B = x.shape[0]
-    dx = torch.empty(B, F * D, dtype=torch.float32, device=x.device)
-    g = _f32c(g)
+    dx = torch.empty(B, F * D, dtype=torch.float32, device=x.device) if into is None else into
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and g.dtype == torch.float32 and g.stride(1) == 1
+    assert dx.dtype == torch.float32 and dx.shape == (B, F * D) and dx.stride(1) == 1
     self.ck.er_dot_interaction_bwd(_p(x), _p(g), B, F, D, x.stride(0), self_interaction,
-                                   g.stride(0), _p(dx), dx.stride(0), 0, _stream())
+                                   g.stride(0), _p(dx), dx.stride(0), int(accumulate), _stream())
     return dx
 
   def rowsum_fwd(self, x, n):

@@ -1,5 +1,6 @@
 """Cases, fp64 references and derived error bounds for the interaction kernels (FM / row sum, DCN cross v1 and the
-cross v2 epilogue, DIN concat and pool, MMoE mixing, sigmoid cross-entropy).  No backend is imported here: the CPU
+cross v2 epilogue, DIN concat and pool, MMoE mixing, sigmoid cross-entropy, the four CIN kernels one by one, the DLRM
+dot interaction).  No backend is imported here: the CPU
 tests (test_interaction_restatement.py) and the GPU tests (test_interaction_gpu.py) hand one to the run_* functions.
 
 Reference.  Every *_formula below is the published formula as the reference project's model code states it, written
@@ -682,6 +683,332 @@ def run_ce(be, case, inp, dev, seen=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# CIN (xDeepFM), the four kernels one by one on given float32 operands - no GEMM in between:
+#   outer_fwd     z[(b, d), h * H0 + m] = xi[b, h, d] * x0[b, m, d]
+#   act_pool_fwd  fm = relu(c + bias) in place,  pooled[b, col0 + n] = sum_d fm[(b, d), n]
+#   act_pool_bwd  dc = d(pooled . dpooled + fm . dnext) / dc               (dnext may be absent, dc may BE dnext)
+#   outer_bwd     dxi (+)= dz . dz/dxi,  dx0 += dz . dz/dx0
+# c and bias are float32, so fl(c + bias) has the sign of the exact sum (it is 0 only when c == -bias, and a sum of two
+# floats that is not 0 is at least half an ulp of the larger away from it): the ReLU mask is the same in float32 and
+# in float64, and every tensor can be held to a strict bound.
+# form 'first': xi IS x0 [B, H0, D] (strides (H0*D, D, 1)), dxi IS dx0 and is added to; form 'later': xi [B, D, H]
+# (strides (D*H, 1, H)), dxi its own buffer - written over NaN (add_xi = 0) or added to (add_xi = 1); dx0 is always
+# added to.
+# ------------------------------------------------------------------------------------------------------------------
+CIN_BLOCK = 256           # er::kBlock: columns of z per workgroup, elements per workgroup of the two act_pool kernels
+CIN_LDS_BUDGET = 60 * 1024
+
+
+def cin_outer_bwd_lds(H, H0):
+  """er_cin_outer_bwd's LDS bytes: the xi column, the x0 column and one row of dz."""
+  return (H + H0 + H * H0) * 4
+
+
+def _cin_cases():
+  cases = []
+
+  def add(form, B, H, H0, D, N, col0, pad, dnext, add_xi):
+    cases.append(dict(id='cin-%s-%dx%dx%dx%dx%d-col%dof%d-%s-add%d' % (form, B, H, H0, D, N, col0, col0 + N + pad, dnext, add_xi), form=form,
+                      B=B, H=H, H0=H0, D=D, N=N, col0=col0, ld=col0 + N + pad, dnext=dnext, add_xi=add_xi))
+
+  for add_xi in (0, 1):
+    add('later', 3, 3, 2, 4, 5, 2, 3, 'present', add_xi)    # K = 6, B*N = 15, B*D*N = 60: everything below one block
+    add('later', 2, 16, 16, 3, 7, 0, 0, 'none', add_xi)     # K = 256: exactly one block of z columns; pooled contiguous
+    add('later', 2, 17, 16, 2, 3, 1, 2, 'alias', add_xi)    # K = 272: a second block in y, 16 columns of it live
+    add('later', 1, 300, 2, 2, 4, 0, 1, 'present', add_xi)  # H > 256: outer_bwd's h loops take two trips
+    add('later', 1, 2, 300, 2, 4, 3, 0, 'alias', add_xi)    # H0 > 256: its m loops take two trips
+    add('later', 1, 122, 123, 2, 2, 0, 0, 'none', add_xi)   # 61004 bytes of LDS, the largest pair 61440 admits; B*D = 2
+    add('later', 5, 3, 2, 3, 65, 4, 2, 'present', add_xi)   # B*N = 325 straddles a block, B*D*N = 975 four of them
+    add('later', 7, 4, 1, 3, 1, 1, 1, 'alias', add_xi)      # H0 = 1 (z is xi scaled), N = 1
+    add('later', 6, 3, 2, 1, 3, 0, 2, 'present', add_xi)    # D = 1: pooled is fm, a row of z per example
+  add('first', 2, 16, 16, 3, 2, 1, 1, 'present', 1)         # the aliased first layer at K = 256
+  add('first', 3, 3, 3, 2, 4, 0, 0, 'alias', 1)             # and small
+  return cases
+
+
+CIN_CASES = _cin_cases()
+# refused by the host, nothing launched: H = H0 = 123 needs 61500 bytes of LDS; dxi aliasing dx0 without adding;
+# H * H0 = 2**24 columns (checked before any access: the buffers are a few floats)
+CIN_REFUSED = [dict(id='cin-refuse-lds-123x123', kernel='outer_bwd', form='first', B=1, H=123, H0=123, D=2, add_xi=1,
+                    match='too many rows / features'),
+               dict(id='cin-refuse-alias-no-add', kernel='outer_bwd', form='first', B=2, H=3, H0=3, D=2, add_xi=0,
+                    match='dxi aliasing dx0 must add'),
+               dict(id='cin-refuse-K-2pow24', kernel='outer_fwd', form='later', B=1, H=4096, H0=4096, D=1, add_xi=0,
+                    match='too many rows / columns')]
+
+
+def cin_strides(case):
+  H, H0, D = case['H'], case['H0'], case['D']
+  return (H0 * D, D, 1) if case['form'] == 'first' else (D * H, 1, H)
+
+
+def cin_inputs(case, seed=17):
+  g = _gen(seed)
+  B, H, H0, D, N, ld = (case[k] for k in ('B', 'H', 'H0', 'D', 'N', 'ld'))
+  inp = dict(x0=_randn(g, B, H0, D), bias=_randn(g, N), c=_randn(g, B * D, N), pooled0=_randn(g, B, ld),
+             dpooled=_randn(g, B, ld), dnext=_randn(g, B * D, N), dz=_randn(g, B * D, H * H0), old0=_randn(g, B, H0, D))
+  if case['form'] == 'later':
+    inp.update(xi=_randn(g, B, D, H), oldi=_randn(g, B, D, H))
+  # planted: flat element 0 of c is -bias exactly (fm 0, no gradient), element 1 is one float32 above -bias (fm > 0)
+  flat, nb = inp['c'].view(-1), -inp['bias']
+  flat[0] = nb[0]
+  flat[1] = torch.nextafter(nb[1 % N], torch.tensor(float('inf')))
+  inp['fm32'] = torch.relu(inp['c'] + inp['bias'])  # what act_pool_bwd is given: one float32 addition, the same bits anywhere
+  return inp
+
+
+def cin_ties(case):
+  """(row, n) of the exact tie and of the entry one ulp above it."""
+  N = case['N']
+  return (0, 0), (1 // N, 1 % N)
+
+
+def _cin_outer(xv, x0):
+  """xv [B, H, D], x0 [B, H0, D] -> z [(b, d), (h, m)]; all-positive coefficients: its own abs formula on abs inputs."""
+  B, H, D = xv.shape
+  return (xv.permute(0, 2, 1)[:, :, :, None] * x0.permute(0, 2, 1)[:, :, None, :]).reshape(B * D, H * x0.shape[1])
+
+
+def _cin_outer_eval(case, inp, dt, absolute):
+  c = (lambda k: _t(inp[k], dt).abs()) if absolute else (lambda k: _t(inp[k], dt))
+  x0 = c('x0').requires_grad_(True)
+  if case['form'] == 'first':  # xi IS x0: both terms of the gradient land in dx0
+    z = _cin_outer(x0, x0)
+    g0, = _grads(z, (x0,), c('dz'))
+    dx0 = c('old0') + g0
+    return dict(z=z, dxi=dx0, dx0=dx0)
+  xi = c('xi').requires_grad_(True)
+  z = _cin_outer(xi.permute(0, 2, 1), x0)
+  g0, gi = _grads(z, (x0, xi), c('dz'))
+  return dict(z=z, dxi=(c('oldi') + gi) if case['add_xi'] else gi, dx0=c('old0') + g0)
+
+
+def _cin_act_pool_eval(case, inp, dt, absolute):
+  B, D, N, col0 = case['B'], case['D'], case['N'], case['col0']
+  sl = slice(col0, col0 + N)
+  c = (lambda k: _t(inp[k], dt).abs()) if absolute else (lambda k: _t(inp[k], dt))
+  cc, bias = c('c').requires_grad_(True), c('bias')
+  if absolute:  # the mask is the true one, a constant; under it fm = c + bias becomes |c| + |bias|
+    fm = (_t(inp['c'], dt) + _t(inp['bias'], dt) > 0).to(dt) * (cc + bias)
+  else:
+    fm = torch.relu(cc + bias)
+  pv = fm.reshape(B, D, N).sum(dim=1)
+  pooled = c('pooled0').clone()
+  pooled[:, sl] = pv
+  if case['dnext'] == 'none':
+    dc, = _grads(pv, cc, c('dpooled')[:, sl])
+  else:
+    dc, = _grads((pv, fm), cc, (c('dpooled')[:, sl], c('dnext')))
+  return dict(fm=fm, pooled=pooled, dc=dc)
+
+
+def cin_formula(case, inp, dt):
+  r = _cin_outer_eval(case, inp, dt, False)
+  r.update(_cin_act_pool_eval(case, inp, dt, False))
+  return r
+
+
+def cin_bound(case, inp):
+  H, H0, D, N, col0, add_xi = (case[k] for k in ('H', 'H0', 'D', 'N', 'col0', 'add_xi'))
+  M = _cin_outer_eval(case, inp, F64, True)
+  M.update(_cin_act_pool_eval(case, inp, F64, True))
+  b = {}
+  # z: one product.  n = 0, c = 2.
+  b['z'] = 2 * U * M['z']
+  # fm = relu(c + bias): one addition, the ReLU selects.  n = 0, c = 2; where the mask is off M is 0: fm must BE 0.
+  b['fm'] = 2 * U * M['fm']
+  # pooled = sum_d fm: fm's addition, then D - 1 more.  n = D, c = 2.  Beside the written columns nothing may move.
+  b['pooled'] = torch.zeros_like(M['pooled'])
+  b['pooled'][:, col0:col0 + N] = (D + 2) * U * M['pooled'][:, col0:col0 + N]
+  # dc = (dpooled + dnext) * mask: one addition, n = 0, c = 2; without dnext a copy of dpooled or a zero: equality
+  b['dc'] = torch.zeros_like(M['dc']) if case['dnext'] == 'none' else 2 * U * M['dc']
+  if case['form'] == 'first':
+    # dx0 = (old + sum_h dz xi) + sum_m dz x0: a monomial of the first sum goes through its product, H - 1 additions and
+    # the two accumulations, one of the second through its product, H0 - 1 additions and one accumulation, old through
+    # both accumulations.  H == H0 here: n = H, c = 6 (product, accumulate, accumulate) covers all three.
+    assert H == H0
+    b['dx0'] = b['dxi'] = (H + 6) * U * M['dx0']
+  else:
+    # dxi = sum_m dz x0: the product, H0 - 1 additions; one more addition, on |old| more, when it adds.
+    # n = H0, c = 2 or 4.
+    b['dxi'] = (H0 + 2 + 2 * add_xi) * U * M['dxi']
+    # dx0 = old + sum_h dz xi: the product, H - 1 additions, the accumulation.  n = H, c = 4.
+    b['dx0'] = (H + 4) * U * M['dx0']
+  return {k: v.detach() for k, v in b.items()}
+
+
+def cin_buffers(case, inp, dev):
+  """Every operand and destination of the four launches, as the kernels are to find them."""
+  B, H, H0, D, N = (case[k] for k in ('B', 'H', 'H0', 'D', 'N'))
+  t = lambda k: inp[k].to(dev).clone()
+  nan = lambda *shape: torch.full(shape, float('nan'), dtype=F32, device=dev)
+  buf = dict(x0=t('x0'), bias=t('bias'), c=t('c'), fm_in=t('fm32'), pooled=t('pooled0'), dpooled=t('dpooled'), dz=t('dz'),
+             dx0=t('old0'), z=nan(B * D, H * H0))
+  if case['form'] == 'first':
+    buf['xi'], buf['dxi'] = buf['x0'], buf['dx0']
+  else:
+    buf['xi'] = t('xi')
+    buf['dxi'] = t('oldi') if case['add_xi'] else nan(B, D, H)  # a write that is skipped leaves a NaN
+  buf['dnext'] = None if case['dnext'] == 'none' else t('dnext')
+  buf['dc'] = buf['dnext'] if case['dnext'] == 'alias' else nan(B * D, N)
+  return buf
+
+
+def cin_launch(be, case, buf):
+  B, H, D, col0 = case['B'], case['H'], case['D'], case['col0']
+  strides = cin_strides(case)
+  be.cin_outer_fwd(buf['xi'], strides, H, buf['x0'], buf['z'])
+  be.cin_act_pool_fwd(buf['c'], buf['bias'], B, D, buf['pooled'], col0)
+  be.cin_act_pool_bwd(buf['fm_in'], buf['dpooled'], col0, buf['dnext'], B, D, buf['dc'])
+  be.cin_outer_bwd(buf['dz'], buf['xi'], strides, H, buf['x0'], buf['dxi'], bool(case['add_xi']), buf['dx0'])
+
+
+def cin_results(buf):
+  return dict(z=buf['z'], fm=buf['c'], pooled=buf['pooled'], dc=buf['dc'], dxi=buf['dxi'], dx0=buf['dx0'])
+
+
+def run_cin(be, case, inp, dev, seen=None):
+  buf = cin_buffers(case, inp, dev)
+  cin_launch(be, case, buf)
+  return cin_results(buf)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# DLRM dot interaction:  out[b, p] = e_i . e_j over the pairs p = (i, j), i ascending, j from i (self_interaction) or
+# i + 1 ascending
+# ------------------------------------------------------------------------------------------------------------------
+# layouts: 'contig' = the backend's defaults (its own out and dx; accumulate into a contiguous buffer);
+# 'wide' = x, out, g and dx are each columns [DOT_OFF, DOT_OFF + width) of a wider buffer whose row stride is no
+# multiple of 4 floats: the base is 4 bytes off a 16-byte boundary, every row starts at another alignment, and the
+# columns beside the operand hold values that must come back bit for bit
+DOT_OFF = 1
+DOT_LDS_BUDGET = 60 * 1024
+DOT_SHAPES = [(5, 2, 3), (3, 9, 1), (4, 27, 16), (1, 40, 8)]
+# (5, 2, 3): the minimum F, one pair; (3, 9, 1): D = 1; (4, 27, 16): P = 351 and F*D = 432, both loops past one block;
+# (1, 40, 8): one example, P = 780 / 820 four trips
+
+
+def dot_pairs(F, si):
+  return F * (F - 1) // 2 + (F if si else 0)
+
+
+def dot_fwd_lds(F, D):
+  return 4 * F * (D + 1)
+
+
+def dot_bwd_lds(F, D, si):
+  return 4 * (F * (D + 1) + dot_pairs(F, si))
+
+
+def _dot_cases():
+  cases = [dict(id='dot-%dx%dx%d-si%d-%s' % (B, F, D, si, lay), B=B, F=F, D=D, si=bool(si), layout=lay, fwd_only=False)
+           for B, F, D in DOT_SHAPES for si in (0, 1) for lay in ('contig', 'wide')]
+  # 33280 bytes of LDS forward, 65792 backward: the forward runs, the backward is refused (DOT_REFUSED)
+  cases.append(dict(id='dot-1x128x64-si0-contig-fwdonly', B=1, F=128, D=64, si=False, layout='contig', fwd_only=True))
+  return cases
+
+
+DOT_CASES = _dot_cases()
+# refused by the host, nothing launched.  what: the ER_REQUIRE that must fire
+DOT_REFUSED = [dict(id='dot-refuse-fwd-lds', what='fwd_lds', B=1, F=128, D=120, si=False, match='exceed the LDS budget'),
+               dict(id='dot-refuse-bwd-lds', what='bwd_lds', B=1, F=128, D=64, si=False, match='exceed the LDS budget'),
+               dict(id='dot-refuse-out-stride', what='out_stride', B=2, F=4, D=3, si=True, match='out_stride'),
+               dict(id='dot-refuse-g-stride', what='g_stride', B=2, F=4, D=3, si=True, match='g_stride')]
+
+
+def dot_ld(case, width):
+  """Row stride of the buffer an operand of `width` columns sits in."""
+  if case['layout'] == 'contig':
+    return width
+  ld = width + DOT_OFF + 2
+  return ld + 1 if ld % 4 == 0 else ld
+
+
+def dot_view(buf, case, width):
+  return buf if case['layout'] == 'contig' else buf[:, DOT_OFF:DOT_OFF + width]
+
+
+def dot_inputs(case):
+  g = _gen(18)
+  B, n, P = case['B'], case['F'] * case['D'], dot_pairs(case['F'], case['si'])
+  return dict(xw=_randn(g, B, dot_ld(case, n)), gw=_randn(g, B, dot_ld(case, P)), out0=_randn(g, B, dot_ld(case, P)),
+              old=_randn(g, B, dot_ld(case, n)))
+
+
+def _dot(e, si):  # all-positive coefficients: its own abs formula on abs inputs
+  F = e.shape[1]
+  i, j = torch.triu_indices(F, F, 0 if si else 1)  # row by row: i ascending, then j
+  return torch.einsum('bnd,bmd->bnm', e, e)[:, i, j]
+
+
+def _dot_eval(case, inp, dt, absolute):
+  B, F, D = case['B'], case['F'], case['D']
+  n, P = F * D, dot_pairs(F, case['si'])
+  c = (lambda k: _t(inp[k], dt).abs()) if absolute else (lambda k: _t(inp[k], dt))
+  x = dot_view(c('xw'), case, n).contiguous().requires_grad_(True)
+  o = _dot(x.reshape(B, F, D), case['si'])
+  out = c('out0').clone()
+  dot_view(out, case, P).copy_(o)
+  if case['fwd_only']:
+    return dict(out=out.detach())
+  g, = _grads(o, x, dot_view(c('gw'), case, P))
+  dx, acc = c('old').clone(), c('old').clone()
+  dot_view(dx, case, n).copy_(g)
+  dot_view(acc, case, n).add_(g)
+  return dict(out=out.detach(), dx=dx, dx_acc=acc)
+
+
+def dot_formula(case, inp, dt):
+  return _dot_eval(case, inp, dt, False)
+
+
+def dot_bound(case, inp):
+  F, D = case['F'], case['D']
+  n, P = F * D, dot_pairs(F, case['si'])
+  M = _dot_eval(case, inp, F64, True)
+
+  def inside(key, width, factor):  # beside the operand's columns nothing may move
+    b = torch.zeros_like(M[key])
+    dot_view(b, case, width).copy_(factor * U * dot_view(M[key], case, width))
+    return b
+
+  # out = sum_d e_i e_j: the product, D - 1 additions.  n = D, c = 2.
+  b = dict(out=inside('out', P, D + 2))
+  if not case['fwd_only']:
+    # dx_f = sum over the partners o of g_(f, o) e_o: at most F terms (the self term is 2 g e, the doubling exact), a
+    # product each.  n = F, c = 2; accumulating is one more addition, on |old| more: c = 4.
+    b['dx'] = inside('dx', n, F + 2)
+    b['dx_acc'] = inside('dx_acc', n, F + 4)
+  return b
+
+
+def run_dot(be, case, inp, dev, seen=None):
+  F, D, si = case['F'], case['D'], case['si']
+  n, P = F * D, dot_pairs(F, si)
+  wide = case['layout'] == 'wide'
+  x = dot_view(inp['xw'].to(dev), case, n)
+  out = inp['out0'].to(dev).clone()
+  if wide:
+    be.dot_interaction_fwd(x, F, D, si, out=dot_view(out, case, P))
+  else:
+    out = be.dot_interaction_fwd(x, F, D, si)
+  if case['fwd_only']:
+    return dict(out=out)
+  g = dot_view(inp['gw'].to(dev), case, P)
+  dx, acc = inp['old'].to(dev).clone(), inp['old'].to(dev).clone()
+  if wide:  # accumulate = 0 into NaN: an element that is not written, or is added to, stays NaN
+    dot_view(dx, case, n).fill_(float('nan'))
+    be.dot_interaction_bwd(x, g, F, D, si, into=dot_view(dx, case, n), accumulate=False)
+  else:
+    dx = be.dot_interaction_bwd(x, g, F, D, si)
+  be.dot_interaction_bwd(x, g, F, D, si, into=dot_view(acc, case, n), accumulate=True)
+  if seen is not None:  # addresses and row strides of the four strided operands
+    views = (x, dot_view(out, case, P), g, dot_view(acc, case, n))
+    seen.update(ptrs=[v.data_ptr() for v in views], strides=[v.stride(0) for v in views])
+  return dict(out=out, dx=dx, dx_acc=acc)
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # the registry: per operation its cases, inputs, formula, bound and runner; references are computed once and shared
 # ------------------------------------------------------------------------------------------------------------------
 OPS = {
@@ -690,6 +1017,8 @@ OPS = {
     'din': (DIN_CASES, din_inputs, din_formula, din_bound, run_din),
     'mmoe': (MMOE_CASES, mmoe_inputs, mmoe_formula, mmoe_bound, run_mmoe),
     'ce': (CE_CASES, ce_inputs, ce_formula, ce_bound, run_ce),
+    'cin': (CIN_CASES, cin_inputs, cin_formula, cin_bound, run_cin),
+    'dot': (DOT_CASES, dot_inputs, dot_formula, dot_bound, run_dot),
 }
 ALL_CASES = [(op, c) for op in OPS for c in OPS[op][0]]
 
