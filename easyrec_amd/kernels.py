@@ -2140,6 +2140,43 @@ class HipBackend(object):
       self.op_log.append(('er::ln_relu_bwd_kernel', 13.0 * n * B * O))
     return dhs
 
+  # -- K8j PPNet's gate multiply (layers/keras/ppnet.py)
+  def gate_scale_grid(self, B, W):
+    return int(self.lib.er_gate_scale_grid(int(B), int(W)))
+
+  def gate_scale_fwd(self, x, z, bias):
+    """x, z [B, W] (row pitches of their own), bias [W] or None -> a fresh x * 2 * sigmoid(z + bias), one launch."""
+    B, W = x.shape
+    x, z = self._row_major(x), self._row_major(z)
+    assert z.shape == (B, W) and (bias is None or (bias.shape == (W,) and bias.is_contiguous()))
+    out = torch.empty(B, W, dtype=torch.float32, device=x.device)
+    (p, ld) = self._rows_table([x, z, out], 'x, z, out')
+    self.ck.er_gate_scale_fwd(p[0], ld[0], p[1], ld[1], _p(None if bias is None else _f32c(bias)), B, W, p[2], ld[2],
+                              _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::gate_scale_fwd_kernel', 8.0 * B * W))
+    return out
+
+  def gate_scale_bwd(self, dout, x, z, bias, grads, acc, want_dx=True):
+    """-> (dx = dout * g or None, dz = dout * x * g * (1 - g / 2)), g recomputed, one launch; with a bias its gradient
+    (the column sums of dz) is added into (acc) or written to `grads` (a ThetaGradTable of the bias's buffer) by the
+    shared fixed-order reduce."""
+    B, W = x.shape
+    dout, x, z = self._row_major(dout), self._row_major(x), self._row_major(z)
+    assert dout.shape == (B, W) and z.shape == (B, W) and (bias is None or (grads is not None and len(grads.grads) == 1))
+    dz = torch.empty(B, W, dtype=torch.float32, device=x.device)
+    dx = torch.empty(B, W, dtype=torch.float32, device=x.device) if want_dx else None
+    grid = self.gate_scale_grid(B, W)
+    partials = torch.empty(grid * W, dtype=torch.float32, device=x.device) if bias is not None else None
+    (p, ld) = self._rows_table([dout, x, z, dz], 'dout, x, z, dz')
+    self.ck.er_gate_scale_bwd(p[0], ld[0], p[1], ld[1], p[2], ld[2], _p(None if bias is None else _f32c(bias)), B, W,
+                              _p(dx), W, p[3], ld[3], _p(partials), _stream())
+    if bias is not None:
+      self.theta_grad_reduce(partials, grid, grads, 8, acc)
+    if self.op_log is not None:
+      self.op_log.append(('er::gate_scale_bwd_kernel', (12.0 if want_dx else 11.0) * B * W))
+    return dx, dz
+
   # -- K8d FiBiNet's field blocks (layers/keras/fibinet.py)
   def bilinear_lds_bytes(self, F, D):
     return int(self.lib.er_bilinear_lds_bytes(int(F), int(D)))
@@ -4715,6 +4752,29 @@ class LnReluFn(torch.autograd.Function):
       dmine = dy
     dhs = hip().ln_relu_bwd(dmine, ctx.y, hs, gb[0::2], mean, rstd, table, acc)
     return (None, None, dout, None) + tuple(dhs) + ret
+
+
+class GateScaleFn(torch.autograd.Function):
+  """reference layers/keras/ppnet.py:51-58, :185-187: apply(grads, x [B, W], z [B, W], bias [W] or None) ->
+  x * 2 * sigmoid(z + bias), one launch each way (er_gate_scale_*); z is the gate's `weight` Dense before its bias.  The
+  backward recomputes the gate.  `grads` = [the bias's gradient buffer]: dbias is ADDED into it by the shared fixed-order
+  reduce and autograd gets None for the bias; grads None: dbias is returned.  A caller whose x does not require a
+  gradient gets none, and the launch skips it."""
+
+  @staticmethod
+  def forward(ctx, grads, x, z, bias):
+    out = hip().gate_scale_fwd(x.detach(), z.detach(), None if bias is None else bias.detach())
+    ctx.save_for_backward(x, z, *(() if bias is None else (bias,)))
+    ctx.grads = grads
+    return out
+
+  @staticmethod
+  def backward(ctx, dout):
+    x, z = ctx.saved_tensors[:2]
+    bias = list(ctx.saved_tensors[2:])
+    table, acc, ret = _theta_grads(ctx, bias) if bias else (None, False, (None,))
+    dx, dz = hip().gate_scale_bwd(dout, x, z, bias[0] if bias else None, table, acc, want_dx=ctx.needs_input_grad[1])
+    return (None, dx, dz) + ret
 
 
 def _seq_column(x):

@@ -6,5 +6,6 @@ from .multi_task import MMoE  # noqa: F401
 from .din import DIN  # noqa: F401
 from .fibinet import BiLinear, FiBiNet, SENet  # noqa: F401
 from .mask_net import MaskBlock, MaskNet  # noqa: F401
+from .ppnet import PPNet  # noqa: F401
 from .standard import Activation, Dense, Dropout  # noqa: F401
 from .text_cnn import TextCNN  # noqa: F401

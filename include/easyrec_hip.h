@@ -1167,6 +1167,42 @@ int er_ln_relu_bwd(const float* dy, int64_t lddy, const float* y, int64_t ldy, c
                    er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8j PPNet's gate multiply (reference layers/keras/ppnet.py:51-58, :185-187): an MLP layer's output times
+ *     2 * sigmoid of the gate's `weight` Dense.  Replaces BiasAdd, Sigmoid and two Mul, their gradients and
+ *     the bias gradient's column sum.  fp32, no atomics, no MFMA, fixed summation orders: two runs and a
+ *     graph replay give the same bits.  x [B, W] at pitch ldx (the MLP layer's output as the layer left
+ *     it); z [B, W] at pitch ldz (the `weight` Dense BEFORE its bias); bias [W] (that layer's bias
+ *     variable) or NULL (a gate with use_bn has none).  The operands are read in place, column slices of
+ *     wider tensors included; nothing is copied or packed.
+ * er_gate_scale_fwd: g = 2 / (1 + exp(-(z + bias))); out[b, c] = x[b, c] * g[b, c], out [B, W] at pitch
+ *   ldout.  Finite for every finite z: g = 0 at z + bias = -100 (exp overflows to +inf), 2 at +100; never
+ *   NaN.  Nothing is saved beyond the inputs.
+ * er_gate_scale_bwd: recomputes g; dx = dout * g (dx may be NULL: a caller whose x needs no gradient);
+ *   dz = dout * x * g * (1 - g / 2), multiplied left to right.  Every element of dx and dz is written.
+ *   partials [er_gate_scale_grid(B, W), W]: per workgroup the column sums of dz over the rows it owns, which
+ *   er_theta_grad_reduce (K8e) sums with row_groups = 8 (one segment of length W) into the bias gradient
+ *   buffer.  partials is required when bias is given; with bias == NULL it may be NULL, and the sums are
+ *   not formed.
+ * Geometry, both directions: er_gate_scale_grid = min(ceil(B / 8), 1024) workgroups of 256 threads;
+ *   workgroup g owns the rows [g * per, min(B, (g + 1) * per)), per = ceil(B / grid).  A row is wc = W / V
+ *   pieces (V = 4 floats on the 16-byte path, 1 on the 4-byte path); TC = min(wc, 256), RL = 256 / TC;
+ *   thread t is piece lane t % TC and row lane t / TC (t >= TC * RL idle) and walks, per piece tc, tc + TC,
+ *   .., the rows r0 + rl, r0 + rl + RL, ...
+ * Summation order of partials: a thread adds its rows' dz in the order it walks them, starting from 0.f;
+ *   with RL > 1 (wc < 256) the row lanes' sums are then combined through LDS in the order 0, 1, .., RL - 1.
+ *   No atomics.
+ * Envelope: 1 <= W <= 4096, B >= 1, every pitch >= W; outside it the launches return an error and launch
+ *   nothing, and er_gate_scale_grid returns 0.  16-byte accesses where W % 4 == 0 and every base and pitch
+ *   is a multiple of 16 bytes; 4-byte accesses otherwise.
+ * -------------------------------------------------------------------------------------------- */
+int32_t er_gate_scale_grid(int64_t B, int32_t W);   /* rows of `partials`; 0 outside the envelope */
+int er_gate_scale_fwd(const float* x, int64_t ldx, const float* z, int64_t ldz, const float* bias, int64_t B, int32_t W,
+                      float* out, int64_t ldout, er_stream_t stream);
+int er_gate_scale_bwd(const float* dout, int64_t lddout, const float* x, int64_t ldx, const float* z, int64_t ldz,
+                      const float* bias, int64_t B, int32_t W, float* dx, int64_t lddx, float* dz, int64_t lddz,
+                      float* partials, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed

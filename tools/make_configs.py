@@ -511,6 +511,33 @@ def masknet_taobao(**kw):
   ''' % (names, block * 3))
 
 
+def ppnet_taobao(**kw):
+  """PPNet, the model section of samples/model_config/ppnet_on_taobao.config: RankModel over a backbone whose one block
+  is `PPNet` on (general, memorize) as a list - `general` the 14 other fields, `memorize` user_id, adgroup_id and pid, all
+  of D = 16 - with MLP [512, 256], mode lazy, full_gate_input (the gates read [stop_gradient(general) | memorize], 272
+  wide); top_mlp [128, 64]; l2 1e-6, embedding l2 1e-5."""
+  cfg = taobao_base('tag', **kw)
+  cfg.model_dir = 'experiments/ppnet_taobao_ckpt'
+  cfg.data_config.label_fields.append('clk')
+  memorize = ['user_id', 'adgroup_id', 'pid']
+  general = [n for n in TAOBAO_USER + TAOBAO_ITEM + ['tag_category_list', 'tag_brand_list'] if n not in memorize]
+  names = lambda feats: ' '.join("feature_names: '%s'" % n for n in feats)
+  return _model_text(cfg, '''
+    model_class: 'RankModel'
+    feature_groups { group_name: 'memorize' %s wide_deep: DEEP }
+    feature_groups { group_name: 'general' %s wide_deep: DEEP }
+    backbone {
+      blocks { name: 'ppnet' inputs { feature_group_name: 'general' } inputs { feature_group_name: 'memorize' }
+               merge_inputs_into_list: true
+               keras_layer { class_name: 'PPNet'
+                             ppnet { mlp { hidden_units: [512, 256] } mode: 'lazy' full_gate_input: true } } }
+      top_mlp { hidden_units: [128, 64] }
+    }
+    model_params { l2_regularization: 1e-6 }
+    embedding_regularization: 1e-5
+  ''' % (names(memorize), names(general)))
+
+
 def dssm_taobao(in_batch=False, **kw):
   """DSSM, the model section of samples/model_config/dssm_on_taobao.config: the user tower over the 8 user fields and
   the two tag lists, the item tower over the 7 item fields, [256, 128, 64, 32] each, cosine similarity with scale_simi,
@@ -1116,6 +1143,7 @@ if __name__ == '__main__':
   write(deepfm_textcnn_movielens(), 'deepfm_textcnn_movielens.config')
   write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
   write(masknet_taobao(item_rows=10000000), 'masknet_taobao_10m.config')
+  write(ppnet_taobao(item_rows=10000000), 'ppnet_taobao_10m.config')
   write(dssm_taobao(item_rows=10000000), 'dssm_taobao_10m.config')
   write(dssm_taobao(in_batch=True, item_rows=10000000), 'dssm_inbatch_taobao_10m.config')
   write(mind_taobao(item_rows=10000000), 'mind_taobao_10m.config')
