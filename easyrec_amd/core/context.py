@@ -33,6 +33,9 @@ class ModelContext(object):
     self.grad_slots = {}
     # dense_dtype 'bf16' on the GPU: the kernels.Bf16Shadows of the model (weight shadows + the step's bf16 operand copies)
     self.bf16_state = None
+    # per step: the feature groups' variational-dropout penalties, [1] each (the reference's `variational_dropout_loss`
+    # collection; layers/variational_dropout_layer.py)
+    self.vdrop_losses = []
 
 
 @contextlib.contextmanager

@@ -2177,6 +2177,55 @@ class HipBackend(object):
       self.op_log.append(('er::gate_scale_bwd_kernel', (12.0 if want_dx else 11.0) * B * W))
     return dx, dz
 
+  # -- K8k variational dropout on a feature group's output (layers/variational_dropout_layer.py)
+  def vdrop_grid(self, B, W):
+    return int(self.lib.er_vdrop_grid(int(B), int(W)))
+
+  @staticmethod
+  def _vdrop_seg(seg):
+    """seg: None (identity) or a VDropSeg -> (host array, device pointer)"""
+    return (None, None) if seg is None else (seg.host, _p(seg.dev))
+
+  def vdrop_fwd(self, x, logit_p, u, seg, lam):
+    """x [B, W] (a row pitch of its own), logit_p [P], u [B, P] or None (evaluation), seg: a VDropSeg or None (identity, P
+    == W), lam = lambda / B -> (a fresh x * m, penalty [1]), one launch."""
+    B, W = x.shape
+    P = logit_p.numel()
+    x = self._row_major(x)
+    u = None if u is None else self._row_major(u)
+    assert (u is None or u.shape == (B, P)) and (seg is None or seg.W == W)
+    out = torch.empty(B, W, dtype=torch.float32, device=x.device)
+    penalty = torch.empty(1, dtype=torch.float32, device=x.device)
+    (p, ld) = self._rows_table([x, out] + ([] if u is None else [u]), 'x, out, u')
+    sh, sd = self._vdrop_seg(seg)
+    self.ck.er_vdrop_fwd(p[0], ld[0], _p(_f32c(logit_p)), None if u is None else p[2], 0 if u is None else ld[2], sh, sd,
+                         B, W, P, float(lam), p[1], ld[1], _p(penalty), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::vdrop_fwd_kernel', 12.0 * B * W))
+    return out, penalty
+
+  def vdrop_bwd(self, dout, dpenalty, x, logit_p, u, seg, lam, grads, acc, want_dx=True):
+    """-> dx = dout * m or None, m recomputed, one launch; dlogit_p (the batch sums and the penalty's own gradient times
+    dpenalty [1], None for none) is added into (acc) or written to `grads` (a ThetaGradTable of logit_p's buffer) by the
+    shared fixed-order reduce."""
+    B, W = x.shape
+    P = logit_p.numel()
+    dout, x = self._row_major(dout), self._row_major(x)
+    u = None if u is None else self._row_major(u)
+    assert dout.shape == (B, W) and len(grads.grads) == 1 and (u is None or u.shape == (B, P))
+    dx = torch.empty(B, W, dtype=torch.float32, device=x.device) if want_dx else None
+    grid = self.vdrop_grid(B, W)
+    partials = torch.empty((grid + 1) * P, dtype=torch.float32, device=x.device)
+    (p, ld) = self._rows_table([dout, x] + ([] if u is None else [u]), 'dout, x, u')
+    sh, sd = self._vdrop_seg(seg)
+    self.ck.er_vdrop_bwd(p[0], ld[0], p[1], ld[1], _p(_f32c(logit_p)), None if u is None else p[2],
+                         0 if u is None else ld[2], sh, sd, B, W, P, float(lam),
+                         None if dpenalty is None else _p(_f32c(dpenalty)), _p(dx), W, _p(partials), _stream())
+    self.theta_grad_reduce(partials, grid + 1, grads, 8, acc)
+    if self.op_log is not None:
+      self.op_log.append(('er::vdrop_bwd_kernel', (16.0 if want_dx else 15.0) * B * W))
+    return dx
+
   # -- K8d FiBiNet's field blocks (layers/keras/fibinet.py)
   def bilinear_lds_bytes(self, F, D):
     return int(self.lib.er_bilinear_lds_bytes(int(F), int(D)))
@@ -4775,6 +4824,43 @@ class GateScaleFn(torch.autograd.Function):
     table, acc, ret = _theta_grads(ctx, bias) if bias else (None, False, (None,))
     dx, dz = hip().gate_scale_bwd(dout, x, z, bias[0] if bias else None, table, acc, want_dx=ctx.needs_input_grad[1])
     return (None, dx, dz) + ret
+
+
+class VDropSeg(object):
+  """The column -> parameter map of feature-wise variational dropout, as er_vdrop_* take it: `dims` = the features'
+  widths in the concatenation's order -> W = sum(dims) int32 entries, once in a host array (checked by every launch) and
+  once on the device (read by the kernel).  Built once per layer."""
+
+  def __init__(self, dims, device):
+    seg = np.repeat(np.arange(len(dims), dtype=np.int32), np.asarray(dims, dtype=np.int64))
+    self.W = int(seg.size)
+    self.host = (ctypes.c_int32 * self.W)(*seg.tolist())
+    self.dev = torch.from_numpy(seg).to(device)
+
+
+class VDropFn(torch.autograd.Function):
+  """reference layers/variational_dropout_layer.py:71-130: apply(grads, x [B, W], logit_p [P], u [B, P] or None
+  (evaluation), seg (a VDropSeg, or None for the identity: P == W), lam = regularization_lambda / B) -> (x * m, penalty
+  [1]), one launch each way (er_vdrop_*).  The backward recomputes m from (logit_p, u).  `grads` = [logit_p's gradient
+  buffer]: dlogit_p - the batch sums and the penalty's own gradient - is ADDED into it by the shared fixed-order reduce
+  and autograd gets None for logit_p; grads None: dlogit_p is returned.  A caller whose x does not require a gradient
+  gets none, and the launch skips it."""
+
+  @staticmethod
+  def forward(ctx, grads, x, logit_p, u, seg, lam):
+    out, penalty = hip().vdrop_fwd(x.detach(), logit_p.detach(), u, seg, lam)
+    ctx.save_for_backward(x, logit_p, *(() if u is None else (u,)))
+    ctx.grads, ctx.seg, ctx.lam = grads, seg, lam
+    return out, penalty
+
+  @staticmethod
+  def backward(ctx, dout, dpenalty):
+    x, logit_p = ctx.saved_tensors[:2]
+    u = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+    table, acc, ret = _theta_grads(ctx, [logit_p])
+    dx = hip().vdrop_bwd(dout, dpenalty.reshape(1).contiguous(), x, logit_p.detach(), u, ctx.seg, ctx.lam, table, acc,
+                         want_dx=ctx.needs_input_grad[1])
+    return (None, dx) + ret + (None, None, None)
 
 
 def _seq_column(x):

@@ -987,8 +987,9 @@ class InputLayer(object):
     self._kernel_regularizer = kernel_regularizer
     self._is_training = is_training
     self._is_predicting = is_predicting
-    if variational_dropout_config is not None:
-      raise NotImplementedError('variational dropout is outside the hot-path scope')
+    # variational dropout on every group's combined output (layers/input_layer.py:348-362): group name -> its layer
+    self._variational_dropout_config = variational_dropout_config
+    self._variational_dropout = OrderedDict()
     assert engine is not None, 'InputLayer needs the EmbeddingEngine of the model'
     self._engine = engine
     self._group_plan = {}  # group name -> dict(gkey, columns, cols, dims)
@@ -1042,6 +1043,8 @@ class InputLayer(object):
       raise ValueError('feature group %s mixes attribute fields of the negative sampler (%s) with other features (%s)' % (
           group_name, ', '.join(sampled), ', '.join(c.raw_name for c in columns if c.raw_name not in sampled)))
     rows = features.extended_rows(sampled[0]) if sampled else B
+    if self._variational_dropout_config is not None and not plain_only:
+      self._check_variational_dropout(group_name, sampled)
     width = sum(c.dimension for c in columns)
     gkey = 'group:' + group_name + (':plain' if plain_only else '')
     eng.declare_group(gkey, width, self._embedding_regularizer, n_rows=rows)
@@ -1079,6 +1082,37 @@ class InputLayer(object):
                           'layer': layer, 'column': c})
       plan['combiners'] = combiners
 
+  def _check_variational_dropout(self, group_name, sampled):
+    """What a group under variational dropout cannot be, at build time."""
+    from easyrec_amd.core import context
+    from easyrec_amd.layers.sharded_embedding import ShardedEmbeddingEngine
+    what = 'feature group %s under variational dropout' % group_name
+    if sampled:
+      raise ValueError('%s: a group fed by a negative sampler (%s) is not supported' % (what, ', '.join(sampled)))
+    if getattr(context.current(), 'dense_dtype', 'f32') == 'bf16':
+      raise ValueError('%s: dense_dtype bf16 is not supported (variational dropout is fp32)' % what)
+    if isinstance(self._engine, ShardedEmbeddingEngine):
+      raise ValueError('%s: embedding-parallel training is not supported' % what)
+
+  def _apply_variational_dropout(self, group_name, out, plan, name_to_out):
+    """reference layers/input_layer.py:348-362 on the group's concatenation `out` of plain columns: -> (the dropped
+    tensor, its split into the features).  The dropped tensor is no engine group
+    output: it carries no gradient sink, and its gradient reaches the engine through autograd (_GroupOutFn.backward).
+    `name_to_out` - what the target attention and is_dict=True get - keeps the tensors from before the dropout, and so
+    does the embedding-output L2, which the engine takes from its own buffers."""
+    from easyrec_amd.layers.variational_dropout_layer import VariationalDropoutLayer
+    layer = self._variational_dropout.get(group_name)
+    if layer is None:
+      # (plain columns only: a group that also combines sequence columns is refused by _check_sequence_combiners)
+      dims = OrderedDict((c.raw_name, int(d)) for c, d in zip(plan['columns'], plan['dims']))
+      layer = self._variational_dropout[group_name] = VariationalDropoutLayer(
+          self._variational_dropout_config, dims, self._is_training, name=group_name)
+    dropped = layer(out)
+    widths = list(layer.features_dimension.values())
+    starts = np.cumsum([0] + widths[:-1]).tolist()
+    views = [dropped[:, c0:c0 + d] for c0, d in zip(starts, widths)]
+    return dropped, FeatureList(views, base=dropped, col0=0, dims=widths)
+
   def _check_sequence_combiners(self, features, group_name, fg, seq_columns):
     """What a group that combines sequence columns over time cannot be, at build time."""
     from easyrec_amd.core import context
@@ -1091,6 +1125,8 @@ class InputLayer(object):
         raise NotImplementedError('sequence_combiner %s of feature %s (the reference raises NotImplementedError too)' % (
             kind, c.raw_name))
     what = 'feature group %s combines sequence columns over time (sequence_combiner)' % group_name
+    if getattr(self, '_variational_dropout_config', None) is not None:
+      raise NotImplementedError('%s: variational dropout over combined sequence columns is not built' % what)
     ctx = context.current()
     if getattr(ctx, 'dense_dtype', 'f32') == 'bf16':
       raise ValueError('%s: dense_dtype bf16 is not supported (the sequence combiners are fp32)' % what)
@@ -1133,6 +1169,8 @@ class InputLayer(object):
     """is_combine=False (layers/input_layer.py:268-278): ([(embedding [B, L, dim], length [B]) per sequence column],
     the plain columns' concat (None when the group has none), their per-feature list).  L = the loaded batch's longest
     sequence."""
+    if self._variational_dropout_config is not None:
+      raise ValueError('variational dropout is not supported in not combined mode now.')
     eng = self._engine
     fg = self._feature_groups[group_name]
     columns, _ = fg.select_columns(self._fc_parser)
@@ -1209,6 +1247,8 @@ class InputLayer(object):
     name_to_out = {c.raw_name: v for c, v in zip(plan['columns'], views)}
     if (group_name, 'combined') in self._seq_plan and not plain_only:
       out, flist, name_to_out = self._append_combined_sequences(features, group_name, out, views, name_to_out)
+    if self._variational_dropout_config is not None and not plain_only:
+      out, flist = self._apply_variational_dropout(group_name, out, plan, name_to_out)
     if is_dict:
       return out, flist, name_to_out
     return out, flist

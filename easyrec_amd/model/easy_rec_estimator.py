@@ -296,6 +296,7 @@ class EasyRecEstimator(object):
       self.model.begin_step()
       self.model.build_predict_graph()
       loss_dict = self.model.build_loss_graph()
+      self.model.add_variational_dropout_loss(loss_dict)
       # the step's tail (single GPU, no clipping): the weight gradients stay queued and are contracted in the grid of the
       # embedding row update, the scalar loss tail rides in that grid and the dense optimizer in the next one
       # (er_emb_bwd_fused_tail) - nothing between here and the end of the step reads what they write
@@ -605,6 +606,22 @@ class EasyRecEstimator(object):
   def load_state_dict(self, state):
     self.varstore.load_state_dict(state, strict=False)
     self.engine.load_state_dict(state)
+
+  def variational_dropout_collection(self):
+    """[[group name, [[feature, width], ..]], ..]: what the reference keeps in its `variational_dropout` collection"""
+    import json
+    layers = getattr(self.model._input_layer, '_variational_dropout', {})
+    return [json.loads(layer.collection_entry) for layer in layers.values()]
+
+  def feature_importance(self):
+    """{group: OrderedDict(feature -> mean dropout probability)}, sorted ascending as the reference's
+    tools/feature_selection.py `_get_feature_importance` sorts (variational dropout)."""
+    from easyrec_amd.layers import variational_dropout_layer as vdl
+    out = OrderedDict()
+    for name, layer in getattr(self.model._input_layer, '_variational_dropout', {}).items():
+      out[name] = vdl.feature_importance(layer.logit_p.detach().cpu().numpy(), layer.features_dimension,
+                                         layer.variational_dropout_wise())
+    return out
 
   def loss_values(self):
     torch.cuda.synchronize() if self.device.type == 'cuda' else None

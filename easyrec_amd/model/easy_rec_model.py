@@ -141,6 +141,7 @@ class EasyRecModel(six.with_metaclass(_meta_type, object)):
       ctx.heads.clear()
       del ctx.tail_jobs[:]
       ctx.grad_slots.clear()
+      del ctx.vdrop_losses[:]
       if getattr(ctx, 'bf16_state', None) is not None:
         ctx.bf16_state.begin_step()
 
@@ -151,6 +152,21 @@ class EasyRecModel(six.with_metaclass(_meta_type, object)):
   @abstractmethod
   def build_loss_graph(self):
     pass
+
+  def add_variational_dropout_loss(self, loss_dict):
+    """reference model/easy_rec_estimator.py:177-181: the sum of the feature groups' penalties as a loss of its own - part
+    of total_loss, not of regularization_loss.  Each group's penalty is seeded with gradient 1 on its own."""
+    penalties = context.current().vdrop_losses
+    if not penalties:
+      return loss_dict
+    total = penalties[0].detach()
+    for p in penalties[1:]:
+      total = total + p.detach()
+    loss_dict['variational_dropout_loss'] = total
+    for p in penalties:
+      if p.requires_grad:
+        self._backward_seeds.append((p, torch.ones_like(p)))
+    return loss_dict
 
   def build_metric_graph(self, eval_config):
     return self._metric_dict

@@ -186,6 +186,12 @@ def save(est, ckpt_path):
     for name, kv in getattr(engine, 'kv_tables', {}).items():
       dense[name + '/kv_meta'] = np.array([kv['seed'], kv['mean'], kv['stddev'], kv['capacity']], dtype=np.float64)
       dense[name + '/kv_seed'] = np.asarray(int(kv['seed']), dtype=np.int64)  # (float64 loses seeds >= 2^53)
+    # variational dropout: the groups' feature widths, which the reference keeps in the meta graph's `variational_dropout`
+    # collection (tools/feature_selection.py reads them from here), as JSON bytes
+    if hasattr(est, 'variational_dropout_collection') and est.variational_dropout_collection():
+      import json
+      dense['variational_dropout'] = np.frombuffer(json.dumps(est.variational_dropout_collection()).encode('utf-8'),
+                                                   dtype=np.uint8).copy()
     dense['global_step'] = np.asarray(int(est.global_step), dtype=np.int64)
     tensor_bundle.write_bundle(ckpt_path, dense)
     tensor_bundle.write_checkpoint_state(ckpt_path)

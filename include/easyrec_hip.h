@@ -1203,6 +1203,56 @@ int er_gate_scale_bwd(const float* dout, int64_t lddout, const float* x, int64_t
                       float* partials, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8k Variational dropout on a feature group's concatenated output (reference
+ *     layers/variational_dropout_layer.py; arXiv 1712.08645).  Replaces about a dozen elementwise launches
+ *     each way and the batch reduction of the probabilities' gradient.  fp32, no atomics, no MFMA, vector
+ *     stores only, fixed summation orders: two runs and a graph replay give the same bits.
+ *     x [B, W] at pitch ldx, read in place (the engine's group output, a column slice of a wider tensor
+ *     included); logit_p [P]; u [B, P] at pitch ldu, the uniform noise drawn by the caller, or NULL for
+ *     evaluation; the column -> parameter map TWICE: seg_host (a HOST array of W entries, checked by every
+ *     launch) and seg (the same W entries in device memory, read by the kernel), both NULL for the identity
+ *     (then P == W: one probability per column).  lambda_over_rows = regularization_lambda / B.
+ * With p = 1 / (1 + exp(-logit_p)) and EPS = 2.220446049250313e-16f:
+ *   training    a = ((log(p + EPS) - log((1 - p) + EPS)) + log(u + EPS)) - log((1 - u) + EPS)
+ *               s = 1 / (1 + exp(-(a / 0.1f))), m = 1 - s
+ *   evaluation  m = 1 - p
+ *   with the precise logf / expf.  exp overflows to +inf where its argument passes about 88.7 and the
+ *   quotient is then 0: every finite input gives a finite m in [0, 1] (|a / 0.1| reaches 720).
+ * er_vdrop_fwd: out[b, c] = x[b, c] * m[b, seg[c]], out [B, W] at pitch ldout; penalty[0] =
+ *   lambda_over_rows * sum_j (1 - p[j]), by workgroup 0: thread t adds j = t, t + 256, .. from 0.f, the 256
+ *   sums meet in the wave butterfly 1, 2, .., 32 and then as (w0 + w1) + (w2 + w3).  One launch.
+ * er_vdrop_bwd: recomputes m (no mask is saved); dx = dout * m (dx may be NULL: a caller whose x needs no
+ *   gradient); partials [er_vdrop_grid(B, W) + 1, P]: row g = workgroup g's sums over its rows of
+ *   dm/dlogit[b, j] * (sum over the columns c of j, ascending, from 0.f, of dout[b, c] * x[b, c]) with
+ *   training    dm/dlogit = -10 s (1 - s) * p (1 - p) (1 / (p + EPS) + 1 / ((1 - p) + EPS))
+ *   evaluation  dm/dlogit = -(p (1 - p));
+ *   the last row is the penalty's own gradient -(lambda_over_rows * (p (1 - p))) * dpenalty[0] (zeros when
+ *   dpenalty is NULL).  er_theta_grad_reduce (K8e) sums the grid + 1 rows with row_groups = 8 into
+ *   logit_p's gradient buffer.
+ * Geometry, both directions: er_vdrop_grid = min(ceil(B / 8), 1024) workgroups of 256 threads; workgroup g
+ *   owns the rows [g * per, min(B, (g + 1) * per)), per = ceil(B / grid).  A row is np pieces: with the
+ *   identity map a piece is V adjacent columns (np = W / V; V = 4 floats on the 16-byte path, 1 on the 4-byte
+ *   path); with a map a piece is one parameter and its columns, walked ascending V at a time (np = P), m
+ *   computed once per (row, parameter).  TC = min(np, 256), RL = 256 / TC; thread t is piece lane t % TC and
+ *   row lane t / TC (t >= TC * RL idle) and walks, per piece tc, tc + TC, .., the rows r0 + rl, r0 + rl +
+ *   RL, ...  A thread adds its rows' terms in the order it walks them, from 0.f; with RL > 1 (np < 256) the
+ *   row lanes' sums are then combined through LDS in the order 0, 1, .., RL - 1.
+ * Envelope: B >= 1, 1 <= W <= 4096, 1 <= P <= W, every pitch >= its row's width; the map non-decreasing
+ *   from 0 to P - 1 in steps of 0 or 1.  Outside it the launches return an error and launch nothing, and
+ *   er_vdrop_grid returns 0.  16-byte accesses where W % 4 == 0, every base and pitch of x, out, dout and
+ *   dx is a multiple of 16 bytes and - identity - so are logit_p's base and u's base and pitch, or - with
+ *   a map - every segment starts at a multiple of 4 columns; 4-byte accesses otherwise.
+ * -------------------------------------------------------------------------------------------- */
+int32_t er_vdrop_grid(int64_t B, int32_t W);   /* rows of `partials` less one; 0 outside the envelope */
+int er_vdrop_fwd(const float* x, int64_t ldx, const float* logit_p, const float* u, int64_t ldu, const int32_t* seg_host,
+                 const int32_t* seg, int64_t B, int32_t W, int32_t P, float lambda_over_rows, float* out, int64_t ldout,
+                 float* penalty, er_stream_t stream);
+int er_vdrop_bwd(const float* dout, int64_t lddout, const float* x, int64_t ldx, const float* logit_p, const float* u,
+                 int64_t ldu, const int32_t* seg_host, const int32_t* seg, int64_t B, int32_t W, int32_t P,
+                 float lambda_over_rows, const float* dpenalty, float* dx, int64_t lddx, float* partials,
+                 er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed

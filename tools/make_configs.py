@@ -95,6 +95,15 @@ def deepfm_criteo(**kw):
   return cfg
 
 
+def deepfm_vdrop_criteo(embedding_wise=True, **kw):
+  """deepfm_criteo plus variational dropout on both feature groups (reference layers/variational_dropout_layer.py): one
+  dropout probability per embedding column, or - embedding_wise False - per feature."""
+  cfg = deepfm_criteo(**kw)
+  cfg.model_config.variational_dropout.regularization_lambda = 0.01
+  cfg.model_config.variational_dropout.embedding_wise_variational_dropout = embedding_wise
+  return cfg
+
+
 def dcn_criteo(**kw):
   """DCN-v1 (model_class DCN) on the same 39 features, one group `all` (BASELINE config 3 shape)."""
   cfg = criteo_base(**kw)
@@ -1144,6 +1153,8 @@ if __name__ == '__main__':
   write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
   write(masknet_taobao(item_rows=10000000), 'masknet_taobao_10m.config')
   write(ppnet_taobao(item_rows=10000000), 'ppnet_taobao_10m.config')
+  write(deepfm_vdrop_criteo(), 'deepfm_vdrop_criteo.config')
+  write(deepfm_vdrop_criteo(embedding_wise=False), 'deepfm_vdrop_criteo_feature_num.config')
   write(dssm_taobao(item_rows=10000000), 'dssm_taobao_10m.config')
   write(dssm_taobao(in_batch=True, item_rows=10000000), 'dssm_inbatch_taobao_10m.config')
   write(mind_taobao(item_rows=10000000), 'mind_taobao_10m.config')
