@@ -3,10 +3,13 @@
 CLASSIFICATION with num_class == 1 -> tf.losses.sigmoid_cross_entropy(label, logits, weights)
 (reduction SUM_BY_NONZERO_WEIGHTS): one HIP launch (`er_sigmoid_ce_fwd_bwd`) produces the loss, the
 probabilities and d(loss)/d(logits); the backward of the model is seeded with that gradient.
+CLASSIFICATION with num_class > 1 -> tf.losses.sparse_softmax_cross_entropy, and JRC_LOSS -> loss/jrc_loss.py: one
+launch each as well (`er_softmax_ce`, `er_jrc`) or their torch compositions (builders/multiclass_loss.py).
 """
 import torch
 
 from easyrec_amd import kernels
+from easyrec_amd.builders import multiclass_loss
 from easyrec_amd.protos.loss_pb2 import LossType
 
 
@@ -71,10 +74,23 @@ def build_many(specs):
                     sp.get('loss_scale', 1.0) * (1.0 if torch.is_tensor(lw) else float(lw))))
     for i, res in zip(fused, be.sigmoid_ce_multi(heads)):
       out[i] = res
+  # ... and so do the multi-class softmax heads (er_softmax_ce_multi: the single-head launch's code per head)
+  multi = [i for i, sp in enumerate(specs) if sp['loss_type'] == LossType.CLASSIFICATION and sp.get('num_class', 1) > 1]
+  if len(multi) >= 2:
+    for sp in (specs[i] for i in multi):
+      head = kernels.pending_head(sp['pred'])
+      if head is not None:
+        kernels.materialize_head(head)
+    res = multiclass_loss.softmax_ce_many([(specs[i]['label'], specs[i]['pred'], specs[i].get('loss_weight', 1.0),
+                                            specs[i].get('loss_scale', 1.0)) for i in multi])
+    for i, (loss, dz, extras) in zip(multi, res):
+      loss._er_extras = extras
+      out[i] = (loss, dz)
   for i, sp in enumerate(specs):
     if out[i] is None:
+      kw = {'session_ids': sp['session_ids']} if sp.get('session_ids') is not None else {}
       out[i] = build(sp['loss_type'], sp['label'], sp['pred'], sp.get('loss_weight', 1.0), sp.get('num_class', 1),
-                     loss_scale=sp.get('loss_scale', 1.0), loss_param=sp.get('loss_param'))
+                     loss_scale=sp.get('loss_scale', 1.0), loss_param=sp.get('loss_param'), **kw)
   return out
 
 
@@ -134,8 +150,23 @@ def build(loss_type, label, pred, loss_weight=1.0, num_class=1, loss_scale=1.0, 
       loss = f1_reweight_sigmoid_cross_entropy(label, z, beta_square, weights) * loss_scale
       dz, = torch.autograd.grad(loss, z)
     return loss.detach().reshape(1), dz
+  if loss_type == LossType.CLASSIFICATION and num_class > 1:
+    # tf.losses.sparse_softmax_cross_entropy: one launch (er_softmax_ce) or its torch composition; what the launch also
+    # computed (the probabilities) rides on the loss tensor for the model's prediction dict
+    loss, dlogits, extras = multiclass_loss.softmax_ce(label, pred, loss_weight, loss_scale)
+    loss._er_extras = extras
+    return loss, dlogits
+  if loss_type == LossType.JRC_LOSS:
+    assert num_class == 2, 'num_class must be 2 when loss type is JRC_LOSS'
+    alpha, same_label, _ = multiclass_loss.check_jrc_param(loss_param)
+    loss, dlogits, extras = multiclass_loss.jrc(label, pred, kwargs.get('session_ids'), loss_weight, loss_scale, alpha,
+                                                same_label)
+    loss._er_extras = extras
+    return loss, dlogits
+  if loss_type == LossType.ZILN_LOSS:
+    raise NotImplementedError('ZILN_LOSS (the zero-inflated lognormal head) is not built')
   if loss_type in (LossType.CLASSIFICATION, LossType.BINARY_CROSS_ENTROPY_LOSS):
-    assert num_class == 1, 'multi-class softmax cross entropy is outside the hot-path scope'
+    assert num_class == 1, 'num_class must be 1 when loss type is BINARY_CROSS_ENTROPY_LOSS'
     weights = loss_weight if torch.is_tensor(loss_weight) else None
     scale = loss_scale * (1.0 if torch.is_tensor(loss_weight) else float(loss_weight))
     labels = label if label.dtype == torch.float32 else label.to(torch.float32)

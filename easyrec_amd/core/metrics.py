@@ -238,3 +238,22 @@ class MaxF1(object):
       p = np.where(self.tp + self.fp > 0, self.tp / (self.tp + self.fp), 0.0)
       r = np.where(self.tp + self.fn > 0, self.tp / (self.tp + self.fn), 0.0)
     return float(np.max(2 * p * r / (p + r + 1e-12)))
+
+
+class TopKHits(object):
+  """accuracy (k = 1) and recall_at_topk { topk: k } of a multi-class head as streaming counts: the share of examples
+  whose label is among the k largest logits of its row, in tf.nn.top_k's order (the lower index first among equals).
+  update() takes the label's rank in that order (er_softmax_ce's label_rank, builders/multiclass_loss.py); the counts
+  stay on the device until result()."""
+
+  def __init__(self, k, device):
+    self.k = int(k)
+    self.hits = torch.zeros(1, dtype=torch.int64, device=device)
+    self.total = 0
+
+  def update(self, label_rank):
+    self.hits += (label_rank < self.k).sum()
+    self.total += int(label_rank.numel())
+
+  def result(self):
+    return float(self.hits.item()) / self.total if self.total else 0.0

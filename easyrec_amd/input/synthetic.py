@@ -2,6 +2,7 @@
 
 Produces the packed batch dict of DeviceFeatures.load directly (no CSV round trip, ids pre-hashed):
   labels      Bernoulli per label field            raw        uniform in [min_val, max_val], normalised
+              (label_classes={field: C}: that field's labels uniform class ids in [0, C) instead)
   hash ids    Zipf(1.05) over the bucket range      int ids    uniform over num_buckets
   TagFeature  ragged lists of 0..max_tag ids (+weights when the feature is weighted); ~10% empty
   SequenceFeature  [B, L] ids padded with -1; lengths uniform in 1..L, the first example has length L
@@ -18,7 +19,10 @@ from easyrec_amd.protos.feature_config_pb2 import FeatureConfig
 class SyntheticBatches(object):
 
   def __init__(self, data_config, feature_configs, batch_size=None, seed=20240607, mode='zipf', max_tag=5,
-               schema_kwargs=None):
+               schema_kwargs=None, label_classes=None):
+    # label_classes: {label field: C} - class ids drawn uniformly from [0, C) for a multi-class head; a field it does not
+    # name keeps the Bernoulli labels (valid class ids for any C >= 2)
+    self.label_classes = dict(label_classes or {})
     self.schema = FeatureSchema(data_config, feature_configs, batch_size=batch_size, **(schema_kwargs or {}))
     self.B = self.schema.batch_size
     self.rng = np.random.default_rng(seed)
@@ -41,6 +45,8 @@ class SyntheticBatches(object):
     B, sch, rng = self.B, self.schema, self.rng
     out = {}
     out['labels'] = (rng.random((max(len(sch.label_fields), 1), B)) < 0.25).astype(np.float32)
+    for field, classes in self.label_classes.items():  # (drawn after the Bernoulli block: without the keyword the stream is unchanged)
+      out['labels'][sch.label_fields.index(field)] = rng.integers(0, int(classes), size=B).astype(np.float32)
     raw = np.zeros((max(sch.n_raw_rows, 1), B), dtype=np.float32)
     for name, r in sch.raw.items():
       fc = self.fcs[name]

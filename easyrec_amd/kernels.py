@@ -2226,6 +2226,90 @@ class HipBackend(object):
       self.op_log.append(('er::vdrop_bwd_kernel', (16.0 if want_dx else 15.0) * B * W))
     return dx
 
+  # -- K8l multi-logit heads: softmax cross entropy and JRC (builders/multiclass_loss.py)
+  def softmax_ce_grid(self, B, C):
+    return int(self.lib.er_softmax_ce_grid(int(B), int(C)))
+
+  def jrc_grid(self, B):
+    return int(self.lib.er_jrc_grid(int(B)))
+
+  def _softmax_ce_outputs(self, logits, labels, weights, want):
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
+    B, C = logits.shape
+    dev = logits.device
+    y = None if labels is None else _f32c(labels)  # (None: a forward-only launch that reads no label)
+    assert (y is None and not {'loss', 'dlogits', 'label_rank'} & set(want)) or y.numel() == B
+    assert weights is None or _f32c(weights).numel() == B
+    grid = self.softmax_ce_grid(B, C)
+    assert grid > 0, 'er_softmax_ce: B = %d, C = %d outside the envelope' % (B, C)
+    f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+    o = {}
+    if 'loss' in want:
+      o['loss_partials'] = f(grid)
+      o['loss'] = f(1)
+      o['loss']._er_partials = (o['loss_partials'], 1.0, 1.0)  # (the loss tail's launch sums them: scale 1, divisor 1)
+    if 'dlogits' in want:
+      o['dlogits'] = f(B, C)
+    if 'probs' in want:
+      o['probs'] = f(B, C)
+    if 'y' in want:
+      o['y'] = torch.empty(B, dtype=torch.int64, device=dev)
+    if 'logits_y' in want:
+      o['logits_y'] = f(B)
+    if 'probs_y' in want:
+      o['probs_y'] = f(B)
+    if 'label_rank' in want:
+      o['label_rank'] = torch.empty(B, dtype=torch.int32, device=dev)
+    return y, o
+
+  def softmax_ce(self, logits, labels, weights, loss_scale=1.0, want=('loss', 'dlogits', 'probs')):
+    """er_softmax_ce: logits [B, C] (row stride >= C), labels [B] fp32 (None for a forward-only launch), weights [B] or
+    None -> dict of the outputs named in `want` (loss, dlogits, probs, y, logits_y, probs_y, label_rank).  'loss': loss
+    [1] with _er_partials set - the loss tail's launch sums loss_partials into it."""
+    y, o = self._softmax_ce_outputs(logits, labels, weights, want)
+    B, C = logits.shape
+    self.ck.er_softmax_ce(logits.data_ptr(), logits.stride(0), _p(y), _p(weights), B, C, float(loss_scale),
+                          _p(o.get('probs')), C, _p(o.get('y')), _p(o.get('logits_y')), _p(o.get('probs_y')),
+                          _p(o.get('dlogits')), C, _p(o.get('label_rank')), _p(o.get('loss_partials')), _stream())
+    return o
+
+  def softmax_ce_multi(self, heads, want=('loss', 'dlogits', 'probs')):
+    """heads: 1 to 8 of (logits, labels, weights or None, loss_scale) -> softmax_ce's dict per head, one launch
+    (er_softmax_ce_multi: the training outputs loss, dlogits and probs only)."""
+    assert set(want) <= {'loss', 'dlogits', 'probs'} and 1 <= len(heads) <= 8
+    n = len(heads)
+    vp, outs, keep = ctypes.c_void_p * n, [], []
+    for logits, labels, weights, _ in heads:
+      y, o = self._softmax_ce_outputs(logits, labels, weights, want)
+      outs.append(o)
+      keep.append(y)
+    self.ck.er_softmax_ce_multi(
+        n, vp(*[h[0].data_ptr() for h in heads]), (ctypes.c_int64 * n)(*[h[0].stride(0) for h in heads]),
+        vp(*[y.data_ptr() for y in keep]), vp(*[_p(h[2]) for h in heads]),
+        (ctypes.c_int64 * n)(*[h[0].shape[0] for h in heads]), (ctypes.c_int32 * n)(*[h[0].shape[1] for h in heads]),
+        (ctypes.c_float * n)(*[float(h[3]) for h in heads]), vp(*[_p(o.get('probs')) for o in outs]),
+        vp(*[_p(o.get('dlogits')) for o in outs]), vp(*[_p(o.get('loss_partials')) for o in outs]), _stream())
+    return outs
+
+  def jrc(self, logits, labels, session_keys, weights, alpha, ce_scale=1.0, loss_scale=1.0, want_grad=True):
+    """er_jrc: logits [B, 2] (row stride >= 2), labels [B] fp32, session_keys [B] int64, weights [B] or None ->
+    dict(loss [1] with _er_partials, loss_partials, dlogits [B, 2] or None, probs [B])."""
+    assert logits.dim() == 2 and logits.shape[1] == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
+    B = logits.shape[0]
+    dev = logits.device
+    assert session_keys.dtype == torch.int64 and session_keys.is_contiguous() and session_keys.numel() == B
+    grid = self.jrc_grid(B)
+    assert grid > 0, 'er_jrc: B = %d outside the envelope' % B
+    o = {'loss_partials': torch.empty(grid, dtype=torch.float32, device=dev),
+         'loss': torch.empty(1, dtype=torch.float32, device=dev),
+         'dlogits': torch.empty(B, 2, dtype=torch.float32, device=dev) if want_grad else None,
+         'probs': torch.empty(B, dtype=torch.float32, device=dev)}
+    o['loss']._er_partials = (o['loss_partials'], 1.0, 1.0)
+    self.ck.er_jrc(logits.data_ptr(), logits.stride(0), _p(_f32c(labels)), session_keys.data_ptr(),
+                   None if weights is None else _p(_f32c(weights)), B, float(alpha), float(ce_scale), float(loss_scale),
+                   _p(o['loss_partials']), _p(o['dlogits']), 2, _p(o['probs']), _stream())
+    return o
+
   # -- K8d FiBiNet's field blocks (layers/keras/fibinet.py)
   def bilinear_lds_bytes(self, F, D):
     return int(self.lib.er_bilinear_lds_bytes(int(F), int(D)))

@@ -29,6 +29,7 @@ from easyrec_amd.core.variables import VarStore
 from easyrec_amd.input.features import DeviceFeatures, FeatureSchema
 from easyrec_amd.layers.input_layer import EmbeddingEngine
 from easyrec_amd.model.easy_rec_model import EasyRecModel
+from easyrec_amd.protos.dataset_pb2 import DatasetConfig
 from easyrec_amd.utils import config_util
 from easyrec_amd.utils.load_class import import_all_models
 
@@ -98,6 +99,11 @@ class EasyRecEstimator(object):
       self.engine.allow_fused = False  # (the norm sits between reduce and apply; the overlapped sweep marks rows first)
 
     labels = OrderedDict((name, self.features.label(name)) for name in self.schema.label_fields)
+    # the device label rows are fp32 whatever the field's type: a multi-class head asks, as the reference asserts on the
+    # dtype, whether its label field is an integer one (builders/multiclass_loss.py check_class_labels)
+    int_fields = {f.input_name for f in cfg.data_config.input_fields if f.input_type in (DatasetConfig.INT32, DatasetConfig.INT64)}
+    for name, row in labels.items():
+      row._er_integral = name in int_fields
     with context.use(self.ctx):
       model_cls = EasyRecModel.create_class(cfg.model_config.model_class)
       if hasattr(model_cls, 'check_data_config'):
@@ -421,7 +427,9 @@ class EasyRecEstimator(object):
   def evaluate(self, batches, eval_config=None):
     """The evaluation pass of the reference (`EasyRecEstimator._eval_model_fn` -> `build_metric_graph`,
     model/easy_rec_estimator.py:355-420, model/rank_model.py:334-470) for `metrics_set { auc | gauc | session_auc |
-    max_f1 }`.  The model runs with is_training=False (BatchNorm moving statistics, no dropout) over `batches` (host
+    max_f1 | accuracy | recall_at_topk }`; accuracy and recall_at_topk are streaming counts of the label's rank among its
+    row's logits (er_softmax_ce's label_rank).  On a two-class softmax head auc, gauc and session_auc read probs[:, 1] and
+    max_f1 logits[:, 1]; with more classes they raise ValueError('Wrong class number') (rank_model.py:358-432).  The model runs with is_training=False (BatchNorm moving statistics, no dropout) over `batches` (host
     batches when a grouped AUC needs its key column); returns {'<metric>'[+ '_<tower>']: value}."""
     from easyrec_amd.core import metrics as metrics_lib
     assert self._built
@@ -429,11 +437,28 @@ class EasyRecEstimator(object):
       self.engine.check_overflow()
     ec = eval_config if eval_config is not None else self.pipeline_config.eval_config
     from easyrec_amd.input.features import host_key_column
-    def specs_of(metrics_set):  # [(output name, metric kind, argument)]
+    from easyrec_amd.builders import multiclass_loss
+    from easyrec_amd.protos.loss_pb2 import LossType
+
+    def specs_of(metrics_set, num_class=1, loss_types=()):  # [(output name, metric kind, argument)]
       specs = []
+      jrc = LossType.JRC_LOSS in loss_types
+      softmax = num_class > 1 and not jrc  # a multi-class head: probs / logits are [B, num_class]
       for m in metrics_set:
         kind = m.WhichOneof('metric')
-        if kind == 'auc':
+        if kind in ('auc', 'gauc', 'session_auc', 'max_f1') and softmax and num_class != 2:
+          raise ValueError('Wrong class number')
+        if kind == 'max_f1' and jrc:
+          raise ValueError('max_f1 on a JRC head: the reference hands it the [B, 2] logits; not built')
+        if kind == 'accuracy':  # rank_model.py:490-495: the argmax against the label = the label ranks first
+          assert LossType.CLASSIFICATION in loss_types and num_class > 1, 'accuracy needs a multi-class CLASSIFICATION head'
+          specs.append(('accuracy', 'topk', 1))
+        elif kind == 'recall_at_topk':  # rank_model.py:433-441: one label per example, so the share of labels in the top k
+          assert num_class > 1, 'recall_at_topk needs num_class > 1'
+          specs.append(('recall_at_topk', 'topk', int(m.recall_at_topk.topk)))
+        elif kind in ('mean_absolute_error', 'mean_squared_error', 'root_mean_squared_error') and num_class > 1:
+          raise ValueError('%s is not supported for this model' % kind)
+        elif kind == 'auc':
           specs.append(('auc', 'auc', int(m.auc.num_thresholds)))
         elif kind == 'gauc':  # rank_model.py:376-399
           specs.append(('gauc', 'grouped', (m.gauc.uid_field, m.gauc.reduction)))
@@ -442,25 +467,31 @@ class EasyRecEstimator(object):
         elif kind == 'max_f1':
           specs.append(('max_f1', 'max_f1', None))
         else:
-          raise NotImplementedError('metric %s is outside the hot-path scope (auc, gauc, session_auc, max_f1)' % kind)
+          raise NotImplementedError('metric %s is outside the hot-path scope (auc, gauc, session_auc, max_f1, accuracy, '
+                                    'recall_at_topk)' % kind)
       return specs
 
     towers = getattr(self.model, '_label_name_dict', None)
     if not towers:
       # a rank model: eval_config.metrics_set (rank_model.py build_metric_graph); auc when it is empty (eval.proto)
       heads = [('', self.model._label_name)]
-      head_specs = {'': specs_of(ec.metrics_set) or [('auc', 'auc', 200)]}
+      shape = {'': (self.model._num_class, tuple(self.model._loss_types()))}
+      head_specs = {'': specs_of(ec.metrics_set, *shape['']) or [('auc', 'auc', 200)]}
     else:
       # a multi-task model: every tower's OWN metrics_set (multi_task_model.py:143-158); a passed eval_config overrides
       heads = [('_' + t, l) for t, l in towers.items()]
       by_name = {t.name: t.config.metrics_set for t in self.model._towers}
-      head_specs = {'_' + t: specs_of(ec.metrics_set if eval_config is not None else by_name[t]) for t in towers}
+      shape = {t.suffix: (t.num_class, tuple(self.model._loss_types_of(t))) for t in self.model._towers}
+      head_specs = {'_' + t: specs_of(ec.metrics_set if eval_config is not None else by_name[t], *shape['_' + t])
+                    for t in towers}
 
     def make(kind, arg):
       if kind == 'auc':
         return metrics_lib.AUC(arg, self.device)
       if kind == 'grouped':
         return metrics_lib.DeviceSeparatedAUC(arg[1], self.device)
+      if kind == 'topk':
+        return metrics_lib.TopKHits(arg, self.device)
       return metrics_lib.DeviceMaxF1(200, self.device)
 
     acc = {}
@@ -476,14 +507,19 @@ class EasyRecEstimator(object):
           label = self.features.label(dict(heads)[suf])
           if label.dtype.is_floating_point:  # tf.to_int64(label) in front of the metrics (rank_model.py:352): truncation
             label = torch.trunc(label)
+          # a two-class softmax head: the positive class's column (rank_model.py:367-373, :427-430); a JRC head's probs are it
+          num_class, loss_types = shape[suf]
+          col = (lambda t: t[:, 1]) if num_class > 1 and LossType.JRC_LOSS not in loss_types else (lambda t: t)
           if kind == 'auc':  # metrics_tf.auc(label, probs, num_thresholds): no weights (rank_model.py:362)
-            m.update(label, pred['probs' + suf], None)
+            m.update(label, col(pred['probs' + suf]), None)
           elif kind == 'grouped':  # labels / predictions stay on the device; only the key column comes from the host batch
-            m.update(label, pred['probs' + suf], host_key_column(self.features.schema, batch, arg[0]))
+            m.update(label, col(pred['probs' + suf]), host_key_column(self.features.schema, batch, arg[0]))
+          elif kind == 'topk':
+            m.update(multiclass_loss.label_rank(pred['logits' + suf].detach(), label))
           else:
             # max_f1 is fed the LOGITS (rank_model.py:424-427: `metrics_lib.max_f1(label, prediction_dict['logits'])`),
             # against its 200 thresholds in [0, 1] - the reference's choice, kept so that the numbers agree
-            m.update(label, pred['logits' + suf])
+            m.update(label, col(pred['logits' + suf]))
     finally:
       self.model._is_training, self.ctx.is_training = was
     return {name + suf: m.result() for (name, suf), (_, _, m) in acc.items()}

@@ -38,6 +38,13 @@ class MultiTaskModel(RankModel):
             'ORDER_CALIBRATE_LOSS / learnt loss weights are outside the hot-path scope'
       assert not cfg.HasField('task_space_indicator_label') and not cfg.HasField('task_space_indicator_name'), \
           'task-space weighting: outside the hot-path scope'
+      # the build-time refusals of a multi-class or JRC tower (RankModel._check_head)
+      for loss in cfg.losses:
+        which = loss.WhichOneof('loss_param')
+        self._check_head(loss.loss_type, cfg.num_class, getattr(loss, which) if which else None,
+                         'task tower [%s]' % cfg.tower_name)
+      if not cfg.losses:
+        self._check_head(cfg.loss_type, cfg.num_class, None, 'task tower [%s]' % cfg.tower_name)
       self._towers.append(_Tower(cfg.tower_name, '_' + cfg.tower_name, cfg.loss_type, cfg.num_class, cfg.weight,
                                  cfg.use_sample_weight, cfg))
       if label_fields is None:

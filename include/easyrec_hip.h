@@ -1253,6 +1253,84 @@ int er_vdrop_bwd(const float* dout, int64_t lddout, const float* x, int64_t ldx,
                  er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8l The heads that read more than one logit per example: multi-class softmax cross entropy and JRC.
+ *     fp32 with the precise expf / logf, no MFMA, no atomics, vector stores only, every sum in one fixed
+ *     order: two runs and a graph replay give the same bits.  Logits are read in place (a row pitch, in
+ *     floats); nothing is packed first.  Every output pointer may be NULL (evaluation and prediction
+ *     leave dlogits and loss_partials out).
+ *
+ * er_softmax_ce: tf.losses.sparse_softmax_cross_entropy(labels, logits, weights), reduction
+ *   SUM_BY_NONZERO_WEIGHTS (reference builders/loss_builder.py:40-46), and what a multi-class head
+ *   (model/rank_model.py:112-122, :433-441, :490-495) takes from the same logits.  logits [B, C] at pitch
+ *   ld_logits; labels [B]: fp32 class ids, as the device label row holds them; weights [B] or NULL (ones).
+ *   Per row r, with the columns folded in ascending order:
+ *     m = max_c z[c];  lse = m + log(sum_c exp(z[c] - m));  ce = lse - z[label];  p[c] = exp(z[c] - lse)
+ *   nz = #{r : w[r] != 0} (B without weights; 1 when that is 0, so all-zero weights give loss 0 and a
+ *   zero gradient, as er_sigmoid_ce_fwd_bwd does);
+ *     loss        = sum over g of loss_partials[g],  loss_partials[g] = loss_scale * (sum of w[r] * ce[r] over
+ *                   workgroup g's rows) / nz,  g < er_softmax_ce_grid(B, C); the loss tail (er_loss_tail, with
+ *                   scale 1 and divisor 1) or any fixed-order sum finishes it
+ *     dlogits     [B, C] at pitch ld_dlogits = loss_scale * w[r] * (p[c] - (c == label)) / nz
+ *     probs       [B, C] at pitch ld_probs = p
+ *     y           [B] int64: the first column that holds the row's maximum (tf.argmax)
+ *     logits_y    [B] = m;  probs_y [B] = exp(m - lse)
+ *     label_rank  [B] int32 = #{c : z[c] > z[label]} + #{c < label : z[c] == z[label]}: the label's place in
+ *                   tf.nn.top_k's order; accuracy counts rank == 0, recall at k counts rank < k
+ *   A label outside [0, C) - NaN included - never indexes its row: the row adds nothing to the loss, its
+ *   dlogits are 0 and its label_rank is C (it is in no top k); its weight still counts in nz; probs, y and
+ *   the maxima are unaffected.  A fractional label is truncated toward zero.
+ *   labels may be NULL when dlogits, label_rank and loss_partials all are (prediction: no label is read).
+ *   Geometry: G lanes share a row, G = 1 for C <= 8 (the row held in registers) and otherwise the power of
+ *   two >= ceil(C / 8), at most 64; lane l owns the columns l, l + G, ..; the lanes meet in the xor butterfly
+ *   1, 2, .., G / 2.  A workgroup of 256 threads holds 256 / G rows at a time and walks the row blocks g,
+ *   g + grid, ..; er_softmax_ce_grid = min(ceil(B / (256 / G)), 1024).  Every workgroup counts nz over all of
+ *   w itself, so none waits for another.  A row's leader lane adds w * ce in the order it walks its rows, from
+ *   0.f; the 256 sums meet in the wave butterfly and then as (w0 + w1) + (w2 + w3).
+ *   Envelope: B >= 1, 2 <= C <= 4096, every pitch >= C.  Outside it the launch returns an error and
+ *   er_softmax_ce_grid returns 0.
+ * er_softmax_ce_multi: the training launch of 1 to 8 heads (the towers of model/multi_task_model.py:228-275)
+ *   as one; HOST arrays of n entries, one per head: the device pointers (weights[t], probs[t], dlogits[t],
+ *   loss_partials[t] may be NULL), the logits' pitch, B, C and loss_scale.  probs and dlogits are dense
+ *   (pitch C).  Head t runs on its own er_softmax_ce_grid(B_t, C_t) workgroups with the single-head launch's
+ *   code: same bits.
+ *
+ * er_jrc: reference loss/jrc_loss.py (arXiv 2208.06164) with same_label_loss = true and the `fixed` weight
+ *   strategy.  logits [B, 2] at pitch ld_logits; labels [B] fp32 (0 is the negative class, anything else the
+ *   positive one); session_keys [B] int64, compared as 64-bit integers; weights [B] or NULL.
+ *     loss = loss_scale * (alpha * ce_scale * ce + (1 - alpha) * ge)
+ *   ce: er_softmax_ce's loss at C = 2 (divided by nz).  ce_scale multiplies ce alone: the reference's
+ *   python-scalar sample weight, which tf.losses applies to ce and jrc_loss never applies to ge; 1 otherwise.
+ *   ge: with S(i) = {k : key[k] == key[i]}, n = |S(i)|, P = sum_S y[k], W = sum_S w[k] (n without weights)
+ *   and lse_c = log-sum-exp over S(i) of z[k, c] (running maximum and sum over k ascending, so the
+ *   session's maximum is subtracted),
+ *     ge = (1 / B) sum_i (W / n) * -(y[i] (z[i, 1] - lse_1) + (1 - y[i]) (z[i, 0] - lse_0))
+ *   which is the reference's sum_i (w[i] / n) * (its session's sum) with each session's sum shared out over
+ *   its members, and what its [B, B] masking with -1e9 evaluates to (exp(-1e9) = 0).  ge is a mean over B
+ *   with or without weights; only ce divides by nz.
+ *     d ge / d z[i, 1] = (1 / B) (W / n) (P exp(z[i, 1] - lse_1) - y[i])
+ *     d ge / d z[i, 0] = (1 / B) (W / n) ((n - P) exp(z[i, 0] - lse_0) - (1 - y[i]))
+ *   dlogits [B, 2] at pitch ld_dlogits = d loss / d logits; probs [B] = softmax(z[i, :])[1];
+ *   loss_partials [er_jrc_grid(B)]: their sum is the loss.
+ *   Geometry: thread i owns example i, ceil(B / 256) workgroups of 256; every workgroup stages all B (key,
+ *   z, y, w) through LDS 256 at a time and each thread compares its key with k = 0, 1, .., B - 1 in that
+ *   order: O(B^2) comparisons, O(B) memory, no [B, B] array.
+ *   Envelope: 1 <= B <= 8192, 2 <= pitch <= 2^20.  Outside it the launch returns an error and er_jrc_grid
+ *   returns 0.
+ * -------------------------------------------------------------------------------------------- */
+int32_t er_softmax_ce_grid(int64_t B, int32_t C);  /* entries of loss_partials; 0 outside the envelope */
+int er_softmax_ce(const float* logits, int64_t ld_logits, const float* labels, const float* weights, int64_t B, int32_t C,
+                  float loss_scale, float* probs, int64_t ld_probs, int64_t* y, float* logits_y, float* probs_y,
+                  float* dlogits, int64_t ld_dlogits, int32_t* label_rank, float* loss_partials, er_stream_t stream);
+int er_softmax_ce_multi(int32_t n, const float* const* logits_host, const int64_t* ld_logits_host,
+                        const float* const* labels_host, const float* const* weights_host, const int64_t* B_host,
+                        const int32_t* C_host, const float* loss_scale_host, float* const* probs_host,
+                        float* const* dlogits_host, float* const* loss_partials_host, er_stream_t stream);
+int32_t er_jrc_grid(int64_t B);                    /* entries of loss_partials; 0 outside the envelope */
+int er_jrc(const float* logits, int64_t ld_logits, const float* labels, const int64_t* session_keys, const float* weights,
+           int64_t B, float alpha, float ce_scale, float loss_scale, float* loss_partials, float* dlogits,
+           int64_t ld_dlogits, float* probs, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed

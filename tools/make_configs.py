@@ -1131,6 +1131,36 @@ def dbmtl_variant(src_name, dst_name, experts=0):
   write(cfg, dst_name)
 
 
+def deepfm_multicls_criteo(num_class=5, **kw):
+  """deepfm_criteo with a five-class softmax head (the shape of the reference's samples/model_config/
+  deepfm_multi_cls_on_avazu_ctr.config): `num_class: 5`, and the label an INT64 field - sparse softmax cross entropy
+  asserts an integer label (builders/loss_builder.py:41-44) - and accuracy / recall_at_topk as the metrics."""
+  cfg = deepfm_criteo(**kw)
+  cfg.model_config.num_class = num_class
+  # (auc is refused on more than two classes, rank_model.py:358-375: the head's own metrics instead)
+  del cfg.eval_config.metrics_set[:]
+  cfg.eval_config.metrics_set.add().accuracy.SetInParent()
+  cfg.eval_config.metrics_set.add().recall_at_topk.topk = 2
+  for field in cfg.data_config.input_fields:
+    if field.input_name in cfg.data_config.label_fields:
+      field.input_type = type(cfg.data_config).INT64
+  return cfg
+
+
+def dbmtl_jrc_variant(src_name, dst_name):
+  """The DBMTL fixture whose cvr tower is a two-class JRC head keyed by `user_id` (the shape of the reference's
+  samples/model_config/dbmtl_on_taobao_with_multi_loss.config)."""
+  from easyrec_amd.protos import pipeline_pb2
+  here = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'configs')
+  cfg = pipeline_pb2.EasyRecConfig()
+  with open(os.path.join(here, src_name)) as f:
+    text_format.Merge(f.read(), cfg)
+  tower = cfg.model_config.dbmtl.task_towers[1]
+  tower.num_class = 2
+  text_format.Merge("losses { loss_type: JRC_LOSS jrc_loss { session_name: 'user_id' alpha: 0.5 } }", tower)
+  write(cfg, dst_name)
+
+
 if __name__ == '__main__':
   write(deepfm_criteo(), 'deepfm_criteo.config')
   write(deepfm_criteo(optimizer='lazy_adam_optimizer'), 'deepfm_criteo_lazy_adam.config')
@@ -1208,3 +1238,5 @@ if __name__ == '__main__':
   write(dbmtl_numeric_sequences_taobao(transform_dnn=True, batch_size=128, scale=0.01, seq_len=12),
         'dbmtl_numeric_sequences_dnn_taobao_small.config')
   mmoe_backbone_variant('mmoe_taobao_small.config', 'mmoe_backbone_bayes_taobao_small.config', senet=False, bayes=True)
+  write(deepfm_multicls_criteo(), 'deepfm_multicls_criteo.config')
+  dbmtl_jrc_variant('dbmtl_taobao_small.config', 'dbmtl_jrc_small_taobao.config')
