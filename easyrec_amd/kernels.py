@@ -1993,6 +1993,52 @@ class HipBackend(object):
     """mha_bwd's arguments and result bits, several units per workgroup."""
     self._mha_bwd(True, q, k, v, to_mask, dctx, B, F, T, H, ds, dq, dk, dv)
 
+  # -- K8f-s the streaming attention kernels beyond the LDS envelope (csrc/er_mha_stream.hip)
+  MHA_STREAM_MAX_LEN = 4096
+
+  def mha_stream_lds_bytes(self, ds, bwd=True):
+    return int(self.lib.er_mha_stream_lds_bytes(int(ds), bool(bwd)))
+
+  def mha_stream_grid(self, B, F, T, H, ds, which):
+    """Workgroups of pass 0 (forward), 1 (delta and dQ), 2 (dK | dV); 0 outside the envelope."""
+    return int(self.lib.er_mha_stream_grid(int(B), int(F), int(T), int(H), int(ds), int(which)))
+
+  def mha_stream_fwd(self, q, k, v, to_mask, B, F, T, H, ds):
+    """mha_fwd's operands at any 1 <= F, T <= 4096 -> (ctx [B * F, H ds], lse [B, H, F]): the keys streamed in tiles, an
+    online softmax, MFMA products."""
+    d = H * ds
+    self._mha_operand(q, B * F, d, 'mha_stream_fwd q')
+    self._mha_operand(k, B * T, d, 'mha_stream_fwd k')
+    self._mha_operand(v, B * T, d, 'mha_stream_fwd v')
+    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
+    ctx = torch.empty(B * F, d, dtype=torch.float32, device=q.device)
+    lse = torch.empty(B, H, F, dtype=torch.float32, device=q.device)
+    self.ck.er_mha_stream_fwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), B, F, T, H, ds,
+                              _p(ctx), _p(lse), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::attn_stream_fwd_kernel', 4.0 * B * F * T * d))
+    return ctx, lse
+
+  def mha_stream_bwd(self, q, k, v, to_mask, dctx, ctx, lse, B, F, T, H, ds, dq, dk, dv):
+    """dq, dk, dv (views as mha_bwd's, written) from dctx, the forward's ctx and lse: two launches, no atomics."""
+    d = H * ds
+    self._mha_operand(q, B * F, d, 'mha_stream_bwd q')
+    self._mha_operand(k, B * T, d, 'mha_stream_bwd k')
+    self._mha_operand(v, B * T, d, 'mha_stream_bwd v')
+    self._mha_operand(dq, B * F, d, 'mha_stream_bwd dq')
+    self._mha_operand(dk, B * T, d, 'mha_stream_bwd dk')
+    self._mha_operand(dv, B * T, d, 'mha_stream_bwd dv')
+    assert dctx.shape == ctx.shape == (B * F, d) and ctx.is_contiguous() and ctx.dtype == torch.float32
+    assert lse.shape == (B, H, F) and lse.is_contiguous() and lse.dtype == torch.float32
+    assert to_mask is None or (to_mask.dtype == torch.int32 and to_mask.shape == (B, T) and to_mask.is_contiguous())
+    delta = torch.empty_like(lse)
+    self.ck.er_mha_stream_bwd(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(to_mask), _p(_f32c(dctx)),
+                              _p(ctx), _p(lse), B, F, T, H, ds, _p(delta), _p(dq), dq.stride(0), _p(dk), dk.stride(0),
+                              _p(dv), dv.stride(0), _stream())
+    if self.op_log is not None:
+      self.op_log.append(('er::attn_stream_bwd_dq_kernel', 6.0 * B * F * T * d))
+      self.op_log.append(('er::attn_stream_bwd_dkv_kernel', 8.0 * B * F * T * d))
+
   SEGMENT_MEAN_MAX_W = 4096
   SEGMENT_MEAN_MAX_S = 4096
   SEGMENT_MEAN_MAX_SEG = 64
@@ -4689,6 +4735,39 @@ class MhaGroupAttnFn(MhaAttnFn):
   @staticmethod
   def backward(ctx, dctx):
     return MhaAttnFn._backward(ctx, True, dctx)
+
+
+class MhaStreamAttnFn(torch.autograd.Function):
+  """MhaAttnFn's arguments and function on the streaming kernels (er_mha_stream_fwd / _bwd): any 1 <= F, T <= 4096.
+  Keeps ctx and lse [B, H, F] for the backward, which recomputes the probabilities tile by tile."""
+
+  @staticmethod
+  def forward(ctx, q_src, kv_src, to_mask, B, F, T, H, ds):
+    be = hip()
+    d = H * ds
+    q_src = q_src if q_src.is_contiguous() else q_src.contiguous()
+    if kv_src is not None:
+      kv_src = kv_src if kv_src.is_contiguous() else kv_src.contiguous()
+    assert q_src.shape == (B * F, d if kv_src is not None else 3 * d) and (kv_src is not None or F == T)
+    assert kv_src is None or kv_src.shape == (B * T, 2 * d)
+    q, k, v = MhaAttnFn._split(q_src, kv_src, d)
+    out, lse = be.mha_stream_fwd(q, k, v, to_mask, B, F, T, H, ds)
+    ctx.save_for_backward(q_src, kv_src, to_mask, out, lse)
+    ctx.shape = (B, F, T, H, ds)
+    return out
+
+  @staticmethod
+  def backward(ctx, dctx):
+    be = hip()
+    q_src, kv_src, to_mask, out, lse = ctx.saved_tensors
+    B, F, T, H, ds = ctx.shape
+    d = H * ds
+    dq_src = torch.empty_like(q_src)
+    dkv_src = None if kv_src is None else torch.empty_like(kv_src)
+    q, k, v = MhaAttnFn._split(q_src, kv_src, d)
+    dq, dk, dv = MhaAttnFn._split(dq_src, dkv_src, d)
+    be.mha_stream_bwd(q, k, v, to_mask, dctx.contiguous(), out, lse, B, F, T, H, ds, dq, dk, dv)
+    return dq_src, dkv_src, None, None, None, None, None, None
 
 
 class SegmentMeanFn(torch.autograd.Function):

@@ -22,7 +22,11 @@ between the projections and the output dense is one launch each way (kernels.Mha
 input are one contraction on a packed operand (kernels.MhaProjFn), and every add & LayerNorm is one launch each way
 (kernels.AddLayerNormFn).  A caller that passes group_units=True (CMBF's towers and blocks) gets the grouped-unit attention
 launch (kernels.MhaGroupAttnFn: several (example, head) units per workgroup, the same result bits) wherever
-mha_group_units(F, T, ds) >= 2, unless EASYREC_AMD_MHA_GROUP_UNITS=0.  Anywhere else - a stand-in backend on the CPU, a shape outside the envelope, a mask that
+mha_group_units(F, T, ds) >= 2, unless EASYREC_AMD_MHA_GROUP_UNITS=0.  A shape whose (example, head) unit does not fit in
+LDS (fits() false) but lies inside stream_fits() - any lengths up to 4096 under a head up to 128 - takes the streaming
+kernels (kernels.MhaStreamAttnFn: key tiles, an online softmax, MFMA products; K8f-s) with EASYREC_AMD_MHA_STREAM=1
+(default 0: the composition, as measured in DESIGN.md 3.24).
+Anywhere else - a stand-in backend on the CPU, a shape outside both envelopes, a mask that
 differs between query rows or is floating point (the kernels take int32 0 / 1 masks), projection activations,
 attention dropout while training, EASYREC_AMD_FUSED_MHA=0 - the same function is composed of torch ops between the
 same dense layers.
@@ -53,6 +57,9 @@ MAX_SEQ_LEN = 4096     # from- and to-length bound of the attention kernels (mha
 LN_MAX_WIDTH = 4096
 MASK_ADDER = -10000.0
 GROUP_UNITS_DEFAULT = '1'  # (the grouped launches measured faster at every CMBF shape: DESIGN.md 3.17)
+# (the streaming kernels measured faster at five of six shapes but 6 % slower at (129, 129, 128) and no faster in the
+# model step of uniter_long_movielens.config: off until they win everywhere)
+STREAM_DEFAULT = '0'
 SEGMENT_MEAN_MAX = 4096  # W and S bound of er_segment_mean; at most 64 segments
 
 
@@ -82,6 +89,18 @@ def mha_group_units(from_len, to_len, head_size):
     if g * unit <= LDS_BUDGET:
       return g
   return 1
+
+
+def stream_fits(from_len, to_len, head_size):
+  """The envelope of the streaming kernels (er_mha_stream_*, include/easyrec_hip.h K8f-s): the lengths and the head size
+  alone - their LDS holds tiles, not the unit."""
+  return 1 <= from_len <= MAX_SEQ_LEN and 1 <= to_len <= MAX_SEQ_LEN and 1 <= head_size <= MAX_HEAD_SIZE
+
+
+def stream_enabled():
+  """EASYREC_AMD_MHA_STREAM=1: a shape outside fits() takes the streaming kernels; 0 (the default): the torch composition
+  (the A/B switch of er_mha_stream_*)."""
+  return os.environ.get('EASYREC_AMD_MHA_STREAM', STREAM_DEFAULT) != '0'
 
 
 def group_units_enabled():
@@ -236,14 +255,15 @@ def attention_layer(from_tensor, to_tensor, size_per_head, num_attention_heads=1
   ctx = context.current()
   drop = attention_probs_dropout_prob if ctx.is_training else 0.0
   row_mask = None if attention_mask is None else _row_mask(attention_mask, B, F, T)
-  fused = (_fused(from_2d) and fits(F, T, ds) and not drop and query_act is None and key_act is None and
-           value_act is None and B * F > 0 and
+  inside = fits(F, T, ds)  # the LDS-resident kernels; else the streaming kernels, else the composition
+  fused = (_fused(from_2d) and (inside or (stream_fits(F, T, ds) and stream_enabled())) and not drop and
+           query_act is None and key_act is None and value_act is None and B * F > 0 and
            # (the kernels read an int32 0 / 1 mask: a floating mask may hold other weights and stays with the composition)
            (attention_mask is None or (row_mask is not None and not row_mask.is_floating_point())))
   if fused:
     to_mask = None if row_mask is None else row_mask.to(torch.int32).contiguous()
     grouped = group_units and group_units_enabled() and mha_group_units(F, T, ds) >= 2
-    attn = kernels.MhaGroupAttnFn if grouped else kernels.MhaAttnFn
+    attn = kernels.MhaStreamAttnFn if not inside else kernels.MhaGroupAttnFn if grouped else kernels.MhaAttnFn
     if self_attention:
       qkv = kernels.MhaProjFn.apply(from_2d, _grads_of(ws + bs), 3, *(ws + bs))
       out = attn.apply(qkv, None, to_mask, B, F, T, H, ds)

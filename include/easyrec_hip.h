@@ -755,6 +755,47 @@ int er_add_ln_bwd(const float* dy, const float* x, const float* res, int64_t row
                   er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8f-s The attention core of K8f beyond its LDS envelope: the keys are streamed in tiles, the softmax is
+ *     online, every product is v_mfma_f32_32x32x2_f32 (csrc/er_mha_stream.hip).  fp32 throughout.
+ * er_mha_stream_fwd: the arguments and semantics of er_mha_fwd (q / k / v with row pitches, head h the
+ *   column block h * ds .., to_mask int32 [B, T] or NULL, scale 1 / sqrt(ds), the adder
+ *   (1 - mask[b, j]) * -10000.f relative to the example's largest adder - an example with every key masked
+ *   is the softmax of the bare scores -, masked keys computed and not skipped, ctx [B * F, H ds]
+ *   contiguous) and one more output, lse [B, H, F]: the row's running maximum plus the log of its sum.
+ *   A wave owns 32 query rows of one (example, head) from the first key tile to the last; a workgroup is
+ *   1, 2 or 4 waves (F <= 32, <= 64, above) that share the K and V tiles through LDS.  The row's maximum,
+ *   sum and rescale are per sub-tile of 32 keys, expf is the precise one, and the row is divided once at the
+ *   end (one reciprocal, one multiplication per element).  A key index >= T contributes exactly 0, a row
+ *   >= F is never stored, columns ds .. 32 ceil(ds / 32) - 1 are zero in LDS.  Nothing of size [F, T] is
+ *   written anywhere.
+ * er_mha_stream_bwd: the arguments of er_mha_bwd plus the forward's ctx and lse and a scratch
+ *   delta [B, H, F].  Two launches on `stream`, no atomics: (a) a wave owns 32 query rows, stores
+ *   delta = rowsum(dctx o ctx), walks the key tiles, recomputes P = exp(s - lse) and accumulates
+ *   dQ_h = dS K_h / sqrt(ds), dS = P o (dctx_h V_h^T - delta); (b) a wave owns 32 keys (1, 2 or 4 waves per
+ *   workgroup by T), walks the query tiles and accumulates dV_h = P^T dctx_h and dK_h = dS^T Q_h / sqrt(ds).
+ *   Every output element has one owner and a fixed summation order: two runs give the same bits.  With
+ *   T = 1, dQ and dK are exactly 0 (delta is summed in the order of dctx_h V_h^T).
+ * Envelope: 1 <= ds <= 128, 1 <= F, T <= 4096, H >= 1, B >= 1, every pitch >= H * ds; outside it both
+ *   return an error and launch nothing.  Tile: KT = 64 keys (launch (b): query rows) up to ds = 64, 32
+ *   above, at the LDS pitch P = 32 ceil(ds / 32) + 1 floats:
+ *   er_mha_stream_lds_bytes(ds, bwd) = 4 * (2 KT P + (bwd ? 2 : 1) KT + 4) (two tiles; the keys' adders, or
+ *   lse and delta; four partial maxima), at most 33808 <= 81920, K8f's budget; 0 outside 1 .. 128.
+ *   er_mha_stream_grid(B, F, T, H, ds, pass): the persistent workgroups of pass 0 (forward), 1 (launch (a)),
+ *   2 (launch (b)): min(2048, B H ceil(rows / (32 waves))), rows = T for pass 2 and F otherwise; 0 outside.
+ *   16-byte global accesses where ds % 4 == 0, the pitch % 4 == 0 and the base is 16-byte aligned; 4-byte
+ *   accesses otherwise.
+ * -------------------------------------------------------------------------------------------- */
+int64_t er_mha_stream_lds_bytes(int32_t ds, int bwd);
+int32_t er_mha_stream_grid(int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds, int32_t pass);
+int er_mha_stream_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                      const int32_t* to_mask, int64_t B, int32_t F, int32_t T, int32_t H, int32_t ds, float* ctx,
+                      float* lse, er_stream_t stream);
+int er_mha_stream_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                      const int32_t* to_mask, const float* dctx, const float* ctx, const float* lse, int64_t B, int32_t F,
+                      int32_t T, int32_t H, int32_t ds, float* delta, float* dq, int64_t lddq, float* dk, int64_t lddk,
+                      float* dv, int64_t lddv, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8d FiBiNet's field blocks.  x [B, F * D]: F fields of the same width D side by side, fp32.
  * Bilinear.  Replaces the per-field Dense (MatMul + BiasAdd), the per-pair expand_dims / MatMul / Squeeze
  *     (use_plus) or Mul, and the ConcatV2 of BiLinear.call layers/keras/fibinet.py:175-203 (types `all`

@@ -375,11 +375,20 @@ model_config {
 """
 
 
-def uniter_movielens(batch_size=1024):
+def uniter_movielens(batch_size=1024, title_len=16):
   """Uniter: samples/model_config/uniter_on_movielens.config (its data, feature and model sections: 1 [CLS] + 1 image
   + 7 general + 16 title + 8 genres = 33 tokens of hidden 512, 4 heads, 2 layers) on synthetic MovieLens-shaped
-  batches; batch size 1024 (the sample's 128 measures little but launch overhead); the metric set is auc alone."""
-  return text_format.Parse(UNITER_MOVIELENS % {'batch_size': batch_size}, pipeline_pb2.EasyRecConfig())
+  batches; batch size 1024 (the sample's 128 measures little but launch overhead); the metric set is auc alone.
+  title_len: the title's max_seq_len (and max_position_embeddings): 64 gives 81 tokens under heads of 128, outside the
+  LDS-resident attention kernels' envelope (34 tokens) and on the streaming ones (uniter_long_movielens.config)."""
+  text = UNITER_MOVIELENS % {'batch_size': batch_size}
+  if title_len != 16:
+    for old, new in (("separator: ' ' max_seq_len: 16", "separator: ' ' max_seq_len: %d" % title_len),
+                     ('max_position_embeddings: 16', 'max_position_embeddings: %d' % title_len),
+                     ('uniter_movielens_ckpt', 'uniter_long_movielens_ckpt')):
+      assert text.count(old) == 1, old
+      text = text.replace(old, new)
+  return text_format.Parse(text, pipeline_pb2.EasyRecConfig())
 
 
 CMBF_MOVIELENS_MODEL = """
@@ -1178,6 +1187,7 @@ if __name__ == '__main__':
   write(bst_taobao(item_rows=10000000), 'bst_taobao_10m.config')
   write(autoint_taobao(item_rows=10000000), 'autoint_taobao_10m.config')
   write(uniter_movielens(), 'uniter_movielens.config')
+  write(uniter_movielens(title_len=64), 'uniter_long_movielens.config')
   write(cmbf_movielens(), 'cmbf_movielens.config')
   write(deepfm_textcnn_movielens(), 'deepfm_textcnn_movielens.config')
   write(fibinet_taobao(item_rows=10000000), 'fibinet_taobao_10m.config')
