@@ -5,11 +5,14 @@ CLASSIFICATION with num_class == 1 -> tf.losses.sigmoid_cross_entropy(label, log
 probabilities and d(loss)/d(logits); the backward of the model is seeded with that gradient.
 CLASSIFICATION with num_class > 1 -> tf.losses.sparse_softmax_cross_entropy, and JRC_LOSS -> loss/jrc_loss.py: one
 launch each as well (`er_softmax_ce`, `er_jrc`) or their torch compositions (builders/multiclass_loss.py).
+PAIR_WISE_LOSS and PAIRWISE_LOGISTIC / HINGE / FOCAL_LOSS -> loss/pairwise_loss.py, with or without session keys: the pair
+kernel `er_pairwise` or their torch compositions (builders/pairwise_loss.py).
 """
 import torch
 
 from easyrec_amd import kernels
 from easyrec_amd.builders import multiclass_loss
+from easyrec_amd.builders import pairwise_loss as pairwise
 from easyrec_amd.protos.loss_pb2 import LossType
 
 
@@ -39,17 +42,9 @@ def pairwise_loss(labels, logits, margin=0.0, temperature=1.0, weights=None):
   """reference easy_rec/python/loss/pairwise_loss.py:15-70 (the deprecated `pairwise_loss`, without session ids): over
   the ordered pairs (i, j) with label_i > label_j, sigmoid cross entropy of z_i - z_j - margin against 1, i.e. the mean of
   softplus(-(z_i - z_j - margin)); per-example weights weigh the pairs of their FIRST member.  No pair: the mean of
-  nothing - 0 with SUM_BY_NONZERO_WEIGHTS' safe division."""
-  y = labels.to(torch.float32)
-  z = logits / temperature if temperature != 1.0 else logits
-  diff = z[:, None] - z[None, :] - margin
-  mask = y[:, None] > y[None, :]
-  x = diff[mask]
-  per = torch.where(x >= 0, x, torch.zeros_like(x)) - x + torch.log1p(torch.exp(torch.where(x >= 0, -x, x)))
-  if weights is None:
-    return per.sum() / max(int(x.numel()), 1)
-  w = weights[:, None].expand_as(diff)[mask]
-  return (w * per).sum() / (w != 0).sum().clamp(min=1).to(torch.float32)
+  nothing - 0 with SUM_BY_NONZERO_WEIGHTS' safe division.  (The composition itself, session keys included, lives in
+  builders/pairwise_loss.py with the three losses that replace this one.)"""
+  return pairwise.pair_wise_compose(labels, logits, None, margin, temperature, weights)
 
 
 _SIGMOID_CE = (LossType.CLASSIFICATION, LossType.BINARY_CROSS_ENTROPY_LOSS)
@@ -125,21 +120,14 @@ def build(loss_type, label, pred, loss_weight=1.0, num_class=1, loss_scale=1.0, 
       loss, dlogits, _ = _fused_head(head, label, loss_scale * float(loss_weight))
       return loss, dlogits
     kernels.materialize_head(head)  # any other loss reads the logits
-  if loss_type == LossType.PAIR_WISE_LOSS:
-    assert num_class == 1, 'num_class must be 1 when loss type is PAIR_WISE_LOSS'
-    assert loss_param is None or not loss_param.session_name, 'session ids in pairwise losses are outside the hot-path scope'
-    margin = 0.0 if loss_param is None else float(loss_param.margin)
-    temperature = 1.0 if loss_param is None else float(loss_param.temperature)
-    z = pred.detach().clone().requires_grad_(True)
-    with torch.enable_grad():
-      # (a python float weight is not a "numeric tensor" for the reference: it multiplies the mean as a scalar)
-      loss = pairwise_loss(label, z, margin, temperature, loss_weight if torch.is_tensor(loss_weight) else None)
-      loss = loss * (loss_scale if torch.is_tensor(loss_weight) else loss_scale * float(loss_weight))
-      if loss.requires_grad:
-        dz, = torch.autograd.grad(loss, z)
-      else:  # no (positive, negative) pair in the batch
-        dz = torch.zeros_like(z)
-    return loss.detach().reshape(1), dz
+  if loss_type in pairwise.LOSS_TYPES:
+    # the four pairwise ranking losses: er_pairwise's two launches or their torch compositions; the pair count rides on
+    # the loss tensor
+    assert num_class == 1, 'num_class must be 1 when loss type is %s' % LossType.Name(loss_type)
+    loss, dlogits, extras = pairwise.build(loss_type, label, pred, loss_weight, loss_scale, loss_param,
+                                           kwargs.get('session_ids'))
+    loss._er_extras = extras
+    return loss, dlogits
   if loss_type == LossType.F1_REWEIGHTED_LOSS:
     assert num_class == 1, 'num_class must be 1 when loss type is F1_REWEIGHTED_LOSS'
     beta_square = 1.0 if loss_param is None else float(loss_param.f1_beta_square)

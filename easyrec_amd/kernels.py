@@ -56,6 +56,9 @@ DenseApplyDesc = abi.RECORDS['er_dense_apply_desc']
          'EPI_BN_BWD', 'EPI_CROSS_FWD', 'EPI_CROSS_BWD', 'GRAD_TERM_ROWSUM', 'GRAD_TERM_FM', 'FRONT_SKIP_ONE_ROW',
          'FRONT_DEFER_CATCH_UP', 'ABI_VERSION'))
 COMBINERS = {'sum': COMBINER_SUM, 'mean': COMBINER_MEAN, 'sqrtn': COMBINER_SQRTN}
+(PAIR_WISE, PAIR_LOGISTIC, PAIR_HINGE, PAIR_FOCAL, PAIR_LABEL_MARGIN, PAIR_HINGE_MARGIN, PAIR_ALPHA) = (
+    abi.CONSTANTS['ER_PAIR_' + name] for name in ('WISE', 'LOGISTIC', 'HINGE', 'FOCAL', 'LABEL_MARGIN', 'HINGE_MARGIN',
+                                                  'ALPHA'))
 # er_opt_hyper as the flat float array the host writes: its length and the index of each field
 HYPER_FLOATS = ctypes.sizeof(OptHyper) // 4
 HYPER_LR, HYPER_LR_T, HYPER_BETA1, HYPER_BETA2, HYPER_OMB1, HYPER_OMB2, HYPER_EPS, HYPER_GSCALE, HYPER_CLIP = (
@@ -2354,6 +2357,35 @@ class HipBackend(object):
     self.ck.er_jrc(logits.data_ptr(), logits.stride(0), _p(_f32c(labels)), session_keys.data_ptr(),
                    None if weights is None else _p(_f32c(weights)), B, float(alpha), float(ce_scale), float(loss_scale),
                    _p(o['loss_partials']), _p(o['dlogits']), 2, _p(o['probs']), _stream())
+    return o
+
+  # -- K8m the pairwise ranking losses (builders/pairwise_loss.py)
+  def pairwise_grid(self, B):
+    return int(self.lib.er_pairwise_grid(int(B)))
+
+  def pairwise_loss(self, logits, labels, session_keys, weights, kind, flags=0, temperature=1.0, label_div=1.0, margin=0.0,
+                    hinge_margin=0.0, gamma=2.0, alpha=0.0, loss_scale=1.0, want_grad=True):
+    """er_pairwise: logits [B] (any stride), labels [B] fp32, session_keys [B] int64 or None, weights [B] or None; kind
+    PAIR_WISE .. PAIR_FOCAL, flags PAIR_LABEL_MARGIN | PAIR_HINGE_MARGIN | PAIR_ALPHA -> dict(loss [1] with _er_partials,
+    loss_partials, dlogits [B] or None, pair_count [1] int32)."""
+    assert logits.dim() == 1 and logits.dtype == torch.float32
+    B = logits.shape[0]
+    dev = logits.device
+    assert session_keys is None or (session_keys.dtype == torch.int64 and session_keys.is_contiguous() and
+                                    session_keys.numel() == B)
+    assert _f32c(labels).numel() == B and (weights is None or _f32c(weights).numel() == B)
+    grid = self.pairwise_grid(B)
+    assert grid > 0, 'er_pairwise: B = %d outside the envelope' % B
+    work = torch.empty(int(self.lib.er_pairwise_work_floats(B)), dtype=torch.float32, device=dev)
+    o = {'loss_partials': torch.empty(grid, dtype=torch.float32, device=dev),
+         'loss': torch.empty(1, dtype=torch.float32, device=dev),
+         'dlogits': torch.empty(B, dtype=torch.float32, device=dev) if want_grad else None,
+         'pair_count': torch.empty(1, dtype=torch.int32, device=dev)}
+    o['loss']._er_partials = (o['loss_partials'], 1.0, 1.0)
+    self.ck.er_pairwise(logits.data_ptr(), logits.stride(0) if B > 1 else 1, _p(_f32c(labels)), _p(session_keys),
+                        None if weights is None else _p(_f32c(weights)), B, int(kind), int(flags), float(temperature),
+                        float(label_div), float(margin), float(hinge_margin), float(gamma), float(alpha), float(loss_scale),
+                        _p(work), _p(o['loss_partials']), _p(o['dlogits']), _p(o['pair_count']), _stream())
     return o
 
   # -- K8d FiBiNet's field blocks (layers/keras/fibinet.py)

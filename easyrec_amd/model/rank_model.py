@@ -34,6 +34,9 @@ _SIGMOID_REGRESSION = _Head('sigmoid_regression', ('y',), 'y', 'l2_loss')
 _F1_REWEIGHTED = _Head('binary', ('probs', 'logits'), 'logits', 'f1_reweighted_loss')
 
 _PAIR_WISE = _Head('binary', ('probs', 'logits'), 'logits', 'pair_wise_loss')
+_PAIRWISE_LOGISTIC = _Head('binary', ('probs', 'logits'), 'logits', 'pairwise_logistic_loss')
+_PAIRWISE_HINGE = _Head('binary', ('probs', 'logits'), 'logits', 'pairwise_hinge_loss')
+_PAIRWISE_FOCAL = _Head('binary', ('probs', 'logits'), 'logits', 'pairwise_focal_loss')
 
 # the heads that read more than one logit per example (builders/multiclass_loss.py); '%s': where the suffix goes
 _MULTICLASS = _Head('multiclass', ('y', 'probs', 'logits', 'probs%s_y', 'logits%s_y', 'probs%s_1', 'logits%s_1'), 'logits',
@@ -44,6 +47,9 @@ _PLAIN_LOSS_NAME = (_BINARY, _REGRESSION, _SIGMOID_REGRESSION, _MULTICLASS)
 
 _HEADS = {
     LossType.PAIR_WISE_LOSS: _PAIR_WISE,
+    LossType.PAIRWISE_LOGISTIC_LOSS: _PAIRWISE_LOGISTIC,
+    LossType.PAIRWISE_HINGE_LOSS: _PAIRWISE_HINGE,
+    LossType.PAIRWISE_FOCAL_LOSS: _PAIRWISE_FOCAL,
     LossType.CLASSIFICATION: _BINARY,
     LossType.BINARY_CROSS_ENTROPY_LOSS: _BINARY,
     LossType.F1_REWEIGHTED_LOSS: _F1_REWEIGHTED,
@@ -154,13 +160,22 @@ class RankModel(EasyRecModel):
     self._prediction_dict['probs' + suffix] = probs
     self._prediction_dict['probs' + suffix + '_1'] = probs[:, 1]
 
-  def _session_ids(self, loss_type, loss_param):
-    """JRC's session keys: the device id column of the feature `session_name`, as the embedding sees it (after the hash
-    bucket: two raw ids that share a bucket are one session)."""
-    if loss_type != LossType.JRC_LOSS:
-      return None
+  @staticmethod
+  def _session_name(loss_type, loss_param):
+    """The `session_name` of a JRC or pairwise loss parameter ('' when the loss has none)"""
     from easyrec_amd.builders import multiclass_loss as mcl
-    return self._feature_dict.batch_ids_of(mcl.check_jrc_param(loss_param)[2])
+    from easyrec_amd.builders import pairwise_loss as pwl
+    if loss_type == LossType.JRC_LOSS:
+      return mcl.check_jrc_param(loss_param)[2]
+    if loss_type in pwl.LOSS_TYPES:
+      return pwl.params_of(loss_type, loss_param)['session_name']
+    return ''
+
+  def _session_ids(self, loss_type, loss_param):
+    """The session keys of a JRC or pairwise loss: the device id column of the feature `session_name`, as the embedding
+    sees it (after the hash bucket: two raw ids that share a bucket are one session)."""
+    session = self._session_name(loss_type, loss_param)
+    return self._feature_dict.batch_ids_of(session) if session else None
 
   def _check_head(self, loss_type, num_class, loss_param=None, what='model'):
     """Build-time refusals of a head (called once per (loss type, num_class) a model or tower declares)."""
@@ -168,12 +183,13 @@ class RankModel(EasyRecModel):
     from easyrec_amd.core import context
     if loss_type == LossType.ZILN_LOSS:
       raise NotImplementedError('%s: ZILN_LOSS (the zero-inflated lognormal head) is not built' % what)
+    session = self._session_name(loss_type, loss_param)  # (and the loss parameter's own build-time refusals)
+    schema = getattr(self._feature_dict, 'schema', None)
+    if session and schema is not None and session not in schema.hash_single and session not in schema.int_single:
+      which = 'jrc_loss' if loss_type == LossType.JRC_LOSS else LossType.Name(loss_type).lower()
+      raise ValueError('%s: %s { session_name: "%s" } names no single-valued id feature' % (what, which, session))
     if loss_type == LossType.JRC_LOSS:
       assert num_class == 2, 'num_class must be 2 when loss type is JRC_LOSS'
-      session = mcl.check_jrc_param(loss_param)[2]
-      schema = getattr(self._feature_dict, 'schema', None)
-      if schema is not None and session not in schema.hash_single and session not in schema.int_single:
-        raise ValueError('%s: jrc_loss { session_name: "%s" } names no single-valued id feature' % (what, session))
     elif not (loss_type == LossType.CLASSIFICATION and num_class > 1):
       return
     ctx = context.current()
@@ -201,7 +217,8 @@ class RankModel(EasyRecModel):
                        loss_param=None, loss_scale=1.0):
     head = _head_of(loss_type, num_class=num_class)
     pred = self._prediction_dict[head.loss_input + suffix]
-    extra = {'session_ids': self._session_ids(loss_type, loss_param)} if head is _JRC else {}
+    session_ids = self._session_ids(loss_type, loss_param)
+    extra = {} if session_ids is None else {'session_ids': session_ids}
     value, dpred = loss_builder.build(loss_type, self._labels[label_name], pred, loss_weight, num_class,
                                       loss_scale=loss_scale, loss_param=loss_param, fuse_head=len(self._losses) <= 1, **extra)
     self._backward_seeds.append((pred, dpred))

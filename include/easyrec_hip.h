@@ -1372,6 +1372,58 @@ int er_jrc(const float* logits, int64_t ld_logits, const float* labels, const in
            int64_t ld_dlogits, float* probs, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8m The session-keyed pairwise ranking losses: reference loss/pairwise_loss.py at ohem_ratio == 1, the focal
+ *     one through loss/focal_loss.py.  fp32 with the precise expf / log1pf / powf, no MFMA (there is no
+ *     contraction: every pair goes through exp, log1p and compares), no atomics, vector stores only, every
+ *     float sum in one fixed order: two runs and a graph replay give the same bits.  Memory is
+ *     O(B * column splits); nothing of size B x B is stored.
+ *
+ * er_pairwise: logits z [B] at pitch ld_logits; labels y [B] fp32, graded or 0 / 1; session_keys [B] int64
+ *   compared as 64-bit integers, or NULL (one session); weights w [B] or NULL (ones).
+ *   With s = z / temperature and yl = y / label_div, a pair is an ordered (i, j) with yl[i] > yl[j],
+ *   key[i] == key[j] and - ER_PAIR_FOCAL with ER_PAIR_HINGE_MARGIN - s[i] - s[j] < hinge_margin.  With
+ *   d = s[i] - s[j] and m = yl[i] - yl[j] under ER_PAIR_LABEL_MARGIN, else `margin`, the pair's loss l is
+ *     ER_PAIR_WISE, ER_PAIR_LOGISTIC  x = d - m;  max(x, 0) - x + log1p(exp(-|x|))   (softplus(-x); derivative
+ *                                     -sigmoid(-x), but 0 at x == 0 for ER_PAIR_LOGISTIC, whose reference form
+ *                                     relu(-x) + log1p(exp(-|x|)) passes no gradient through relu and abs there)
+ *     ER_PAIR_HINGE                   max(m - d, 0)                                  (derivative 0 at m == d)
+ *     ER_PAIR_FOCAL                   wf * (max(d, 0) - d + log1p(exp(-|d|))),  wf = (1 - p)^gamma [* alpha
+ *                                     under ER_PAIR_ALPHA],  p = clip(sigmoid(d), 1e-7, 1 - 1e-7)
+ *   The caller folds the reference's options into these: pairwise_loss -> margin; pairwise_logistic_loss ->
+ *   ER_PAIR_LABEL_MARGIN with label_div = temperature, else margin = hinge_margin or 0; pairwise_hinge_loss
+ *   -> label_div = temperature under label_is_logits.  label_div is 1 otherwise.
+ *   Per-example weights weigh the pairs of their FIRST member.  Reduction SUM_BY_NONZERO_WEIGHTS:
+ *     nz   = #{pairs : w[i] * (wf for focal, else 1) != 0}, 1 when that is 0 (no pair: loss 0, zero gradient)
+ *     loss = loss_scale * sum over the pairs of w[i] * l / nz = the sum of loss_partials [er_pairwise_grid(B)];
+ *            the loss tail (er_loss_tail, scale 1 and divisor 1) or any fixed-order sum finishes it
+ *     dlogits [B] = d loss / d z with nz held constant.  The focal gradient runs through wf, as the
+ *            reference's does (it stops no gradient there): d l / d d = -wf * sigmoid(-d) - gamma * wf * p * ce
+ *            (ce the cross entropy above; the second term is 0 where the clip holds p)
+ *     pair_count [1] int32 = the number of pairs, whatever their weights
+ *   dlogits, loss_partials and pair_count may each be NULL.
+ *   Geometry: the pair matrix is cut into ceil(B / 256) row blocks by `splits` column chunks, splits =
+ *   ceil(B / chunk), chunk = ceil(B / min(ceil(256 / row blocks), ceil(B / 64))) <= 1024: B = 4096 runs on
+ *   16 x 16 = 256 workgroups.  Thread t of a row block owns example i and keeps (s, yl, key, w) in
+ *   registers; the workgroup stages its chunk's (s, yl, key, w) in LDS once and every lane reads the same
+ *   LDS word per column.  yl[i] > yl[j] and yl[j] > yl[i] exclude each other, so each column costs one pair
+ *   evaluation: the pair (i, j) adds to the thread's loss, counts and dz[i], the pair (j, i) subtracts
+ *   w[j] * dl/dd from dz[i]; columns ascending, from 0.f.  A second launch of ceil(B / 256) workgroups sums
+ *   the integer counts, then the splits' dz partials in the order 0, 1, .. and applies loss_scale / nz.
+ *   work: er_pairwise_work_floats(B) floats (the dz partials [splits, B], the workgroups' loss sums and
+ *   counts); its contents are overwritten by every launch.
+ *   Envelope: 1 <= B <= 8192, 1 <= pitch <= 2^20, temperature > 0, label_div > 0, gamma >= 0.  Outside it
+ *   the launch returns an error, and er_pairwise_grid and er_pairwise_work_floats return 0.
+ * -------------------------------------------------------------------------------------------- */
+enum { ER_PAIR_WISE = 0, ER_PAIR_LOGISTIC = 1, ER_PAIR_HINGE = 2, ER_PAIR_FOCAL = 3 };
+enum { ER_PAIR_LABEL_MARGIN = 1, ER_PAIR_HINGE_MARGIN = 2, ER_PAIR_ALPHA = 4 };
+int32_t er_pairwise_grid(int64_t B);         /* entries of loss_partials; 0 outside the envelope */
+int64_t er_pairwise_work_floats(int64_t B);  /* floats of `work`; 0 outside the envelope */
+int er_pairwise(const float* logits, int64_t ld_logits, const float* labels, const int64_t* session_keys,
+                const float* weights, int64_t B, int32_t kind, int32_t flags, float temperature, float label_div,
+                float margin, float hinge_margin, float gamma, float alpha, float loss_scale, float* work,
+                float* loss_partials, float* dlogits, int32_t* pair_count, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed
