@@ -7,10 +7,13 @@ CLASSIFICATION with num_class > 1 -> tf.losses.sparse_softmax_cross_entropy, and
 launch each as well (`er_softmax_ce`, `er_jrc`) or their torch compositions (builders/multiclass_loss.py).
 PAIR_WISE_LOSS and PAIRWISE_LOGISTIC / HINGE / FOCAL_LOSS -> loss/pairwise_loss.py, with or without session keys: the pair
 kernel `er_pairwise` or their torch compositions (builders/pairwise_loss.py).
+LISTWISE_RANK_LOSS and LISTWISE_DISTILL_LOSS -> loss/listwise_loss.py, over the sessions `session_name` gives: the
+sorted-segment kernel `er_listwise` or their torch compositions (builders/listwise_loss.py).
 """
 import torch
 
 from easyrec_amd import kernels
+from easyrec_amd.builders import listwise_loss as listwise
 from easyrec_amd.builders import multiclass_loss
 from easyrec_amd.builders import pairwise_loss as pairwise
 from easyrec_amd.protos.loss_pb2 import LossType
@@ -126,6 +129,14 @@ def build(loss_type, label, pred, loss_weight=1.0, num_class=1, loss_scale=1.0, 
     assert num_class == 1, 'num_class must be 1 when loss type is %s' % LossType.Name(loss_type)
     loss, dlogits, extras = pairwise.build(loss_type, label, pred, loss_weight, loss_scale, loss_param,
                                            kwargs.get('session_ids'))
+    loss._er_extras = extras
+    return loss, dlogits
+  if loss_type in listwise.LOSS_TYPES:
+    # the two listwise ranking losses: er_listwise's launch or their torch compositions; the session count rides on the
+    # loss tensor, the scale variables' gradients go into their buffers
+    assert num_class == 1, 'num_class must be 1 when loss type is %s' % LossType.Name(loss_type)
+    loss, dlogits, extras = listwise.build(loss_type, label, pred, loss_weight, loss_scale, loss_param,
+                                           kwargs.get('session_ids'), kwargs.get('scale_vars'))
     loss._er_extras = extras
     return loss, dlogits
   if loss_type == LossType.F1_REWEIGHTED_LOSS:

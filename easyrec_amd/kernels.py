@@ -59,6 +59,8 @@ COMBINERS = {'sum': COMBINER_SUM, 'mean': COMBINER_MEAN, 'sqrtn': COMBINER_SQRTN
 (PAIR_WISE, PAIR_LOGISTIC, PAIR_HINGE, PAIR_FOCAL, PAIR_LABEL_MARGIN, PAIR_HINGE_MARGIN, PAIR_ALPHA) = (
     abi.CONSTANTS['ER_PAIR_' + name] for name in ('WISE', 'LOGISTIC', 'HINGE', 'FOCAL', 'LABEL_MARGIN', 'HINGE_MARGIN',
                                                   'ALPHA'))
+(LIST_RANK, LIST_DISTILL, LIST_LABEL_IS_LOGITS, LIST_LABEL_READY) = (
+    abi.CONSTANTS['ER_LIST_' + name] for name in ('RANK', 'DISTILL', 'LABEL_IS_LOGITS', 'LABEL_READY'))
 # er_opt_hyper as the flat float array the host writes: its length and the index of each field
 HYPER_FLOATS = ctypes.sizeof(OptHyper) // 4
 HYPER_LR, HYPER_LR_T, HYPER_BETA1, HYPER_BETA2, HYPER_OMB1, HYPER_OMB2, HYPER_EPS, HYPER_GSCALE, HYPER_CLIP = (
@@ -2386,6 +2388,42 @@ class HipBackend(object):
                         None if weights is None else _p(_f32c(weights)), B, int(kind), int(flags), float(temperature),
                         float(label_div), float(margin), float(hinge_margin), float(gamma), float(alpha), float(loss_scale),
                         _p(work), _p(o['loss_partials']), _p(o['dlogits']), _p(o['pair_count']), _stream())
+    return o
+
+  # -- K8n the listwise ranking losses (builders/listwise_loss.py)
+  def listwise_grid(self, B):
+    return int(self.lib.er_listwise_grid(int(B)))
+
+  def listwise_loss(self, logits, labels, session_keys, kind, flags=0, temperature=1.0, label_clip_max=512.0, scale_w=None,
+                    scale_b=None, loss_scale=1.0, grads=None, acc=True, want=('loss', 'dlogits', 'num_sessions')):
+    """er_listwise: logits [B] (any stride), labels [B] fp32, session_keys [B] int64; kind LIST_RANK / LIST_DISTILL, flags
+    LIST_LABEL_IS_LOGITS | LIST_LABEL_READY; scale_w / scale_b: one-float tensors or both None -> dict of the outputs named
+    in `want` (loss [1] with _er_partials and loss_partials, dlogits [B], num_sessions [1] int32).  With `grads` (a
+    ThetaGradTable of scale_w's and scale_b's buffers) their gradients are added into (acc) or written to them."""
+    assert logits.dim() == 1 and logits.dtype == torch.float32
+    B = logits.shape[0]
+    dev = logits.device
+    assert session_keys.dtype == torch.int64 and session_keys.is_contiguous() and session_keys.numel() == B
+    assert _f32c(labels).numel() == B and (scale_w is None) == (scale_b is None) and (grads is None or scale_w is not None)
+    rows = self.listwise_grid(B)
+    assert rows > 0, 'er_listwise: B = %d outside the envelope' % B
+    o = {}
+    if 'loss' in want:
+      o['loss_partials'] = torch.empty(rows, dtype=torch.float32, device=dev)
+      o['loss'] = torch.empty(1, dtype=torch.float32, device=dev)
+      o['loss']._er_partials = (o['loss_partials'], 1.0, 1.0)
+    if 'dlogits' in want:
+      o['dlogits'] = torch.empty(B, dtype=torch.float32, device=dev)
+    if 'num_sessions' in want:
+      o['num_sessions'] = torch.empty(1, dtype=torch.int32, device=dev)
+    partials = torch.empty(rows * 2, dtype=torch.float32, device=dev) if grads is not None else None
+    self.ck.er_listwise(logits.data_ptr(), logits.stride(0) if B > 1 else 1, _p(_f32c(labels)), session_keys.data_ptr(), B,
+                        int(kind), int(flags), float(temperature), float(label_clip_max),
+                        None if scale_w is None else _p(_f32c(scale_w)), None if scale_b is None else _p(_f32c(scale_b)),
+                        float(loss_scale), _p(o.get('loss_partials')), _p(o.get('dlogits')), 1, _p(partials),
+                        _p(o.get('num_sessions')), _stream())
+    if grads is not None:
+      self.theta_grad_reduce(partials, rows, grads, 1, acc)
     return o
 
   # -- K8d FiBiNet's field blocks (layers/keras/fibinet.py)
@@ -5162,6 +5200,31 @@ class MatchSoftmaxLossFn(torch.autograd.Function):
     dU, dI = hip().match_softmax_bwd(U, I, inv_temperature, sw, sb, item_ids, ignore_in_batch, weight, stats, losses,
                                      g_ce.reshape(1).contiguous(), g_reg.reshape(1).contiguous(), table, acc)
     return (dU, dI, None, None, None, None, None) + ret
+
+
+class ListwiseLossFn(torch.autograd.Function):
+  """reference loss/listwise_loss.py: apply(logits [B], labels [B] fp32, session_keys [B] int64, cfg = dict(kind, flags,
+  temperature, label_clip_max, loss_scale), scale_w, scale_b) -> (loss [1], num_sessions [1] int32) (er_listwise: ONE
+  launch computes the loss and every gradient, and the backward multiplies them by the upstream gradient).  scale_w /
+  scale_b: one-float tensors, or both None for no scale.  The labels take no gradient.  (A model's step does not come
+  through here: builders/listwise_loss.py hands the launch's dlogits on as the backward seed and has the scale gradients
+  added into the variables' buffers.)"""
+
+  @staticmethod
+  def forward(ctx, logits, labels, session_keys, cfg, scale_w, scale_b):
+    sw = None if scale_w is None else scale_w.detach()
+    sb = None if scale_b is None else scale_b.detach()
+    fresh = () if sw is None else (torch.empty_like(sw), torch.empty_like(sb))
+    o = hip().listwise_loss(logits.detach(), labels, session_keys, scale_w=sw, scale_b=sb,
+                            grads=ThetaGradTable(fresh) if fresh else None, acc=False, **cfg)
+    ctx.save_for_backward(o['dlogits'], *fresh)
+    ctx.mark_non_differentiable(o['num_sessions'])
+    return o['loss_partials'].clone(), o['num_sessions']  # (one partial: the loss itself)
+
+  @staticmethod
+  def backward(ctx, g, _):
+    saved = ctx.saved_tensors
+    return (g * saved[0], None, None, None) + (tuple(g * r for r in saved[1:]) if len(saved) > 1 else (None, None))
 
 
 class CapsuleRoutingFn(torch.autograd.Function):

@@ -37,6 +37,8 @@ _PAIR_WISE = _Head('binary', ('probs', 'logits'), 'logits', 'pair_wise_loss')
 _PAIRWISE_LOGISTIC = _Head('binary', ('probs', 'logits'), 'logits', 'pairwise_logistic_loss')
 _PAIRWISE_HINGE = _Head('binary', ('probs', 'logits'), 'logits', 'pairwise_hinge_loss')
 _PAIRWISE_FOCAL = _Head('binary', ('probs', 'logits'), 'logits', 'pairwise_focal_loss')
+_LISTWISE_RANK = _Head('binary', ('probs', 'logits'), 'logits', 'listwise_rank_loss')
+_LISTWISE_DISTILL = _Head('binary', ('probs', 'logits'), 'logits', 'listwise_distill_loss')
 
 # the heads that read more than one logit per example (builders/multiclass_loss.py); '%s': where the suffix goes
 _MULTICLASS = _Head('multiclass', ('y', 'probs', 'logits', 'probs%s_y', 'logits%s_y', 'probs%s_1', 'logits%s_1'), 'logits',
@@ -50,6 +52,8 @@ _HEADS = {
     LossType.PAIRWISE_LOGISTIC_LOSS: _PAIRWISE_LOGISTIC,
     LossType.PAIRWISE_HINGE_LOSS: _PAIRWISE_HINGE,
     LossType.PAIRWISE_FOCAL_LOSS: _PAIRWISE_FOCAL,
+    LossType.LISTWISE_RANK_LOSS: _LISTWISE_RANK,
+    LossType.LISTWISE_DISTILL_LOSS: _LISTWISE_DISTILL,
     LossType.CLASSIFICATION: _BINARY,
     LossType.BINARY_CROSS_ENTROPY_LOSS: _BINARY,
     LossType.F1_REWEIGHTED_LOSS: _F1_REWEIGHTED,
@@ -162,9 +166,12 @@ class RankModel(EasyRecModel):
 
   @staticmethod
   def _session_name(loss_type, loss_param):
-    """The `session_name` of a JRC or pairwise loss parameter ('' when the loss has none)"""
+    """The `session_name` of a JRC, pairwise or listwise loss parameter ('' when the loss has none)"""
+    from easyrec_amd.builders import listwise_loss as lwl
     from easyrec_amd.builders import multiclass_loss as mcl
     from easyrec_amd.builders import pairwise_loss as pwl
+    if loss_type in lwl.LOSS_TYPES:
+      return lwl.params_of(loss_type, loss_param)['session_name']
     if loss_type == LossType.JRC_LOSS:
       return mcl.check_jrc_param(loss_param)[2]
     if loss_type in pwl.LOSS_TYPES:
@@ -172,13 +179,14 @@ class RankModel(EasyRecModel):
     return ''
 
   def _session_ids(self, loss_type, loss_param):
-    """The session keys of a JRC or pairwise loss: the device id column of the feature `session_name`, as the embedding
+    """The session keys of a JRC, pairwise or listwise loss: the device id column of the feature `session_name`, as the embedding
     sees it (after the hash bucket: two raw ids that share a bucket are one session)."""
     session = self._session_name(loss_type, loss_param)
     return self._feature_dict.batch_ids_of(session) if session else None
 
   def _check_head(self, loss_type, num_class, loss_param=None, what='model'):
     """Build-time refusals of a head (called once per (loss type, num_class) a model or tower declares)."""
+    from easyrec_amd.builders import listwise_loss as lwl
     from easyrec_amd.builders import multiclass_loss as mcl
     from easyrec_amd.core import context
     if loss_type == LossType.ZILN_LOSS:
@@ -188,6 +196,8 @@ class RankModel(EasyRecModel):
     if session and schema is not None and session not in schema.hash_single and session not in schema.int_single:
       which = 'jrc_loss' if loss_type == LossType.JRC_LOSS else LossType.Name(loss_type).lower()
       raise ValueError('%s: %s { session_name: "%s" } names no single-valued id feature' % (what, which, session))
+    if loss_type in lwl.LOSS_TYPES:
+      return self._check_listwise(loss_type, loss_param, what)
     if loss_type == LossType.JRC_LOSS:
       assert num_class == 2, 'num_class must be 2 when loss type is JRC_LOSS'
     elif not (loss_type == LossType.CLASSIFICATION and num_class > 1):
@@ -203,6 +213,20 @@ class RankModel(EasyRecModel):
     if len(self._base_model_config.kd) > 0:
       raise NotImplementedError('%s: a `kd` section (knowledge distillation) on a model with a multi-logit head is not '
                                 'built' % what)
+
+  def _check_listwise(self, loss_type, loss_param, what):
+    """A listwise loss' refusals beyond its parameters' own, and - this runs in the build pass - its scale variables."""
+    from easyrec_amd.builders import listwise_loss as lwl
+    from easyrec_amd.core import context
+    name = LossType.Name(loss_type).lower()
+    ctx = context.current()
+    if getattr(ctx, 'dense_dtype', 'f32') == 'bf16':
+      raise ValueError('%s: dense_dtype bf16 with %s is not supported (the loss kernel is fp32)' % (what, name))
+    from easyrec_amd.layers.sharded_embedding import ShardedEmbeddingEngine
+    if isinstance(getattr(ctx, 'engine', None), ShardedEmbeddingEngine):
+      raise ValueError('%s: embedding-parallel training with %s is not supported (a session must lie on one rank)' %
+                       (what, name))
+    lwl.scale_variables(lwl.params_of(loss_type, loss_param))
 
   def _loss_types(self):
     """The loss types this model's single output feeds: the `losses` list, else the one `loss_type`."""

@@ -1424,6 +1424,70 @@ int er_pairwise(const float* logits, int64_t ld_logits, const float* labels, con
                 float* loss_partials, float* dlogits, int32_t* pair_count, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8n The session-keyed listwise ranking losses: reference loss/listwise_loss.py, listwise_rank_loss and
+ *     listwise_distill_loss.  fp32 with the precise expf / logf / log1pf, no MFMA (there is no contraction:
+ *     the work is a sort by key and segmented reductions), no atomics, vector stores only, every float sum
+ *     in one fixed order: two runs and a graph replay give the same bits.  Memory is O(B): nothing of size
+ *     S x B or B x B exists, and nothing is read back to the host (the reference's tf.unique + tf.map_fn
+ *     builds one boolean mask over the batch per session).
+ *
+ * er_listwise: logits z [B] at pitch ld_logits; labels y [B] fp32; session_keys [B] int64, compared as signed
+ *   64-bit integers; scale_w, scale_b: device scalars (`<loss_name>/scale_w`, `/scale_b`), both NULL for no
+ *   scale.  In the reference's order:
+ *     a = z * |scale_w| + scale_b (when scaled);  temperature != 1: a = a / temperature
+ *     ER_LIST_RANK     temperature != 1 and ER_LIST_LABEL_IS_LOGITS: y = y / temperature.  Over the members
+ *                      M(s) of session s: t = softmax of y under ER_LIST_LABEL_IS_LOGITS (maximum subtracted),
+ *                      else t = y as it is (not normalised)
+ *     ER_LIST_DISTILL  y = min(max(y, 1), label_clip_max);  y = log1p(label_clip_max) - log(y);
+ *                      t = y / sum over M(s) of y
+ *   ER_LIST_LABEL_READY: the caller has done everything up to `t = ..` to the labels already (a transform_fn
+ *   runs on the host in place of, or after, those steps): the kernel divides, clips and transforms nothing.
+ *     m_s = max over M(s) of a;  se_s = sum over M(s) of exp(a - m_s);  logp_i = (a_i - m_s) - log(se_s)
+ *     loss_s = - sum over M(s) of t_i * logp_i;  S = the number of distinct keys
+ *     loss   = loss_scale * (1 / S) sum_s loss_s = loss_partials[0] (er_listwise_grid(B) = 1 entry; the loss
+ *              tail, er_loss_tail with scale 1 and divisor 1, takes it as it takes the other heads' partials)
+ *     g_i    = d loss / d a_i = loss_scale / S * (T_s * exp(a_i - m_s) / se_s - t_i),  T_s = sum over M(s) of t
+ *     dlogits [B] at pitch ld_dlogits = g_i * |scale_w| / temperature (each factor only where it applied)
+ *     scale_partials [er_listwise_grid(B), 2] = sign(scale_w) / temperature * sum_i g_i z_i | sum_i g_i /
+ *              temperature: er_theta_grad_reduce (K8e) sums them with row_groups = 1 into scale_w's and scale_b's
+ *              buffers, as er_match_softmax_bwd's sim_w / sim_b partials are.  sign(0) = 0.
+ *     num_sessions [1] int32 = S
+ *   Labels take no gradient.  loss_partials, dlogits, scale_partials and num_sessions may each be NULL.
+ *   Geometry: ONE workgroup of 1024 lanes.  N = the power of two >= max(B, 2); the records (key, example
+ *   index), 12 bytes each, lie in LDS as key[N] | index[N] (B = 8192: 96 KB of the 160 KB).  Example i is
+ *   loaded by lane i mod 1024; the records N > i >= B are (INT64_MAX, i), so a real key of INT64_MAX - its
+ *   index is below B - still sorts in front of them.  A bitonic network, log2 N (log2 N + 1) / 2 steps of N / 2
+ *   compare-exchanges with a workgroup barrier after each, orders the records lexicographically on (signed
+ *   key, index): the order is total, so the result is a pure function of the data.  After it every session is
+ *   one run of positions with its members in ascending example index, and the B real records are the
+ *   positions 0 .. B - 1.  Lane l then owns the E = max(N / 1024, 1) positions l E .. l E + E - 1: it reads
+ *   their keys and their neighbours' (a position whose predecessor holds another key is a head, one whose
+ *   successor does is a tail), gathers z and y through the index and keeps everything in registers; the key
+ *   array is dead from here on and its space becomes the per-session scratch.  A reduction over the sessions
+ *   is an inclusive segmented scan over the positions - the lane's E elements in order, then the lanes of
+ *   its wavefront by __shfl_up over the offsets 1, 2, .., 32 on (head seen, value), then the 16 wavefronts' last
+ *   values through LDS, folded in wave order - so a session may span elements, lanes and wavefronts; the
+ *   tail of each session stores the result at scratch[session number] and, after a barrier, every member
+ *   reads it back.  The session numbers are the same scan over the head flags as integers, and S is its
+ *   last value.  Five such reductions run at most (max a, sum exp; max y, sum exp y or sum y; sum t).
+ *   The terms t_i * logp_i, g_i and g_i z_i are summed over the positions in sorted order: a lane's
+ *   elements ascending from 0.f, the wavefront's xor butterfly 1, 2, .., 32, the 16 wavefronts in order.
+ *   dlogits is scattered back through the index.
+ *   Envelope: 1 <= B <= 8192, 1 <= every pitch <= 2^20, temperature > 0, kind ER_LIST_RANK or
+ *   ER_LIST_DISTILL, scale_w and scale_b both NULL or neither, label_clip_max >= 1 for ER_LIST_DISTILL
+ *   without ER_LIST_LABEL_READY.  Outside it the launch returns an error, and er_listwise_grid and
+ *   er_listwise_lds_bytes return 0.
+ * -------------------------------------------------------------------------------------------- */
+enum { ER_LIST_RANK = 0, ER_LIST_DISTILL = 1 };
+enum { ER_LIST_LABEL_IS_LOGITS = 1, ER_LIST_LABEL_READY = 2 };
+int32_t er_listwise_grid(int64_t B);       /* rows of loss_partials and scale_partials (1); 0 outside the envelope */
+int64_t er_listwise_lds_bytes(int64_t B);  /* the launch's dynamic LDS: 12 N bytes; 0 outside the envelope */
+int er_listwise(const float* logits, int64_t ld_logits, const float* labels, const int64_t* session_keys, int64_t B,
+                int32_t kind, int32_t flags, float temperature, float label_clip_max, const float* scale_w,
+                const float* scale_b, float loss_scale, float* loss_partials, float* dlogits, int64_t ld_dlogits,
+                float* scale_partials, int32_t* num_sessions, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed
