@@ -22,9 +22,11 @@ since its loss_builder passes none - `listwise_loss` for the rank loss, `listwis
 Which path runs is decided by what the code can see.  On the HIP backend, with fp32 logits on the GPU and B inside the
 kernel's envelope (include/easyrec_hip.h K8n), ONE launch (csrc/er_listwise.hip: an in-LDS sort by key, then segmented
 scans) yields the loss - as the partial the loss tail's launch takes - d loss / d logits, the scale variables' gradient
-partials and the session count, without a device-to-host read.  Anywhere else - a stand-in backend on the CPU, a batch
-outside the envelope, EASYREC_AMD_FUSED_LISTWISE=0 - the compositions below run: the reference's forms op for op as
-torch ops (unique keys, one boolean mask per session), differentiated by autograd.
+partials and the session count, without a device-to-host read.  Beyond that envelope, 8192 < B <= 131072, and with
+EASYREC_AMD_LISTWISE_TILED=1 the same outputs come from the tiled launches (K8o, er_listwise_tiled: a tile sort, merge
+passes, three reduction stages with one carry record per workgroup), one row of partials per workgroup.  Anywhere else -
+a stand-in backend on the CPU, a batch outside the envelopes, EASYREC_AMD_FUSED_LISTWISE=0 - the compositions below run:
+the reference's forms op for op as torch ops (unique keys, one boolean mask per session), differentiated by autograd.
 """
 import functools
 import logging
@@ -50,6 +52,35 @@ def fused_enabled():
 
 def fits(B):
   return 1 <= B <= MAX_BATCH
+
+
+TILED_DEFAULT = '0'        # EASYREC_AMD_LISTWISE_TILED when the environment does not set it
+TILED_MAX_BATCH = 131072   # er_listwise_tiled: B
+TILES = (1024, 2048, 4096, 8192)
+DEFAULT_TILE = 1024        # what tile = 0 selects
+
+
+def tiled_enabled():
+  """EASYREC_AMD_LISTWISE_TILED=1: batches beyond er_listwise's envelope run on er_listwise_tiled (K8o), not on the
+  compositions."""
+  return os.environ.get('EASYREC_AMD_LISTWISE_TILED', TILED_DEFAULT) != '0'
+
+
+def fits_tiled(B):
+  return MAX_BATCH < B <= TILED_MAX_BATCH
+
+
+def tiled_grid(B, tile=0):
+  """er_listwise_tiled_grid: the workgroups, one row of partials each; 0 outside the envelope"""
+  if tile == 0:
+    tile = DEFAULT_TILE if fits_tiled(B) else -1
+  return -(-B // tile) if tile in TILES and 1 <= B <= TILED_MAX_BATCH else 0
+
+
+def tiled_workspace_bytes(B, tile=0):
+  """er_listwise_tiled_workspace_bytes: two buffers of G T records of 12 bytes and 16 words of carry per workgroup"""
+  G = tiled_grid(B, tile)
+  return G * (tile or DEFAULT_TILE) * 24 + G * 64
 
 
 @functools.lru_cache(maxsize=None)
@@ -164,10 +195,20 @@ def on_kernel(pred, p):
       p['temperature'] > 0 and isinstance(kernels.hip(), kernels.HipBackend)
 
 
-def fused(loss_type, labels, logits, session_ids, p, scale_w=None, scale_b=None, loss_scale=1.0):
+def on_tiled_kernel(pred, p):
+  """the second branch: beyond er_listwise's envelope, inside er_listwise_tiled's, and switched on"""
+  return fused_enabled() and tiled_enabled() and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 1 and \
+      fits_tiled(pred.shape[0]) and p['temperature'] > 0 and isinstance(kernels.hip(), kernels.HipBackend)
+
+
+def fused(loss_type, labels, logits, session_ids, p, scale_w=None, scale_b=None, loss_scale=1.0, tile=None):
   """The autograd function over er_listwise -> (loss [1], num_sessions [1] int32); differentiable in logits, scale_w and
-  scale_b."""
+  scale_b.  tile: er_listwise_tiled at that tile (0: its default); None: by the batch size as build() chooses."""
   y, kw = kernel_args(loss_type, labels.to(torch.float32), p)
+  if tile is None and not on_kernel(logits, p) and on_tiled_kernel(logits, p):
+    tile = 0
+  if tile is not None:
+    kw['tile'] = tile
   return kernels.ListwiseLossFn.apply(logits, y, session_ids.to(torch.int64).contiguous(), dict(loss_scale=loss_scale, **kw),
                                       scale_w, scale_b)
 
@@ -192,12 +233,14 @@ def build(loss_type, label, pred, loss_weight=1.0, loss_scale=1.0, loss_param=No
     loss_weight = 1.0
   scale = loss_scale * float(loss_weight)
   sw, sb = scale_vars if scale_vars is not None else scale_variables(p)
-  if on_kernel(pred, p):
+  tiled = not on_kernel(pred, p) and on_tiled_kernel(pred, p)
+  if on_kernel(pred, p) or tiled:
     labels, kw = kernel_args(loss_type, label if label.dtype == torch.float32 else label.to(torch.float32), p)
     grads = None if sw is None else kernels.ThetaGradTable(_grad_buffers((sw, sb)))
-    res = kernels.hip().listwise_loss(pred.detach(), labels, session_ids.to(torch.int64).contiguous(),
-                                      scale_w=None if sw is None else sw.detach(), scale_b=None if sb is None else sb.detach(),
-                                      loss_scale=scale, grads=grads, acc=True, **kw)
+    launch = kernels.hip().listwise_loss_tiled if tiled else kernels.hip().listwise_loss
+    res = launch(pred.detach(), labels, session_ids.to(torch.int64).contiguous(),
+                 scale_w=None if sw is None else sw.detach(), scale_b=None if sb is None else sb.detach(),
+                 loss_scale=scale, grads=grads, acc=True, **kw)
     return res['loss'], res['dlogits'], res
   z = pred.detach().clone().requires_grad_(True)
   with torch.enable_grad():

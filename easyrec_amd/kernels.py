@@ -2426,6 +2426,47 @@ class HipBackend(object):
       self.theta_grad_reduce(partials, rows, grads, 1, acc)
     return o
 
+  # -- K8o the listwise ranking losses beyond one workgroup's LDS (builders/listwise_loss.py)
+  def listwise_tiled_grid(self, B, tile=0):
+    return int(self.lib.er_listwise_tiled_grid(int(B), int(tile)))
+
+  def listwise_loss_tiled(self, logits, labels, session_keys, kind, flags=0, temperature=1.0, label_clip_max=512.0,
+                          scale_w=None, scale_b=None, loss_scale=1.0, grads=None, acc=True,
+                          want=('loss', 'dlogits', 'num_sessions'), tile=0):
+    """er_listwise_tiled: listwise_loss's arguments and outputs for 8192 < B <= 131072 (tile = 0) or, with a tile of 1024,
+    2048, 4096 or 8192 records, 1 <= B <= 131072.  loss_partials has one entry per workgroup (listwise_tiled_grid), summed
+    by the loss tail.  The workspace is kept per (device, B, tile): launches on one stream use it in order."""
+    assert logits.dim() == 1 and logits.dtype == torch.float32
+    B = logits.shape[0]
+    dev = logits.device
+    assert session_keys.dtype == torch.int64 and session_keys.is_contiguous() and session_keys.numel() == B
+    assert _f32c(labels).numel() == B and (scale_w is None) == (scale_b is None) and (grads is None or scale_w is not None)
+    rows = self.listwise_tiled_grid(B, tile)
+    assert rows > 0, 'er_listwise_tiled: B = %d, tile = %d outside the envelope' % (B, tile)
+    cache = self.__dict__.setdefault('_listwise_workspaces', {})
+    work = cache.get((dev, B, int(tile)))
+    if work is None:
+      nbytes = int(self.lib.er_listwise_tiled_workspace_bytes(B, int(tile)))
+      work = cache[(dev, B, int(tile))] = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    o = {}
+    if 'loss' in want:
+      o['loss_partials'] = torch.empty(rows, dtype=torch.float32, device=dev)
+      o['loss'] = torch.empty(1, dtype=torch.float32, device=dev)
+      o['loss']._er_partials = (o['loss_partials'], 1.0, 1.0)
+    if 'dlogits' in want:
+      o['dlogits'] = torch.empty(B, dtype=torch.float32, device=dev)
+    if 'num_sessions' in want:
+      o['num_sessions'] = torch.empty(1, dtype=torch.int32, device=dev)
+    partials = torch.empty(rows * 2, dtype=torch.float32, device=dev) if grads is not None else None
+    self.ck.er_listwise_tiled(logits.data_ptr(), logits.stride(0) if B > 1 else 1, _p(_f32c(labels)), session_keys.data_ptr(),
+                              B, int(kind), int(flags), float(temperature), float(label_clip_max),
+                              None if scale_w is None else _p(_f32c(scale_w)), None if scale_b is None else _p(_f32c(scale_b)),
+                              float(loss_scale), _p(o.get('loss_partials')), _p(o.get('dlogits')), 1, _p(partials),
+                              _p(o.get('num_sessions')), int(tile), _p(work), work.numel() * 8, _stream())
+    if grads is not None:
+      self.theta_grad_reduce(partials, rows, grads, 1, acc)
+    return o
+
   # -- K8d FiBiNet's field blocks (layers/keras/fibinet.py)
   def bilinear_lds_bytes(self, F, D):
     return int(self.lib.er_bilinear_lds_bytes(int(F), int(D)))
@@ -5208,17 +5249,23 @@ class ListwiseLossFn(torch.autograd.Function):
   launch computes the loss and every gradient, and the backward multiplies them by the upstream gradient).  scale_w /
   scale_b: one-float tensors, or both None for no scale.  The labels take no gradient.  (A model's step does not come
   through here: builders/listwise_loss.py hands the launch's dlogits on as the backward seed and has the scale gradients
-  added into the variables' buffers.)"""
+  added into the variables' buffers.)  A `tile` key in cfg selects er_listwise_tiled (K8o) at that tile, 0 its default:
+  the loss is then er_reduce_sum over the workgroups' partials."""
 
   @staticmethod
   def forward(ctx, logits, labels, session_keys, cfg, scale_w, scale_b):
     sw = None if scale_w is None else scale_w.detach()
     sb = None if scale_b is None else scale_b.detach()
     fresh = () if sw is None else (torch.empty_like(sw), torch.empty_like(sb))
-    o = hip().listwise_loss(logits.detach(), labels, session_keys, scale_w=sw, scale_b=sb,
-                            grads=ThetaGradTable(fresh) if fresh else None, acc=False, **cfg)
+    launch = hip().listwise_loss_tiled if 'tile' in cfg else hip().listwise_loss
+    o = launch(logits.detach(), labels, session_keys, scale_w=sw, scale_b=sb,
+               grads=ThetaGradTable(fresh) if fresh else None, acc=False, **cfg)
     ctx.save_for_backward(o['dlogits'], *fresh)
     ctx.mark_non_differentiable(o['num_sessions'])
+    if 'tile' in cfg:
+      loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+      hip().reduce_sum(o['loss_partials'], 1.0, loss)
+      return loss, o['num_sessions']
     return o['loss_partials'].clone(), o['num_sessions']  # (one partial: the loss itself)
 
   @staticmethod

@@ -1488,6 +1488,62 @@ int er_listwise(const float* logits, int64_t ld_logits, const float* labels, con
                 float* scale_partials, int32_t* num_sessions, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8o The listwise ranking losses of K8n for batches beyond one workgroup's LDS, 8192 < B <= 131072, on
+ *     G = ceil(B / T) workgroups of 1024 lanes.  Semantics, formulas, pitches and the rule that loss_partials,
+ *     dlogits, scale_partials and num_sessions may each be NULL are K8n's; so are its properties: fp32 with
+ *     the precise expf / logf / log1pf, no MFMA (there is no contraction), no atomics, vector stores only,
+ *     every float sum in one fixed order - two runs and a graph replay give the same bits - O(B) memory and
+ *     no device-to-host read.  Nothing is launched cooperatively and no workgroup waits for another
+ *     workgroup's write: every dependency between workgroups is a kernel boundary.
+ *
+ * er_listwise_tiled: K8n's parameters, then `tile`, the workspace and its size.  What differs from K8n:
+ *     loss_partials [G] and scale_partials [G, 2], one row per workgroup: er_loss_tail and
+ *     er_theta_grad_reduce (row_groups = 1) sum the rows as they sum other heads'.  The sum of the rows is
+ *     K8n's value; each row carries the factor loss_scale / S already.
+ *   Geometry: `tile` T is 1024, 2048, 4096 or 8192 records, E = T / 1024 a lane; tile = 0 selects the
+ *   default, 1024.  The workspace holds two record buffers of G T records, key [2][G T] int64 | index
+ *   [2][G T] int32, and one carry record of 16 words per workgroup: 24 G T + 64 G bytes.
+ *   1. Tile sort, one launch of G workgroups: workgroup g loads the examples g T .. g T + T - 1 - positions
+ *      >= B as (INT64_MAX, position), as in K8n - sorts them in LDS (12 T bytes) with K8n's bitonic network
+ *      on (signed key, index) and writes its run to buffer 0.
+ *   2. Merge passes, ceil(log2 G) launches of G workgroups that go from one buffer to the other: a pass
+ *      makes runs of 2 L out of neighbouring runs of L.  Each workgroup produces T consecutive output
+ *      records: two of its lanes find the merge-path split of the chunk's first and last diagonal by binary
+ *      search on (signed key, index) in the two runs; the workgroup loads the records between the splits, T
+ *      together, the second run's reversed behind the first run's, and the log2 T compare-exchange steps of
+ *      a bitonic merge order them.  A run without a partner (G no power of two) is copied, so every pass
+ *      reads one buffer and writes the other.  The records are distinct - every index is unique - so the
+ *      order is total and the result a pure function of the data.
+ *   3. Three launches of G workgroups over the sorted positions, workgroup g on g T .. g T + T - 1.  A
+ *      position is a head if the record before it holds another key and a tail likewise against the record
+ *      after it, read from global memory where that lies in another chunk: true session edges.  Inside a
+ *      chunk the reductions are K8n's segmented scans over the sessions cut at the chunk's edges.  Only
+ *      the chunk's first and last segment can belong to a session that goes on elsewhere, so a launch
+ *      leaves per workgroup the leading segment's partial, the trailing segment's partial, the flags
+ *      (the chunk is one segment; open at its start; open at its end) and the count of heads; in the next
+ *      launch every workgroup folds, in workgroup order, the carries of the chunks its two edge sessions
+ *      touch - the trailing partial of the chunk that holds the head, then the leading partials of the
+ *      chunks after it up to the one that holds the tail - and sums the head counts to S.
+ *        A: (m, se) = (max a, sum exp(a - max)), and by the label form (max y, sum exp(y - max)) or sum y.
+ *           Pairs combine as (m1, s1) + (m2, s2) = (m, s1 e^(m1 - m) + s2 e^(m2 - m)), m = max(m1, m2).
+ *        B: t_i from the y totals, and the partials of T_s = sum t_i.
+ *        C: logp_i, the loss terms, g_i, dlogits through the index, the partial rows, num_sessions.
+ *      Each launch recomputes what it needs of the one before from the inputs (a pure function of them).
+ *      A session inside one chunk is reduced exactly as K8n reduces it.
+ *   Envelope: K8n's, but for B: with tile 1024, 2048, 4096 or 8192, 1 <= B <= 131072 (a small tile crosses
+ *   tile edges at a small B); with tile 0, 8192 < B <= 131072.  Any other tile is outside.  The workspace is
+ *   8-byte aligned and holds at least er_listwise_tiled_workspace_bytes(B, tile).  Outside the envelope
+ *   the launch returns an error and the two helpers return 0.
+ * -------------------------------------------------------------------------------------------- */
+int32_t er_listwise_tiled_grid(int64_t B, int32_t tile);             /* G: rows of the partials; 0 outside */
+int64_t er_listwise_tiled_workspace_bytes(int64_t B, int32_t tile);  /* 24 G T + 64 G; 0 outside */
+int er_listwise_tiled(const float* logits, int64_t ld_logits, const float* labels, const int64_t* session_keys,
+                      int64_t B, int32_t kind, int32_t flags, float temperature, float label_clip_max,
+                      const float* scale_w, const float* scale_b, float loss_scale, float* loss_partials,
+                      float* dlogits, int64_t ld_dlogits, float* scale_partials, int32_t* num_sessions, int32_t tile,
+                      void* workspace, int64_t workspace_bytes, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed
