@@ -11,8 +11,11 @@ SUM_BY_NONZERO_WEIGHTS with the safe division (no pair: loss 0).
 
 Which path runs is decided by what the code can see.  On the HIP backend, with fp32 logits on the GPU, ohem_ratio == 1 and
 B inside the kernel's envelope (include/easyrec_hip.h K8m), two launches (csrc/er_pairwise.hip) yield the loss - as
-partial sums that the loss tail's launch finishes - d loss / d logits and the pair count in O(B) memory.  Anywhere else -
-a stand-in backend on the CPU, ohem_ratio < 1, a batch outside the envelope, EASYREC_AMD_FUSED_PAIRWISE=0 - the
+partial sums that the loss tail's launch finishes - d loss / d logits and the pair count in O(B) memory.  Beyond that
+envelope, 8192 < B <= 131072, and with EASYREC_AMD_PAIRWISE_SORTED=1 the same outputs come from the sorted-run launches
+(K8p, er_pairwise_sorted: K8o's sort by session key, then one lane per sorted row over its session's columns alone), the
+pair count as int64.  Anywhere else -
+a stand-in backend on the CPU, ohem_ratio < 1, a batch outside the envelopes, EASYREC_AMD_FUSED_PAIRWISE=0 - the
 compositions below run: the reference's forms op for op as torch ops ([B, B] differences and masks, a boolean-mask
 gather), differentiated by autograd.
 
@@ -39,6 +42,36 @@ def fused_enabled():
 
 def fits(B):
   return 1 <= B <= MAX_BATCH
+
+
+SORTED_DEFAULT = '1'      # EASYREC_AMD_PAIRWISE_SORTED when the environment does not set it
+MAX_BATCH_SORTED = 131072  # er_pairwise_sorted: B
+TILES = (1024, 2048, 4096, 8192)
+DEFAULT_TILE = 1024        # what tile = 0 selects
+
+
+def sorted_enabled():
+  """EASYREC_AMD_PAIRWISE_SORTED=1: batches beyond er_pairwise's envelope run on er_pairwise_sorted (K8p), not on the
+  compositions."""
+  return os.environ.get('EASYREC_AMD_PAIRWISE_SORTED', SORTED_DEFAULT) != '0'
+
+
+def fits_sorted(B):
+  return MAX_BATCH < B <= MAX_BATCH_SORTED
+
+
+def sorted_grid(B, tile=0):
+  """er_pairwise_sorted_grid: the workgroups of 256 sorted rows, one row of partials each; 0 outside the envelope"""
+  inside = fits_sorted(B) if tile == 0 else (tile in TILES and 1 <= B <= MAX_BATCH_SORTED)
+  return -(-B // 256) if inside else 0
+
+
+def sorted_workspace_bytes(B, tile=0):
+  """er_pairwise_sorted_workspace_bytes: the sort's two buffers of G T records of 12 bytes, 24 bytes per example (column
+  record, hi, sorted dz) and 20 per workgroup"""
+  rows = sorted_grid(B, tile)
+  T = tile or DEFAULT_TILE
+  return -(-B // T) * T * 24 + 24 * B + 20 * rows if rows else 0
 
 
 def params_of(loss_type, loss_param):
@@ -216,16 +249,25 @@ def _on_kernel(pred, p):
       p['ohem_ratio'] == 1.0 and p['temperature'] > 0 and isinstance(kernels.hip(), kernels.HipBackend)
 
 
+def _on_sorted_kernel(pred, p):
+  """the second branch: beyond er_pairwise's envelope, inside er_pairwise_sorted's, and switched on"""
+  return fused_enabled() and sorted_enabled() and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 1 and \
+      fits_sorted(pred.shape[0]) and p['ohem_ratio'] == 1.0 and p['temperature'] > 0 and \
+      isinstance(kernels.hip(), kernels.HipBackend)
+
+
 def build(loss_type, label, pred, loss_weight=1.0, loss_scale=1.0, loss_param=None, session_ids=None):
   """-> (loss [1], d loss / d pred [B], extras: the launch's outputs - the pair count among them - or None).  pred [B]."""
   p = params_of(loss_type, loss_param)
   weights = loss_weight if torch.is_tensor(loss_weight) else None
   scale = loss_scale * (1.0 if weights is not None else float(loss_weight))
-  if _on_kernel(pred, p):
+  on_sorted = not _on_kernel(pred, p) and _on_sorted_kernel(pred, p)
+  if _on_kernel(pred, p) or on_sorted:
     labels = (label if label.dtype == torch.float32 else label.to(torch.float32)).contiguous()
     keys = None if session_ids is None else session_ids.to(torch.int64).contiguous()
-    res = kernels.hip().pairwise_loss(pred.detach(), labels, keys, None if weights is None else weights.contiguous(),
-                                      loss_scale=scale, **kernel_args(loss_type, p))
+    launch = kernels.hip().pairwise_loss_sorted if on_sorted else kernels.hip().pairwise_loss
+    res = launch(pred.detach(), labels, keys, None if weights is None else weights.contiguous(), loss_scale=scale,
+                 **kernel_args(loss_type, p))
     return res['loss'], res['dlogits'], res
   z = pred.detach().clone().requires_grad_(True)
   with torch.enable_grad():

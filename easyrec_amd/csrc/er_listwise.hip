@@ -22,13 +22,12 @@
 #include <math.h>
 
 #include "er_common.h"
+#include "er_listwise_sort.h"
 
 namespace er {
 
-constexpr int kLwMaxB = 8192;
 constexpr int kLwThreads = 1024;
 constexpr int kLwWaves = kLwThreads / kWave;
-constexpr int kLwRecordBytes = 12;     // int64 key + int32 index
 constexpr int kLwPlainLds = 64 << 10;  // dynamic LDS a launch gets without opting in
 
 // N: the power of two >= max(B, 2); 0 outside the envelope
@@ -397,21 +396,12 @@ int er_listwise(const float* logits, int64_t ld_logits, const float* labels, con
 // atomics, vector stores only, every float sum in one fixed order: two runs and a graph replay give the same bits.
 namespace er {
 
-constexpr int kLwtMaxB = 131072;
 constexpr int kLwtMaxG = kLwtMaxB / kLwThreads;  // chunks at the smallest tile
-constexpr int kLwtDefaultTile = 1024;            // what tile = 0 selects
 // a chunk's carry record, 16 words: slot q (0: the a pair, 1: the y pair or sum, 2: sum t) holds its leading partial at
 // words 4 q, 4 q + 1 and its trailing partial at 4 q + 2, 4 q + 3; the flags at word 12, the head count at word 13
 constexpr int kLwtCarry = 16;
 constexpr int kLwtFlags = 12, kLwtHeads = 13;
 enum { kLwtWhole = 1, kLwtOpenStart = 2, kLwtOpenEnd = 4 };
-
-// the tile a launch runs at; 0 outside the envelope
-inline int lwt_tile(int64_t B, int tile) {
-  if (B < 1 || B > kLwtMaxB) return 0;
-  if (tile == 0) return B > kLwMaxB ? kLwtDefaultTile : 0;
-  return (tile == 1024 || tile == 2048 || tile == 4096 || tile == 8192) ? tile : 0;
-}
 
 // the steps k = k_from, 2 k_from, .., N of K8n's bitonic network over N records in LDS (k_from = 2: the sort; k_from = N:
 // the merge of a bitonic sequence, ascending); a workgroup barrier lies before it and after every step
@@ -822,6 +812,32 @@ inline int64_t lwt_workspace_bytes(int64_t B, int tile) {
   return G * T * 2 * kLwRecordBytes + G * kLwtCarry * 4;
 }
 
+int lwt_sort(const int64_t* keys, int B, int T, int64_t* const key[2], int32_t* const idx[2], er_stream_t stream, int* cur) {
+  const int G = static_cast<int>(ceil_div(B, T)), NP = G * T;
+  // more than 64 KB of dynamic LDS is opted in to once per kernel (no stream work: safe inside a capture)
+  static bool opted = false;
+  const int lds = T * kLwRecordBytes;
+  if (lds > kLwPlainLds && !opted) {
+    ER_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(listwise_tile_sort_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLwMaxB * kLwRecordBytes));
+    ER_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(listwise_merge_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLwMaxB * kLwRecordBytes));
+    opted = true;
+  }
+  hipLaunchKernelGGL(listwise_tile_sort_kernel, dim3(G), dim3(kLwThreads), static_cast<size_t>(lds), as_stream(stream), keys,
+                     B, T, key[0], idx[0]);
+  ER_LAUNCH_CHECK();
+  int c = 0;
+  for (int L = T; L < NP; L <<= 1) {  // ceil(log2 G) passes
+    hipLaunchKernelGGL(listwise_merge_kernel, dim3(G), dim3(kLwThreads), static_cast<size_t>(lds), as_stream(stream), key[c],
+                       idx[c], NP, L, T, key[c ^ 1], idx[c ^ 1]);
+    ER_LAUNCH_CHECK();
+    c ^= 1;
+  }
+  *cur = c;
+  return 0;
+}
+
 }  // namespace er
 
 extern "C" {
@@ -862,27 +878,8 @@ int er_listwise_tiled(const float* logits, int64_t ld_logits, const float* label
   int32_t* idx[2] = {reinterpret_cast<int32_t*>(ws + static_cast<size_t>(NP) * 16),
                      reinterpret_cast<int32_t*>(ws + static_cast<size_t>(NP) * 16) + NP};
   float* carry = reinterpret_cast<float*>(ws + static_cast<size_t>(NP) * 24);
-
-  // more than 64 KB of dynamic LDS is opted in to once per kernel (no stream work: safe inside a capture)
-  static bool opted = false;
-  const int lds = T * er::kLwRecordBytes;
-  if (lds > er::kLwPlainLds && !opted) {
-    ER_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(er::listwise_tile_sort_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, er::kLwMaxB * er::kLwRecordBytes));
-    ER_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(er::listwise_merge_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, er::kLwMaxB * er::kLwRecordBytes));
-    opted = true;
-  }
-  hipLaunchKernelGGL(er::listwise_tile_sort_kernel, dim3(G), dim3(er::kLwThreads), static_cast<size_t>(lds),
-                     er::as_stream(stream), session_keys, Bi, T, key[0], idx[0]);
-  ER_LAUNCH_CHECK();
   int cur = 0;
-  for (int L = T; L < NP; L <<= 1) {  // ceil(log2 G) passes
-    hipLaunchKernelGGL(er::listwise_merge_kernel, dim3(G), dim3(er::kLwThreads), static_cast<size_t>(lds),
-                       er::as_stream(stream), key[cur], idx[cur], NP, L, T, key[cur ^ 1], idx[cur ^ 1]);
-    ER_LAUNCH_CHECK();
-    cur ^= 1;
-  }
+  if (const int rc = er::lwt_sort(session_keys, Bi, T, key, idx, stream, &cur)) return rc;
   er::LwtArgs a;
   a.z = logits; a.ldz = ld_logits; a.y = labels; a.skey = key[cur]; a.sidx = idx[cur]; a.B = Bi; a.G = G;
   a.p.temperature = temperature; a.p.clip_max = label_clip_max; a.p.loss_scale = loss_scale;

@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "er_common.h"
+#include "er_listwise_sort.h"
 
 namespace er {
 
@@ -264,6 +265,259 @@ int er_pairwise(const float* logits, int64_t ld_logits, const float* labels, con
   ER_LAUNCH_CHECK();
   hipLaunchKernelGGL(er::pair_finish_kernel, dim3(static_cast<unsigned>(g.rb)), dim3(er::kBlock), 0, er::as_stream(stream),
                      pdz, ploss, pcnt, Bi, g.splits, grid, loss_scale, temperature, dlogits, loss_partials, pair_count);
+  ER_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // extern "C"
+
+// K8p: the same losses for 8192 < B <= 131072 on examples sorted by (session key, example index).
+//
+// K8m evaluates all B x B column positions and keeps `splits x B` gradient partials, whatever the session keys leave of
+// them.  After K8o's record sort (er_listwise_sort.h) a session is one run of consecutive positions, so a row's pairs
+// lie in [lo, hi), its session's first position and one past its last:
+//
+//   pws_gather_kernel   one lane per sorted position p: (s, yl, w) through the index, lo and hi by two binary searches
+//                       over the B real keys (the padding behind them is never read, so a real INT64_MAX key ends at
+//                       B), one 16-byte column record (s, yl, w, lo as bits) and hi.  Without keys position p is
+//                       example p and [lo, hi) = [0, B).
+//   pws_pair_kernel     one lane per sorted row, 256 rows a workgroup.  The workgroup's columns run from lo of its
+//                       first row to hi of its last real row (both ascend with the position) and pass through LDS in
+//                       chunks of at most 1024 records; of a chunk a wavefront walks only the columns inside [lo of its
+//                       first row, hi of its last real row) - wave-uniform bounds - and every lane reads the SAME LDS
+//                       record per column.  A column is of the row's session when lo_j == lo_i; K8m's single pw_pair
+//                       evaluation then serves both orientations.  A row sees every column of its session, so dz_i is
+//                       complete in the lane's register: no column splits, no partial buffer.
+//   pws_finish_kernel   the same grid.  Each workgroup sums the workgroups' 64-bit counts, scales its loss row and its
+//                       rows' dz by loss_scale / nz (dz also by 1 / T) and scatters dz through the index.
+//
+// The float sums run over sorted positions (columns ascending from 0.f, block_sum_256's tree, the rows by the loss tail):
+// a pure function of the inputs, not bit-equal to K8m.  No atomics, vector stores only, nothing read back to the host,
+// every dependency between workgroups a kernel boundary.
+namespace er {
+
+constexpr int kPwsChunk = 1024;  // column records staged in LDS: 16 bytes each
+
+struct PwsWork {  // (host only) the workspace's parts
+  int64_t* key[2]; int32_t* idx[2]; float4* rec; int64_t* pcnt; int32_t* hi; float* dzs; float* ploss;
+};
+
+// key [2][NP] int64 | index [2][NP] int32 | records [B] 16 bytes | counts [rows][2] int64 | hi [B] | dz [B] | loss [rows]
+inline int64_t pws_workspace_bytes(int64_t B, int tile) {
+  const int T = lwt_tile(B, tile);
+  if (T == 0) return 0;
+  const int64_t NP = ceil_div(B, T) * T, rows = ceil_div(B, kBlock);
+  return NP * 2 * kLwRecordBytes + 24 * B + 20 * rows;
+}
+
+inline PwsWork pws_carve(void* workspace, int64_t B, int T) {
+  const int64_t NP = ceil_div(B, T) * T, rows = ceil_div(B, kBlock);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  PwsWork k;
+  k.key[0] = reinterpret_cast<int64_t*>(ws);
+  k.key[1] = k.key[0] + NP;
+  k.idx[0] = reinterpret_cast<int32_t*>(ws + NP * 16);
+  k.idx[1] = k.idx[0] + NP;
+  ws += NP * 2 * kLwRecordBytes;
+  k.rec = reinterpret_cast<float4*>(ws);
+  k.pcnt = reinterpret_cast<int64_t*>(ws + 16 * B);
+  k.hi = reinterpret_cast<int32_t*>(ws + 16 * B + 16 * rows);
+  k.dzs = reinterpret_cast<float*>(ws + 20 * B + 16 * rows);
+  k.ploss = k.dzs + B;
+  return k;
+}
+
+__global__ __launch_bounds__(kBlock) void pws_gather_kernel(const float* __restrict__ z, int64_t ldz,
+                                                           const float* __restrict__ y, const float* __restrict__ w,
+                                                           const int64_t* __restrict__ skey, const int32_t* __restrict__ sidx,
+                                                           int B, float temperature, float label_div,
+                                                           float4* __restrict__ rec, int32_t* __restrict__ hi) {
+  const int p = static_cast<int>(blockIdx.x) * kBlock + static_cast<int>(threadIdx.x);
+  if (p >= B) return;
+  int i = p, first = 0, past = B;
+  if (skey) {
+    i = sidx[p];
+    const int64_t k = skey[p];
+    int a = 0, b = p;  // the first position whose key is not below k: in [0, p]
+    while (a < b) {
+      const int mid = (a + b) >> 1;
+      if (skey[mid] < k) a = mid + 1; else b = mid;
+    }
+    first = a;
+    a = p + 1; b = B;  // the first position whose key is above k, or B: in [p + 1, B]
+    while (a < b) {
+      const int mid = (a + b) >> 1;
+      if (skey[mid] > k) b = mid; else a = mid + 1;
+    }
+    past = a;
+  }
+  rec[p] = make_float4(z[i * ldz] / temperature, y[i] / label_div, w ? w[i] : 1.f, __int_as_float(first));
+  hi[p] = past;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void pws_pair_kernel(const float4* __restrict__ rec, const int32_t* __restrict__ hi,
+                                                         int B, PwParam p, float* __restrict__ dzs,
+                                                         float* __restrict__ ploss, int64_t* __restrict__ pcnt) {
+  __shared__ float4 s_rec[kPwsChunk];
+  __shared__ float red[4];
+  __shared__ long long lred[8];
+  const int tid = static_cast<int>(threadIdx.x), r0 = static_cast<int>(blockIdx.x) * kBlock;
+  const int i = r0 + tid;
+  const bool live = i < B;
+  const float4 me = rec[live ? i : B - 1];
+  const float si = me.x, yi = me.y, wi = me.z;
+  const int loi = live ? __float_as_int(me.w) : -1;  // (no column's lo is negative: a dead row meets no pair)
+  // the workgroup's columns, and inside them the wavefront's (an idle wavefront: none)
+  const int c_begin = __float_as_int(rec[r0].w), c_end = hi[min(r0 + kBlock, B) - 1];
+  const int wr = r0 + (tid & ~(kWave - 1));
+  const int wlo = __builtin_amdgcn_readfirstlane(wr < B ? __float_as_int(rec[wr].w) : 0);
+  const int whi = __builtin_amdgcn_readfirstlane(wr < B ? hi[min(wr + kWave, B) - 1] : 0);
+  float loss = 0.f, dzi = 0.f;
+  int cnt = 0, nzc = 0;
+  for (int c0 = c_begin; c0 < c_end; c0 += kPwsChunk) {
+    const int n = min(kPwsChunk, c_end - c0);
+    if (c0 > c_begin) __syncthreads();  // (the chunk before is read to its end)
+    for (int t = tid; t < n; t += kBlock) s_rec[t] = rec[c0 + t];
+    __syncthreads();
+    const int from = max(c0, wlo), to = min(c0 + n, whi);
+    for (int c = from; c < to; ++c) {
+      const float4 col = s_rec[c - c0];
+      const float yj = col.y;
+      const bool first = yi > yj;
+      if ((first || yj > yi) && __float_as_int(col.w) == loi) {
+        const float sj = col.x;
+        const float d = first ? si - sj : sj - si, dy = first ? yi - yj : yj - yi, wt = first ? wi : col.z;
+        float l, g, present;
+        if (pw_pair<KIND>(p, d, dy, &l, &g, &present)) {
+          if (first) {
+            loss = loss + wt * l;
+            dzi = dzi + wt * g;
+            cnt += 1;
+            nzc += wt * present != 0.f ? 1 : 0;
+          } else {
+            dzi = dzi - wt * g;
+          }
+        }
+      }
+    }
+  }
+  if (live) dzs[i] = dzi;
+  const float tot = block_sum_256(loss, red);
+  long long c64 = cnt, n64 = nzc;  // (a lane meets at most B columns; beyond the lane the counts are 64-bit)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    c64 += __shfl_xor(c64, off, kWave);
+    n64 += __shfl_xor(n64, off, kWave);
+  }
+  if ((tid & 63) == 0) {
+    lred[tid >> 6] = c64;
+    lred[4 + (tid >> 6)] = n64;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    ploss[blockIdx.x] = tot;
+    pcnt[2 * blockIdx.x] = lred[0] + lred[1] + lred[2] + lred[3];
+    pcnt[2 * blockIdx.x + 1] = lred[4] + lred[5] + lred[6] + lred[7];
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void pws_finish_kernel(const float* __restrict__ dzs, const float* __restrict__ ploss,
+                                                           const int64_t* __restrict__ pcnt,
+                                                           const int32_t* __restrict__ sidx, int B, float scale,
+                                                           float temperature, float* __restrict__ dz,
+                                                           float* __restrict__ loss_partials,
+                                                           int64_t* __restrict__ pair_count) {
+  __shared__ long long lred[8];
+  const int tid = static_cast<int>(threadIdx.x), rows = static_cast<int>(gridDim.x);
+  long long cnt = 0, nzc = 0;
+  for (int g = tid; g < rows; g += kBlock) {  // (at most 512 rows: two a lane, in workgroup order)
+    cnt += pcnt[2 * g];
+    nzc += pcnt[2 * g + 1];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    cnt += __shfl_xor(cnt, off, kWave);
+    nzc += __shfl_xor(nzc, off, kWave);
+  }
+  if ((tid & 63) == 0) {
+    lred[tid >> 6] = cnt;
+    lred[4 + (tid >> 6)] = nzc;
+  }
+  __syncthreads();
+  cnt = lred[0] + lred[1] + lred[2] + lred[3];
+  nzc = lred[4] + lred[5] + lred[6] + lred[7];
+  const float nz = nzc > 0 ? static_cast<float>(nzc) : 1.f;  // (no pair present: every sum is 0 - loss 0, zero gradient)
+  const int i = static_cast<int>(blockIdx.x) * kBlock + tid;
+  if (dz && i < B) dz[sidx ? sidx[i] : i] = scale * ((dzs[i] / nz) / temperature);
+  if (tid == 0) {
+    if (loss_partials) loss_partials[blockIdx.x] = scale * (ploss[blockIdx.x] / nz);
+    if (pair_count && blockIdx.x == 0) pair_count[0] = cnt;
+  }
+}
+
+template <int KIND>
+static void pws_launch_pairs(int rows, er_stream_t stream, const PwsWork& k, int B, const PwParam& p) {
+  hipLaunchKernelGGL(pws_pair_kernel<KIND>, dim3(static_cast<unsigned>(rows)), dim3(kBlock), 0, as_stream(stream), k.rec, k.hi,
+                     B, p, k.dzs, k.ploss, k.pcnt);
+}
+
+}  // namespace er
+
+extern "C" {
+
+int32_t er_pairwise_sorted_grid(int64_t B, int32_t tile) {
+  return er::lwt_tile(B, tile) > 0 ? static_cast<int32_t>(er::ceil_div(B, er::kBlock)) : 0;
+}
+
+int64_t er_pairwise_sorted_workspace_bytes(int64_t B, int32_t tile) { return er::pws_workspace_bytes(B, tile); }
+
+int er_pairwise_sorted(const float* logits, int64_t ld_logits, const float* labels, const int64_t* session_keys,
+                       const float* weights, int64_t B, int32_t kind, int32_t flags, float temperature, float label_div,
+                       float margin, float hinge_margin, float gamma, float alpha, float loss_scale, int32_t tile,
+                       void* workspace, int64_t workspace_bytes, float* loss_partials, float* dlogits, int64_t* pair_count,
+                       er_stream_t stream) {
+  const int T = er::lwt_tile(B, tile);
+  ER_REQUIRE(T > 0, "er_pairwise_sorted: B = %lld, tile = %d outside the envelope (tile 0: %d < B <= %d; tile 1024, 2048, "
+             "4096 or 8192: 1 <= B <= %d)", static_cast<long long>(B), tile, er::kLwMaxB, er::kLwtMaxB, er::kLwtMaxB);
+  ER_REQUIRE(logits && labels, "er_pairwise_sorted: logits and labels are required");
+  ER_REQUIRE(ld_logits >= 1 && ld_logits <= (1 << 20), "er_pairwise_sorted: a logits pitch outside [1, 2^20]");
+  ER_REQUIRE(kind >= ER_PAIR_WISE && kind <= ER_PAIR_FOCAL, "er_pairwise_sorted: kind %d", kind);
+  ER_REQUIRE(temperature > 0.f && label_div > 0.f, "er_pairwise_sorted: temperature %g and label_div %g must be positive",
+             static_cast<double>(temperature), static_cast<double>(label_div));
+  ER_REQUIRE(kind != ER_PAIR_FOCAL || gamma >= 0.f, "er_pairwise_sorted: gamma %g below zero", static_cast<double>(gamma));
+  ER_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 &&
+                 workspace_bytes >= er::pws_workspace_bytes(B, tile),
+             "er_pairwise_sorted: the workspace is missing, not 16-byte aligned or below %lld bytes",
+             static_cast<long long>(er::pws_workspace_bytes(B, tile)));
+  er::PwParam p;
+  p.temperature = temperature; p.label_div = label_div; p.margin = margin; p.hinge_margin = hinge_margin;
+  p.gamma = gamma; p.alpha = alpha;
+  p.label_margin = (flags & ER_PAIR_LABEL_MARGIN) ? 1 : 0;
+  p.has_hinge = (flags & ER_PAIR_HINGE_MARGIN) ? 1 : 0;
+  p.has_alpha = (flags & ER_PAIR_ALPHA) ? 1 : 0;
+  const er::PwsWork k = er::pws_carve(workspace, B, T);
+  const int Bi = static_cast<int>(B), rows = static_cast<int>(er::ceil_div(B, er::kBlock));
+  const int64_t* skey = nullptr;
+  const int32_t* sidx = nullptr;
+  if (session_keys) {
+    int cur = 0;
+    if (const int rc = er::lwt_sort(session_keys, Bi, T, k.key, k.idx, stream, &cur)) return rc;
+    skey = k.key[cur];
+    sidx = k.idx[cur];
+  }
+  hipLaunchKernelGGL(er::pws_gather_kernel, dim3(static_cast<unsigned>(rows)), dim3(er::kBlock), 0, er::as_stream(stream),
+                     logits, ld_logits, labels, weights, skey, sidx, Bi, temperature, label_div, k.rec, k.hi);
+  ER_LAUNCH_CHECK();
+  switch (kind) {
+    case ER_PAIR_WISE: er::pws_launch_pairs<ER_PAIR_WISE>(rows, stream, k, Bi, p); break;
+    case ER_PAIR_LOGISTIC: er::pws_launch_pairs<ER_PAIR_LOGISTIC>(rows, stream, k, Bi, p); break;
+    case ER_PAIR_HINGE: er::pws_launch_pairs<ER_PAIR_HINGE>(rows, stream, k, Bi, p); break;
+    default: er::pws_launch_pairs<ER_PAIR_FOCAL>(rows, stream, k, Bi, p);
+  }
+  ER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(er::pws_finish_kernel, dim3(static_cast<unsigned>(rows)), dim3(er::kBlock), 0, er::as_stream(stream),
+                     k.dzs, k.ploss, k.pcnt, sidx, Bi, loss_scale, temperature, dlogits, loss_partials, pair_count);
   ER_LAUNCH_CHECK();
   return 0;
 }

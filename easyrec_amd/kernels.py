@@ -2390,6 +2390,41 @@ class HipBackend(object):
                         _p(work), _p(o['loss_partials']), _p(o['dlogits']), _p(o['pair_count']), _stream())
     return o
 
+  # -- K8p the pairwise ranking losses beyond 8192 examples, on sorted sessions (builders/pairwise_loss.py)
+  def pairwise_sorted_grid(self, B, tile=0):
+    return int(self.lib.er_pairwise_sorted_grid(int(B), int(tile)))
+
+  def pairwise_loss_sorted(self, logits, labels, session_keys, weights, kind, flags=0, temperature=1.0, label_div=1.0,
+                           margin=0.0, hinge_margin=0.0, gamma=2.0, alpha=0.0, loss_scale=1.0, want_grad=True, tile=0):
+    """er_pairwise_sorted: pairwise_loss's arguments and outputs for 8192 < B <= 131072 (tile = 0) or, with a sort tile of
+    1024, 2048, 4096 or 8192 records, 1 <= B <= 131072.  loss_partials has one entry per workgroup of 256 sorted rows
+    (pairwise_sorted_grid); pair_count [1] is int64.  The workspace is kept per (device, B, tile): launches on one stream
+    use it in order, and a captured step allocates nothing for it."""
+    assert logits.dim() == 1 and logits.dtype == torch.float32
+    B = logits.shape[0]
+    dev = logits.device
+    assert session_keys is None or (session_keys.dtype == torch.int64 and session_keys.is_contiguous() and
+                                    session_keys.numel() == B)
+    assert _f32c(labels).numel() == B and (weights is None or _f32c(weights).numel() == B)
+    grid = self.pairwise_sorted_grid(B, tile)
+    assert grid > 0, 'er_pairwise_sorted: B = %d, tile = %d outside the envelope' % (B, tile)
+    cache = self.__dict__.setdefault('_pairwise_workspaces', {})
+    work = cache.get((dev, B, int(tile)))
+    if work is None:
+      nbytes = int(self.lib.er_pairwise_sorted_workspace_bytes(B, int(tile)))
+      work = cache[(dev, B, int(tile))] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    o = {'loss_partials': torch.empty(grid, dtype=torch.float32, device=dev),
+         'loss': torch.empty(1, dtype=torch.float32, device=dev),
+         'dlogits': torch.empty(B, dtype=torch.float32, device=dev) if want_grad else None,
+         'pair_count': torch.empty(1, dtype=torch.int64, device=dev)}
+    o['loss']._er_partials = (o['loss_partials'], 1.0, 1.0)
+    self.ck.er_pairwise_sorted(logits.data_ptr(), logits.stride(0) if B > 1 else 1, _p(_f32c(labels)), _p(session_keys),
+                               None if weights is None else _p(_f32c(weights)), B, int(kind), int(flags),
+                               float(temperature), float(label_div), float(margin), float(hinge_margin), float(gamma),
+                               float(alpha), float(loss_scale), int(tile), _p(work), work.numel() * 8,
+                               _p(o['loss_partials']), _p(o['dlogits']), _p(o['pair_count']), _stream())
+    return o
+
   # -- K8n the listwise ranking losses (builders/listwise_loss.py)
   def listwise_grid(self, B):
     return int(self.lib.er_listwise_grid(int(B)))

@@ -1544,6 +1544,58 @@ int er_listwise_tiled(const float* logits, int64_t ld_logits, const float* label
                       void* workspace, int64_t workspace_bytes, er_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * K8p The pairwise ranking losses of K8m for 8192 < B <= 131072, on examples sorted by (signed session key,
+ *     example index).  The kinds, the flags, the pair definition, every pair's loss and derivative, the weighing
+ *     by the FIRST member, the SUM_BY_NONZERO_WEIGHTS reduction and the rule that dlogits, loss_partials and
+ *     pair_count may each be NULL are K8m's; so are its properties: fp32 with the precise expf / log1pf / powf,
+ *     no MFMA, no atomics, vector stores only, every float sum in one fixed order.  Nothing is launched
+ *     cooperatively, no workgroup waits for another workgroup's write - every dependency between workgroups is
+ *     a kernel boundary - and nothing is read back to the host.  Memory is O(B).
+ *
+ * er_pairwise_sorted: K8m's parameters, `tile` and the workspace in place of `work`.  What differs from K8m:
+ *   - 64-bit counts.  B = 131072 allows 8.6e9 pairs: a lane counts in 32 bits (it meets at most B columns), a
+ *     workgroup and the finish sum in 64, nz is the 64-bit count converted to float, pair_count [1] is int64.
+ *   - Summation order.  The float sums run over sorted positions, not over example order: a row's columns
+ *     ascending by position from 0.f, the workgroup's loss in K8m's tree, one row of loss_partials
+ *     [er_pairwise_sorted_grid(B, tile)] per workgroup of 256 sorted rows, each with the factor loss_scale /
+ *     nz already.  The result is a pure function of the inputs - two runs and a graph replay give the same
+ *     bits - but it is not bit-equal to er_pairwise.
+ *   Launches:
+ *   1. With session_keys: K8o's tile sort and ceil(log2 G) merge passes at tile T (tile = 0: 1024), G =
+ *      ceil(B / T), as er_listwise_tiled issues them.  A session is then one run of positions and the real
+ *      records are the positions 0 .. B - 1.  With NULL keys nothing is sorted: position p is example p and
+ *      all of them are one session.
+ *   2. Gather, one lane per position: s = z / temperature, yl = y / label_div and w through the index, the
+ *      session's first position lo and one past its last, hi, by two binary searches over the B real keys
+ *      (the padding records, INT64_MAX too, lie behind them and are never read: a real INT64_MAX key ends at
+ *      B).  One 16-byte column record (s, yl, w, lo as bits) and hi per position.
+ *   3. Pairs, ceil(B / 256) workgroups of 256 lanes, one lane per sorted row.  A workgroup's columns run from
+ *      lo of its first row to hi of its last real row and pass through LDS in chunks of at most 1024 records
+ *      (16 KB); of a chunk a wavefront walks only the columns inside [lo of its first row, hi of its last
+ *      real row), a wave-uniform range, and every lane reads the same LDS record per column.  Column j is of
+ *      row i's session when lo[j] == lo[i].  As in K8m one pair evaluation serves both orientations.  A row
+ *      sees every column of its session, so dz[i] is complete in one lane's register: no column splits, no
+ *      partial buffer.  The workgroup leaves dz in sorted order and one row (loss sum, nz, pair count).
+ *   4. Finish, the same grid: every workgroup sums the count rows, scales its loss row and its dz by
+ *      loss_scale / nz (dz by 1 / temperature as well) and scatters dz to dlogits [B] through the index;
+ *      workgroup 0 stores pair_count.
+ *   workspace: er_pairwise_sorted_workspace_bytes(B, tile) bytes, 16-byte aligned: the two record buffers of
+ *   the sort (24 G T), the column records and hi (20 B), the sorted dz (4 B) and 20 bytes per workgroup; its
+ *   contents are overwritten by every launch.
+ *   Envelope: K8m's pitch, temperature > 0, label_div > 0, gamma >= 0; with tile 1024, 2048, 4096 or 8192,
+ *   1 <= B <= 131072 (a small tile crosses tile and row-block edges at a small B); with tile 0, 8192 < B <=
+ *   131072.  Any other tile is outside.  Outside the envelope the launch returns an error and the two
+ *   helpers return 0.
+ * -------------------------------------------------------------------------------------------- */
+int32_t er_pairwise_sorted_grid(int64_t B, int32_t tile);             /* rows of loss_partials; 0 outside */
+int64_t er_pairwise_sorted_workspace_bytes(int64_t B, int32_t tile);  /* 24 G T + 24 B + 20 ceil(B / 256); 0 outside */
+int er_pairwise_sorted(const float* logits, int64_t ld_logits, const float* labels, const int64_t* session_keys,
+                       const float* weights, int64_t B, int32_t kind, int32_t flags, float temperature, float label_div,
+                       float margin, float hinge_margin, float gamma, float alpha, float loss_scale, int32_t tile,
+                       void* workspace, int64_t workspace_bytes, float* loss_partials, float* dlogits,
+                       int64_t* pair_count, er_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * K8e Theta gradient reduce: the second half of every backward whose block packs its parameters
  *     side by side into one vector `theta` of P floats (K8b, K8d).  The backward leaves per-workgroup
  *     partial sums in partials [rows, P] without atomics; this launch sums the rows in a fixed

@@ -17,7 +17,11 @@ Every window is kept: a line holds the windows of each side (microseconds per ca
 windows.  Each line carries the rocm-smi clocks read when it was written.  Prints one JSON line per measurement and
 appends them to --out.
 
+--sorted: the same two sides beyond er_pairwise's envelope, B = 16384 .. 131072, on er_pairwise_sorted (see
+sorted_sweep(); its lines go to profiles/pairwise_sorted_bench_lines.jsonl).
+
 usage: python tools/pairwise_bench.py [--iters 100] [--rounds 3] [--out FILE]
+                                      [--sorted [--sorted-iters 10] [--torch-iters 1] [--batches B ...]]
 """
 import argparse
 import json
@@ -30,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from cmbf_bench import clocks, verdict, windows  # noqa: E402
+from cmbf_bench import GRAPH_CALLS, _graphed, clocks, verdict, windows  # noqa: E402
 from multiclass_bench import session_keys  # noqa: E402
 from easyrec_amd import kernels  # noqa: E402
 from easyrec_amd.builders import pairwise_loss as pwl  # noqa: E402
@@ -43,14 +47,121 @@ KINDS = (('pair_wise', LT.PAIR_WISE_LOSS, None),
          ('focal', LT.PAIRWISE_FOCAL_LOSS, loss_pb2.PairwiseFocalLoss(gamma=2.0, hinge_margin=1.0)))
 
 
+def _window(fn, calls):
+  """fn() `calls` times between two device events -> us per call"""
+  start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  start.record()
+  for _ in range(calls):
+    fn()
+  end.record()
+  torch.cuda.synchronize()
+  return start.elapsed_time(end) * 1000.0 / calls
+
+
+def sorted_sweep(a):
+  """--sorted: er_pairwise_sorted (K8p) against the composition at B = 16384 .. 131072, forward plus gradient, the four
+  kinds with and without per-example weights, on `user_id` sessions of mean length 8 to 10 (folded to 1024 keys inside
+  every block of 8192 examples, as tools/listwise_bench.py --tiled folds them), on one single session and without keys.
+  Both sides are issued call by call in alternating windows, --sorted-iters calls of the kernel and --torch-iters of the
+  composition a window; the kernel's launches replayed from a captured graph of GRAPH_CALLS calls are timed beside them
+  (`kernel_graph_us`) where a call takes under 5 ms.  A composition that cannot allocate its [B, B] tensors is the
+  cell's result (`torch_ops: 'out of memory'`), and the cell keeps the kernel's windows."""
+  dev = 'cuda:0'
+  be = kernels.hip()
+  g = torch.Generator(device=dev).manual_seed(1)
+  lines = []
+
+  def emit(line):  # (written as it is measured: a sweep cut short keeps its lines)
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    if a.out:
+      with open(a.out, 'a') as f:
+        f.write(json.dumps(line) + '\n')
+
+  for B in a.batches:
+    z = torch.randn(B, device=dev, generator=g)
+    y = (torch.rand(B, device=dev, generator=g) < 0.25).to(torch.float32)
+    w_all = torch.rand(B, device=dev, generator=g) + 0.5
+    w_all[torch.rand(B, device=dev, generator=g) < 0.1] = 0.0
+    block = torch.arange(B, device=dev) // 8192
+    user = session_keys(B, dev) % 1024 + 1024 * block
+    for sessions, keys in (('user_id', user), ('single', torch.zeros(B, dtype=torch.int64, device=dev)), ('none', None)):
+      for name, loss_type, param in KINDS:
+        for w in (w_all, None):
+          p = pwl.params_of(loss_type, param)
+          args = pwl.kernel_args(loss_type, p)
+          got = {}
+
+          def run_hip():
+            o = be.pairwise_loss_sorted(z, y, keys, w, **args)
+            loss = torch.empty(1, device=dev)
+            be.reduce_sum(o['loss_partials'], 1.0, loss)  # (the loss tail's share of a step: the sum of the partial rows)
+            got['hip'] = (loss, o['dlogits'], o['pair_count'])
+
+          def run_torch():
+            zr = z.detach().clone().requires_grad_(True)
+            loss = pwl.compose(loss_type, y, zr, keys, w, p)
+            dz, = torch.autograd.grad(loss, zr)
+            got['torch'] = (loss.detach().reshape(1), dz)
+
+          run_hip()
+          torch.cuda.synchronize()
+          line = dict(measure='pairwise_sorted_fwd_bwd', kind=name, B=B, sessions=sessions, weights=w is not None,
+                      pairs=int(got['hip'][2]), grid=be.pairwise_sorted_grid(B), timing='eager')
+          try:
+            run_torch()
+            torch.cuda.synchronize()
+            composed = True
+          except torch.cuda.OutOfMemoryError:
+            composed = False
+            torch.cuda.empty_cache()
+          wk, wt = [], []
+          for _ in range(a.rounds):  # alternating windows
+            wk.append(_window(run_hip, a.sorted_iters))
+            if composed:
+              wt.append(_window(run_torch, a.torch_iters))
+          med = lambda ws: sorted(ws)[len(ws) // 2]  # noqa: E731
+          line.update(kernel_us=wk, kernel_median_us=med(wk))
+          if composed:
+            mk, mt, faster = verdict(wk, wt)
+            diff = max(float((h - t).abs().max() / t.abs().max().clamp(min=1e-30)) for h, t in zip(got['hip'], got['torch']))
+            line.update(torch_ops_us=wt, torch_ops_median_us=mt, kernel_faster=bool(faster), max_rel_diff=diff)
+          else:
+            line.update(torch_ops='out of memory', kernel_faster=None)
+          if med(wk) < 5000.0:
+            replay = _graphed(run_hip)
+            line['kernel_graph_us'] = [_window(replay, 1) / GRAPH_CALLS for _ in range(a.rounds)]
+          line['clocks'] = clocks()
+          got.clear()
+          torch.cuda.empty_cache()
+          emit(line)
+  measured = [ln for ln in lines if ln['kernel_faster'] is not None]
+  summary = {'measure': 'summary',
+             'kernel_faster_at_every_measured_shape': all(ln['kernel_faster'] for ln in measured),
+             'kernel_not_faster_at': [[ln['kind'], ln['B'], ln['sessions'], ln['weights']] for ln in measured if not ln['kernel_faster']],
+             'composition_out_of_memory_at': [[ln['kind'], ln['B'], ln['sessions'], ln['weights']] for ln in lines
+                                              if ln['kernel_faster'] is None],
+             # the switch's default: 1 only if the kernel path is faster at every shape the composition could run
+             'switch_default_supported': '1' if measured and all(ln['kernel_faster'] for ln in measured) else '0',
+             'sorted_iters': a.sorted_iters, 'torch_iters': a.torch_iters, 'rounds': a.rounds, 'device': be.device_info(),
+             'clocks': clocks()}
+  emit(summary)
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--iters', type=int, default=100)
   ap.add_argument('--rounds', type=int, default=3)
   ap.add_argument('--out', default='')
+  ap.add_argument('--sorted', action='store_true', help='the sweep of er_pairwise_sorted beyond B = 8192')
+  ap.add_argument('--sorted-iters', type=int, default=10, help='--sorted: calls of the kernel a window')
+  ap.add_argument('--torch-iters', type=int, default=1, help='--sorted: calls of the composition a window')
+  ap.add_argument('--batches', type=int, nargs='+', default=[16384, 32768, 65536, 131072], help='--sorted: the sizes B')
   a = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit('pairwise_bench: needs a GPU')
+  if a.sorted:
+    return sorted_sweep(a)
   dev = 'cuda:0'
   be = kernels.hip()
   g = torch.Generator(device=dev).manual_seed(1)
